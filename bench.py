@@ -7,13 +7,21 @@ Workload at N=1: the metric configuration of BASELINE.json (256x256x4 output, 4 
 64 samples per GPU).  `value` = global samples / s with inputs resident in HBM.
 
   python bench.py --gpus 1 --steps 10 --warmup 3
+  python bench.py --gpus 1 --steps 10 --warmup 3 --full
+  python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-The JSON line also carries
+A plain run sets up, warms up, times the steps and prints the line (`value`, `ms_per_step`, ...).  With --full the
+JSON line also carries
   roofline:     the dominant kernel's algorithmic TFLOP/s (HIP events on the launch stream, live in the
-                timed region) against the fp32 matrix peak of gfx950 (157.3 TFLOP/s)
+                timed region) against the fp32 matrix peak of gfx950 (157.3 TFLOP/s), and the per-kernel tables
+  density_direction, wino_bf16x3_variant, mix_f16_variant / mix_f16_speedup: the other direction and precisions,
+                a few steps each after the timed region
   cpu_baseline: the CPU oracle (oracle/tmglow_oracle.py, a port of the reference's torch-CPU path) timed on
                 this box's host cores on a bounded sample of the same workload.
+--dump-outputs DIR writes what the last timed step computed (dump_outputs()).  That step starts from the seeded starting
+state (weights, fresh optimizer; restored outside the clock) and seeded inputs, so two runs with the same arguments agree to
+the rounding of one step and two builds can be compared output for output.
 """
 import time
 _T0 = time.perf_counter()      # (before the heavy imports: on a fresh box the first `import torch` alone can take a minute or two)
@@ -185,6 +193,66 @@ def pmc_traffic(kernel):
     return round(tot / n) if n else None
 
 
+DUMP_CAP = {"grads": 6_000_000}     # entries per array (float32); every other array: DUMP_CAP_DEFAULT
+DUMP_CAP_DEFAULT = 1 << 20
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _flat(obj):
+    """Every tensor of a (nested) output structure, flattened and concatenated in traversal order, as float32."""
+    if isinstance(obj, torch.Tensor):
+        return [obj.detach().reshape(-1).float()]
+    if isinstance(obj, (list, tuple)):
+        return [t for o in obj for t in _flat(o)]
+    return []
+
+
+def restart_from(model, opt, start):
+    """Put the model back into its state `start` (a state_dict copy) and the optimizer into the state of a fresh one (moments and
+    step counters zero), in place: the same tensors, so every cached pointer stays valid."""
+    import tmg_ops
+    with torch.no_grad():
+        for k, v in model.state_dict().items():
+            v.copy_(start[k])
+        for st in opt.state.values():
+            for v in st.values():
+                if torch.is_tensor(v):
+                    v.zero_()
+    tmg_ops.invalidate_derived()      # (the version counters moved as well: belt and braces for the parameter-derived caches)
+
+
+def dump_outputs(out_dir, outputs, model):
+    """--dump-outputs: what the last timed step handed its caller - the step's outputs (`outputs`: name -> tensor or nested
+    list / tuple of tensors, e.g. the recurrent states) and the parameter gradients the optimizer consumed (zeros where a parameter
+    has none), each as one flat float32 array `out_dir/<name>.npy`.  The updated parameters are not written: the step starts from
+    the seeded weights, so they are a fixed function of the gradients, and where a parameter's true gradient is zero (a bias in
+    front of a normalisation) Adam's first step g / (|g| + eps) turns the rounding noise of the float-atomic sum into a weight
+    change - rounding that would read as a difference.  An array with more entries than its cap
+    (DUMP_CAP) is a fixed sample of them: indices drawn with replacement from a generator seeded by the name, sorted - the same
+    entries on every run and build with the same arguments."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for _, p in model.named_parameters()]
+    arrays = dict(outputs)
+    arrays["grads"] = [p.grad if p.grad is not None else torch.zeros_like(p) for p in params]
+    total = 0
+    for name, obj in sorted(arrays.items()):
+        parts = _flat(obj)
+        if not parts:
+            continue
+        v = torch.cat(parts)
+        cap = DUMP_CAP.get(name, DUMP_CAP_DEFAULT)
+        if v.numel() > cap:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, v.numel(), (cap,), generator=g).sort().values
+            v = v[idx.to(v.device)]
+        a = v.cpu().numpy().astype(np.float32)
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, "--dump-outputs exceeds %d bytes" % DUMP_MAX_BYTES
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 _PHASES = []
 
 
@@ -205,8 +273,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="M", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=None, help="samples per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-events", action="store_true", help="skip per-launch HIP-event timing")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel HIP-event timing and the roofline, the density direction, "
+                         "the other-precision variants and the CPU baselines (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-events", action="store_true", help="with --full: skip per-launch HIP-event timing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (flat float32 arrays; one "
+                         "larger than its cap as a fixed, seeded sample of its entries; 64 MB in all at most); that step starts from the seeded "
+                         "starting state, restored outside the clock, so runs with the same arguments compute it from the same inputs")
     ap.add_argument("--direction", default="sample", choices=["sample", "forward"],
                     help="sample: the generative direction the reference trains through (the metric); forward: density direction "
                          "forward(x, y) with loss -mean(logp)/(noc*H*W), reported beside it (SURVEY 8-D)")
@@ -225,6 +300,8 @@ def main():
                     help="N = 1 only: a process group of ONE rank on the real collective backend (RCCL) with the gradient buckets, their hooks "
                          "and the all-reduce in the step - what a multi-GPU rank runs, minus the peers; config.allreduce / backend report it")
     args = ap.parse_args()
+    if not args.full:
+        args.no_events = args.no_cpu_baseline = True
     if args.force_bucket and args.gpus == 1:
         os.environ["TMG_FORCE_DIST"] = "1"
 
@@ -276,6 +353,8 @@ def main():
     else:
         opt = torch.optim.Adam(model.parameters(), lr=1e-3, weight_decay=1e-8, amsgrad=True,
                                fused=(args.adam == "fused") or None)
+    # --dump-outputs: the seeded starting state, to which the last timed step returns (see restart_from)
+    start = {k: v.detach().clone() for k, v in model.state_dict().items()} if args.dump_outputs else None
     Hin, Win = cfg["_in_hw"]
     up = cfg["_up"]
     g = torch.Generator().manual_seed(12345 + rank)
@@ -289,14 +368,20 @@ def main():
     torch.cuda.synchronize()
     _phase("inputs + seed states (host RNG of the reference, once per seed)")
 
+    last = {}     # --dump-outputs: what the latest step handed its caller (references only, read after the timed region)
+
     def step():
         opt.zero_grad(set_to_none=True)
         if y_fwd is None:
-            y, ld, _ = model.sample(x, states)
+            y, ld, st = model.sample(x, states)
             loss = tmg_ops.reverse_loss(y, ld)      # = tests/common.py::loss_reverse (mean(y^2) + mean(logdet) / (noc H W)), two launches
+            if args.dump_outputs:
+                last.update(y=y, logdet=ld, states=st)
         else:
-            _, logp, _, _ = model.forward(x, y_fwd, states)
+            z, logp, st, _ = model.forward(x, y_fwd, states)
             loss = C.loss_forward(logp, y_fwd)
+            if args.dump_outputs:
+                last.update(z=z, logp=logp, states=st)
         loss.backward()
         if bucket is not None:
             bucket.allreduce_mean()
@@ -350,11 +435,24 @@ def main():
     if dom is not None:
         tmg_hip.prof_enable(100 + tmg_hip.prof_kernel_id(dom))
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - (start is not None)):
         loss = step()
     barrier()
     dt = time.perf_counter() - t0
+    if start is not None:
+        # the last timed step runs from the seeded starting state, restored outside the clock: so its inputs are the same bits on
+        # every run (a chain of training steps is not - the float atomics of the gradient sums differ in their last bit from run
+        # to run and the optimizer carries that into the weights, visibly after a few tens of steps) and the dump is comparable
+        restart_from(model, opt, start)
+        barrier()
+        t1 = time.perf_counter()
+        loss = step()
+        barrier()
+        dt += time.perf_counter() - t1
     _phase("TIMED REGION (%d steps)" % args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(last, loss=loss), model)
+        _phase("outputs of the last timed step written to %s" % args.dump_outputs)
     prof, prof_steps = {}, {}
     if not args.no_events:
         live = tmg_hip.prof_collect()      # the dominant kernel, timed live inside the timed region
@@ -402,7 +500,7 @@ def main():
         del yd
         _phase("density direction (7 steps)")
     f16_variant = None
-    if args.config == "cfg5" and mix == "f32" and graph is None and args.direction == "sample":
+    if args.full and args.config == "cfg5" and mix == "f32" and graph is None and args.direction == "sample":
         def few(n=4):
             step()
             torch.cuda.synchronize()
@@ -445,7 +543,7 @@ def main():
                  "ms_per_step_f32_mfma": round(1e3 * t32w, 3), "value": round(B * world / t3w, 2), "unit": "samples/s",
                  "speedup": round(t32w / t3w, 4)}
         _phase("bf16x3 Winograd variant (16 steps)")
-    if mix == "f16" and graph is None:
+    if args.full and mix == "f16" and graph is None:
         # the fp16-operand 1x1 mixes against this package's own fp32 mixes on the same workload, a few steps each AFTER the timed
         # region (every rank runs them: the steps contain the gradient exchange).  The stand-alone mixes read and write fp32
         # activations either way - bandwidth kernels at K = C <= 256 - so the variant buys no time; the line says so.
