@@ -1726,6 +1726,15 @@ def test_bptt_window_at_stated_batch_matches_oracle():
                    tensor_tol=max(C.GRAD_TENSOR_REL_MAX, GRAD_YARDSTICK * fl[1]), kink=r64["kink"])
 
 
+def _every_sample_term(xr, ldr, h, seed=17):
+    """A seeded loss term with its own weight per sample on EVERY sample of the level output, its log-det and the new hidden state:
+    the loss on two samples leaves the backward tiles of samples 2 .. B-1 multiplying zeros, where a tile loop that skips, repeats
+    or mis-indexes tiles past the first images changes nothing."""
+    g = torch.Generator().manual_seed(seed)
+    w = (torch.rand(3, xr.shape[0], generator=g, dtype=torch.float64) + 0.5).float().to(xr.device)
+    return ((w[0].view(-1, 1, 1, 1) * xr ** 2).sum() * 0.5 + (w[1] * ldr).sum() * 0.02 + (w[2].view(-1, 1, 1, 1) * h ** 2).sum() * 0.1)
+
+
 @pytest.mark.parametrize("cin,hw,B", [(4, (64, 64), 8), (8, (17, 33), 4), (3, (30, 30), 4), (16, (16, 16), 8)])
 def test_recompute_backward_matches_stored_activations_level(cin, hw, B):
     """tmg_ops.set_recompute (round 5): the level node of a narrow flow level keeps NO per-layer activations and its backward rebuilds
@@ -1750,7 +1759,7 @@ def test_recompute_backward_matches_stored_activations_level(cin, hw, B):
             blk.zero_grad()
             zi, ci, hi, cc = (t.clone().requires_grad_(True) for t in (z, cond, hst, cst))
             xr, ldr, st = blk.reverse(zi, ci, (hi, cc), eps=eps)
-            ((xr[:2] ** 2).sum() * 0.5 + ldr[:2].sum() * 0.02 + (st[0][:2] ** 2).sum() * 0.1).backward()
+            ((xr[:2] ** 2).sum() * 0.5 + ldr[:2].sum() * 0.02 + (st[0][:2] ** 2).sum() * 0.1 + _every_sample_term(xr, ldr, st[0])).backward()
             gr = {k: p.grad.clone() for k, p in blk.named_parameters() if p.grad is not None}
             gr.update({"@dz": zi.grad.clone(), "@dcond": ci.grad.clone(), "@dh": hi.grad.clone(), "@dc": cc.grad.clone()})
             res[tag] = (xr.detach(), ldr.detach(), gr)
@@ -1854,7 +1863,7 @@ def test_level_with_bf16x3_winograd_matches_fp32_winograd(cin, hw, B):
             blk.zero_grad()
             zi, ci, hi, cc = (t.clone().requires_grad_(True) for t in (z, cond, hst, cst))
             xr, ldr, st = blk.reverse(zi, ci, (hi, cc), eps=eps)
-            ((xr[:2] ** 2).sum() * 0.5 + ldr[:2].sum() * 0.02 + (st[0][:2] ** 2).sum() * 0.1).backward()
+            ((xr[:2] ** 2).sum() * 0.5 + ldr[:2].sum() * 0.02 + (st[0][:2] ** 2).sum() * 0.1 + _every_sample_term(xr, ldr, st[0])).backward()
             gr = {k: p.grad.clone() for k, p in blk.named_parameters() if p.grad is not None}
             gr.update({"@dz": zi.grad.clone(), "@dcond": ci.grad.clone(), "@dh": hi.grad.clone(), "@dc": cc.grad.clone()})
             res[tag] = (xr.detach(), ldr.detach(), st[0].detach(), gr)
@@ -1870,10 +1879,10 @@ def test_level_with_bf16x3_winograd_matches_fp32_winograd(cin, hw, B):
 
 @pytest.mark.parametrize("cin,hw,B", [(4, (64, 64), 64), (8, (17, 33), 32), (16, (16, 16), 128), (16, (9, 23), 64), (32, (8, 16), 64), (3, (30, 30), 64)])
 def test_level_kernels_across_field_and_batch_sizes(cin, hw, B):
-    """One flow level (generative direction + backward, recurrent states with gradients, loss on two samples) through the level-fused
-    node and its fused / grouped kernels against the per-layer path on the general kernels (TMG_NO_LEVEL_FUSION=1), over the model's
-    channel widths (16 .. 128, and the padded 12), ragged fields and batch sizes up to 128: the launch plans of the persistent, grouped
-    and fused kernels depend on the pixel count (tools/level_sweep.py is the long form)."""
+    """One flow level (generative direction + backward, recurrent states with gradients, loss on two samples plus _every_sample_term)
+    through the level-fused node and its fused / grouped kernels against the per-layer path on the general kernels
+    (TMG_NO_LEVEL_FUSION=1), over the model's channel widths (16 .. 128, and the padded 12), ragged fields and batch sizes up to 128:
+    the launch plans of the persistent, grouped and fused kernels depend on the pixel count (tools/level_sweep.py is the long form)."""
     import os
     from nn.modules.flowLSTMBlock import LSTMFLowBlock
     hs, ws = hw
@@ -1893,7 +1902,7 @@ def test_level_kernels_across_field_and_batch_sizes(cin, hw, B):
             blk.zero_grad()
             zi, ci, hi, cc = (t.clone().requires_grad_(True) for t in (z, cond, hst, cst))
             xr, ldr, st = blk.reverse(zi, ci, (hi, cc), eps=eps)
-            ((xr[:2] ** 2).sum() * 0.5 + ldr[:2].sum() * 0.02 + (st[0][:2] ** 2).sum() * 0.1).backward()
+            ((xr[:2] ** 2).sum() * 0.5 + ldr[:2].sum() * 0.02 + (st[0][:2] ** 2).sum() * 0.1 + _every_sample_term(xr, ldr, st[0])).backward()
         finally:
             os.environ.pop("TMG_NO_LEVEL_FUSION", None)
         gr = {k: p.grad.clone() for k, p in blk.named_parameters() if p.grad is not None}
