@@ -181,11 +181,7 @@ static __device__ float tmg_zero_page[64];
 // flat loads - a prefetched tile is then waited for at the first fragment read of the current one (round 5: found in every
 // wino_wgrad_kernel and conv_wgrad_kernel<..,true> instance).  These helpers state the address space.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-#ifdef TMG_FLAT_LOADS      // (A/B builds only: the generic loads of rounds 1-4)
-#define TMG_GAS
-#else
 #define TMG_GAS __attribute__((address_space(1)))
-#endif
 __device__ __forceinline__ float4 tmg_ldg4(const float* p) {
     const f32x4 v = *(const TMG_GAS f32x4*)p;
     return make_float4(v[0], v[1], v[2], v[3]);
@@ -201,22 +197,18 @@ __device__ __forceinline__ float tmg_ldg1(const float* p) { return *(const TMG_G
 // tile = blockIdx.x neighbouring tiles of an image always sit on DIFFERENT L2s and every halo line is fetched from the fabric
 // by each of them.  The tile kernels below walk a LOGICAL block order instead in which an XCD owns one contiguous eighth of the
 // tiles (whole images at the large levels): halo lines and the half-used cache lines of neighbouring tiles are then shared in
-// one L2.  TMG_NO_XCD_MAP=1 (read once per process by the launchers) restores the plain order for A/B measurements.
-static inline int tmg_xcd_map_on() {
-    static const int on = getenv("TMG_NO_XCD_MAP") ? 0 : 1;
-    return on;
-}
+// one L2.
 // logical id of physical block b of a grid of G: XCD x = b % 8 owns the contiguous logical ids [x G/8 + min(x, G%8), ...)
-__device__ __forceinline__ int tmg_xcd_block(int b, int G, int on) {
-    if (!on || G < 16) return b;
+__device__ __forceinline__ int tmg_xcd_block(int b, int G) {
+    if (G < 16) return b;
     const int qn = G >> 3, rn = G & 7, x = b & 7;
     return x * qn + min(x, rn) + (b >> 3);
 }
 // grid-stride tile loop of block b: for (t = first; t < end; t += step).  XCD x walks the tiles [n x / 8, n (x + 1) / 8) with
 // the blocks it holds.
 struct TmgTileRange { int first, end, step; };
-__device__ __forceinline__ TmgTileRange tmg_xcd_tiles(int ntiles, int b, int G, int on) {
-    if (!on || G < 16 || ntiles < 64) return TmgTileRange{b, ntiles, G};
+__device__ __forceinline__ TmgTileRange tmg_xcd_tiles(int ntiles, int b, int G) {
+    if (G < 16 || ntiles < 64) return TmgTileRange{b, ntiles, G};
     const int x = b & 7;
     const int nb = (G >> 3) + (x < (G & 7) ? 1 : 0);
     const int lo = (int)(((long long)ntiles * x) >> 3), hi = (int)(((long long)ntiles * (x + 1)) >> 3);

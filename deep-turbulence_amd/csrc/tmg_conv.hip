@@ -580,7 +580,6 @@ struct WgradP {
     int tiles_x, tiles_y, ntiles;
     int CITG;  // input-channel tiles (of 16) a block group stages at most (LDS sizing)
     int PPG;   // (input-channel tile, tap) pairs per block group: grid.z walks consecutive ranges of the tile-major pair list
-    int dbg;     // timing experiments (TMG_WG_DBG): 1 = no MFMA loop, 2 = no staging
     int fstage;  // 1: every segment / dy is float4-addressable and offsets fit 24-bit multiplies -> lean staging path
     // grouped launch (tmg_conv_wgrad_grouped): group g = blockIdx.y / bpg reads its own input segments from gtab[g],
     // dy channels [g*dy_goff, +Cout) and writes dW + g*dw_gstride / dbias + g*db_gstride; null: one group
@@ -877,8 +876,8 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_kernel(WgradP p) {
         // inside its round.
 #define TMG_WG_STAGE_ROUND                                                                                        \
         if constexpr (LEAN) {                                                                                     \
-            if (k >= -1 && tile + G < p.ntiles && p.dbg != 2) TMG_WG_COMMIT_F(((k + 1) & 1) * bufw)              \
-            if (tile + 2 * G < p.ntiles && p.dbg != 2) {                                                          \
+            if (k >= -1 && tile + G < p.ntiles) TMG_WG_COMMIT_F(((k + 1) & 1) * bufw)                             \
+            if (tile + 2 * G < p.ntiles) {                                                                        \
                 TMG_WG_ISSUE_F(tile + 2 * G)                                                                      \
                 wi_x += Gx;                                                                                       \
                 if (wi_x >= p.tiles_x) { wi_x -= p.tiles_x; ++wi_y; }                                             \
@@ -907,7 +906,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_kernel(WgradP p) {
         // k-step's reads, then this k-step's MFMAs") or over the k-steps [KA, KB) (generic walk for narrow tiles / stride 2:
         // per-k-step addresses, reads one k-step ahead; KB - KA is even)
 #define TMG_WG_RUN(UA, UB, KA, KB)                                                                                \
-        if (k >= 0 && p.dbg != 1) {                                                                               \
+        if (k >= 0) {                                                                                             \
             const int cbw = (k & 1) * bufw;                                                                       \
             float av[NP], bfr[NCO], avn[NP], bfn[NCO];                                                            \
             if (fast) {                                                                                           \
@@ -1568,20 +1567,12 @@ static int conv_fwd_lean(ConvP p, hipStream_t st) {
     if (ntt <= 4) { WM = 8; WN = 1; NTW = ntt; }
     else if (ntt <= 8) { WM = 4; WN = 2; NTW = ntt <= 6 ? 3 : 4; }
     else { WM = 2; WN = 4; NTW = ntt <= 12 ? 3 : 4; }
-    // TMG_FWD_PLAN=MT,WM,WN,NTW,GMUL,KCHMAX (0 = planner's choice): launch-plan override for measurements (tools/bench_wide.py)
-    static int fp[6] = {-1, 0, 0, 0, 0, 0};
-    if (fp[0] < 0) {
-        fp[0] = 0;
-        if (const char* e = getenv("TMG_FWD_PLAN")) sscanf(e, "%d,%d,%d,%d,%d,%d", &fp[0], &fp[1], &fp[2], &fp[3], &fp[4], &fp[5]);
-    }
-    if (fp[1] > 0 && fp[2] > 0 && fp[3] > 0 && p.ksize == 3) { WM = fp[1]; WN = fp[2]; NTW = fp[3]; }
     const int gy = (ntt + WN * NTW - 1) / (WN * NTW);
     const long npix = (long)p.B * p.Hout * p.Wout;
     const int halo = p.ksize >> 1;
     for (int MT = 4; MT >= 1; MT >>= 1) {
         // m-tiles per wave: 4 when the image is large; fewer when that would leave CUs idle (small levels)
-        if (fp[0] > 0 && p.ksize == 3) { if (MT != fp[0]) continue; }
-        else if (MT > 1 && (npix / (16 * MT * WM)) * gy < 256) continue;
+        if (MT > 1 && (npix / (16 * MT * WM)) * gy < 256) continue;
         const int MBLK = 16 * MT * WM;
         int twl = ilog2_ceil(p.Wout);
         if (twl > 5) twl = 5;
@@ -1594,7 +1585,6 @@ static int conv_fwd_lean(ConvP p, hipStream_t st) {
         // channel chunks: as few as possible, evenly sized, each fitting the register window (7 float4 x 512 threads,
         // float4 slots per pixel padded to a power of two) and two LDS buffers
         int nchunks = (p.Cin_pad + 63) / 64, kch = 0;
-        if (fp[5] >= 16 && p.ksize == 3) nchunks = (p.Cin_pad + fp[5] - 1) / fp[5];
         for (; nchunks <= p.Cin_pad / 16; ++nchunks) {
             kch = (((p.Cin_pad / 16) + nchunks - 1) / nchunks) * 16;
             const int k4p = kch <= 16 ? 4 : (kch <= 32 ? 8 : 16);
@@ -1609,7 +1599,6 @@ static int conv_fwd_lean(ConvP p, hipStream_t st) {
         p.KCH = kch;
         p.nchunks = (p.Cin_pad + kch - 1) / kch;
         int G = tmg_num_cus() / gy;
-        if (fp[4] > 0 && p.ksize == 3) G *= fp[4];
         if (G < 1) G = 1;
         if (G > p.ntiles) G = p.ntiles;
         const size_t lds_bytes = 2 * (size_t)PHPW * (kch + 8) * 4;
@@ -1829,16 +1818,6 @@ static int launch_wgrad(const WgradP& p, dim3 grid, size_t lds_bytes, hipStream_
     return 0;
 }
 
-// TMG_WG_PLAN=MPIXMAX,GXMUL (0 = planner's choice): plan override of conv_wgrad_kernel for measurements (tools/bench_wgrad_groups.py)
-static int tmg_wg_plan(int i) {
-    static int v[2] = {-1, 0};
-    if (v[0] < 0) {
-        v[0] = 0;
-        if (const char* e = getenv("TMG_WG_PLAN")) sscanf(e, "%d,%d", &v[0], &v[1]);
-    }
-    return v[i];
-}
-
 struct WgradPlan {
     int twl, TH, MPIX, tiles_x, tiles_y, ntiles, CITG, PPG, NCO, NP, ksplit, gx, gy, gz;
     size_t lds_bytes, ws_floats;
@@ -1918,7 +1897,7 @@ static int plan_wgrad_impl(int B, int Hout, int Wout, int ksize, int stride, int
         // the read/MFMA pipeline never fills.  Larger tiles (as far as registers, LDS and the tile count allow) give each
         // wave 2-4 units per tile and less halo per staged pixel.
         const int k4p = pl->CITG <= 1 ? 4 : (pl->CITG <= 2 ? 8 : (pl->CITG <= 4 ? 16 : 32));
-        for (int mp = (tmg_wg_plan(0) >= 128 ? tmg_wg_plan(0) : 512); mp > 128; mp >>= 1) {
+        for (int mp = 512; mp > 128; mp >>= 1) {
             const int th = mp >> twl, ph = th + 2 * halo;
             const int tiles = B * ((Wout + TW - 1) / TW) * ((Hout + th - 1) / th);
             if (ph * PW * k4p <= 7 * 512 && 2 * ((size_t)(ph * PW * 16 + 16) * pl->CITG + (size_t)(mp * 16 + 16) * NCO) * 4 <= 160 * 1024 &&
@@ -1997,7 +1976,6 @@ static int wgrad_impl(const void* const* in_ptrs, const int64_t* in_desc, int64_
         // (blockIdx.z still walks the input-channel blocks of a group wider than one block)
         pl.gy = bpg * ngroups;
         int gx = tmg_num_cus() / (pl.gy * pl.gz);
-        if (tmg_wg_plan(1) > 1) gx = tmg_wg_plan(1) * tmg_num_cus() / (pl.gy * pl.gz);
         if (gx > pl.ntiles / 4) gx = pl.ntiles / 4;
         if (gx < 1) gx = 1;
         pl.gx = gx;
@@ -2012,7 +1990,6 @@ static int wgrad_impl(const void* const* in_ptrs, const int64_t* in_desc, int64_
     for (int i = 0; i < p.nseg; ++i)
         if (p.in[i].stride >= (1 << 24) || (long)p.B * p.Hin * p.Win * p.in[i].stride >= (1L << 31)) p.fstage = 0;
     if (p.dy.stride >= (1 << 24) || (long)p.B * p.Hout * p.Wout * p.dy.stride >= (1L << 31)) p.fstage = 0;
-    p.dbg = 0;
     if (ngroups > 1 && (!p.fstage || !p.ws)) return -100;  // grouped launches exist only on the lean, slab-reduced path
     int lrc = -7;
 #define TMG_WG_CASE(NP_, NCO_)                                                                    \
@@ -2062,7 +2039,6 @@ extern "C" int64_t tmg_conv_wgrad_grouped_ws_floats(const int64_t* dims, int64_t
     if (plan_wgrad((int)dims[0], (int)dims[3], (int)dims[4], (int)dims[5], (int)dims[6], (int)dims[7], (int)dims[8], &pl) != 0) return 0;
     const int gy = pl.gy * (int)ngroups;
     int gx = tmg_num_cus() / (gy * pl.gz);
-    if (tmg_wg_plan(1) > 1) gx = tmg_wg_plan(1) * tmg_num_cus() / (gy * pl.gz);
     if (gx > pl.ntiles / 4) gx = pl.ntiles / 4;
     if (gx < 1) gx = 1;
     return (int64_t)((size_t)gx * gy * pl.gz * (pl.ksplit ? 1 : 4) * pl.NP * pl.NCO * 256 + (size_t)gx * gy * 64);

@@ -55,7 +55,6 @@ struct CplFP {
     float* logdet;                   // [B], accumulated
     int B, H, W, C, reverse;
     int tiles_x, tiles_y, ntiles;
-    int xmap;                        // XCD-aware tile order (tmg_common.h)
 };
 
 // CT: 16-channel output tiles (C <= 16 CT); K4: input-channel quads of the zero conv = ch/4 + 1 (the last quad is d1, d2, 0, 0)
@@ -147,7 +146,7 @@ __global__ __launch_bounds__(256, CT == 1 ? 3 : 2) void cpl_fwd_kernel(CplFP p) 
     // a block owns a contiguous range of tiles (neighbouring tiles share halo lines in L2, and the log-det partial sums of an
     // image stay in registers until the range moves on to the next image: one atomic per wave and image, not per tile)
     const int per = (p.ntiles + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int t0 = tmg_xcd_block((int)blockIdx.x, (int)gridDim.x, p.xmap) * per, t1 = min(t0 + per, p.ntiles);
+    const int t0 = tmg_xcd_block((int)blockIdx.x, (int)gridDim.x) * per, t1 = min(t0 + per, p.ntiles);
     // The staging items' patch coordinates (i / K4, / PW) depend on the thread alone: left to the compiler they are hoisted out of the
     // tile loop - NPI items x (LDS offsets, patch row / column) - and, at C = 32 where the weight fragments already hold 114 registers,
     // spilled (152 bytes per lane, reloaded in every tile's commit).  An opaque copy of the thread index per tile keeps them where
@@ -347,7 +346,6 @@ extern "C" int tmg_coupling_fwd_halves(const void* x1, const void* x2, void* out
                                        const void* hc, const void* wz, const void* bz, const void* kappa, const void* Wm, const void* bm,
                                        void* logdet, const int64_t* dims, hipStream_t st) {
     CplFP p;
-    p.xmap = tmg_xcd_map_on();
     p.B = (int)dims[0]; p.H = (int)dims[1]; p.W = (int)dims[2]; p.C = (int)dims[3]; p.reverse = (int)dims[4];
     p.x = (const float*)x1; p.xs = (int)dims[5];
     p.x2 = (const float*)x2; p.x2s = (int)dims[10];
@@ -407,7 +405,6 @@ struct CplBP {
     float* GD;                       // [npix][4]
     int B, H, W, C;
     int tiles_x, tiles_y, ntiles;
-    int xmap;                        // XCD-aware tile order (tmg_common.h)
     // fwd = 1: the DENSITY direction's layer (mix -> coupling, flowAffine.py:76-83): no mix in front of the coupling's backward (dout
     // IS the gradient w.r.t. the coupling output; the mix input gradient is a launch of its own after tmg_dense2_bwd), x = the second
     // half of the coupling OUTPUT y2, and  dtin2 = dy2 e^{sg};  da = dy2 e^{sg};  dsg = 2 dy2 y2 + 2 g_b;  dr = dsg / (1 + |r|)^2
@@ -459,7 +456,7 @@ __global__ __launch_bounds__(256, CT == 1 ? 2 : 2) void cpl_bwd_kernel(CplBP p) 
             }
 
     const int per = (p.ntiles + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int t0 = tmg_xcd_block((int)blockIdx.x, (int)gridDim.x, p.xmap) * per, t1 = min(t0 + per, p.ntiles);
+    const int t0 = tmg_xcd_block((int)blockIdx.x, (int)gridDim.x) * per, t1 = min(t0 + per, p.ntiles);
     for (int tile = t0; tile < t1; ++tile) {
         // lane coordinates re-derived from an opaque copy of the thread index per tile: the index arithmetic built on them is
         // tile-invariant, the compiler hoists it out of the loop and - at C = 32, where the weight fragments hold 160 registers - spills
@@ -702,7 +699,6 @@ extern "C" int tmg_coupling_bwd_halves(const void* dout1, const void* dout2, con
                                        const void* wz, const void* kappa, void* DH, void* dtin1, void* dtin2, void* G0, void* GD,
                                        const int64_t* dims, hipStream_t st) {
     CplBP p;
-    p.xmap = tmg_xcd_map_on();
     p.B = (int)dims[0]; p.H = (int)dims[1]; p.W = (int)dims[2]; p.C = (int)dims[3];
     p.dout = (const float*)dout1; p.dos = (int)dims[4];
     p.dout2 = (const float*)dout2; p.do2s = (int)dims[10];

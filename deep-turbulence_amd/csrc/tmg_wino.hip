@@ -90,19 +90,6 @@ extern "C" int tmg_conv_wino_pack(const void* w, void* U, int64_t Cout, int64_t 
     return 0;
 }
 
-// Diagnostic build only (-DTMG_WINO_STAMP, tools/scratch/wino_stamps.py): s_memtime stamps at the phase boundaries of wino_fwd_kernel,
-// cycles per phase summed over waves into g_wino_stamps (never read by the kernel; the product build contains no stamp).
-#ifdef TMG_WINO_STAMP
-__device__ unsigned long long g_wino_stamps[16];
-#define TMG_STAMP(I) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[I] += (unsigned)(t_ - st_last); st_last = t_; }
-extern "C" int tmg_wino_stamps(unsigned long long* out, int reset) {
-    if (reset) { unsigned long long z[16] = {0}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_wino_stamps), z, sizeof(z)); }
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wino_stamps), 16 * sizeof(unsigned long long));
-}
-#else
-#define TMG_STAMP(I)
-#endif
-
 // NPW: 16-channel output tiles per wave.  2: a block covers up to 256 output channels (wave w: n-tiles 2w, 2w+1).  1: up to 128 -
 // the contractions with 64..128 output channels (the ConvLSTM block's out-conv input gradient, 40 -> 104 at the first level) would leave
 // waves 4-7 of the 2-tile form multiplying repeated tiles; with one tile per wave all eight waves carry live work.
@@ -165,11 +152,7 @@ extern "C" int tmg_wino_stamps(unsigned long long* out, int reset) {
             }                                                                                                         \
         }                                                                                                             \
     }
-#ifdef TMG_WINO_FLAT_U
-#define TMG_WN_ULOAD(DST, PTR, BOFF) DST = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(PTR) + (BOFF));
-#else
 #define TMG_WN_ULOAD(DST, PTR, BOFF) DST = tmg_bload4(urs, BOFF, (unsigned)(((PTR) - p.U) * 4));
-#endif
 // (TMG_PACKED_F32: this kernel keeps the packed-fp32 instructions the rest of the file is built without - its float4 input transform and
 // the tile additions of the output transform halve their instruction count: gate conv 2.045 -> 2.023 ms, conditioning contraction
 // 0.663 -> 0.636 ms; wino_fwdp_kernel, wino_nn_kernel (+3 %) and wino_wgrad_kernel (+-0) measured no better with them, round 6)
@@ -246,12 +229,7 @@ __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd_kernel(WinoP p
             for (int n = 0; n < NPW; ++n) Y[o][m][n] = bvr[n];
 
     float4 bfr[4][2][NPW];   // U fragments [ring][16-channel group][n-tile], three positions ahead of the MFMAs
-#ifdef TMG_WINO_STAMP
-    unsigned st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long st_last = __builtin_amdgcn_s_memtime();
-#endif
     for (int k = -2; k < nst; ++k) {
-        TMG_STAMP(7)   // loop overhead / previous barrier exit
         // ---- commit stage k+1 --------------------------------------------------------------------------------------------------
         if (k >= -1 && k + 1 < nst) {
             float* rb = lds + ((k + 1) & 1) * RAWW;
@@ -265,7 +243,6 @@ __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd_kernel(WinoP p
             }
             if (++cc == nchunks) cc = 0;
         }
-        TMG_STAMP(0)   // commit
         // ---- issue the loads of stage k+2 -------------------------------------------------------------------------------------
         if (k + 2 < nst) {
             int t_ = ti;
@@ -303,7 +280,6 @@ __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd_kernel(WinoP p
             }
             if (++ci == nchunks) { ci = 0; ti += G; }
         }
-        TMG_STAMP(1)   // issue
         if (k >= 0) {
             // ---- input transform of stage k: V = B^T d B,  B^T = [[1,0,-1,0],[0,1,1,0],[0,-1,1,0],[0,1,0,-1]] ----------------------
             {
@@ -330,9 +306,7 @@ __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd_kernel(WinoP p
                 }
 #undef TMG_W4
             }
-            TMG_STAMP(2)   // transform
             __syncthreads();
-            TMG_STAMP(3)   // barrier 1
             // ---- 16 position GEMMs over this chunk, output transform folded in ---------------------------------------------------
             {
                 const int c0 = cm * KC;
@@ -385,7 +359,6 @@ __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd_kernel(WinoP p
 #undef TMG_WN_P
 #undef TMG_WN_LOADB
             }
-            TMG_STAMP(4)   // MFMA loop
             if (cm + 1 == nchunks) {
                 // ---- epilogue: lane (li, q) holds channels 4 q .. 4 q + 3 (of each n-tile) of Winograd tile 16 m + li -------------
                 int t_ = tm;
@@ -425,15 +398,8 @@ __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd_kernel(WinoP p
                 ++cm;
             }
         }
-        TMG_STAMP(5)   // epilogue
         __syncthreads();   // V and the raw buffer just read are rewritten next round; the raw buffer just written is complete
-        TMG_STAMP(6)   // barrier 2
     }
-#ifdef TMG_WINO_STAMP
-    if (lane == 0)
-        for (int i = 0; i < 8; ++i) atomicAdd(&g_wino_stamps[i], (unsigned long long)st_acc[i]);
-    if (tid == 0) atomicAdd(&g_wino_stamps[8], 1ull);
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -693,10 +659,9 @@ extern "C" int tmg_conv_wino_fwd(const void* const* in_ptrs, const int64_t* in_d
     // Producer-wave form (round 6) for the contractions with <= 128 output channels (one n-tile per wave: 100 registers, twelve waves
     // fit): 0.592 -> 0.551 ms (40 -> 104 at 128^2), 0.157 -> 0.146, 0.051 -> 0.049 (profiles/r6_ab_wino_producer_waves.txt).  Two
     // n-tiles per wave need 221 registers with the four-deep U ring; at the 168 that twelve waves leave, a two-deep ring measured 2.375 ms
-    // against 2.294 for the gate conv and a three-deep one spills: the wide shapes stay on wino_fwd_kernel<2>.  TMG_WINO_PC=0: off,
-    // =2: the one-tile producer form for every shape (two blocks per pixel tile above 128 channels: 2.355 ms).
-    static const int pc = getenv("TMG_WINO_PC") ? atoi(getenv("TMG_WINO_PC")) : 1;
-    if ((pc == 1 && npw == 1) || pc == 2) {
+    // against 2.294 for the gate conv and a three-deep one spills: the wide shapes stay on wino_fwd_kernel<2>.  The one-tile producer
+    // form for every shape (two blocks per pixel tile above 128 channels) measured 2.355 ms.
+    if (npw == 1) {
         const size_t ldsp = (size_t)(2 * 16 * 32 * 40) * sizeof(float);      // two V buffers: all 160 KB of the CU
         const int gyp = (ntt + 7) / 8;
         int Gp = tmg_num_cus() / gyp;
@@ -707,13 +672,8 @@ extern "C" int tmg_conv_wino_fwd(const void* const* in_ptrs, const int64_t* in_d
         TMG_CHECK_LAUNCH();
         return 0;
     }
-    if (npw == 1) {
-        TMG_LDS_OPTIN((&wino_fwd_kernel<1>));
-        hipLaunchKernelGGL(wino_fwd_kernel<1>, dim3(G, gy, 1), dim3(512), lds_bytes, st, p);
-    } else {
-        TMG_LDS_OPTIN((&wino_fwd_kernel<2>));
-        hipLaunchKernelGGL(wino_fwd_kernel<2>, dim3(G, gy, 1), dim3(512), lds_bytes, st, p);
-    }
+    TMG_LDS_OPTIN((&wino_fwd_kernel<2>));
+    hipLaunchKernelGGL(wino_fwd_kernel<2>, dim3(G, gy, 1), dim3(512), lds_bytes, st, p);
     TMG_CHECK_LAUNCH();
     return 0;
 }
@@ -1512,7 +1472,7 @@ struct WinoWP {
     int tiles_x, tiles_y, ntiles;
 };
 
-// DB (round 6): TWO tile buffers where they fit the CU's 160 KB (every instance except 4 x 3 and 4 x 4).  The single-buffered form commits
+// DB (round 6): TWO tile buffers where they fit the CU's 160 KB (every instance except 4 x 4).  The single-buffered form commits
 // the prefetched tile, meets at a barrier, multiplies, meets again: commit + issue + two barriers are 16 % of a launch during which no wave
 // feeds the matrix pipe (round-4 ablation).  With two buffers the next tile is committed into the idle buffer BETWEEN k-steps 3 and 4 of
 // the current one - LDS writes and the next global loads beside the other waves' MFMAs - and a tile costs one barrier.
@@ -1864,16 +1824,11 @@ template <int CIT, int NCO>
 static int launch_wino_wgrad(const WinoWP& p, const WinoWPlan& pl, hipStream_t st) {
     constexpr size_t one = (size_t)(180 * (CIT * 16 + 8) + 128 * (NCO * 16 + 8)) * sizeof(float);
     constexpr bool DB = 2 * one <= 160 * 1024;       // two tile buffers where they fit (see the kernel)
-    static const int nodb = getenv("TMG_WW_NO_DB") ? 1 : 0;      // A / B switch
     const double ngr = p.gtab ? (double)(pl.gy / (p.bpg > 0 ? p.bpg : 1)) : 1.0;      // (a grouped launch: every group's flops)
     TmgProf prof(TMG_PROF_WINO_WG, ngr * 2.0 * p.B * p.Hin * p.Win * (double)p.Cout * p.Cin * 9, st);
-    if (DB && !nodb) {
-        TMG_LDS_OPTIN((&wino_wgrad_kernel<CIT, NCO, DB>));
-        hipLaunchKernelGGL((wino_wgrad_kernel<CIT, NCO, DB>), dim3(pl.gx, pl.gy, pl.gz), dim3(512), 2 * one, st, p);
-    } else {
-        TMG_LDS_OPTIN((&wino_wgrad_kernel<CIT, NCO, false>));
-        hipLaunchKernelGGL((wino_wgrad_kernel<CIT, NCO, false>), dim3(pl.gx, pl.gy, pl.gz), dim3(512), one < 8192 ? 8192 : one, st, p);
-    }
+    const size_t lds = DB ? 2 * one : (one < 8192 ? 8192 : one);
+    TMG_LDS_OPTIN((&wino_wgrad_kernel<CIT, NCO, DB>));
+    hipLaunchKernelGGL((wino_wgrad_kernel<CIT, NCO, DB>), dim3(pl.gx, pl.gy, pl.gz), dim3(512), lds, st, p);
     TMG_CHECK_LAUNCH();
     return 0;
 }

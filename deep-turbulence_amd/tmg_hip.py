@@ -27,7 +27,6 @@ SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hi
 # files are listed; the vector-ALU kernels (tmg_pointwise.hip, tmg_physics.hip) keep the packed forms, which double their arithmetic
 # rate.  Round 3 measured the switch inside the noise and left the list empty; round 5 on one box, alternating three times: packed
 # everywhere 43.62 / 43.98 / 43.76 ms per step, this list 43.51 / 43.60 / 43.37 (wino + conv + coupling alone 43.64 / 43.52 / 43.58).
-# TMG_NOPK=wino,conv (env, build time; TMG_NOPK= for none) overrides the list for A/B measurements.
 NO_PACKED_F32 = ["tmg_wino.hip", "tmg_conv.hip", "tmg_coupling.hip", "tmg_thin.hip", "tmg_mix16.hip"]
 _lib = None
 
@@ -54,28 +53,20 @@ def build(force=False, verbose=False):
     os.makedirs(objdir, exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result", "-I", inc]
-    nopk = os.environ.get("TMG_NOPK")
-    nopk = NO_PACKED_F32 if nopk is None else [("tmg_%s.hip" % n) for n in nopk.split(",") if n]
-    jobs, objs = [], []
-    stamps = []
+    jobs, objs, stamps = [], [], []
     for src in SOURCES:
         sp, ob = os.path.join(CSRC, src), os.path.join(objdir, src.replace(".hip", ".o"))
         objs.append(ob)
-        extra = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"] if src in nopk else []
-        extra += os.environ.get("TMG_EXTRA_DEFS", "").split()      # diagnostic builds (e.g. -DTMG_WINO_STAMP), never the product's
-        # an object is stale when its source / a header is newer OR when it was compiled with other flags (a diagnostic build
-        # leaves objects that are newer than their sources: the next plain build must not link them into the product library)
+        extra = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"] if src in NO_PACKED_F32 else []
+        # an object is stale when its source / a header is newer OR when its flags (kept beside it) are not this build's:
+        # an edit of NO_PACKED_F32 or of the flag list recompiles what it changes
         line = " ".join(flags + extra)
         stamp = ob + ".flags"
         old = open(stamp).read() if os.path.exists(stamp) else None
-        if (force or not os.path.exists(ob) or os.path.getmtime(ob) < max(os.path.getmtime(sp), hmt)
-                or (old is not None and old != line) or (old is None and extra)):
+        if force or old != line or not os.path.exists(ob) or os.path.getmtime(ob) < max(os.path.getmtime(sp), hmt):
             jobs.append([hipcc] + flags + extra + ["-c", sp, "-o", ob])
-        stamps.append((stamp, line))
+            stamps.append((stamp, line))
     if not jobs and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(o) for o in objs):
-        for stamp, line in stamps:
-            if not os.path.exists(stamp):
-                open(stamp, "w").write(line)
         return LIB_PATH
 
     def run(cmd):
@@ -357,15 +348,14 @@ def conv_fwd(inputs, wpk, Cout, ksize, stride, outs, bias=None, kappa=None, in_s
 
 def wino_eligible(Cin, Cout, ksize, stride):
     """Shapes the Winograd F(2x2, 3x3) kernel takes over from the direct implicit GEMM: 3x3 / stride 1 with many output
-    channels (the matrix-pipe-bound contractions).  TMG_NO_WINOGRAD=1 keeps everything on the direct kernel."""
-    return (ksize == 3 and stride == 1 and Cout >= 64 and Cout % 4 == 0 and Cin % 4 == 0 and Cin >= 16
-            and os.environ.get("TMG_NO_WINOGRAD") is None)
+    channels (the matrix-pipe-bound contractions)."""
+    return ksize == 3 and stride == 1 and Cout >= 64 and Cout % 4 == 0 and Cin % 4 == 0 and Cin >= 16
 
 
 def wino_narrow_eligible(Cin, Cout):
     """Shapes of the few-output-channel Winograd kernel (the input gradients of the wide contractions, the ConvLSTM block's
     narrow convs): 3x3 / stride 1, Cout <= 48, Cin >= 64."""
-    return Cout <= 48 and Cout % 4 == 0 and Cin % 4 == 0 and Cin >= 64 and os.environ.get("TMG_NO_WINOGRAD") is None
+    return Cout <= 48 and Cout % 4 == 0 and Cin % 4 == 0 and Cin >= 64
 
 
 def conv_wino_pack(w, mode=0, nvalid=0):
@@ -498,6 +488,11 @@ def workspace(nfloats, device):
     return buf
 
 
+# conv_wgrad's Winograd routing of the 3x3 contractions with 32 - 127 output channels: at least this many input channels and pixels
+_WINO_WGRAD_CIN_MIN = 32
+_WINO_WGRAD_PIX_MIN = 1 << 20
+
+
 def conv_wgrad(inputs, dy, dW, dbias, ksize, stride, kappa=None, in_scale=None, in_shift=None, relu_in=False, pad_rep=False,
                use_ws=True, cin_dst=0, cin_valid=0, ci_split=0, ci_off0=0, ci_off1=0):
     B, Hin, Win, _ = inputs[0].shape
@@ -505,8 +500,7 @@ def conv_wgrad(inputs, dy, dW, dbias, ksize, stride, kappa=None, in_scale=None, 
     ip, idesc, n_in = _segs(inputs)
     Cin = sum(t.shape[3] for t in inputs)
     if (ksize == 3 and stride == 1 and kappa is None and in_scale is None and use_ws and Cin >= 32
-            and (os.environ.get("TMG_WINO_WGRAD_ALL") is not None or Cout >= 128 or (Cout >= 32 and Cin >= int(os.environ.get("TMG_WW_CIN_MIN", 32)) and B * Hin * Win >= int(os.environ.get("TMG_WW_PIX_MIN", 1 << 20))))
-            and os.environ.get("TMG_NO_WINOGRAD") is None and os.environ.get("TMG_NO_WINOGRAD_WGRAD") is None
+            and (Cout >= 128 or (Cout >= 32 and Cin >= _WINO_WGRAD_CIN_MIN and B * Hin * Win >= _WINO_WGRAD_PIX_MIN))
             # Winograd F(3x3, 2x2), 2.25x fewer matrix-core operations.  Measured per call site at config M: it wins wherever the
             # contraction is matrix-pipe bound (many output channels, or many pixels x input channels) and loses to the direct kernel
             # on the small ones (its 16-position slabs make the reduce step the larger part)
@@ -520,7 +514,7 @@ def conv_wgrad(inputs, dy, dW, dbias, ksize, stride, kappa=None, in_scale=None, 
 
 def wino_wgrad_eligible(Cin, Cout):
     """conv_wgrad's routing rule for the Winograd weight-gradient kernel at large pixel counts (see conv_wgrad)."""
-    return (Cin >= 32 and Cout >= 128 and os.environ.get("TMG_NO_WINOGRAD") is None and os.environ.get("TMG_NO_WINOGRAD_WGRAD") is None)
+    return Cin >= 32 and Cout >= 128
 
 
 def conv_wino_wgrad(inputs, dy, dW, dbias, relu_in=False, pad_rep=False, cin_dst=0, cin_valid=0, ci_split=0, ci_off0=0, ci_off1=0):
@@ -627,8 +621,7 @@ def conv_wgrad_grouped(group_inputs, dy, dy_group_channels, dW, dbias, ksize, st
             row += [seg(group_dy[len(rows)])[0], seg(group_dy[len(rows)])[1], 0, 0]
         rows.append(row)
     gtab = _segment_table(rows, dy.device)
-    if (group_dy is None and ksize == 3 and stride == 1 and Cin >= 20 and Cg >= 32 and os.environ.get("TMG_NO_WINOGRAD") is None
-            and os.environ.get("TMG_NO_WINOGRAD_WGRAD") is None):
+    if group_dy is None and ksize == 3 and stride == 1 and Cin >= 20 and Cg >= 32:
         # the wide levels' per-layer zero-conv weight gradients: Winograd F(3x3, 2x2), all layers of the level in one launch
         wd = _i64(B, Hin, Win, Cin, Cg, relu_in, pad_rep, cin_dst, cin_valid, ci_split, ci_off0, ci_off1)
         need = lib().tmg_conv_wino_wgrad_grouped_ws_floats(wd, c_i64(G))

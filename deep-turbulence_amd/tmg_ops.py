@@ -28,20 +28,19 @@ class _ZeroPool:
     (device, stream), so a step pays one or two fill launches instead.  A carved buffer is an ordinary tensor on the chunk's storage:
     it keeps the chunk alive and is never handed out twice; chunks are freed by the caching allocator once every buffer is gone (for
     parameter gradients: at the next zero_grad).  Bypassed during hipGraph capture - a replay would not re-zero a chunk filled before the
-    capture - and with TMG_NO_ZERO_POOL."""
+    capture."""
     CHUNK = 8 << 20
     LIMIT = 2 << 20
 
     def __init__(self):
         self.lock = threading.Lock()
         self.cur = {}
-        self.off = os.environ.get("TMG_NO_ZERO_POOL") is not None
 
     def zeros(self, shape, device):
         shape = tuple(int(v) for v in (shape if isinstance(shape, (tuple, list, torch.Size)) else (shape,)))
         n = math.prod(shape)
         device = torch.device(device)
-        if self.off or n == 0 or n > self.LIMIT or device.type != "cuda" or torch.cuda.is_current_stream_capturing():
+        if n == 0 or n > self.LIMIT or device.type != "cuda" or torch.cuda.is_current_stream_capturing():
             return torch.zeros(shape, device=device, dtype=torch.float32)
         if device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
@@ -113,7 +112,7 @@ class DerivedCache:
             return build()
         key = (tuple((p.data_ptr(), p._version) for p in params), PARAM_GENERATION[0], torch.is_grad_enabled(), extra)
         e = self.entries.get(name)
-        if e is not None and e["key"] == key and not e["stale"][0] and os.environ.get("TMG_NO_DERIVED_CACHE") is None:
+        if e is not None and e["key"] == key and not e["stale"][0]:
             return e["val"]
         if e is not None:
             for i_ in e["ids"]:
@@ -238,14 +237,10 @@ class fused_grad_accumulation:
     def __enter__(self):
         if _GradSink.active is not None:
             raise RuntimeError("fused_grad_accumulation is not re-entrant")
-        self.off = os.environ.get("TMG_NO_FUSED_ACCUM") is not None      # ablation switch: autograd's own accumulation
-        if not self.off:
-            _GradSink.active = _GradSink()
+        _GradSink.active = _GradSink()
         return self
 
     def __exit__(self, et, ev, tb):
-        if self.off:
-            return False
         sink, _GradSink.active = _GradSink.active, None
         if et is None:
             sink.flush()
@@ -1046,7 +1041,7 @@ def _mix_fwd(x, Wk, bk, packed=None):
     if _mix16_ok(C):
         H.mix_f16(x, Wk.contiguous(), bk, y)
         return y
-    if os.environ.get("TMG_NO_MIX32") is None and x.stride(3) == 1 and H.mix_f32(x, Wk.contiguous(), bk, y):
+    if x.stride(3) == 1 and H.mix_f32(x, Wk.contiguous(), bk, y):
         return y
     H.conv_fwd([x], packed if packed is not None else H.conv_pack(Wk.reshape(C, C, 1, 1), 0), C, 1, 1, [y], bias=bk)
     return y
@@ -1080,7 +1075,7 @@ def _mix_bwd(x, dy, Wk, dWk, dbk, packed_t=None, defer=None):
     dx = torch.empty(dy.shape, device=dy.device, dtype=torch.float32)
     if _mix16_ok(C):
         H.mix_f16(dy, Wk.contiguous(), None, dx, transposed=True)
-    elif not (os.environ.get("TMG_NO_MIX32") is None and H.mix_f32(dy, Wk.contiguous(), None, dx, transposed=True)):
+    elif not H.mix_f32(dy, Wk.contiguous(), None, dx, transposed=True):
         H.conv_fwd([dy], packed_t if packed_t is not None else H.conv_pack(Wk.reshape(C, C, 1, 1), 1), C, 1, 1, [dx])
     xs = x if isinstance(x, list) else [x]      # the mix input may be given as channel segments
     if defer is not None:
@@ -1177,15 +1172,14 @@ class LevelCouplingFn(torch.autograd.Function):
         cur = x
         # narrow levels: zero conv, coupling, log-det and - in the generative direction - the following channel mix are ONE launch
         # (tmg_coupling_fwd) after the growth layers' launch; wide levels keep one launch per op
-        fuse = (8 <= C <= 32 and ch % 4 == 0 and os.environ.get("TMG_NO_FUSED_COUPLING") is None
-                and all(w.is_contiguous() for w in wts))
+        fuse = 8 <= C <= 32 and ch % 4 == 0 and all(w.is_contiguous() for w in wts)
         # Split-halves layout (round 4; generative direction on the levels whose per-layer kernels are bandwidth-bound): between
         # the layers of the node an activation lives as TWO [B,h,w,C/2] tensors (x1, x2) instead of one [B,h,w,C].  The kernels
         # that read x1 alone - growth layers, their backward, three weight gradients - then use every byte of the lines they
         # fetch (a 64-byte pixel of the 16-channel level shares its 128-byte line with the neighbour's other half), and the fused
         # coupling kernel's x1 patch loads and x2 epilogue loads no longer pull each other's half-used lines through L2 twice.
         # The node's input and output stay single tensors (addressed as two channel-slice views).
-        split = fuse and reverse and C in (16, 32) and os.environ.get("TMG_NO_SPLIT_HALVES") is None
+        split = fuse and reverse and C in (16, 32)
         mixaff = (reverse and C in (64, 128) and Wm.is_contiguous() and bm.is_contiguous()
                   and os.environ.get("TMG_NO_MIX_AFFINE") is None)
         # Recompute mode (set_recompute; narrow levels, generative direction - where ~80 % of the per-layer activations of the model
@@ -1291,7 +1285,7 @@ class LevelCouplingFn(torch.autograd.Function):
         # The NL zero-conv weight gradients (x1 | D part) are independent of each other once DH holds every layer's
         # exp(kappa)*dhh: they run as ONE grouped launch after the loop (a few microseconds of MFMA work each otherwise,
         # dominated by launch / pipeline-fill).  Their inputs stay alive until then (NL * C floats per pixel).
-        grouped = NL > 1 and ch + 4 <= 132 and os.environ.get("TMG_NO_GROUPED_WGRAD") is None
+        grouped = NL > 1 and ch + 4 <= 132
         PZt = H.conv_pack_batched(Wz, 1, ch + 4, (ch + 2, ch, Cc))          # input-gradient operands of all layers: one launch
         PMt = H.conv_pack_batched(Wm.reshape(NL, C, C, 1, 1), 1)
         wg_in = [None] * NL
@@ -1323,7 +1317,7 @@ class LevelCouplingFn(torch.autograd.Function):
             else:
                 xin, tin, D, r, y = saved[k]
                 saved[k] = None
-            if reverse and ctx.fuse and os.environ.get("TMG_NO_FUSED_COUPLING_BWD") is None:
+            if reverse and ctx.fuse:
                 # one launch: mix input gradient -> coupling backward -> zero-conv input gradient (exact replicate adjoint)
                 if ctx.split and k != NL - 1:    # gradient w.r.t. a layer input that lives as two halves: the same layout
                     dtin = (torch.empty((B, Hh, Ww, ch), device=dev, dtype=torch.float32), torch.empty((B, Hh, Ww, ch), device=dev, dtype=torch.float32))
@@ -1348,7 +1342,7 @@ class LevelCouplingFn(torch.autograd.Function):
                 dcur = dtin
                 del xin, tin, D, r, y
                 continue
-            if (not reverse) and ctx.fuse and os.environ.get("TMG_NO_FUSED_COUPLING_BWD") is None:
+            if (not reverse) and ctx.fuse:
                 # density direction (mix -> coupling): coupling backward + zero-conv input gradient in one launch (tmg_coupling_bwd in its
                 # `fwd` mode: the gradient arrives at the coupling output itself), then the growth layers' backward, then the input
                 # gradient of the leading mix (round 4: this direction ran affine_bwd + conv dgrad + border fold per layer before)

@@ -205,7 +205,7 @@ def test_baseline_configs_match_fp64_oracle(name, cfg, B):
     # forward (direct contraction, Winograd contraction, either 1x1 kernel) put on different sides of zero; that element happens to
     # be the largest entry of its upstream gradient, so the flip moves two weight-gradient tensors by 2-10 % while the forward pass
     # and every other gradient agree to 1e-6 (measured element by element when the Winograd kernels came in).  Seed 37 has no such
-    # element for any of the kernel selections (TMG_NO_WINOGRAD / TMG_NO_MIX32 on or off).
+    # element for any of the kernel selections (direct or Winograd contraction, either 1x1 kernel).
     g = torch.Generator().manual_seed(int(os.environ.get("TMG_TEST_INPUT_SEED", 37 if name == "cfg5-64x64" else 31)))
     x = torch.randn(B, cfg["in_features"], h, w, generator=g)
     y = torch.randn(B, cfg["out_features"], H_, W_, generator=g)

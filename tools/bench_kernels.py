@@ -107,7 +107,7 @@ if __name__ == "__main__" and "tail" in sys.argv:
 
 
 def bench_d2():
-    """dense2 backward alone at level-1 shape; TMG_D2_DBG=1 skips the input-gradient part, =2 the weight-gradient part."""
+    """dense2 backward alone at the four levels' shapes."""
     dev = "cuda"
     for lvl, (hw, C) in enumerate([(128, 16), (64, 32), (32, 64), (16, 128)], 1):
         B, Cc = 64, 32
@@ -122,11 +122,8 @@ def bench_d2():
         w1, w2 = torch.randn(cin, 9, device=dev), torch.randn(cin + 1, 9, device=dev)
         dw1, dw2 = torch.zeros_like(w1), torch.zeros_like(w2)
         nn_in = [x[..., :ch], cond]
-        for dbg in ("0", "1", "2", "3"):
-            os.environ["TMG_D2_DBG"] = dbg
-            t = timeit(lambda: H.dense2_bwd(nn_in + [D], w1, w2, dw1, dw2, GD, D, G, [dx[..., :ch], G[1]], cin, add0=dy[..., :ch], rows1=cin, rows2=cin + 1))
-            print("dense2_bwd L%d dbg=%s: %7.3f ms" % (lvl, dbg, t), flush=True)
-        os.environ["TMG_D2_DBG"] = "0"
+        t = timeit(lambda: H.dense2_bwd(nn_in + [D], w1, w2, dw1, dw2, GD, D, G, [dx[..., :ch], G[1]], cin, add0=dy[..., :ch], rows1=cin, rows2=cin + 1))
+        print("dense2_bwd L%d: %7.3f ms" % (lvl, t), flush=True)
         D0 = torch.zeros(B, hw, hw, 4, device=dev)
         t = timeit(lambda: H.c1_fwd(nn_in, w1, D0[..., 0:1], relu_in=True))
         print("c1_fwd L%d: %7.3f ms" % (lvl, t), flush=True)

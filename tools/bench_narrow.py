@@ -4,7 +4,6 @@ configuration's first two levels (B 64: 128^2 x 16 channels, 64^2 x 32 channels)
 
   LAYOUT=slice (default): x1 = the leading half of a [.., C] tensor (the layout of round 3)
   LAYOUT=split:           x1 / x2 in tensors of their own ([.., C/2] each)
-  TMG_NO_XCD_MAP=1:       plain tile order (read once per process by the library)
 """
 import os
 import sys
@@ -33,7 +32,7 @@ def main():
     dev = "cuda"
     split = os.environ.get("LAYOUT", "slice") == "split"
     B, Cc, NL = 64, 32, 15
-    tag = "%s, xcd map %s" % ("split halves" if split else "slices", "off" if os.environ.get("TMG_NO_XCD_MAP") else "on")
+    tag = "split halves" if split else "slices"
     for lvl, (hw, C) in enumerate([(128, 16), (64, 32)], 1):
         ch = C // 2
         cin = ch + Cc

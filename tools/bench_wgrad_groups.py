@@ -2,8 +2,6 @@
 """Micro-benchmark of the narrow levels' grouped weight-gradient launches (one launch per level for all 15 coupling layers) at the
 metric configuration's first two levels (B 64: 128^2 x 16 channels, 64^2 x 32 channels) - GPU only: the zero convs' (x1 | D rows,
 replicate padding), the growth layers' (4 output channels per group) and the 1x1 mixes'.  Algorithmic bytes = every operand read once.
-
-  TMG_WG_PLAN=MPIXMAX,GXMUL   plan override of conv_wgrad_kernel (largest pixel tile, multiplier of the pixel-share count)
 """
 import os
 import sys
@@ -33,7 +31,6 @@ def timeit(fn, n=20):
 def main():
     dev = "cuda"
     B, Cc, NL = 64, 32, 15
-    tag = os.environ.get("TMG_WG_PLAN", "default plan")
     for lvl, (hw, C) in enumerate([(128, 16), (64, 32)], 1):
         ch = C // 2
         cin = ch + Cc
@@ -46,18 +43,18 @@ def main():
         t = timeit(lambda: H.conv_wgrad_grouped(wg_in, DH, C, dWz, dBz, 3, 1, relu_in=True, pad_rep=True, cin_dst=cin + 2, cin_valid=ch + 2,
                                                 ci_split=ch, ci_off0=0, ci_off1=Cc))
         byts = npx * 4.0 * NL * (ch + 4 + C)
-        print("[%s] L%d zero-conv weight gradients (15 groups)   %7.1f us  alg %.2f TB/s  %5.1f TF" % (tag, lvl, t, byts / t / 1e6, 2.0 * npx * NL * (ch + 4) * C * 9 / t / 1e6), flush=True)
+        print("L%d zero-conv weight gradients (15 groups)   %7.1f us  alg %.2f TB/s  %5.1f TF" % (lvl, t, byts / t / 1e6, 2.0 * npx * NL * (ch + 4) * C * 9 / t / 1e6), flush=True)
         tmpX = ops.zeros((NL, 4, ch + 4, 3, 3), dev)
         t = timeit(lambda: H.conv_wgrad_grouped(wg_in, DD, 4, tmpX, None, 3, 1, relu_in=True))
         byts = npx * 4.0 * NL * (ch + 4 + 4)
-        print("[%s] L%d growth-layer weight gradients (15 groups) %7.1f us  alg %.2f TB/s" % (tag, lvl, t, byts / t / 1e6), flush=True)
+        print("L%d growth-layer weight gradients (15 groups) %7.1f us  alg %.2f TB/s" % (lvl, t, byts / t / 1e6), flush=True)
         ys = [(mk(ch), mk(ch)) for _ in range(NL)]
         gs = [(mk(ch), mk(ch)) for _ in range(NL)]
         dWm = ops.zeros((NL, C, C, 1, 1), dev)
         dbm = ops.zeros((NL, C), dev)
         t = timeit(lambda: H.conv_wgrad_grouped([list(y) for y in ys], None, C, dWm, dbm, 1, 1, group_dy=gs))
         byts = npx * 4.0 * NL * 2 * C
-        print("[%s] L%d 1x1 mix weight gradients (15 groups)      %7.1f us  alg %.2f TB/s" % (tag, lvl, t, byts / t / 1e6), flush=True)
+        print("L%d 1x1 mix weight gradients (15 groups)      %7.1f us  alg %.2f TB/s" % (lvl, t, byts / t / 1e6), flush=True)
 
 
 if __name__ == "__main__":

@@ -4,8 +4,6 @@
 Generative direction, one coupling layer: c1x2_fwd -> conv_fwd (zero conv with the conditioning addend, bias, exp(kappa)) ->
 mix_affine_fwd; backward: mix_affine_bwd -> conv_fwd (zero-conv input gradient) -> border fold -> dense2_bwd.
 The matrix-pipe share of the two convs is printed against the fp32 MFMA peak (157.3 TF).
-
-  TMG_FWD_PLAN=MT,WM,WN,NTW,GMUL,KCHMAX   launch-plan override of conv_fwd_kernel (read once per process by the library)
 """
 import os
 import sys
@@ -34,7 +32,6 @@ def timeit(fn, n=50):
 def main():
     dev = "cuda"
     B, Cc, NL = 64, 32, 15
-    tag = os.environ.get("TMG_FWD_PLAN", "default plan")
     tot = 0.0
     for lvl, (hw, C) in ((3, (32, 64)), (4, (16, 128))):
         ch = C // 2
@@ -88,12 +85,12 @@ def main():
             t = timeit(lambda: H.conv3x3_auto([dhh], wz_eff, ch + 4, [G0, GD], dgrad=True))
             rows.append(("WINOGRAD probe input gradient %d -> %d+4" % (C, ch), t, 2.0 * npx * (ch + 4) * C * 9))
         for name, t, fl in rows:
-            print("[%s] L%d %-36s %7.1f us%s" % (tag, lvl, name, t, "" if fl is None else "  %5.1f TF = %.2f of the fp32 MFMA peak" % (fl / t / 1e6, fl / t / 1e6 / 157.3)),
+            print("L%d %-36s %7.1f us%s" % (lvl, name, t, "" if fl is None else "  %5.1f TF = %.2f of the fp32 MFMA peak" % (fl / t / 1e6, fl / t / 1e6 / 157.3)),
                   flush=True)
         s = sum(t for _, t, _ in rows)
         tot += s
-        print("[%s] L%d layer chain %.1f us (x %d layers = %.2f ms)" % (tag, lvl, s, NL, s * NL / 1e3), flush=True)
-    print("[%s] both levels, per-layer launches: %.2f ms per step" % (tag, tot * NL / 1e3))
+        print("L%d layer chain %.1f us (x %d layers = %.2f ms)" % (lvl, s, NL, s * NL / 1e3), flush=True)
+    print("both levels, per-layer launches: %.2f ms per step" % (tot * NL / 1e3))
 
 
 if __name__ == "__main__":

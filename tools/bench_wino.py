@@ -93,7 +93,4 @@ for B, Hh, Ww, segs, Cout in [(64, 128, 128, [8, 32, 64], 256), (64, 128, 128, [
         e1.synchronize()
         return e0.elapsed_time(e1) / n
     tw = t(lambda: H.conv_wino_wgrad(xs, dy, dW, None))
-    os.environ["TMG_NO_WINOGRAD"] = "1"
-    td = t(lambda: H.conv_wgrad(xs, dy, dW, None, 3, 1))
-    del os.environ["TMG_NO_WINOGRAD"]
-    print("%4dx%-4d %4d -> %4d   winograd %7.3f ms (%6.1f TF)   direct %7.3f ms (%6.1f TF)" % (Hh, Ww, sum(segs), Cout, tw, fl / tw / 1e9, td, fl / td / 1e9))
+    print("%4dx%-4d %4d -> %4d   winograd %7.3f ms (%6.1f TF)" % (Hh, Ww, sum(segs), Cout, tw, fl / tw / 1e9))

@@ -8,7 +8,7 @@ variant and direction, the global rel-L2, the worst per-tensor rel-max and the f
 to the fp32 oracle's error on the same tensors.
 
   python tools/parity_report.py --config M --batch 1 --out gpurun_out/parity_report_M.json
-  python tools/parity_report.py --config cfg3 --variants default,no_wino,no_wino_wgrad,no_fused_bwd
+  python tools/parity_report.py --config cfg3 --variants default,no_thin_wgrad,no_lu_fold
 
 The oracle is used here as the CHECKER only (tools/ is diagnostics, like tests/)."""
 import argparse
@@ -29,22 +29,9 @@ import common as C  # noqa: E402
 
 VARIANTS = {
     "default": {},
-    "no_wino": {"TMG_NO_WINOGRAD": "1"},
-    "no_wino_wgrad": {"TMG_NO_WINOGRAD_WGRAD": "1"},
-    "no_fused_bwd": {"TMG_NO_FUSED_COUPLING_BWD": "1"},
-    "no_fused": {"TMG_NO_FUSED_COUPLING": "1"},
-    "no_grouped_wgrad": {"TMG_NO_GROUPED_WGRAD": "1"},
     "no_thin_wgrad": {"TMG_NO_THIN_WGRAD": "1", "TMG_NO_MIX_WGRAD_KERNEL": "1"},
     "no_level_fusion": {"TMG_NO_LEVEL_FUSION": "1"},
     "no_lu_fold": {"TMG_NO_LU_FOLD_KERNEL": "1"},
-    "no_mix32": {"TMG_NO_MIX32": "1"},
-    "plain_wino": {"TMG_NO_FUSED_COUPLING": "1", "TMG_NO_THIN_WGRAD": "1", "TMG_NO_MIX_WGRAD_KERNEL": "1", "TMG_NO_LU_FOLD_KERNEL": "1", "TMG_NO_MIX32": "1"},
-    "plain_fused": {"TMG_NO_WINOGRAD": "1", "TMG_NO_THIN_WGRAD": "1", "TMG_NO_MIX_WGRAD_KERNEL": "1", "TMG_NO_LU_FOLD_KERNEL": "1", "TMG_NO_MIX32": "1"},
-    "plain_thin": {"TMG_NO_WINOGRAD": "1", "TMG_NO_FUSED_COUPLING": "1", "TMG_NO_LU_FOLD_KERNEL": "1", "TMG_NO_MIX32": "1"},
-    "plain_lufold": {"TMG_NO_WINOGRAD": "1", "TMG_NO_FUSED_COUPLING": "1", "TMG_NO_THIN_WGRAD": "1", "TMG_NO_MIX_WGRAD_KERNEL": "1", "TMG_NO_MIX32": "1"},
-    "plain_mix32": {"TMG_NO_WINOGRAD": "1", "TMG_NO_FUSED_COUPLING": "1", "TMG_NO_THIN_WGRAD": "1", "TMG_NO_MIX_WGRAD_KERNEL": "1", "TMG_NO_LU_FOLD_KERNEL": "1"},
-    "plain": {"TMG_NO_WINOGRAD": "1", "TMG_NO_FUSED_COUPLING": "1", "TMG_NO_THIN_WGRAD": "1", "TMG_NO_MIX_WGRAD_KERNEL": "1",
-              "TMG_NO_LU_FOLD_KERNEL": "1", "TMG_NO_MIX32": "1"},
 }
 CONFIGS = {"M": C.CFG_M, "cfg3": C.CFG3, "cfg2": C.CFG2, "cfg1": C.CFG1, "tiny": C.CFG_TINY, "cfg5": C.CFG5}
 
@@ -176,7 +163,7 @@ def main():
     ap.add_argument("--config", default="M", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--seed", type=int, default=31)
-    ap.add_argument("--variants", default="default,no_wino,no_wino_wgrad,no_fused_bwd")
+    ap.add_argument("--variants", default="default,no_thin_wgrad,no_level_fusion,no_lu_fold")
     ap.add_argument("--forward", action="store_true", help="also the density direction")
     ap.add_argument("--loss-samples", type=int, default=0, help="loss on the first n samples of the batch only (oracle: encoder on the "
                                                                 "whole batch, flow on n samples): stated-batch parity")
