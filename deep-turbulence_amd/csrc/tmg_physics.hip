@@ -377,6 +377,178 @@ extern "C" int tmg_phys_fields(const void* u, const void* p, void* ustar, void* 
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Adjoint of phys_fields_kernel<K1, K2>: d/du and d/dp of  sum(gustar * ustar) + sum(gpstar * pstar)  (the backward of
+// PhysConstrainedLES.calcDivergence / calcPressurePoisson).  One 16x16 pixel tile per 256-thread block, in two stages as
+// phys_bwd_kernel:
+//   1. u, v, p of tile + halo 2*RM (+1 column on the left for the divergence's replicated column) go to LDS, zero outside the
+//      image.  The pre-clamp residuals are recomputed with the forward's arithmetic; where -1 <= raw <= 1 (torch's clamp backward)
+//      the adjoint sources are formed on tile + halo:
+//        pressure  a = sp * gpstar:  S0 = 2a ux_x, S1 = 2a uy_x (factor on ux_y), S2 = 2a ux_y (factor on uy_x), S3 = 2a uy_y, S4 = a / rho
+//        divergence on the widened grid (column jw of [0, W + 2)):  S5 = sd * gustar
+//   2. every output pixel gathers the sources through the transposed stencils (exact transposes: the 5x5 second-derivative
+//      stencil is not symmetric).  Widened column jw read original column clamp(jw - 1, 0, W - 1), so original column 0 also
+//      collects widened column 0 and column W - 1 widened column W + 1.
+// No atomics: every output is written once by one thread (bitwise reproducible).
+// ---------------------------------------------------------------------------------------------------------------------------
+template <int K>
+__device__ __forceinline__ float pf_w1(int a, int b) { return K == 3 ? g1w(a, b) : g1w5(a, b) / 108.f; }
+template <int K>
+__device__ __forceinline__ float pf_w2(int a, int b) { return K == 3 ? g2w(a, b) : g2w5(a, b) / 108.f; }
+
+template <int K1, int K2>
+__global__ __launch_bounds__(256) void phys_fields_bwd_kernel(const float* __restrict__ u, const float* __restrict__ pr,
+                                                              const float* __restrict__ gus, const float* __restrict__ gps,
+                                                              float* __restrict__ du, float* __restrict__ dp, int H, int W, float dx,
+                                                              float dy, float rho, float sd, float sp) {
+    constexpr int R1 = K1 / 2, R2 = K2 / 2, RM = R1 > R2 ? R1 : R2;
+    constexpr int FH = PT + 4 * RM, FW = PT + 4 * RM + 2;   // staged fields: rows i0 - 2RM.., columns j0 - 2RM - 1..
+    constexpr int SE = PT + 2 * RM;                         // pressure sources: rows / columns i0 - RM.., j0 - RM..
+    constexpr int DH = PT + 2 * R1, DW = PT + 2 + 2 * R1;   // divergence sources: rows i0 - R1.., widened columns j0 - R1..
+    __shared__ float f[3][FH][FW];
+    __shared__ float S[5][SE][SE];
+    __shared__ float D[DH][DW];
+    const int n = blockIdx.z;
+    const int i0 = blockIdx.y * PT, j0 = blockIdx.x * PT;
+    const int fi0 = i0 - 2 * RM, fj0 = j0 - 2 * RM - 1;
+    const int tid = threadIdx.x;
+    const size_t plane = (size_t)H * W;
+    const bool hasP = gps != nullptr, hasD = gus != nullptr;
+    const float* U = u + (size_t)n * 2 * plane;
+    const float* V = U + plane;
+    const int nf = hasP ? 3 : 2;
+    for (int k = tid; k < nf * FH * FW; k += 256) {
+        const int c = k / (FH * FW);
+        const int r = k - c * (FH * FW);
+        const int li = r / FW, lj = r - li * FW;
+        const int i = fi0 + li, j = fj0 + lj;
+        float v = 0.f;
+        if (i >= 0 && i < H && j >= 0 && j < W) v = (c == 2 ? pr + (size_t)n * plane : U + (size_t)c * plane)[(size_t)i * W + j];
+        f[c][li][lj] = v;
+    }
+    __syncthreads();
+    // ---- stage 1a: pressure adjoint sources on tile + halo RM
+    for (int k = tid; k < SE * SE; k += 256) {
+        const int si = k / SE, sj = k - si * SE;
+        const int i = i0 - RM + si, j = j0 - RM + sj;
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f;
+        if (hasP && i >= 0 && i < H && j >= 0 && j < W) {
+            const int bi = i - R1 - fi0, bj = j - R1 - fj0;   // staged position of tap (0, 0)
+            float ux_x = 0.f, ux_y = 0.f, uy_x = 0.f, uy_y = 0.f, pxx = 0.f, pyy = 0.f;
+#pragma unroll
+            for (int a = 0; a < K1; ++a)
+#pragma unroll
+                for (int b = 0; b < K1; ++b) {
+                    const float uu = f[0][bi + a][bj + b], vv = f[1][bi + a][bj + b];
+                    ux_x += pf_w1<K1>(a, b) * uu; ux_y += pf_w1<K1>(b, a) * uu;
+                    uy_x += pf_w1<K1>(a, b) * vv; uy_y += pf_w1<K1>(b, a) * vv;
+                }
+            const int ci = i - R2 - fi0, cj = j - R2 - fj0;
+#pragma unroll
+            for (int a = 0; a < K2; ++a)
+#pragma unroll
+                for (int b = 0; b < K2; ++b) {
+                    const float pp = f[2][ci + a][cj + b];
+                    pxx += pf_w2<K2>(a, b) * pp; pyy += pf_w2<K2>(b, a) * pp;
+                }
+            ux_x /= dx; uy_x /= dx; ux_y /= dy; uy_y /= dy;
+            const float raw = sp * ((pxx / (dx * dx) + pyy / (dy * dy)) / rho + ux_x * ux_x + 2.f * ux_y * uy_x + uy_y * uy_y);
+            if (raw >= -1.f && raw <= 1.f) {
+                const float a_ = sp * gps[((size_t)n * H + i) * W + j];
+                s0 = 2.f * a_ * ux_x; s1 = 2.f * a_ * uy_x; s2 = 2.f * a_ * ux_y; s3 = 2.f * a_ * uy_y; s4 = a_ / rho;
+            }
+        }
+        S[0][si][sj] = s0; S[1][si][sj] = s1; S[2][si][sj] = s2; S[3][si][sj] = s3; S[4][si][sj] = s4;
+    }
+    // ---- stage 1b: divergence adjoint sources on widened columns [j0 - R1, j0 + PT + 2 + R1), rows of tile + halo R1
+    for (int k = tid; k < DH * DW; k += 256) {
+        const int si = k / DW, sj = k - si * DW;
+        const int i = i0 - R1 + si, jw = j0 - R1 + sj;
+        float s5 = 0.f;
+        if (hasD && i >= 0 && i < H && jw >= 0 && jw < W + 2) {
+            float dux = 0.f, dvy = 0.f;
+#pragma unroll
+            for (int a = 0; a < K1; ++a)
+#pragma unroll
+                for (int b = 0; b < K1; ++b) {
+                    const int jj = jw + b - R1;
+                    if (jj < 0 || jj >= W + 2) continue;   // zero beyond the widened field (rows: zero in the staged fields)
+                    const int lj = min(max(jj - 1, 0), W - 1) - fj0;
+                    const int li = i + a - R1 - fi0;
+                    dux += pf_w1<K1>(a, b) * f[0][li][lj];
+                    dvy += pf_w1<K1>(b, a) * f[1][li][lj];
+                }
+            const float raw = sd * (dvy / dy + dux / dx);
+            if (raw >= -1.f && raw <= 1.f) s5 = sd * gus[((size_t)n * H + i) * (W + 2) + jw];
+        }
+        D[si][sj] = s5;
+    }
+    __syncthreads();
+    // ---- stage 2: gather through the transposed stencils.  Source pixel q - (a - R, b - R) used q through tap (a, b).
+    const int ti = tid / PT, tj = tid % PT;
+    const int i = i0 + ti, j = j0 + tj;
+    if (i >= H || j >= W) return;
+    float gU = 0.f, gV = 0.f, gP = 0.f;
+    if (hasP) {
+#pragma unroll
+        for (int a = 0; a < K1; ++a)
+#pragma unroll
+            for (int b = 0; b < K1; ++b) {
+                const int si = ti + RM + R1 - a, sj = tj + RM + R1 - b;
+                gU += S[0][si][sj] * (pf_w1<K1>(a, b) / dx) + S[1][si][sj] * (pf_w1<K1>(b, a) / dy);
+                gV += S[2][si][sj] * (pf_w1<K1>(a, b) / dx) + S[3][si][sj] * (pf_w1<K1>(b, a) / dy);
+            }
+#pragma unroll
+        for (int a = 0; a < K2; ++a)
+#pragma unroll
+            for (int b = 0; b < K2; ++b) {
+                const int si = ti + RM + R2 - a, sj = tj + RM + R2 - b;
+                gP += S[4][si][sj] * (pf_w2<K2>(a, b) / (dx * dx) + pf_w2<K2>(b, a) / (dy * dy));
+            }
+    }
+    if (hasD) {
+        // widened column cw = j + 1 always; cw = 0 for j == 0 and cw = W + 1 for j == W - 1 in addition (both when W == 1)
+        const int nc = 1 + (j == 0) + (j == W - 1);
+        for (int e = 0; e < nc; ++e) {
+            const int cw = e == 0 ? j + 1 : ((e == 1 && j == 0) ? 0 : W + 1);
+#pragma unroll
+            for (int a = 0; a < K1; ++a)
+#pragma unroll
+                for (int b = 0; b < K1; ++b) {
+                    const float s5 = D[ti + 2 * R1 - a][cw - j0 + 2 * R1 - b];
+                    gU += s5 * (pf_w1<K1>(a, b) / dx);
+                    gV += s5 * (pf_w1<K1>(b, a) / dy);
+                }
+        }
+    }
+    const size_t o = (size_t)i * W + j;
+    du[(size_t)n * 2 * plane + o] = gU;
+    du[(size_t)n * 2 * plane + plane + o] = gV;
+    if (dp) dp[(size_t)n * plane + o] = gP;
+}
+
+// u [N][2][H][W], p [N][1][H][W] (may be null when gpstar is null); gustar [N][1][H][W + 2] / gpstar [N][1][H][W] (either may be null);
+// du [N][2][H][W] and dp [N][1][H][W] (may be null) are overwritten.  dims = {N, H, W, k1, k2, scale}; fl = {dx, dy, rho}.
+extern "C" int tmg_phys_fields_bwd(const void* u, const void* p, const void* gustar, const void* gpstar, void* du, void* dp,
+                                   const int64_t* dims, const float* fl, hipStream_t st) {
+    const int N = (int)dims[0], H = (int)dims[1], W = (int)dims[2], k1 = (int)dims[3], k2 = (int)dims[4], scale = (int)dims[5];
+    if ((k1 != 3 && k1 != 5) || (k2 != 3 && k2 != 5)) return -100;
+    if (!du || (gpstar && !p)) return -3;
+    if (N <= 0 || H <= 0 || W <= 0) return 0;
+    const float dx = fl[0], dy = fl[1], rho = fl[2];
+    const float sd = scale ? dx : 1.f, sp = scale ? dx * dy : 1.f;
+    dim3 grid((W + PT - 1) / PT, (H + PT - 1) / PT, N);
+#define TMG_PFB(K1_, K2_) hipLaunchKernelGGL((phys_fields_bwd_kernel<K1_, K2_>), grid, dim3(256), 0, st, (const float*)u, (const float*)p, \
+                                             (const float*)gustar, (const float*)gpstar, (float*)du, (float*)dp, H, W, dx, dy, rho, sd, sp)
+    if (k1 == 3 && k2 == 3) TMG_PFB(3, 3);
+    else if (k1 == 3) TMG_PFB(3, 5);
+    else if (k2 == 3) TMG_PFB(5, 3);
+    else TMG_PFB(5, 5);
+#undef TMG_PFB
+    TMG_CHECK_LAUNCH();
+    return 0;
+}
+
 // dims = {B, T, 3*H*W}
 extern "C" int tmg_phys_rms(const void* y, const void* trms, void* mean_out, void* coef_out, void* sum_out, const int64_t* dims,
                             hipStream_t st) {

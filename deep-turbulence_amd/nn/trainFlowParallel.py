@@ -8,6 +8,7 @@ import torch.nn as nn
 
 import tmg_hip as H
 import tmg_ops as ops
+from pc.physicsConstrained import PhysConstrainedLES
 
 
 _INV_COUNTS = {}
@@ -106,11 +107,27 @@ class TMGLowLoss(nn.Module):
         # per call was a device->host synchronisation inside every BPTT window
         self._sd = [float(v) for v in self.output_std.flatten().tolist()]
         self._mu = [float(v) for v in self.output_mu.flatten().tolist()]
+        # the residuals on their own (reference :112), for calcVPres / calcVDiv; forward keeps the fused kernels of _PhysLossFn
+        self.phys = PhysConstrainedLES(args.dx, args.dy, grad_kernels=[3, 3])
 
     def forward(self, yPred, logp, target, target_mean, target_rms):
         data = _PhysLossFn.apply(yPred, target, target_rms, self._sd, self._mu, float(self.beta), float(self.dx), float(self.dy))
         n_out_pixels = yPred.size(-3) * yPred.size(-2) * yPred.size(-1)
         return data + logp.mean() / math.log(2.) / n_out_pixels
+
+    def calcVPres(self, yPred):
+        """Mean squared pressure-Poisson residual over the interior of un-normalised [b,3,H,W] predictions (reference :153-164);
+        differentiable."""
+        yPredHat = self.output_std * yPred + self.output_mu
+        pStar = self.phys.calcPressurePoisson(yPredHat[:, :2], yPredHat[:, 2:])
+        return torch.mean(torch.pow(pStar[:, :, 1:-1, 1:-1], 2))
+
+    def calcVDiv(self, yPred):
+        """Mean squared divergence residual over the interior rows of un-normalised [b,3,H,W] predictions (reference :166-177);
+        differentiable."""
+        yPredHat = self.output_std * yPred + self.output_mu
+        uStar = self.phys.calcDivergence(yPredHat[:, :2])
+        return torch.mean(torch.pow(uStar[:, :, 1:-1, 1:-1], 2))
 
 
 class TrainFlow(object):

@@ -449,6 +449,14 @@ int tmg_phys_fwd(const void* y, const void* target, void* sums, void* pstar_out,
  * p [N][1][H][W] (may be NULL when pstar is NULL); ustar [N][1][H][W+2] and / or pstar [N][1][H][W], clamped to [-1, 1].
  * dims = {N, H, W, k1, k2, scale}; fl = {dx, dy, rho}.  k1, k2 outside {3, 5}: -100, nothing launched. */
 int tmg_phys_fields(const void* u, const void* p, void* ustar, void* pstar, const int64_t* dims, const float* fl, tmg_stream_t st);
+/* Adjoint of tmg_phys_fields (the backward of calcDivergence / calcPressurePoisson): du = d/du and dp = d/dp of
+ * sum(gustar * ustar) + sum(gpstar * pstar), through the clamp (gradient where -1 <= pre-clamp value <= 1), the transposed stencils
+ * and the divergence's replicated first / last column.  u [N][2][H][W], p [N][1][H][W] (may be NULL when gpstar is NULL); upstream
+ * gustar [N][1][H][W+2] and gpstar [N][1][H][W], either may be NULL; du [N][2][H][W] and dp [N][1][H][W] (may be NULL) are
+ * overwritten.  No atomics (bitwise reproducible), no allocation, no synchronisation.  dims = {N, H, W, k1, k2, scale};
+ * fl = {dx, dy, rho}.  k1, k2 outside {3, 5}: -100, nothing launched. */
+int tmg_phys_fields_bwd(const void* u, const void* p, const void* gustar, const void* gpstar, void* du, void* dp, const int64_t* dims,
+                        const float* fl, tmg_stream_t st);
 /* Per-pixel RMS over the T steps of y = [B,T,3,H,W] against target_rms [B,3,H,W] (trainFlowParallel.py:143-144);
  * writes mean / coefficient maps for the backward pass; sum_out += sum (rms - target_rms)^2.  dims = {B,T,3*H*W}. */
 int tmg_phys_rms(const void* y, const void* trms, void* mean_out, void* coef_out, void* sum_out, const int64_t* dims,
