@@ -61,23 +61,26 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void gauss_sample_kernel(const float* __restrict__ hz, int hs, const float* __restrict__ eps_in, int es,
                                                            const float* __restrict__ pass, int ps, float* __restrict__ out, int os, int oo,
                                                            int po, float* __restrict__ eps_out, float* __restrict__ logp,
-                                                           const unsigned long long* __restrict__ nonce, unsigned site, int pix_per_img,
-                                                           int Ch, int clip_mean, float mlo, float mhi, float slo, float shi) {
+                                                           const unsigned long long* __restrict__ nonce, unsigned site, int rows_per_key,
+                                                           int pix_per_img, int Ch, int clip_mean, float mlo, float mhi, float slo,
+                                                           float shi) {
     __shared__ float red[4];
     const int b = blockIdx.y;
     const size_t base = (size_t)b * pix_per_img;
     const unsigned total = (unsigned)pix_per_img * (unsigned)Ch;
     const unsigned nquad = (total + 3u) >> 2;
+    const int mem = b / rows_per_key;                  // the key's row of the table; the counter restarts at every key
+    const unsigned long long brow = (unsigned long long)(b - mem * rows_per_key);
     uint2 key = make_uint2(0u, 0u);
     if (!eps_in) {
-        const unsigned long long k0 = nonce[0], k1 = nonce[1];
+        const unsigned long long k0 = nonce[2 * mem], k1 = nonce[2 * mem + 1];
         key = make_uint2((unsigned)k0 ^ (unsigned)(k1 >> 32), (unsigned)(k0 >> 32) ^ (unsigned)k1);
     }
     float lp = 0.f;
     for (unsigned q = blockIdx.x * 256u + threadIdx.x; q < nquad; q += gridDim.x * 256u) {
         float nrm[4];
         if (!eps_in) {
-            const unsigned long long gq = (unsigned long long)b * nquad + q;
+            const unsigned long long gq = brow * nquad + q;
             normal4(philox4x32_10(make_uint4((unsigned)gq, (unsigned)(gq >> 32), site, 0x7467u), key), nrm);
         }
         if constexpr (VEC) {
@@ -127,14 +130,16 @@ __global__ __launch_bounds__(256) void gauss_sample_kernel(const float* __restri
     if (threadIdx.x == 0) atomicAdd(logp + b, tot);
 }
 
-// dims = {B, pixels per image, Ch, clip_mean, site}; d-arrays = {pixel stride, channel offset}; fl = {mean_lo, mean_hi, lsd_lo, lsd_hi}
-extern "C" int tmg_gauss_sample(const void* hz, const int64_t* hz_d, const void* eps_in, const int64_t* ei_d, const void* pass,
-                                const int64_t* p_d, void* out, const int64_t* o_d, int64_t pass_off, void* eps_out, void* logp,
-                                const void* nonce, const int64_t* dims, const float* fl, hipStream_t st) {
+// dims = {B, pixels per image, Ch, clip_mean, site}; d-arrays = {pixel stride, channel offset}; fl = {mean_lo, mean_hi, lsd_lo, lsd_hi}.
+// rows_per_key: image b draws with key row b / rows_per_key of `nonce` and counter (b % rows_per_key) * nquad + q.
+static int gauss_sample_launch(const void* hz, const int64_t* hz_d, const void* eps_in, const int64_t* ei_d, const void* pass,
+                               const int64_t* p_d, void* out, const int64_t* o_d, int64_t pass_off, void* eps_out, void* logp,
+                               const void* nonce, int rows_per_key, const int64_t* dims, const float* fl, hipStream_t st) {
     const int B = (int)dims[0], ppi = (int)dims[1], Ch = (int)dims[2];
     const size_t per = (size_t)ppi * Ch;
     if (per >= (1ull << 31)) return -2;
     if (!eps_in && !nonce) return -3;
+    if (rows_per_key < 1 || B % rows_per_key != 0) return -4;
     int gx = (int)((per / 4 + 255) / 256);      // as tmg_gauss_fwd: few blocks per image (one atomic each), enough to fill the chip
     int cap = (2048 + B - 1) / B;
     if (cap < 4) cap = 4;
@@ -150,12 +155,27 @@ extern "C" int tmg_gauss_sample(const void* hz, const int64_t* hz_d, const void*
     if (pp) vec = vec && (p_d[0] & 3) == 0 && (((uintptr_t)pp) & 15) == 0;
 #define TMG_GS_ARGS dim3(gx, B), dim3(256), 0, st, hzp, (int)hz_d[0], ep, eps_in ? (int)ei_d[0] : 0, pp, pass ? (int)p_d[0] : 0, (float*)out, \
                     (int)o_d[0], (int)o_d[1], (int)pass_off, (float*)eps_out, (float*)logp, (const unsigned long long*)nonce, (unsigned)dims[4], \
-                    ppi, Ch, (int)dims[3], fl[0], fl[1], fl[2], fl[3]
+                    rows_per_key, ppi, Ch, (int)dims[3], fl[0], fl[1], fl[2], fl[3]
     if (vec) hipLaunchKernelGGL(gauss_sample_kernel<true>, TMG_GS_ARGS);
     else hipLaunchKernelGGL(gauss_sample_kernel<false>, TMG_GS_ARGS);
 #undef TMG_GS_ARGS
     TMG_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int tmg_gauss_sample(const void* hz, const int64_t* hz_d, const void* eps_in, const int64_t* ei_d, const void* pass,
+                                const int64_t* p_d, void* out, const int64_t* o_d, int64_t pass_off, void* eps_out, void* logp,
+                                const void* nonce, const int64_t* dims, const float* fl, hipStream_t st) {
+    // one key for the whole call: counter b * nquad + q
+    return gauss_sample_launch(hz, hz_d, eps_in, ei_d, pass, p_d, out, o_d, pass_off, eps_out, logp, nonce, (int)dims[0], dims, fl, st);
+}
+
+// The folded ensemble's draw: keys = [B / rows_per_key][2] int64 on the device, dims = {B, pixels per image, Ch, clip_mean, site,
+// rows_per_key}.  Member m (rows m * rows_per_key ..) draws exactly what a rows_per_key-row tmg_gauss_sample call keyed by row m does.
+extern "C" int tmg_gauss_sample_keyed(const void* hz, const int64_t* hz_d, const void* eps_in, const int64_t* ei_d, const void* pass,
+                                      const int64_t* p_d, void* out, const int64_t* o_d, int64_t pass_off, void* eps_out, void* logp,
+                                      const void* keys, const int64_t* dims, const float* fl, hipStream_t st) {
+    return gauss_sample_launch(hz, hz_d, eps_in, ei_d, pass, p_d, out, o_d, pass_off, eps_out, logp, keys, (int)dims[5], dims, fl, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -100,7 +100,8 @@ class GaussianDiag(object):
         return (logp, H.nchw(eps)) if return_eps else logp
 
     def sample(self, eps=None, rng=None):
-        """mean + exp(log_stddev) eps; eps None: drawn inside the kernel (rng = (nonce, site) of the model call, or a fresh nonce)."""
+        """mean + exp(log_stddev) eps; eps None: drawn inside the kernel (rng = (nonce, site) of the model call, (key table, site,
+        rows per key) of a folded ensemble call, or a fresh nonce)."""
         if eps is None and rng is None:
             rng = (ops.latent_nonce(self._hz().device), 0)
         z, _ = ops.GaussDrawFn.apply(self._hz(), None, None if eps is None else H.nhwc(eps), rng, 0, ops.TOP_LIMITS)
@@ -164,7 +165,8 @@ class Split(nn.Module):
 
     def reverse(self, z1, eps=None, rng=None):
         """cat(z1, z2 = mean + exp(log-std) eps) and its log-prob; the sample is written into the second half of the result by the
-        kernel (no torch.cat), eps None: drawn inside it (rng = (nonce, site) of the model call, default a fresh nonce)."""
+        kernel (no torch.cat), eps None: drawn inside it (rng = (nonce, site) of the model call, or (key table, site, rows per key)
+        of a folded ensemble call; default a fresh nonce)."""
         z1n = H.nhwc(z1)
         hz = self.latent_encoder.raw(z1n)
         if eps is None and rng is None:

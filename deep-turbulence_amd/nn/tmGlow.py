@@ -114,12 +114,15 @@ class LSTMCFlowDecoder(nn.Module):
             s_out.append(s0)
         return z, ops.sum_logdet(lds, z.shape[0], z.device), s_out, eps
 
-    def reverse(self, z, c_in, h_in, eps, nonce=None):
-        """nonce: key of the in-kernel latent draws of this call (TMGlow.sample); None: every split draws its own."""
+    def reverse(self, z, c_in, h_in, eps, nonce=None, rows_per_key=None):
+        """nonce: key of the in-kernel latent draws of this call (TMGlow.sample); None: every split draws its own.  rows_per_key:
+        nonce is a [K, 2] key table and rows m * rows_per_key .. draw with row m (TMGlow.sampleEnsemble)."""
         assert (len(c_in) == len(self.flow_blocks)), 'List of conditions need to be same length as flow blocks.'
         x, lds, s_out = z, [], []
         for i in range(len(self.flow_blocks) - 1, -1, -1):
-            rng = (nonce, i) if (nonce is not None and eps[i] is None) else None
+            rng = None
+            if nonce is not None and eps[i] is None:
+                rng = (nonce, i) if rows_per_key is None else (nonce, i, rows_per_key)
             x, ld, s0 = self.flow_blocks[i].reverse(x, c_in[i], None if h_in is None else h_in[i], eps[i], rng=rng)
             lds.append(ld)
             s_out.insert(0, s0)
@@ -173,6 +176,31 @@ class TMGlow(nn.Module):
         z_samp = cprior.sample(rng=(nonce, L))
         eps = [None for _ in range(L)]
         return self.glow.reverse(z_samp, c_out, h_in, eps, nonce=nonce)
+
+    @_on_input_device
+    def sampleEnsemble(self, x, h_in, members):
+        """`members` samples of the B cases of x in ONE folded call of members * B rows, member-major (row m * B + b: member m, case
+        b; h_in holds the states of those rows).  The encoder and the top prior run once for the B cases and their maps are tiled
+        to the member rows; member m draws its latents with row m of one latent_nonces table, so it is exactly what a B-row
+        sample call keyed by that row computes.  Returns sample's structure for the members * B rows.  Rows are independent only
+        in eval mode (BatchNorm on running statistics): the caller sets the mode, as for sample."""
+        members = int(members)
+        if members < 1:
+            raise ValueError("sampleEnsemble needs at least one member, got %d" % members)
+        if not x.is_cuda:
+            raise RuntimeError("TMGlow.sampleEnsemble runs on the HIP path: the input is on %s (there is no CPU path)" % x.device)
+        B = x.shape[0]
+        cprior, c_out = self._prior(x)
+        L = len(self.glow_blocks)
+
+        def tile(t):                                 # NHWC [B, ...] -> [members * B, ...], member-major
+            return t if members == 1 else t.repeat(members, 1, 1, 1)
+
+        c_rep = [H.nchw(tile(H.nhwc(c))) for c in c_out]
+        keys = ops.latent_nonces(x.device, members)  # one launch: the keys of all members' L + 1 latents
+        z_samp = GaussianDiag(hz=tile(cprior._hz())).sample(rng=(keys, L, B))
+        eps = [None for _ in range(L)]
+        return self.glow.reverse(z_samp, c_rep, h_in, eps, nonce=keys, rows_per_key=B)
 
     @_on_input_device
     def reconstruct(self, x, h_in, eps):

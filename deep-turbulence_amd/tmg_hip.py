@@ -20,7 +20,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmglow_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip"]
+SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip"]
 # Sources compiled WITHOUT the packed-fp32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32): beside MFMAs a packed
 # f32 instruction costs ~13 cycles more than the two scalar ones it replaces (MI355X_MICROARCH.md, cycle constants, 'price of one
 # filler beside MFMAs'), and the compiler SLP-packs adjacent scalar adds / multiplies by itself under -O3.  The matrix-core kernels'
@@ -39,6 +39,7 @@ EXPORTS = [
     "tmg_gauss_bwd", "tmg_checker", "tmg_upsample_fwd", "tmg_upsample_bwd", "tmg_chan_reduce", "tmg_bn_bwd_apply",
     "tmg_phys_fwd", "tmg_phys_rms", "tmg_phys_bwd", "tmg_conv_wgrad_grouped", "tmg_conv_wgrad_grouped_ws_floats", "tmg_conv_pack_batched", "tmg_masked_add", "tmg_c1x2_fwd", "tmg_c1_fwd", "tmg_c1_bwd", "tmg_dense2_bwd", "tmg_dkappa", "tmg_prof_enable", "tmg_prof_collect", "tmg_mix_f16", "tmg_phys_bwd_dev", "tmg_coupling_fwd", "tmg_coupling_bwd",
     "tmg_conv_wino_pack", "tmg_conv_wino_fwd", "tmg_conv_wino_narrow", "tmg_conv_wino_wgrad", "tmg_conv_wino_wgrad_ws_floats", "tmg_mix_f32", "tmg_lu_fold_fwd", "tmg_lu_fold_bwd", "tmg_lu_fold_bwd_split", "tmg_level_finish", "tmg_conv_wgrad_thin_grouped", "tmg_mix_wgrad_grouped", "tmg_layer_planes", "tmg_conv_wino_wgrad_grouped", "tmg_conv_wino_wgrad_grouped_ws_floats", "tmg_adam_step", "tmg_chan_moments", "tmg_bn_finalize64", "tmg_mix_f32_affine_fwd", "tmg_mix_f32_affine_bwd", "tmg_conv_pack_many", "tmg_pad_halves", "tmg_coupling_fwd_halves", "tmg_coupling_bwd_halves", "tmg_fill_i64", "tmg_conv_wino_pack3", "tmg_conv_wino_fwd3", "tmg_mat_inverse", "tmg_gauss_sample", "tmg_reverse_loss_fwd", "tmg_reverse_loss_bwd", "tmg_sum_terms", "tmg_vec_sum", "tmg_level_pack", "tmg_spread2", "tmg_phys_fields", "tmg_phys_fields_bwd",
+    "tmg_gauss_sample_keyed", "tmg_ens_accum", "tmg_ens_time_finalize",
 ]
 
 
@@ -889,6 +890,40 @@ def gauss_sample(hz, eps, z1, out, logp, clip_mean, limits, eps_out=None, nonce=
     od = seg(out)
     _chk(lib().tmg_gauss_sample(_ptr(hz), _d2(hz), _ptr(eps), zd(eps), _ptr(z1), zd(z1), _ptr(out), _i64(od[1], off), c_i64(0), _ptr(eps_out),
                                 _ptr(logp), _ptr(nonce), _i64(B, Hh * Ww, Ch, clip_mean, site), _fl(limits), _stream()), "tmg_gauss_sample")
+
+
+def gauss_sample_keyed(hz, eps, z1, out, logp, clip_mean, limits, keys, rows_per_key, site=0, eps_out=None):
+    """gauss_sample for a batch of members of rows_per_key images each: member m draws with key row m of `keys` ([K, 2] int64 on the
+    device) exactly the latents a rows_per_key-image gauss_sample call keyed by that row draws (tmg_gauss_sample_keyed)."""
+    B, Hh, Ww, Co = out.shape
+    Ch = hz.shape[3] // 2
+    off = Co - Ch
+    zd = lambda t: _d2(t) if t is not None else _i64(0, 0)  # noqa: E731
+    od = seg(out)
+    if eps is None and (keys is None or keys.dtype != torch.int64 or not keys.is_cuda or not keys.is_contiguous()
+                        or keys.numel() != 2 * (B // max(int(rows_per_key), 1))):
+        raise RuntimeError("gauss_sample_keyed needs a contiguous [B / rows_per_key, 2] int64 key table on the device")
+    _chk(lib().tmg_gauss_sample_keyed(_ptr(hz), _d2(hz), _ptr(eps), zd(eps), _ptr(z1), zd(z1), _ptr(out), _i64(od[1], off), c_i64(0),
+                                      _ptr(eps_out), _ptr(logp), _ptr(keys), _i64(B, Hh * Ww, Ch, clip_mean, site, rows_per_key),
+                                      _fl(limits), _stream()), "tmg_gauss_sample_keyed")
+
+
+def ens_accum(y, u, out_mu, out_std, smean, sm2, tmean, tm2, outs, ostrides, k, n_before, m0, t_before, flags):
+    """Fold one roll-out step of k members (y: NHWC [k*B, H, W, C] or a channel-slice view) into the step's running statistics and,
+    flags & 1, the members' time statistics; flags & 2: the step's last chunk, write (mean, std, mag_mean, mag_std) = `outs` with the
+    per-case strides ostrides = (channel outputs, magnitude outputs) instead of the step state (tmg_ens_accum)."""
+    kB, Hh, Ww, Cc = y.shape
+    ptr, ps, co, _ = seg(y)
+    outs = outs if outs is not None else (None,) * 4
+    _chk(lib().tmg_ens_accum(c_vp(ptr), _i64(ps, co), _ptr(u), _ptr(out_mu), _ptr(out_std), _ptr(smean), _ptr(sm2), _ptr(tmean),
+                             _ptr(tm2), *[_ptr(t) for t in outs], _i64(*ostrides), _i64(k, kB // k, Hh * Ww, Cc, n_before, m0, t_before, flags),
+                             _stream()), "tmg_ens_accum")
+
+
+def ens_time_finalize(tmean, tm2, tm_mean, tm_std, rms_mean, rms_std, S, B, HW, C, T):
+    """Per member time mean and RMS fluctuation over T steps, then their mean / std over the S members (tmg_ens_time_finalize)."""
+    _chk(lib().tmg_ens_time_finalize(_ptr(tmean), _ptr(tm2), _ptr(tm_mean), _ptr(tm_std), _ptr(rms_mean), _ptr(rms_std),
+                                     _i64(S, B, HW, C, T), _stream()), "tmg_ens_time_finalize")
 
 
 def reverse_loss_fwd(y, ld, loss, s1, s2):

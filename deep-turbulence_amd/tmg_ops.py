@@ -703,11 +703,18 @@ def latent_nonce(device):
     return torch.empty(2, dtype=torch.int64, device=device).random_()
 
 
+def latent_nonces(device, k):
+    """A [k, 2] int64 key table on `device` from ONE random_() launch: row m keys the in-kernel latent draws of member m of a folded
+    ensemble call (TMGlow.sampleEnsemble, tmg_gauss_sample_keyed), as latent_nonce keys a single sample call."""
+    return torch.empty((int(k), 2), dtype=torch.int64, device=device).random_()
+
+
 class GaussDrawFn(torch.autograd.Function):
     """Split.reverse / GaussianDiag.sample on the HIP path as ONE launch: z2 = mean + exp(log-std) eps, written into the second half
     of the [B,h,w,2 Ch] tensor whose first half is z1 (the reference's torch.cat((z1, z2), 1), flowUtils.py:334; z1 None: the
     deepest prior, output [B,h,w,Ch]), with the log-prob per sample (:331-333).  eps given (reconstruct) or drawn in the kernel from
-    (nonce, site) (sample, :206 / :328).  Gradients: d(hz) by tmg_gauss_bwd (mode 1), d(z1) = the first half of the output's
+    (nonce, site) (sample, :206 / :328), or from a [K, 2] key table (table, site, rows_per_key): row b draws with key row
+    b // rows_per_key (TMGlow.sampleEnsemble).  Gradients: d(hz) by tmg_gauss_bwd (mode 1), d(z1) = the first half of the output's
     gradient (a channel-slice view: no copy), none for eps."""
 
     @staticmethod
@@ -724,9 +731,13 @@ class GaussDrawFn(torch.autograd.Function):
             eps = eps if eps.stride(3) == 1 else eps.contiguous()
             H.gauss_sample(hz, eps, z1, out, logp, clip_mean, limits)
         else:
-            nonce, site = rng
             eps = torch.empty((B, Hh, Ww, Ch), device=dev, dtype=torch.float32)
-            H.gauss_sample(hz, None, z1, out, logp, clip_mean, limits, eps_out=eps, nonce=nonce, site=site)
+            if len(rng) == 3:
+                table, site, rows_per_key = rng
+                H.gauss_sample_keyed(hz, None, z1, out, logp, clip_mean, limits, table, rows_per_key, site=site, eps_out=eps)
+            else:
+                nonce, site = rng
+                H.gauss_sample(hz, None, z1, out, logp, clip_mean, limits, eps_out=eps, nonce=nonce, site=site)
         ctx.cfg = (clip_mean, limits, Ch, z1 is not None)
         ctx.save_for_backward(hz, eps)
         ctx.set_materialize_grads(False)
@@ -1528,3 +1539,77 @@ class LeadingChannelsFn(torch.autograd.Function):
             dx = torch.zeros(d1.shape[:3] + (ctx.C,), device=d1.device, dtype=d1.dtype)
         dx[..., :ctx.n] += d1
         return dx, None
+
+
+class EnsembleStats:
+    """On-device statistics over the members of sampled roll-outs of B cases (tmg_ens_accum / tmg_ens_time_finalize): for every kept
+    step the mean and population standard deviation (ddof 0, as np.std) over the members of each un-normalised channel
+    yh = u[b, c] (out_std[c] y + out_mu[c]) and of the velocity magnitude sqrt(yh0^2 + yh1^2); per member the time mean and RMS
+    fluctuation of each channel over the steps folded with time=True, and their mean / std over the members.
+
+    Feed every step's members in chunks of whole members, in member order (m0 = 0 first), each step's chunks before the next step's.
+    Outputs (device tensors): mean, std [B, Tk, C, H, W]; mag_mean, mag_std [B, Tk, H, W]; finalize() adds time_mean_mean,
+    time_mean_std, time_rms_mean, time_rms_std [B, C, H, W]."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None):
+        if not (2 <= C <= 4):
+            raise ValueError("ensemble statistics need 2 <= C <= 4 channels (the magnitude is formed from channels 0 and 1), got %d" % C)
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("ensemble statistics run on the HIP path: device %s is not a GPU (there is no CPU path)" % dev)
+        self.S, self.B, self.C, self.H, self.W, self.Tk = int(members), int(B), int(C), int(Hh), int(Ww), int(steps)
+        HW = self.H * self.W
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.mu = torch.as_tensor(out_mu, **f32).reshape(-1)[:C].contiguous()
+        self.sd = torch.as_tensor(out_std, **f32).reshape(-1)[:C].contiguous()
+        if self.mu.numel() != C or self.sd.numel() != C:
+            raise ValueError("out_mu / out_std need %d entries, got %d / %d" % (C, self.mu.numel(), self.sd.numel()))
+        self.u = None if u is None else torch.as_tensor(u, **f32).reshape(B, C).contiguous()
+        self.step_state = torch.empty((2, B, C + 1, HW), **f32)
+        self.time_state = torch.empty((2, self.S, B, C, HW), **f32)
+        self.out = {"mean": torch.empty((B, self.Tk, C, Hh, Ww), **f32), "std": torch.empty((B, self.Tk, C, Hh, Ww), **f32),
+                    "mag_mean": torch.empty((B, self.Tk, Hh, Ww), **f32), "mag_std": torch.empty((B, self.Tk, Hh, Ww), **f32)}
+        self._n = 0           # members folded into the current step
+        self._step = 0        # the step being filled
+        self._t = [0] * self.S  # steps folded into each member's time statistics
+
+    def add(self, y, m0, time=True):
+        """Fold the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
+        channel-slice; rows member-major)."""
+        yn = y.permute(0, 2, 3, 1)
+        kB = yn.shape[0]
+        if kB % self.B or tuple(yn.shape[1:]) != (self.H, self.W, self.C):
+            raise ValueError("chunk shape %s does not hold whole members of [%d, %d, %d, %d]" % (tuple(y.shape), self.B, self.C, self.H, self.W))
+        k = kB // self.B
+        if m0 != self._n or m0 + k > self.S or self._step >= self.Tk:
+            raise ValueError("members must be fed in order, every step's chunks before the next step's")
+        t_before = self._t[m0]
+        if time and any(self._t[m] != t_before for m in range(m0, m0 + k)):
+            raise ValueError("members of one chunk hold different numbers of time steps")
+        last = m0 + k == self.S
+        HW = self.H * self.W
+        o = self.out
+        t = self._step
+        outs = (o["mean"][:, t], o["std"][:, t], o["mag_mean"][:, t], o["mag_std"][:, t]) if last else None
+        H.ens_accum(yn, self.u, self.mu, self.sd, self.step_state[0], self.step_state[1], self.time_state[0], self.time_state[1], outs,
+                    (self.Tk * self.C * HW, self.Tk * HW), k, self._n, m0, t_before, (1 if time else 0) | (2 if last else 0))
+        if time:
+            for m in range(m0, m0 + k):
+                self._t[m] += 1
+        self._n = 0 if last else self._n + k
+        self._step += 1 if last else 0
+
+    def finalize(self):
+        """-> dict of the outputs; the time statistics cover the steps folded with time=True."""
+        if self._step != self.Tk:
+            raise RuntimeError("%d of %d steps folded" % (self._step, self.Tk))
+        T = self._t[0]
+        if T < 1 or any(t != T for t in self._t):
+            raise RuntimeError("no time statistics: no step was folded with time=True")
+        shp = (self.B, self.C, self.H, self.W)
+        names = ("time_mean_mean", "time_mean_std", "time_rms_mean", "time_rms_std")
+        for n in names:
+            self.out[n] = torch.empty(shp, device=self.step_state.device, dtype=torch.float32)
+        H.ens_time_finalize(self.time_state[0], self.time_state[1], *[self.out[n] for n in names], self.S, self.B, self.H * self.W,
+                            self.C, T)
+        return self.out

@@ -91,3 +91,73 @@ def modelPred(args, model, testing_loader, log, samples=1, stride=1, tmax=1):
             log.log('Number of elements unset: {}'.format(int((mb > 10000).sum())))
             preds.append(mb.cpu())
     return torch.cat(preds, dim=1), torch.cat(targets, dim=0), torch.cat(inputs, dim=0)
+
+
+def modelPredStats(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64):
+    """Ensemble statistics of `samples` roll-outs per test case, computed on the device without forming modelPred's
+    [samples, N, T, C, H, W] tensor.  The roll-outs are modelPred's: fresh seeds from random_(0, 1e8) drawn member by member in
+    modelPred's order (cache=False), states re-anchored half-way to their seed states every 20 steps, fields un-normalised and scaled
+    by the case's inlet velocity u0 (velocities x u0, pressure x u0^2), every `stride`-th of `tmax` steps kept.  The members are
+    folded into TMGlow.sampleEnsemble calls of at most `max_rows` rows, each chunk holding whole members (one member per call when
+    a batch alone exceeds max_rows).
+
+    Returns a dict of CPU tensors:
+      mean, std [N, Tk, C, H, W]        mean and population std (ddof 0) over the members, per kept step (Tk = tmax // stride)
+      mag_mean, mag_std [N, Tk, H, W]   the same of the velocity magnitude sqrt(ux^2 + uy^2)
+      time_mean_mean, time_mean_std     mean / std over the members of each member's time mean over the kept steps t_start..Tk-1
+      time_rms_mean, time_rms_std       ... of each member's RMS fluctuation sqrt(mean_t (y - mean_t y)^2) over those steps
+                                        (all four [N, C, H, W]; t_start indexes the kept steps)
+      target [N, T, C, H, W], input [N, T, 3, h, w]   as modelPred returns them."""
+    import tmg_ops as ops
+    core = getattr(model, "module", model)
+    core.eval()
+    dev = torch.device(args.device) if getattr(args, "device", None) is not None else next(core.parameters()).device
+    if dev.type != "cuda" or next(core.parameters()).device.type != "cuda":
+        raise RuntimeError("modelPredStats runs on the HIP path: the model must live on a GPU (there is no CPU path)")
+    samples, max_rows = int(samples), int(max_rows)
+    nkeep = tmax // stride
+    if samples < 1 or nkeep < 1:
+        raise ValueError("modelPredStats needs samples >= 1 and tmax >= stride (samples=%d, tmax=%d, stride=%d)" % (samples, tmax, stride))
+    if not 0 <= t_start < nkeep:
+        raise ValueError("t_start=%d outside the %d kept steps" % (t_start, nkeep))
+    shp = (1, -1, 1, 1)
+    in_std, in_mu = core.in_std.to(dev).view(shp), core.in_mu.to(dev).view(shp)
+    out_std, out_mu = core.out_std.to(dev), core.out_mu.to(dev)
+    outs, targets, inputs = {}, [], []
+    with torch.no_grad():
+        for mbIdx, (input0, target0, u0) in enumerate(testing_loader):
+            log.log('Running mini-batch {:d}/{:d}'.format(mbIdx + 1, len(testing_loader)))
+            u = u0.to(dev).view(-1, 1, 1, 1, 1)
+            u = torch.cat((u, u, u ** 2), dim=2)                      # [N,1,3,1,1]: (ux, uy, p) scales
+            inp = input0.to(dev)
+            tgt = u * (out_std.view(shp) * target0.to(dev) + out_mu.view(shp))
+            inputs.append((u * (in_std * inp[:, :, :3] + in_mu)).cpu())
+            targets.append(tgt.cpu())
+            B, C, Hh, Ww = inp.size(0), tgt.size(2), tgt.size(-2), tgt.size(-1)
+            if C != 3:
+                raise ValueError("modelPredStats scales (ux, uy, p) by (u0, u0, u0^2) as modelPred does: 3 target channels, got %d" % C)
+            keys = []
+            for i in range(samples):                                   # modelPred's seed draws, member by member
+                seeds = torch.LongTensor(B).random_(0, int(1e8))
+                keys.append(core.initLSTMStates(seeds, [Hh, Ww], cache=False))
+            per = max(1, max_rows // B)
+            chunks = [(m0, min(per, samples - m0)) for m0 in range(0, samples, per)]
+            # per chunk: the members' seed states stacked member-major, and the running states
+            anchors = [[tuple(torch.cat([keys[m0 + j][lv][s] for j in range(k)]) for s in (0, 1)) for lv in range(len(keys[0]))]
+                       for m0, k in chunks]
+            states = [[(h.clone(), c.clone()) for h, c in a] for a in anchors]
+            st = ops.EnsembleStats(samples, B, C, Hh, Ww, nkeep, dev, out_mu, out_std, u=u.view(B, 3)[:, :C])
+            for tstep in range(tmax):
+                keep = tstep % stride == 0 and tstep // stride < nkeep
+                for ci, (m0, k) in enumerate(chunks):
+                    y0, _logp, states[ci] = core.sampleEnsemble(inp[:, tstep], states[ci], k)
+                    if keep:
+                        st.add(y0, m0, time=tstep // stride >= t_start)
+                    if tstep % 20 == 0:
+                        states[ci] = [(0.5 * h + 0.5 * hk, 0.5 * c + 0.5 * ck) for (h, c), (hk, ck) in zip(states[ci], anchors[ci])]
+            for name, t in st.finalize().items():
+                outs.setdefault(name, []).append(t.cpu())
+    res = {name: torch.cat(v, dim=0) for name, v in outs.items()}
+    res["target"] = torch.cat(targets, dim=0)
+    res["input"] = torch.cat(inputs, dim=0)
+    return res

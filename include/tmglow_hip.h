@@ -410,6 +410,30 @@ int tmg_mix_f32_affine_bwd(const void* dy, const int64_t* dy_d, const void* W, c
 int tmg_gauss_sample(const void* hz, const int64_t* hz_d, const void* eps_in, const int64_t* ei_d, const void* pass,
                      const int64_t* p_d, void* out, const int64_t* o_d, int64_t pass_off, void* eps_out, void* logp, const void* nonce,
                      const int64_t* dims, const float* fl, tmg_stream_t st);
+/* tmg_gauss_sample for a batch of members that each hold rows_per_key images: image b draws with the key in row b / rows_per_key of
+ * keys ([B / rows_per_key][2] int64 on the device) and the counter (b % rows_per_key) * nquad + q, so member m's latents are bitwise
+ * those of a rows_per_key-image tmg_gauss_sample call keyed by row m.  dims = {B, pixels per image, Ch, clip_mean, site,
+ * rows_per_key}; B not a multiple of rows_per_key: -4. */
+int tmg_gauss_sample_keyed(const void* hz, const int64_t* hz_d, const void* eps_in, const int64_t* ei_d, const void* pass,
+                           const int64_t* p_d, void* out, const int64_t* o_d, int64_t pass_off, void* eps_out, void* logp,
+                           const void* keys, const int64_t* dims, const float* fl, tmg_stream_t st);
+
+/* Ensemble statistics of sampled roll-outs (tmg_ensemble.hip; no atomics: bitwise reproducible).
+ * tmg_ens_accum folds one roll-out step of a chunk of k members into the step's running statistics and into each member's running
+ * time statistics.  y: [k*B][HW] pixels of C <= 4 fp32 channels, pixel stride y_d[0], channel offset y_d[1], row j*B + b = member
+ * m0 + j, case b.  Every value is un-normalised as yh = u[b][c] * (out_std[c] * y + out_mu[c]) (u: [B][C] or NULL for 1), and
+ * |u| = sqrt(yh0^2 + yh1^2) is formed.  Step state: smean, sm2 [B][C+1][HW] (channel C: |u|), holding n_before members; with
+ * n_before = 0 it is not read.  flags & 1: Welford of yh into the members' time statistics tmean, tm2 [S][B][C][HW] that hold
+ * t_before steps.  flags & 2: the chunk is the step's last: mean and population std are written to mean_out / std_out
+ * (case b, channel c at + b * o_d[0] + c * HW) and mag_mean / mag_std (+ b * o_d[1]) instead of the step state.
+ * dims = {k, B, HW, C, n_before, m0, t_before, flags}. */
+int tmg_ens_accum(const void* y, const int64_t* y_d, const void* u, const void* out_mu, const void* out_std, void* smean, void* sm2,
+                  void* tmean, void* tm2, void* mean_out, void* std_out, void* mag_mean, void* mag_std, const int64_t* o_d,
+                  const int64_t* dims, tmg_stream_t st);
+/* Per member its time mean and RMS fluctuation sqrt(tm2 / T) over the T folded steps, then the mean and population std of both
+ * over the S members: tm_mean, tm_std, rms_mean, rms_std [B][C][HW].  dims = {S, B, HW, C, T}. */
+int tmg_ens_time_finalize(const void* tmean, const void* tm2, void* tm_mean, void* tm_std, void* rms_mean, void* rms_std,
+                          const int64_t* dims, tmg_stream_t st);
 
 /* The benchmark loss of SURVEY 8-D, generative direction: *loss += fl[0] sum(y^2) + fl[1] sum(logdet) (the caller zeroes *loss;
  * fl = {1 / numel(y), 1 / (B noc H W)}), and its gradient dy = 2 fl[0] *g y, dld[b] = fl[1] *g with the upstream gradient read from
