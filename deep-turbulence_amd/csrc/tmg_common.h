@@ -62,6 +62,17 @@ __device__ __forceinline__ float out_scale_of(const float* kappa) {
     return expf(k);
 }
 
+// Select the segment (of <= 3) holding concatenated channel C_ BY VALUE into three new locals (taking a pointer into the
+// kernel-argument struct would push the whole struct into scratch memory); C_ becomes the channel within that segment.
+// (A macro on purpose: as a __forceinline__ function returning the segment the same chain moved instructions in 13 - 35 kernels.)
+#define TMG_PICK_SEG(PTYPE_, ARR, C_, PTR_, STRIDE_, OFF_)                                                \
+    PTYPE_ PTR_ = ARR[0].p;                                                                               \
+    int STRIDE_ = ARR[0].stride, OFF_ = ARR[0].off;                                                       \
+    if (C_ >= ARR[0].n) {                                                                                 \
+        C_ -= ARR[0].n; PTR_ = ARR[1].p; STRIDE_ = ARR[1].stride; OFF_ = ARR[1].off;                      \
+        if (C_ >= ARR[1].n) { C_ -= ARR[1].n; PTR_ = ARR[2].p; STRIDE_ = ARR[2].stride; OFF_ = ARR[2].off; } \
+    }
+#define TMG_PICK_OSEG(ARR, NL_, PTR_, STRIDE_, OFF_) TMG_PICK_SEG(float*, ARR, NL_, PTR_, STRIDE_, OFF_)
 
 // 4 consecutive (concatenated) input channels c..c+3 of pixel (b,iy,ix), after padding rule,
 // optional affine and optional ReLU.
@@ -76,20 +87,9 @@ __device__ __forceinline__ float4 load_in4(const P& p, int b, int iy, int ix, in
     }
     if (c >= p.Cin) return v;
     const size_t pix = ((size_t)b * p.Hin + iy) * p.Win + ix;
-    // segment lookup by value (no pointer into the kernel-argument struct: keeps it out of scratch)
-    const int n0 = p.in[0].n, n1 = p.in[1].n;
     if (p.vec4) {
         int cl = c;
-        const float* sp = p.in[0].p;
-        int ss = p.in[0].stride, so = p.in[0].off;
-        if (cl >= n0) {
-            cl -= n0;
-            sp = p.in[1].p; ss = p.in[1].stride; so = p.in[1].off;
-            if (cl >= n1) {
-                cl -= n1;
-                sp = p.in[2].p; ss = p.in[2].stride; so = p.in[2].off;
-            }
-        }
+        TMG_PICK_SEG(const float*, p.in, cl, sp, ss, so)
         v = *reinterpret_cast<const float4*>(sp + pix * ss + so + cl);
     } else {
         float t[4];
@@ -98,16 +98,7 @@ __device__ __forceinline__ float4 load_in4(const P& p, int b, int iy, int ix, in
             int cl = c + e;
             float x = 0.f;
             if (cl < p.Cin) {
-                const float* sp = p.in[0].p;
-                int ss = p.in[0].stride, so = p.in[0].off;
-                if (cl >= n0) {
-                    cl -= n0;
-                    sp = p.in[1].p; ss = p.in[1].stride; so = p.in[1].off;
-                    if (cl >= n1) {
-                        cl -= n1;
-                        sp = p.in[2].p; ss = p.in[2].stride; so = p.in[2].off;
-                    }
-                }
+                TMG_PICK_SEG(const float*, p.in, cl, sp, ss, so)
                 x = sp[pix * ss + so + cl];
             }
             t[e] = x;
@@ -223,16 +214,7 @@ __device__ __forceinline__ const float* in4_addr(const P& p, int b, int iy, int 
     oob = !p.pad_rep && (iy != iyc || ix != ixc);
     const size_t pix = ((size_t)b * p.Hin + iyc) * p.Win + ixc;
     int cl = c;
-    const float* sp = p.in[0].p;
-    int ss = p.in[0].stride, so = p.in[0].off;
-    if (cl >= p.in[0].n) {
-        cl -= p.in[0].n;
-        sp = p.in[1].p; ss = p.in[1].stride; so = p.in[1].off;
-        if (cl >= p.in[1].n) {
-            cl -= p.in[1].n;
-            sp = p.in[2].p; ss = p.in[2].stride; so = p.in[2].off;
-        }
-    }
+    TMG_PICK_SEG(const float*, p.in, cl, sp, ss, so)
     const float* a = sp + pix * ss + so + cl;
     return (oob || c >= p.Cin) ? tmg_zero_page : a;
 }
@@ -343,16 +325,6 @@ __device__ __forceinline__ void stage_commit(const P& p, StageRegs<U>& R, float*
     }
 }
 
-// Select the output segment holding concatenated channel `nl` BY VALUE (taking a pointer into the
-// kernel-argument struct would push the whole struct into scratch memory).
-#define TMG_PICK_OSEG(ARR, NL_, PTR_, STRIDE_, OFF_)                                                      \
-    float* PTR_ = ARR[0].p;                                                                               \
-    int STRIDE_ = ARR[0].stride, OFF_ = ARR[0].off;                                                       \
-    if (NL_ >= ARR[0].n) {                                                                                \
-        NL_ -= ARR[0].n; PTR_ = ARR[1].p; STRIDE_ = ARR[1].stride; OFF_ = ARR[1].off;                     \
-        if (NL_ >= ARR[1].n) { NL_ -= ARR[1].n; PTR_ = ARR[2].p; STRIDE_ = ARR[2].stride; OFF_ = ARR[2].off; } \
-    }
-
 // One-time opt-in of a kernel to > 64 KB of dynamic LDS, per DEVICE: the attribute belongs to the (function, device) pair, so a
 // per-process flag would leave the second GPU of a multi-device process (the reference's thread-per-GPU replicas,
 // utils/parallel.py:222-231) without it.  hipGetDevice is a thread-local read.
@@ -393,6 +365,42 @@ static inline int tmg_num_cus() {
     }();
     return n;
 }
+
+// clamp(CUs / gy, 1, ntiles): the grid of a persistent tile kernel whose block rows (gy) share the CUs
+static inline int tmg_persistent_grid(int gy, int ntiles) {
+    const int g = tmg_num_cus() / gy;
+    return g > ntiles ? ntiles : (g < 1 ? 1 : g);
+}
+
+// ---- C-ABI marshalling (host) -------------------------------------------------------------------------------------------------
+// A segment list arrives as a pointer table plus {stride, off, n} per segment.  The decoders fill ALL `slots` entries of the
+// kernel-argument array (unused ones null; a count beyond `slots` is never written through - the launcher that has a code for a
+// bad count tests the count itself) and return the channel sum and whether every segment is float4-addressable: stride, offset
+// and count multiples of 4, pointer 16-byte aligned.
+struct TmgSegList { int csum; bool vec4; };
+template <typename SEG, typename PTRS>
+static inline TmgSegList tmg_decode_segs(SEG* dst, int slots, PTRS ptrs, const int64_t* desc, int64_t n) {
+    TmgSegList r{0, true};
+    for (int i = 0; i < slots; ++i) {
+        if (i >= n) { dst[i] = SEG{nullptr, 0, 0, 0}; continue; }
+        dst[i] = SEG{(decltype(dst[i].p))ptrs[i], (int)desc[3 * i], (int)desc[3 * i + 1], (int)desc[3 * i + 2]};
+        if (((dst[i].stride | dst[i].off | dst[i].n) & 3) || (((uintptr_t)ptrs[i]) & 15)) r.vec4 = false;
+        r.csum += dst[i].n;
+    }
+    return r;
+}
+static inline TmgSegList tmg_decode_in(TmgSeg* dst, const void* const* ptrs, const int64_t* desc, int64_t n, int slots = TMG_MAX_IN_SEG) {
+    return tmg_decode_segs(dst, slots, ptrs, desc, n);
+}
+static inline TmgSegList tmg_decode_out(TmgOSeg* dst, void* const* ptrs, const int64_t* desc, int64_t n, int slots = TMG_MAX_OUT_SEG) {
+    return tmg_decode_segs(dst, slots, ptrs, desc, n);
+}
+static inline bool tmg_bad_seg_count(int64_t nin, int64_t nout) {
+    return nin < 1 || nin > TMG_MAX_IN_SEG || nout < 1 || nout > TMG_MAX_OUT_SEG;
+}
+// The optional {stride, off} operand: zeros when its tensor is absent (the descriptor is then not read).
+struct TmgD2 { int stride, off; };
+static inline TmgD2 tmg_opt_d2(const void* p, const int64_t* d) { return p ? TmgD2{(int)d[0], (int)d[1]} : TmgD2{0, 0}; }
 
 #define TMG_CHECK_LAUNCH()                          \
     do {                                            \

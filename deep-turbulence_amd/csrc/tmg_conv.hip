@@ -1598,9 +1598,7 @@ static int conv_fwd_lean(ConvP p, hipStream_t st) {
         p.ntiles = p.B * p.tiles_x * p.tiles_y;
         p.KCH = kch;
         p.nchunks = (p.Cin_pad + kch - 1) / kch;
-        int G = tmg_num_cus() / gy;
-        if (G < 1) G = 1;
-        if (G > p.ntiles) G = p.ntiles;
+        const int G = tmg_persistent_grid(gy, p.ntiles);
         const size_t lds_bytes = 2 * (size_t)PHPW * (kch + 8) * 4;
 #define TMG_FWD_CASE(NTW_, WM_, WN_)                                                                   \
         if (NTW == NTW_ && WM == WM_ && WN == WN_) {                                                   \
@@ -1615,18 +1613,6 @@ static int conv_fwd_lean(ConvP p, hipStream_t st) {
         return -100;
     }
     return -100;
-}
-
-static void fill_segs(TmgSeg* dst, const void* const* ptrs, const int64_t* desc, int n, int* vec4) {
-    for (int i = 0; i < TMG_MAX_IN_SEG; ++i) dst[i] = TmgSeg{nullptr, 0, 0, 0};
-    for (int i = 0; i < n; ++i) {
-        dst[i].p = (const float*)ptrs[i];
-        dst[i].stride = (int)desc[3 * i + 0];
-        dst[i].off = (int)desc[3 * i + 1];
-        dst[i].n = (int)desc[3 * i + 2];
-        if ((dst[i].stride | dst[i].off | dst[i].n) & 3) *vec4 = 0;
-        if (((uintptr_t)ptrs[i]) & 15) *vec4 = 0;
-    }
 }
 
 extern "C" int tmg_conv_pack_map(const void* w, void* wpk, int64_t Cout, int64_t Cin, int64_t cin_eff, int64_t ksize, int64_t mode,
@@ -1715,29 +1701,22 @@ extern "C" int tmg_conv_fwd_add(const void* const* in_ptrs, const int64_t* in_de
                                 const int64_t* add_desc, void* const* out_ptrs, const int64_t* out_desc, int64_t nout,
                                 const int64_t* dims, hipStream_t st) {
     ConvP p;
-    p.add = TmgSeg{(const float*)add, add ? (int)add_desc[0] : 0, add ? (int)add_desc[1] : 0, 0};
+    const TmgD2 ad = tmg_opt_d2(add, add_desc);
+    p.add = TmgSeg{(const float*)add, ad.stride, ad.off, 0};
     p.nseg = (int)nseg;
-    p.vec4 = 1;
-    fill_segs(p.in, in_ptrs, in_desc, (int)nseg, &p.vec4);
+    const TmgSegList si = tmg_decode_in(p.in, in_ptrs, in_desc, nseg);
+    p.vec4 = si.vec4;
     p.B = (int)dims[0]; p.Hin = (int)dims[1]; p.Win = (int)dims[2]; p.Hout = (int)dims[3]; p.Wout = (int)dims[4];
     p.ksize = (int)dims[5]; p.stride = (int)dims[6]; p.Cin = (int)dims[7]; p.Cout = (int)dims[8];
     p.relu_in = (int)dims[9]; p.pad_rep = (int)dims[10]; p.relu_out = (int)dims[11]; p.accumulate = (int)dims[12];
     if (p.ksize != 1 && p.ksize != 3) return -2;
-    int csum = 0;
-    for (int i = 0; i < p.nseg; ++i) csum += p.in[i].n;
-    if (csum != p.Cin || p.nseg < 1 || p.nseg > TMG_MAX_IN_SEG || nout < 1 || nout > TMG_MAX_OUT_SEG) return -3;
+    if (si.csum != p.Cin || tmg_bad_seg_count(nseg, nout)) return -3;
     p.Cin_pad = (p.Cin + 15) & ~15;
     p.Cout_pad = (p.Cout + 15) & ~15;
     p.wpk = (const float*)wpk; p.bias = (const float*)bias; p.kappa = (const float*)kappa;
     p.in_scale = (const float*)in_scale; p.in_shift = (const float*)in_shift;
     p.nout = (int)nout;
-    int osum = 0;
-    for (int i = 0; i < TMG_MAX_OUT_SEG; ++i) p.out[i] = TmgOSeg{nullptr, 0, 0, 0};
-    for (int i = 0; i < p.nout; ++i) {
-        p.out[i] = TmgOSeg{(float*)out_ptrs[i], (int)out_desc[3 * i], (int)out_desc[3 * i + 1], (int)out_desc[3 * i + 2]};
-        osum += p.out[i].n;
-    }
-    if (osum != p.Cout) return -4;
+    if (tmg_decode_out(p.out, out_ptrs, out_desc, nout).csum != p.Cout) return -4;   // (the kernels store scalars where a segment is not float4-addressable)
 
     {
         const int rc = conv_fwd_lean(p, st);
@@ -1948,8 +1927,7 @@ static int wgrad_impl(const void* const* in_ptrs, const int64_t* in_desc, int64_
                       const long long* gtab, int ngroups, int dy_goff, long long dw_gstride, int db_gstride) {
     WgradP p;
     p.nseg = (int)nseg;
-    p.vec4 = 1;
-    fill_segs(p.in, in_ptrs, in_desc, (int)nseg, &p.vec4);
+    p.vec4 = tmg_decode_in(p.in, in_ptrs, in_desc, nseg).vec4;   // (neither the segment count nor the channel sum is tested here)
     p.B = (int)dims[0]; p.Hin = (int)dims[1]; p.Win = (int)dims[2]; p.Hout = (int)dims[3]; p.Wout = (int)dims[4];
     p.ksize = (int)dims[5]; p.stride = (int)dims[6]; p.Cin = (int)dims[7]; p.Cout = (int)dims[8];
     p.relu_in = (int)dims[9]; p.pad_rep = (int)dims[10];
@@ -2056,17 +2034,13 @@ extern "C" int tmg_conv_rep_border_fix(const void* dy, const int64_t* dy_desc, c
     p.Npad = (p.Cx + 15) & ~15;
     p.KB = (p.Cdy + 15) >> 4;
     p.dy_vec = ((p.Cdy & 15) == 0) && (((p.dy_stride | p.dy_off) & 3) == 0) && ((((uintptr_t)dy) & 15) == 0);
-    for (int i = 0; i < TMG_MAX_OUT_SEG; ++i) p.out[i] = TmgOSeg{nullptr, 0, 0, 0};
-    for (int i = 0; i < (int)nout; ++i)
-        p.out[i] = TmgOSeg{(float*)out_ptrs[i], (int)out_desc[3 * i], (int)out_desc[3 * i + 1], (int)out_desc[3 * i + 2]};
+    const TmgSegList so = tmg_decode_out(p.out, out_ptrs, out_desc, nout);
     if (p.H == 1 && p.W == 1) p.nborder = 1;
     else if (p.H == 1) p.nborder = p.W;
     else p.nborder = 2 * p.W + (p.W > 1 ? 2 : 1) * (p.H - 2);
     // matrix-core path: images with an interior (H, W >= 2), float4-addressable dy and dx segments, <= 8 channel tiles
     bool mf = p.H >= 2 && p.W >= 2 && (p.Cdy & 3) == 0 && (((p.dy_stride | p.dy_off) & 3) == 0) && ((((uintptr_t)dy) & 15) == 0) &&
-              (p.Cx & 3) == 0 && p.Npad <= 128;
-    for (int i = 0; i < (int)nout; ++i)
-        if (((p.out[i].stride | p.out[i].off | p.out[i].n) & 3) || (((uintptr_t)p.out[i].p) & 15)) mf = false;
+              (p.Cx & 3) == 0 && p.Npad <= 128 && so.vec4;
     if (mf) {
         BorderMP m;
         m.b = p;

@@ -1715,8 +1715,9 @@ extern "C" int tmg_chan_reduce(const void* x, const int64_t* x_d, const void* g,
     blocks = (blocks + 31) / 32;  // >= 32 pixels per lane
     if (blocks > 1024) blocks = 1024;
     if (blocks < 1) blocks = 1;
+    const TmgD2 gd = tmg_opt_d2(g, g_d);
     hipLaunchKernelGGL(chan_reduce_kernel, dim3((int)blocks), dim3(256), 0, st, (const float*)x, (int)x_d[0], (int)x_d[1],
-                       (const float*)g, g ? (int)g_d[0] : 0, g ? (int)g_d[1] : 0, (const float*)v0, (const float*)v1, (const float*)v2,
+                       (const float*)g, gd.stride, gd.off, (const float*)v0, (const float*)v1, (const float*)v2,
                        (const float*)v3, (float*)s0, (float*)s1, npix, C, (int)dims[2], dims[3] > 0 ? 1.0f / (float)dims[3] : 1.0f);
     TMG_CHECK_LAUNCH();
     return 0;
@@ -1778,6 +1779,7 @@ extern "C" int tmg_masked_add(const void* src, const int64_t* s_d, const void* r
     const size_t npix = (size_t)dims[0];
     const int n = (int)dims[1];
     if (npix == 0 || n == 0) return 0;
+    const TmgD2 sd = tmg_opt_d2(src, s_d), rd = tmg_opt_d2(ref, r_d), ad = tmg_opt_d2(add, a_d);
     {
         long long m = n | d_d[0] | d_d[1];
         uintptr_t al = (uintptr_t)dst;
@@ -1785,30 +1787,21 @@ extern "C" int tmg_masked_add(const void* src, const int64_t* s_d, const void* r
         if (ref) { m |= r_d[0] | r_d[1]; al |= (uintptr_t)ref; }
         if (add) { m |= a_d[0] | a_d[1]; al |= (uintptr_t)add; }
         if ((m & 3) == 0 && (al & 15) == 0 && npix * (size_t)(n / 4) < (1ull << 31)) {
-            hipLaunchKernelGGL(masked_add4_kernel, dim3(grid_for(npix * (n / 4))), dim3(256), 0, st, (const float*)src, src ? (int)s_d[0] : 0,
-                               src ? (int)s_d[1] : 0, (const float*)ref, ref ? (int)r_d[0] : 0, ref ? (int)r_d[1] : 0, (const float*)add,
-                               add ? (int)a_d[0] : 0, add ? (int)a_d[1] : 0, (float*)dst, (int)d_d[0], (int)d_d[1], (unsigned)npix, n / 4,
-                               (int)dims[2]);
+            hipLaunchKernelGGL(masked_add4_kernel, dim3(grid_for(npix * (n / 4))), dim3(256), 0, st, (const float*)src, sd.stride,
+                               sd.off, (const float*)ref, rd.stride, rd.off, (const float*)add, ad.stride, ad.off, (float*)dst, (int)d_d[0],
+                               (int)d_d[1], (unsigned)npix, n / 4, (int)dims[2]);
             TMG_CHECK_LAUNCH();
             return 0;
         }
     }
-    hipLaunchKernelGGL(masked_add_kernel, dim3(grid_for(npix * n)), dim3(256), 0, st, (const float*)src, src ? (int)s_d[0] : 0,
-                       src ? (int)s_d[1] : 0, (const float*)ref, ref ? (int)r_d[0] : 0, ref ? (int)r_d[1] : 0, (const float*)add,
-                       add ? (int)a_d[0] : 0, add ? (int)a_d[1] : 0, (float*)dst, (int)d_d[0], (int)d_d[1], npix, n, (int)dims[2]);
+    hipLaunchKernelGGL(masked_add_kernel, dim3(grid_for(npix * n)), dim3(256), 0, st, (const float*)src, sd.stride,
+                       sd.off, (const float*)ref, rd.stride, rd.off, (const float*)add, ad.stride, ad.off, (float*)dst, (int)d_d[0], (int)d_d[1],
+                       npix, n, (int)dims[2]);
     TMG_CHECK_LAUNCH();
     return 0;
 }
 
-static void fill_segs_pw(TmgSeg* dst, const void* const* ptrs, const int64_t* desc, int n, int* vec4) {
-    for (int i = 0; i < TMG_MAX_IN_SEG; ++i) dst[i] = TmgSeg{nullptr, 0, 0, 0};
-    for (int i = 0; i < n; ++i) {
-        dst[i] = TmgSeg{(const float*)ptrs[i], (int)desc[3 * i], (int)desc[3 * i + 1], (int)desc[3 * i + 2]};
-        if ((dst[i].stride | dst[i].off | dst[i].n) & 3) *vec4 = 0;
-        if (((uintptr_t)ptrs[i]) & 15) *vec4 = 0;
-    }
-}
-
+// (The growth-1 launchers below test neither the segment count nor the channel sum: the decoder never writes past the slots.)
 static int c1_tile(int W, int H, int* twl) {
     int l = 0;
     while ((1 << l) < W) ++l;
@@ -1828,16 +1821,16 @@ extern "C" int tmg_c1x2_fwd(const void* const* in_ptrs, const int64_t* in_desc, 
                             const int64_t* out_d, const int64_t* dims, hipStream_t st) {
     C1X2P p;
     p.nseg = (int)nseg;
-    p.vec4 = 1;
-    fill_segs_pw(p.in, in_ptrs, in_desc, (int)nseg, &p.vec4);
+    p.vec4 = tmg_decode_in(p.in, in_ptrs, in_desc, nseg).vec4;
     p.B = (int)dims[0]; p.Hin = (int)dims[1]; p.Win = (int)dims[2]; p.Cin = (int)dims[3]; p.relu_in = (int)dims[4];
     p.w_rows = (dims[5] > 0 && dims[5] < p.Cin) ? (int)dims[5] : p.Cin;
     p.w_split = dims[6] > 0 ? (int)dims[6] : 0x7fffffff; p.w_gap = (int)dims[7]; p.w2_d1 = (int)dims[8];
     if (p.Cin & 3) p.vec4 = 0;
     p.pad_rep = 0; p.in_scale = nullptr; p.in_shift = nullptr;
     p.w1 = (const float*)w1; p.w2 = (const float*)w2;
-    p.add1 = (const float*)add1; p.a1_stride = add1 ? (int)add1_d[0] : 0; p.a1_off = add1 ? (int)add1_d[1] : 0;
-    p.add2 = (const float*)add2; p.a2_stride = add2 ? (int)add2_d[0] : 0; p.a2_off = add2 ? (int)add2_d[1] : 0;
+    const TmgD2 a1 = tmg_opt_d2(add1, add1_d), a2 = tmg_opt_d2(add2, add2_d);
+    p.add1 = (const float*)add1; p.a1_stride = a1.stride; p.a1_off = a1.off;
+    p.add2 = (const float*)add2; p.a2_stride = a2.stride; p.a2_off = a2.off;
     if ((out_d[0] & 3) || out_d[1] != 0 || (((uintptr_t)out) & 15)) return -2;
     p.out = (float*)out; p.out_stride = (int)out_d[0];
     c1_tile(p.Win, p.Hin, &p.TW_log2);
@@ -1889,13 +1882,13 @@ extern "C" int tmg_c1_fwd_add(const void* const* in_ptrs, const int64_t* in_desc
                               const int64_t* add_d, void* out, const int64_t* out_d, const int64_t* dims, hipStream_t st) {
     C1P p;
     p.nseg = (int)nseg;
-    p.vec4 = 1;
-    fill_segs_pw(p.in, in_ptrs, in_desc, (int)nseg, &p.vec4);
+    p.vec4 = tmg_decode_in(p.in, in_ptrs, in_desc, nseg).vec4;
     p.B = (int)dims[0]; p.Hin = (int)dims[1]; p.Win = (int)dims[2]; p.Cin = (int)dims[3]; p.relu_in = (int)dims[4];
     p.w_rows = (dims[5] > 0 && dims[5] < p.Cin) ? (int)dims[5] : p.Cin;
     p.fill4 = (int)dims[6];
     p.w_split = dims[7] > 0 ? (int)dims[7] : 0x7fffffff; p.w_gap = (int)dims[8];
-    p.add = (const float*)add; p.add_stride = add ? (int)add_d[0] : 0; p.add_off = add ? (int)add_d[1] : 0;
+    const TmgD2 ad = tmg_opt_d2(add, add_d);
+    p.add = (const float*)add; p.add_stride = ad.stride; p.add_off = ad.off;
     if (p.Cin & 3) p.vec4 = 0;
     p.pad_rep = 0; p.in_scale = nullptr; p.in_shift = nullptr;
     p.w = (const float*)w; p.out = (float*)out; p.out_stride = (int)out_d[0]; p.out_off = (int)out_d[1];
@@ -1918,17 +1911,15 @@ extern "C" int tmg_c1_bwd(const void* const* in_ptrs, const int64_t* in_desc, in
                           int64_t ng, const int64_t* dims, hipStream_t st) {
     C1BP p;
     p.nseg = (int)nseg;
-    p.vec4 = 1;
-    fill_segs_pw(p.in, in_ptrs, in_desc, (int)nseg, &p.vec4);
+    p.vec4 = tmg_decode_in(p.in, in_ptrs, in_desc, nseg).vec4;
     p.B = (int)dims[0]; p.Hin = (int)dims[1]; p.Win = (int)dims[2]; p.Cin = (int)dims[3]; p.relu_in = (int)dims[4];
     if (p.Cin & 3) p.vec4 = 0;
     p.pad_rep = 0; p.in_scale = nullptr; p.in_shift = nullptr;
     p.w = (const float*)w; p.dW = (float*)dW;
     p.dd = (const float*)dd; p.dd_stride = (int)dd_d[0]; p.dd_off = (int)dd_d[1];
-    p.dref = (const float*)dref; p.dref_stride = dref ? (int)dref_d[0] : 0; p.dref_off = dref ? (int)dref_d[1] : 0;
-    for (int i = 0; i < TMG_MAX_OUT_SEG; ++i) p.g[i] = TmgOSeg{nullptr, 0, 0, 0};
-    for (int i = 0; i < (int)ng; ++i)
-        p.g[i] = TmgOSeg{(float*)g_ptrs[i], (int)g_desc[3 * i], (int)g_desc[3 * i + 1], (int)g_desc[3 * i + 2]};
+    const TmgD2 rd = tmg_opt_d2(dref, dref_d);
+    p.dref = (const float*)dref; p.dref_stride = rd.stride; p.dref_off = rd.off;
+    tmg_decode_out(p.g, g_ptrs, g_desc, ng);
     c1_tile(p.Win, p.Hin, &p.TW_log2);
     const int TW = 1 << p.TW_log2, TH = 256 >> p.TW_log2;
     p.tiles_x = (p.Win + TW - 1) / TW;
@@ -1956,21 +1947,18 @@ extern "C" int tmg_dense2_bwd(const void* const* in_ptrs, const int64_t* in_desc
                               int64_t ng, const void* add0, int64_t add0_stride, const int64_t* dims, hipStream_t st) {
     D2BP p;
     p.nseg = (int)nseg;
-    p.vec4 = 1;
-    fill_segs_pw(p.in, in_ptrs, in_desc, (int)nseg, &p.vec4);
+    p.vec4 = tmg_decode_in(p.in, in_ptrs, in_desc, nseg).vec4;
     p.B = (int)dims[0]; p.Hin = (int)dims[1]; p.Win = (int)dims[2]; p.Cin = (int)dims[3]; p.cin_nn = (int)dims[4];
     p.rows1 = (int)dims[5]; p.rows2 = (int)dims[6];
     p.relu_in = 1; p.pad_rep = 0; p.in_scale = nullptr; p.in_shift = nullptr;
     if (p.Cin & 3) p.vec4 = 0;
     p.w1 = (const float*)w1; p.w2 = (const float*)w2; p.dW1 = (float*)dW1; p.dW2 = (float*)dW2;
     p.GD = (const float*)GD; p.gd_stride = (int)gd_stride; p.Dp = (const float*)Dp; p.d_stride = (int)d_stride;
-    for (int i = 0; i < 2; ++i) { p.g0[i] = TmgSeg{nullptr, 0, 0, 0}; p.out[i] = TmgOSeg{nullptr, 0, 0, 0}; }
-    for (int i = 0; i < (int)ng; ++i) {
-        p.g0[i] = TmgSeg{(const float*)g0_ptrs[i], (int)g0_desc[3 * i], (int)g0_desc[3 * i + 1], (int)g0_desc[3 * i + 2]};
-        p.out[i] = TmgOSeg{(float*)out_ptrs[i], (int)out_desc[3 * i], (int)out_desc[3 * i + 1], (int)out_desc[3 * i + 2]};
-        if ((p.g0[i].stride | p.g0[i].off | p.g0[i].n | p.out[i].stride | p.out[i].off) & 3) p.vec4 = 0;
-        if ((((uintptr_t)g0_ptrs[i]) | ((uintptr_t)out_ptrs[i])) & 15) p.vec4 = 0;
-    }
+    if (!tmg_decode_in(p.g0, g0_ptrs, g0_desc, ng, 2).vec4) p.vec4 = 0;
+    tmg_decode_out(p.out, out_ptrs, out_desc, ng, 2);
+    // (an output segment's channel count is not part of this launcher's float4 test - the kernels split by g0's counts: kept)
+    for (int i = 0; i < 2; ++i)
+        if (((p.out[i].stride | p.out[i].off) & 3) || (((uintptr_t)p.out[i].p) & 15)) p.vec4 = 0;
     p.add0 = (const float*)add0; p.add0_stride = (int)add0_stride;
     p.dd1_out = (float*)dims[7]; p.dd2_out = (float*)dims[8]; p.dd_stride = (int)dims[9];
     p.dd_quad = dims[12] && p.dd1_out && p.dd2_out == p.dd1_out + 1 && !(p.dd_stride & 3) && !(((uintptr_t)p.dd1_out) & 15);

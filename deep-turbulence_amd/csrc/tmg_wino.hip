@@ -611,36 +611,27 @@ __global__ __launch_bounds__(768, 1) void wino_fwdp_kernel(WinoP p) {
     }
 }
 
-// out = conv3x3_stride1(pad(act(in))) + bias with the Winograd operand of tmg_conv_wino_pack.
-// dims = {B, H, W, Cin, Cout, relu_in, pad_replicate}; in_desc / out_desc = {stride, off, n} per segment (<= 3 each).
-// Envelope: float4-addressable segments, Cin % 4 == 0, Cout % 4 == 0, Cout >= 64; returns -100 outside it (the caller
-// uses tmg_conv_fwd).
-extern "C" int tmg_conv_wino_fwd(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* U, const void* bias,
-                                 void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, hipStream_t st) {
-    WinoP p;
+// Decode, validation and tile geometry shared by the three Winograd forwards (WinoP / WinoNP carry the same fields); they differ in
+// the channel envelope (`narrow`), the granule of Cin_pad and what they launch.  Returns 1 when the caller should launch, else the
+// code to hand back: -3 bad segment count or channel sums, -100 outside the envelope (not float4-addressable, misaligned bias,
+// >= 2^31 pixels), 0 nothing to do.  The channel-sum test comes before the envelope test, the pixel-count test after the zero-tile one.
+template <typename P>
+static int wino_fwd_setup(P& p, const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* U, const void* bias,
+                          void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, int cin_granule, bool narrow) {
     p.nseg = (int)nseg;
-    if (p.nseg < 1 || p.nseg > TMG_MAX_IN_SEG || nout < 1 || nout > TMG_MAX_OUT_SEG) return -3;
-    int csum = 0, osum = 0;
-    bool ok = true;
-    for (int i = 0; i < TMG_MAX_IN_SEG; ++i) p.in[i] = TmgSeg{nullptr, 0, 0, 0};
-    for (int i = 0; i < p.nseg; ++i) {
-        p.in[i] = TmgSeg{(const float*)in_ptrs[i], (int)in_desc[3 * i], (int)in_desc[3 * i + 1], (int)in_desc[3 * i + 2]};
-        if (((p.in[i].stride | p.in[i].off | p.in[i].n) & 3) || (((uintptr_t)in_ptrs[i]) & 15)) ok = false;
-        csum += p.in[i].n;
-    }
-    for (int i = 0; i < TMG_MAX_OUT_SEG; ++i) p.out[i] = TmgOSeg{nullptr, 0, 0, 0};
-    for (int i = 0; i < (int)nout; ++i) {
-        p.out[i] = TmgOSeg{(float*)out_ptrs[i], (int)out_desc[3 * i], (int)out_desc[3 * i + 1], (int)out_desc[3 * i + 2]};
-        if (((p.out[i].stride | p.out[i].off | p.out[i].n) & 3) || (((uintptr_t)out_ptrs[i]) & 15)) ok = false;
-        osum += p.out[i].n;
-    }
+    if (tmg_bad_seg_count(nseg, nout)) return -3;
+    const TmgSegList si = tmg_decode_in(p.in, in_ptrs, in_desc, nseg), so = tmg_decode_out(p.out, out_ptrs, out_desc, nout);
     p.B = (int)dims[0]; p.Hin = (int)dims[1]; p.Win = (int)dims[2]; p.Cin = (int)dims[3]; p.Cout = (int)dims[4];
     p.relu_in = (int)dims[5]; p.pad_rep = (int)dims[6];
-    if (csum != p.Cin || osum != p.Cout) return -3;
-    if ((p.Cout & 3) || (p.Cin & 3) || p.Cout < 64) ok = false;
+    if (si.csum != p.Cin || so.csum != p.Cout) return -3;
+    bool ok = si.vec4 && so.vec4 && !(p.Cout & 3) && !(p.Cin & 3);
+    // narrow: 48 - the M buffer of 4 channel tiles does not fit LDS.  (FEW output channels - the input-gradient shapes 256 -> 40,
+    // 240 -> 32 .. of wino_nn_kernel - were measured on wino_fwd3_kernel with three of eight waves live: 0.47-0.69x of wino_nn_kernel,
+    // the per-chunk transform / staging / barriers of 8-60 chunks dominate)
+    if (narrow ? (p.Cout > 48 || p.Cin < 64) : p.Cout < 64) ok = false;
     if (bias && (((uintptr_t)bias) & 15)) ok = false;
     if (!ok) return -100;
-    p.Cin_pad = (p.Cin + 15) & ~15;
+    p.Cin_pad = (p.Cin + cin_granule - 1) & ~(cin_granule - 1);
     p.Npad = (p.Cout + 15) & ~15;
     p.U = (const float*)U; p.bias = (const float*)bias;
     p.tiles_x = (p.Win + 15) / 16; p.tiles_y = (p.Hin + 7) / 8;
@@ -648,12 +639,22 @@ extern "C" int tmg_conv_wino_fwd(const void* const* in_ptrs, const int64_t* in_d
     p.nchunks = (p.Cin_pad + 31) / 32;
     if (p.ntiles <= 0) return 0;
     if ((long long)p.B * p.Hin * p.Win >= (1LL << 31)) return -100;      // 32-bit pixel indices in the kernels
+    return 1;
+}
+
+// out = conv3x3_stride1(pad(act(in))) + bias with the Winograd operand of tmg_conv_wino_pack.
+// dims = {B, H, W, Cin, Cout, relu_in, pad_replicate}; in_desc / out_desc = {stride, off, n} per segment (<= 3 each).
+// Envelope: float4-addressable segments, Cin % 4 == 0, Cout % 4 == 0, Cout >= 64; returns -100 outside it (the caller
+// uses tmg_conv_fwd).
+extern "C" int tmg_conv_wino_fwd(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* U, const void* bias,
+                                 void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, hipStream_t st) {
+    WinoP p;
+    const int rc = wino_fwd_setup(p, in_ptrs, in_desc, nseg, U, bias, out_ptrs, out_desc, nout, dims, 16, false);
+    if (rc != 1) return rc;
     const int ntt = p.Npad / 16;
     const int npw = ntt <= 8 ? 1 : 2;           // output-channel tiles per wave (see the kernel)
     const int gy = (ntt + 8 * npw - 1) / (8 * npw);
-    int G = tmg_num_cus() / gy;
-    if (G < 1) G = 1;
-    if (G > p.ntiles) G = p.ntiles;
+    const int G = tmg_persistent_grid(gy, p.ntiles);
     const size_t lds_bytes = (size_t)(2 * 180 * 40 + 16 * 32 * 40) * sizeof(float);
     TmgProf prof(TMG_PROF_WINO, 2.0 * p.B * p.Hin * p.Win * (double)p.Cout * p.Cin * 9, st);   // algorithmic (direct) flops
     // Producer-wave form (round 6) for the contractions with <= 128 output channels (one n-tile per wave: 100 registers, twelve waves
@@ -664,9 +665,7 @@ extern "C" int tmg_conv_wino_fwd(const void* const* in_ptrs, const int64_t* in_d
     if (npw == 1) {
         const size_t ldsp = (size_t)(2 * 16 * 32 * 40) * sizeof(float);      // two V buffers: all 160 KB of the CU
         const int gyp = (ntt + 7) / 8;
-        int Gp = tmg_num_cus() / gyp;
-        if (Gp < 1) Gp = 1;
-        if (Gp > p.ntiles) Gp = p.ntiles;
+        const int Gp = tmg_persistent_grid(gyp, p.ntiles);
         TMG_LDS_OPTIN((&wino_fwdp_kernel<1>));
         hipLaunchKernelGGL(wino_fwdp_kernel<1>, dim3(Gp, gyp, 1), dim3(768), ldsp, st, p);
         TMG_CHECK_LAUNCH();
@@ -1051,44 +1050,12 @@ __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd3_kernel(WinoP 
 extern "C" int tmg_conv_wino_fwd3(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* U, const void* bias,
                                   void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, hipStream_t st) {
     WinoP p;
-    p.nseg = (int)nseg;
-    if (p.nseg < 1 || p.nseg > TMG_MAX_IN_SEG || nout < 1 || nout > TMG_MAX_OUT_SEG) return -3;
-    int csum = 0, osum = 0;
-    bool ok = true;
-    for (int i = 0; i < TMG_MAX_IN_SEG; ++i) p.in[i] = TmgSeg{nullptr, 0, 0, 0};
-    for (int i = 0; i < p.nseg; ++i) {
-        p.in[i] = TmgSeg{(const float*)in_ptrs[i], (int)in_desc[3 * i], (int)in_desc[3 * i + 1], (int)in_desc[3 * i + 2]};
-        if (((p.in[i].stride | p.in[i].off | p.in[i].n) & 3) || (((uintptr_t)in_ptrs[i]) & 15)) ok = false;
-        csum += p.in[i].n;
-    }
-    for (int i = 0; i < TMG_MAX_OUT_SEG; ++i) p.out[i] = TmgOSeg{nullptr, 0, 0, 0};
-    for (int i = 0; i < (int)nout; ++i) {
-        p.out[i] = TmgOSeg{(float*)out_ptrs[i], (int)out_desc[3 * i], (int)out_desc[3 * i + 1], (int)out_desc[3 * i + 2]};
-        if (((p.out[i].stride | p.out[i].off | p.out[i].n) & 3) || (((uintptr_t)out_ptrs[i]) & 15)) ok = false;
-        osum += p.out[i].n;
-    }
-    p.B = (int)dims[0]; p.Hin = (int)dims[1]; p.Win = (int)dims[2]; p.Cin = (int)dims[3]; p.Cout = (int)dims[4];
-    p.relu_in = (int)dims[5]; p.pad_rep = (int)dims[6];
-    if (csum != p.Cin || osum != p.Cout) return -3;
-    // (FEW output channels - the input-gradient shapes 256 -> 40, 240 -> 32 .. of wino_nn_kernel - were measured on this kernel with
-    // three of eight waves live: 0.47-0.69x of wino_nn_kernel, the per-chunk transform / staging / barriers of 8-60 chunks dominate)
-    if ((p.Cout & 3) || (p.Cin & 3) || p.Cout < 64) ok = false;
-    if (bias && (((uintptr_t)bias) & 15)) ok = false;
-    if (!ok) return -100;
-    p.Cin_pad = (p.Cin + 31) & ~31;
-    p.Npad = (p.Cout + 15) & ~15;
-    p.U = (const float*)U; p.bias = (const float*)bias;
-    p.tiles_x = (p.Win + 15) / 16; p.tiles_y = (p.Hin + 7) / 8;
-    p.ntiles = p.B * p.tiles_x * p.tiles_y;
-    p.nchunks = p.Cin_pad / 32;
-    if (p.ntiles <= 0) return 0;
-    if ((long long)p.B * p.Hin * p.Win >= (1LL << 31)) return -100;
+    const int rc = wino_fwd_setup(p, in_ptrs, in_desc, nseg, U, bias, out_ptrs, out_desc, nout, dims, 32, false);
+    if (rc != 1) return rc;
     const int ntt = p.Npad / 16;
     const int npw = ntt <= 8 ? 1 : 2;
     const int gy = (ntt + 8 * npw - 1) / (8 * npw);
-    int G = tmg_num_cus() / gy;
-    if (G < 1) G = 1;
-    if (G > p.ntiles) G = p.ntiles;
+    const int G = tmg_persistent_grid(gy, p.ntiles);
     const size_t lds_bytes = (size_t)(2 * 180 * 40) * sizeof(float) + (size_t)16 * 3 * 4 * 512;
     TmgProf prof(TMG_PROF_WINO, 2.0 * p.B * p.Hin * p.Win * (double)p.Cout * p.Cin * 9, st);   // algorithmic (direct) flops
     if (npw == 1) {
@@ -1404,37 +1371,10 @@ static int launch_wino_nn(const WinoNP& p, int G, hipStream_t st) {
 extern "C" int tmg_conv_wino_narrow(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* U, const void* bias,
                                     void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, hipStream_t st) {
     WinoNP p;
-    p.nseg = (int)nseg;
-    if (p.nseg < 1 || p.nseg > TMG_MAX_IN_SEG || nout < 1 || nout > TMG_MAX_OUT_SEG) return -3;
-    int csum = 0, osum = 0;
-    bool ok = true;
-    for (int i = 0; i < TMG_MAX_IN_SEG; ++i) p.in[i] = TmgSeg{nullptr, 0, 0, 0};
-    for (int i = 0; i < p.nseg; ++i) {
-        p.in[i] = TmgSeg{(const float*)in_ptrs[i], (int)in_desc[3 * i], (int)in_desc[3 * i + 1], (int)in_desc[3 * i + 2]};
-        if (((p.in[i].stride | p.in[i].off | p.in[i].n) & 3) || (((uintptr_t)in_ptrs[i]) & 15)) ok = false;
-        csum += p.in[i].n;
-    }
-    for (int i = 0; i < TMG_MAX_OUT_SEG; ++i) p.out[i] = TmgOSeg{nullptr, 0, 0, 0};
-    for (int i = 0; i < (int)nout; ++i) {
-        p.out[i] = TmgOSeg{(float*)out_ptrs[i], (int)out_desc[3 * i], (int)out_desc[3 * i + 1], (int)out_desc[3 * i + 2]};
-        if (((p.out[i].stride | p.out[i].off | p.out[i].n) & 3) || (((uintptr_t)out_ptrs[i]) & 15)) ok = false;
-        osum += p.out[i].n;
-    }
-    p.B = (int)dims[0]; p.Hin = (int)dims[1]; p.Win = (int)dims[2]; p.Cin = (int)dims[3]; p.Cout = (int)dims[4];
-    p.relu_in = (int)dims[5]; p.pad_rep = (int)dims[6]; p.relu_out = (int)dims[7];
-    if (csum != p.Cin || osum != p.Cout) return -3;
-    if ((p.Cout & 3) || (p.Cin & 3) || p.Cout > 48 || p.Cin < 64) ok = false;   // 48: the M buffer of 4 channel tiles does not fit LDS
-    if (bias && (((uintptr_t)bias) & 15)) ok = false;
-    if (!ok) return -100;
-    p.Cin_pad = (p.Cin + 15) & ~15;
-    p.Npad = (p.Cout + 15) & ~15;
-    p.U = (const float*)U; p.bias = (const float*)bias;
-    p.tiles_x = (p.Win + 15) / 16; p.tiles_y = (p.Hin + 7) / 8;
-    p.ntiles = p.B * p.tiles_x * p.tiles_y;
-    p.nchunks = (p.Cin_pad + 31) / 32;
-    if (p.ntiles <= 0) return 0;
-    if ((long long)p.B * p.Hin * p.Win >= (1LL << 31)) return -100;      // 32-bit pixel indices in the kernels
-    const int G = p.ntiles < tmg_num_cus() ? p.ntiles : tmg_num_cus();
+    const int rc = wino_fwd_setup(p, in_ptrs, in_desc, nseg, U, bias, out_ptrs, out_desc, nout, dims, 16, true);
+    if (rc != 1) return rc;
+    p.relu_out = (int)dims[7];
+    const int G = tmg_persistent_grid(1, p.ntiles);
     switch (p.Npad >> 4) {
         case 1: return launch_wino_nn<1>(p, G, st);
         case 2: return launch_wino_nn<2>(p, G, st);
@@ -1839,21 +1779,15 @@ static int wino_wgrad_impl(const void* const* in_ptrs, const int64_t* in_desc, i
     WinoWP p;
     p.nseg = (int)nseg;
     if (p.nseg < 1 || p.nseg > TMG_MAX_IN_SEG) return -3;
-    int csum = 0;
-    bool ok = true;
-    for (int i = 0; i < TMG_MAX_IN_SEG; ++i) p.in[i] = TmgSeg{nullptr, 0, 0, 0};
-    for (int i = 0; i < p.nseg; ++i) {
-        p.in[i] = TmgSeg{(const float*)in_ptrs[i], (int)in_desc[3 * i], (int)in_desc[3 * i + 1], (int)in_desc[3 * i + 2]};
-        if (((p.in[i].stride | p.in[i].off | p.in[i].n) & 3) || (((uintptr_t)in_ptrs[i]) & 15)) ok = false;
-        csum += p.in[i].n;
-    }
+    const TmgSegList si = tmg_decode_in(p.in, in_ptrs, in_desc, nseg);
+    bool ok = si.vec4;
     p.B = (int)dims[0]; p.Hin = (int)dims[1]; p.Win = (int)dims[2]; p.Cin = (int)dims[3]; p.Cout = (int)dims[4];
     p.relu_in = (int)dims[5]; p.pad_rep = (int)dims[6];
     const int cin_dst = dims[7] > 0 ? (int)dims[7] : p.Cin;
     const int cin_valid = dims[8] > 0 ? (int)dims[8] : (cin_dst < p.Cin ? cin_dst : p.Cin);
     const int ci_split = dims[9] > 0 ? (int)dims[9] : 0x7fffffff;
     const int ci_off0 = (int)dims[10], ci_off1 = (int)dims[11];
-    if (csum != p.Cin) return -3;
+    if (si.csum != p.Cin) return -3;
     p.dy = (const float*)dy; p.dy_stride = (int)dy_desc[0]; p.dy_off = (int)dy_desc[1];
     if (((p.dy_stride | p.dy_off | dy_goff) & 3) || (((uintptr_t)dy) & 15) || (p.Cin & 3) || (p.Cout & 3)) ok = false;
     WinoWPlan pl;

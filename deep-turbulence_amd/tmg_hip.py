@@ -41,6 +41,10 @@ EXPORTS = [
     "tmg_conv_wino_pack", "tmg_conv_wino_fwd", "tmg_conv_wino_narrow", "tmg_conv_wino_wgrad", "tmg_conv_wino_wgrad_ws_floats", "tmg_mix_f32", "tmg_lu_fold_fwd", "tmg_lu_fold_bwd", "tmg_lu_fold_bwd_split", "tmg_level_finish", "tmg_conv_wgrad_thin_grouped", "tmg_mix_wgrad_grouped", "tmg_layer_planes", "tmg_conv_wino_wgrad_grouped", "tmg_conv_wino_wgrad_grouped_ws_floats", "tmg_adam_step", "tmg_chan_moments", "tmg_bn_finalize64", "tmg_mix_f32_affine_fwd", "tmg_mix_f32_affine_bwd", "tmg_conv_pack_many", "tmg_pad_halves", "tmg_coupling_fwd_halves", "tmg_coupling_bwd_halves", "tmg_fill_i64", "tmg_conv_wino_pack3", "tmg_conv_wino_fwd3", "tmg_mat_inverse", "tmg_gauss_sample", "tmg_reverse_loss_fwd", "tmg_reverse_loss_bwd", "tmg_sum_terms", "tmg_vec_sum", "tmg_level_pack", "tmg_spread2", "tmg_phys_fields", "tmg_phys_fields_bwd",
     "tmg_gauss_sample_keyed", "tmg_ens_accum", "tmg_ens_time_finalize",
 ]
+# Every export returns int except the workspace sizes, which the header declares int64_t (read through a 32-bit return a request of
+# 2^31 floats or more would be truncated and the kernel handed a buffer smaller than it planned for).
+RET_I64 = ("tmg_conv_wgrad_ws_floats", "tmg_conv_wgrad_grouped_ws_floats", "tmg_conv_wino_wgrad_ws_floats",
+           "tmg_conv_wino_wgrad_grouped_ws_floats")
 
 
 def build(force=False, verbose=False):
@@ -97,9 +101,8 @@ def lib():
                                "There is no fallback path." % LIB_PATH)
         _lib = ctypes.CDLL(LIB_PATH)
         for name in EXPORTS:
-            getattr(_lib, name).restype = ctypes.c_int
-        _lib.tmg_conv_wgrad_ws_floats.restype = ctypes.c_int64
-        _lib.tmg_conv_wgrad_grouped_ws_floats.restype = ctypes.c_int64
+            getattr(_lib, name).restype = c_i64 if name in RET_I64 else ctypes.c_int
+        _lib.tmg_prof_name.restype = ctypes.c_char_p
     return _lib
 
 
@@ -111,7 +114,6 @@ def prof_enable(on):
 def prof_kernel_id(name):
     """Kernel id of a name returned by prof_collect (for prof_enable(100 + id): time only that kernel)."""
     l = lib()
-    l.tmg_prof_name.restype = ctypes.c_char_p
     for k in range(64):
         if l.tmg_prof_name(c_i64(k)).decode() == name:
             return k
@@ -122,7 +124,6 @@ def prof_collect():
     """{kernel name: (launches, total ms, total algorithmic work)} of the event-timed kernels: work = flops for the matrix-core
     kernels, HBM bytes for the classes whose name starts with "hbm:"."""
     l = lib()
-    l.tmg_prof_name.restype = ctypes.c_char_p
     nk = 64
     buf = (ctypes.c_double * (3 * nk))()
     n = l.tmg_prof_collect(buf, c_i64(nk))
@@ -198,12 +199,33 @@ def _segs(tensors):
 
 
 def _d2(t):
-    s = seg(t)
-    return (c_i64 * 2)(s[1], 0)
+    """{pixel stride, 0} of a tensor (the channel offset of a slice view is already folded into its data pointer); zeros for None
+    (an optional operand: its pointer is null and the library does not read the descriptor)."""
+    return (c_i64 * 2)(seg(t)[1] if t is not None else 0, 0)
 
 
 def _i64(*v):
     return (c_i64 * len(v))(*[int(x) for x in v])
+
+
+def _flts(vals):
+    return (ctypes.c_float * len(vals))(*[float(v) for v in vals])
+
+
+def _launched(rc, name):
+    """The envelope convention: -100 = the shape is outside the kernel's envelope and nothing was launched (False); any other
+    non-zero code raises."""
+    if rc == -100:
+        return False
+    _chk(rc, name)
+    return True
+
+
+def _packed_numel(mode, ce, Cout, k):
+    """Floats of the direct kernels' packed operand (tmg_conv_pack): k k taps of [K -> 16][N -> 16], K x N = ce x Cout (mode 0) or
+    Cout x ce (mode 1)."""
+    K, N = (ce, Cout) if mode == 0 else (Cout, ce)
+    return k * k * ((K + 15) // 16 * 16) * ((N + 15) // 16 * 16)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -269,16 +291,12 @@ def conv_pack(w, mode, cin_eff=0, cmap=None):
     Cout, Cin, k, _ = w.shape
     if cmap is not None:
         ce = int(cin_eff)
-        K, N = (ce, Cout) if mode == 0 else (Cout, ce)
-        Kp, Np = (K + 15) // 16 * 16, (N + 15) // 16 * 16
-        wpk = torch.empty(k * k * Kp * Np, device=w.device, dtype=torch.float32)
+        wpk = torch.empty(_packed_numel(mode, ce, Cout, k), device=w.device, dtype=torch.float32)
         _chk(lib().tmg_conv_pack_map(_ptr(w), _ptr(wpk), c_i64(Cout), c_i64(Cin), c_i64(ce), c_i64(k), c_i64(mode), _i64(*cmap), _stream()),
              "tmg_conv_pack_map")
         return wpk
     ce = max(int(cin_eff), Cin)
-    K, N = (ce, Cout) if mode == 0 else (Cout, ce)
-    Kp, Np = (K + 15) // 16 * 16, (N + 15) // 16 * 16
-    wpk = torch.empty(k * k * Kp * Np, device=w.device, dtype=torch.float32)
+    wpk = torch.empty(_packed_numel(mode, ce, Cout, k), device=w.device, dtype=torch.float32)
     _chk(lib().tmg_conv_pack(_ptr(w), _ptr(wpk), c_i64(Cout), c_i64(Cin), c_i64(ce), c_i64(k), c_i64(mode), _stream()), "tmg_conv_pack")
     return wpk
 
@@ -295,11 +313,9 @@ def conv_pack_many(jobs):
             assert w.is_contiguous()
             Cout, Cin, k, _ = w.shape
             ce = int(cin_eff) if cmap is not None else max(int(cin_eff), Cin)
-            K, N = (ce, Cout) if mode == 0 else (Cout, ce)
-            Kp, Np = (K + 15) // 16 * 16, (N + 15) // 16 * 16
             m = cmap if cmap is not None else (Cin, 0x7fffffff, 0)
             desc += [Cout, Cin, ce, k, mode, m[0], m[1], m[2]]
-            sizes.append(k * k * Kp * Np)
+            sizes.append(_packed_numel(mode, ce, Cout, k))
             ws.append(w)
         flat = torch.empty(sum(sizes), device=ws[0].device, dtype=torch.float32)
         views, o = [], 0
@@ -319,9 +335,7 @@ def conv_pack_batched(w, mode, cin_eff=0, cmap=None):
     w = w.contiguous()
     N_, Cout, Cin, k, _ = w.shape
     ce = int(cin_eff) if cmap is not None else max(int(cin_eff), Cin)
-    K, N = (ce, Cout) if mode == 0 else (Cout, ce)
-    Kp, Np = (K + 15) // 16 * 16, (N + 15) // 16 * 16
-    wpk = torch.empty((N_, k * k * Kp * Np), device=w.device, dtype=torch.float32)
+    wpk = torch.empty((N_, _packed_numel(mode, ce, Cout, k)), device=w.device, dtype=torch.float32)
     m = cmap if cmap is not None else (Cin, 0x7fffffff, 0)
     _chk(lib().tmg_conv_pack_batched(_ptr(w), _ptr(wpk), c_i64(N_), c_i64(Cout), c_i64(Cin), c_i64(ce), c_i64(k), c_i64(mode), _i64(*m),
                                      _stream()), "tmg_conv_pack_batched")
@@ -398,8 +412,8 @@ def conv_wino_pack3(w, mode=0, nvalid=0):
     return U
 
 
-def conv_wino_fwd3(inputs, U, Cout, outs, bias=None, relu_in=False, pad_rep=False):
-    """conv_wino_fwd with the bf16x3 operand of conv_wino_pack3; False outside the envelope (nothing was launched)."""
+def _wino_fwd(name, inputs, U, Cout, outs, bias, *flags):
+    """The three Winograd forwards: same marshalling, dims = {B, H, W, Cin, Cout, flags..}."""
     if isinstance(outs, torch.Tensor):
         outs = [outs]
     B, Hin, Win, _ = inputs[0].shape
@@ -407,46 +421,25 @@ def conv_wino_fwd3(inputs, U, Cout, outs, bias=None, relu_in=False, pad_rep=Fals
     op, odesc, n_out = _segs(outs)
     Cin = sum(t.shape[3] for t in inputs)
     assert sum(t.shape[3] for t in outs) == Cout and outs[0].shape[1] == Hin and outs[0].shape[2] == Win
-    rc = lib().tmg_conv_wino_fwd3(ip, idesc, c_i64(n_in), _ptr(U), _ptr(bias), op, odesc, c_i64(n_out),
-                                  _i64(B, Hin, Win, Cin, Cout, relu_in, pad_rep), _stream())
-    if rc == -100:
-        return False
-    _chk(rc, "tmg_conv_wino_fwd3")
-    return True
+    return _launched(getattr(lib(), name)(ip, idesc, c_i64(n_in), _ptr(U), _ptr(bias), op, odesc, c_i64(n_out),
+                                          _i64(B, Hin, Win, Cin, Cout, *flags), _stream()), name)
+
+
+def conv_wino_fwd3(inputs, U, Cout, outs, bias=None, relu_in=False, pad_rep=False):
+    """conv_wino_fwd with the bf16x3 operand of conv_wino_pack3; False outside the envelope (nothing was launched)."""
+    return _wino_fwd("tmg_conv_wino_fwd3", inputs, U, Cout, outs, bias, relu_in, pad_rep)
 
 
 def conv_wino_narrow(inputs, U, Cout, outs, bias=None, relu_in=False, pad_rep=False, relu_out=False):
     """Few output channels: outs = list of <= 3 NHWC tensors / channel-slice views forming the Cout channels.  False when the
     shape is outside the kernel's envelope (nothing was launched)."""
-    B, Hin, Win, _ = inputs[0].shape
-    ip, idesc, n_in = _segs(inputs)
-    op, odesc, n_out = _segs(outs)
-    Cin = sum(t.shape[3] for t in inputs)
-    assert sum(t.shape[3] for t in outs) == Cout
-    rc = lib().tmg_conv_wino_narrow(ip, idesc, c_i64(n_in), _ptr(U), _ptr(bias), op, odesc, c_i64(n_out),
-                                    _i64(B, Hin, Win, Cin, Cout, relu_in, pad_rep, relu_out), _stream())
-    if rc == -100:
-        return False
-    _chk(rc, "tmg_conv_wino_narrow")
-    return True
+    return _wino_fwd("tmg_conv_wino_narrow", inputs, U, Cout, outs, bias, relu_in, pad_rep, relu_out)
 
 
 def conv_wino_fwd(inputs, U, Cout, outs, bias=None, relu_in=False, pad_rep=False):
     """outs = conv3x3(pad(act(cat(inputs)))) + bias through the Winograd kernel (outs: tensor or list of <= 3 segments); False when
     the shape is outside its envelope (nothing was launched: the caller runs conv_fwd with the direct operand)."""
-    if isinstance(outs, torch.Tensor):
-        outs = [outs]
-    B, Hin, Win, _ = inputs[0].shape
-    ip, idesc, n_in = _segs(inputs)
-    op, odesc, n_out = _segs(outs)
-    Cin = sum(t.shape[3] for t in inputs)
-    assert sum(t.shape[3] for t in outs) == Cout and outs[0].shape[1] == Hin and outs[0].shape[2] == Win
-    rc = lib().tmg_conv_wino_fwd(ip, idesc, c_i64(n_in), _ptr(U), _ptr(bias), op, odesc, c_i64(n_out),
-                                 _i64(B, Hin, Win, Cin, Cout, relu_in, pad_rep), _stream())
-    if rc == -100:
-        return False
-    _chk(rc, "tmg_conv_wino_fwd")
-    return True
+    return _wino_fwd("tmg_conv_wino_fwd", inputs, U, Cout, outs, bias, relu_in, pad_rep)
 
 
 def conv3x3_auto(inputs, weight, Cout, outs, bias=None, relu_in=False, pad_rep=False, relu_out=False, dgrad=False, nvalid=0):
@@ -530,8 +523,7 @@ def conv_wino_wgrad(inputs, dy, dW, dbias, relu_in=False, pad_rep=False, cin_dst
     if need > 0:
         ws = workspace(need, dy.device)
         rc = lib().tmg_conv_wino_wgrad(ip, idesc, c_i64(n_in), _ptr(dy), _d2(dy), _ptr(dW), _ptr(dbias), _ptr(ws), c_i64(ws.numel()), wd, _stream())
-        if rc != -100:
-            _chk(rc, "tmg_conv_wino_wgrad")
+        if _launched(rc, "tmg_conv_wino_wgrad"):
             return True
     return False
 
@@ -631,8 +623,7 @@ def conv_wgrad_grouped(group_inputs, dy, dy_group_channels, dW, dbias, ksize, st
             gd = _i64(Cg, dW[0].numel(), dbias[0].numel() if dbias is not None else 0)
             rc = lib().tmg_conv_wino_wgrad_grouped(ip, idesc, c_i64(n_in), _ptr(gtab), c_i64(G), gd, _ptr(dy), _d2(dy), _ptr(dW), _ptr(dbias),
                                                    _ptr(ws), c_i64(ws.numel()), wd, _stream())
-            if rc != -100:
-                _chk(rc, "tmg_conv_wino_wgrad_grouped")
+            if _launched(rc, "tmg_conv_wino_wgrad_grouped"):
                 return True
     if (group_dy is not None and ksize == 1 and stride == 1 and Cg == Cin and Cin in (16, 32) and cin_dst in (0, Cin)
             and cin_valid in (0, Cin) and ci_split == 0 and os.environ.get("TMG_NO_MIX_WGRAD_KERNEL") is None
@@ -640,8 +631,7 @@ def conv_wgrad_grouped(group_inputs, dy, dy_group_channels, dW, dbias, ksize, st
             and all(_pixel_linear(t) for e in group_dy for t in (e if dy_pairs else (e,)))):
         # the 1x1 mixes' weight gradients: streaming GEMM over the pixels, operands straight from global memory
         rc = lib().tmg_mix_wgrad_grouped(_ptr(gtab), c_i64(G), _ptr(dW), _ptr(dbias), _i64(B * Hin * Win, Cin), _stream())
-        if rc != -100:
-            _chk(rc, "tmg_mix_wgrad_grouped")
+        if _launched(rc, "tmg_mix_wgrad_grouped"):
             return True
     if dy_pairs:    # outside the streaming kernel's envelope after all: the general kernels read one tensor per group
         return conv_wgrad_grouped(group_inputs, None, dy_group_channels, dW, dbias, ksize, stride, relu_in=relu_in, pad_rep=pad_rep,
@@ -654,18 +644,14 @@ def conv_wgrad_grouped(group_inputs, dy, dy_group_channels, dW, dbias, ksize, st
         # instead of 16x16 tiles that would be 2/16 used
         rc = lib().tmg_conv_wgrad_thin_grouped(_ptr(gtab), c_i64(G), _i64(*[t.shape[3] for t in first]), c_i64(n_in), _ptr(dy),
                                                c_i64(dy.stride(2)), _ptr(dW), _i64(B, Hin, Win, Cin, relu_in, Cg), _stream())
-        if rc != -100:
-            _chk(rc, "tmg_conv_wgrad_thin_grouped")
+        if _launched(rc, "tmg_conv_wgrad_thin_grouped"):
             return True
     dims = _i64(B, Hin, Win, Hout, Wout, ksize, stride, Cin, Cg, relu_in, pad_rep, cin_dst, cin_valid, ci_split, ci_off0, ci_off1)
     ws = workspace(lib().tmg_conv_wgrad_grouped_ws_floats(dims, c_i64(G)), dy.device)
     gd = _i64(Cg, dW[0].numel(), dbias[0].numel() if dbias is not None else 0)
     rc = lib().tmg_conv_wgrad_grouped(ip, idesc, c_i64(n_in), _ptr(gtab), c_i64(G), gd, _ptr(dy), _d2(dy), _ptr(dW), _ptr(dbias),
                                       _ptr(ws), c_i64(ws.numel()), dims, _stream())
-    if rc == -100:
-        return False
-    _chk(rc, "tmg_conv_wgrad_grouped")
-    return True
+    return _launched(rc, "tmg_conv_wgrad_grouped")
 
 
 def _halves(t):
@@ -692,10 +678,7 @@ def coupling_fwd(x, out, rsave, y2save, D, hc, wz, bz, kappa, Wm, bm, logdet, re
     dims = _i64(B, Hh, Ww, 2 * ch, 1 if reverse else 0, s1[1], t1[1], sh[1], wz.shape[1], wz_d1col, s2[1], t2[1])
     rc = lib().tmg_coupling_fwd_halves(c_vp(s1[0]), c_vp(s2[0]), c_vp(t1[0]), c_vp(t2[0]), _ptr(rsave), _ptr(y2save), _ptr(D), c_vp(sh[0]),
                                        _ptr(wz), _ptr(bz), _ptr(kappa), _ptr(Wm), _ptr(bm), _ptr(logdet), dims, _stream())
-    if rc == -100:
-        return False
-    _chk(rc, "tmg_coupling_fwd_halves")
-    return True
+    return _launched(rc, "tmg_coupling_fwd_halves")
 
 
 def coupling_bwd(dout, x2, r, g, Wm, wz, kappa, DH, dtin, G0, GD, wz_d1col, fwd=False):
@@ -713,10 +696,7 @@ def coupling_bwd(dout, x2, r, g, Wm, wz, kappa, DH, dtin, G0, GD, wz_d1col, fwd=
     dims = _i64(B, Hh, Ww, 2 * ch, sd1[1], sx[1], sh[1], st1[1], wz.shape[1], wz_d1col, sd2[1], st2[1], 1 if fwd else 0)
     rc = lib().tmg_coupling_bwd_halves(c_vp(sd1[0]), c_vp(sd2[0]), c_vp(sx[0]), _ptr(r), _ptr(g), _ptr(Wm), _ptr(wz), _ptr(kappa), c_vp(sh[0]),
                                        c_vp(st1[0]), c_vp(st2[0]), _ptr(G0), _ptr(GD), dims, _stream())
-    if rc == -100:
-        return False
-    _chk(rc, "tmg_coupling_bwd_halves")
-    return True
+    return _launched(rc, "tmg_coupling_bwd_halves")
 
 
 def mix_f16(x, W, bias, y, transposed=False):
@@ -782,31 +762,20 @@ def mix_f32(x, W, bias, y, transposed=False):
     return True
 
 
-def _d2o(t):
-    """{pixel stride, 0}: the channel offset of a slice view is already folded into its data pointer."""
-    return _d2(t)
-
-
 def mix_affine_fwd(x, hh, W, bias, y, r, y2, logdet):
     """Coupling (generative direction) + trailing mix in one launch (tmg_mix_f32_affine_fwd).  False outside the envelope."""
     B, Hh, Ww, C = x.shape
-    rc = lib().tmg_mix_f32_affine_fwd(_ptr(x), _d2o(x), _ptr(hh), _d2o(hh), _ptr(W), _ptr(bias), _ptr(y), _d2o(y), _ptr(r), _ptr(y2),
+    rc = lib().tmg_mix_f32_affine_fwd(_ptr(x), _d2(x), _ptr(hh), _d2(hh), _ptr(W), _ptr(bias), _ptr(y), _d2(y), _ptr(r), _ptr(y2),
                                       _ptr(logdet), _i64(B * Hh * Ww, C, Hh * Ww), _stream())
-    if rc == -100:
-        return False
-    _chk(rc, "tmg_mix_f32_affine_fwd")
-    return True
+    return _launched(rc, "tmg_mix_f32_affine_fwd")
 
 
 def mix_affine_bwd(dy, W, r, t2, g, kappa, dto1, dtin2, dhh):
     """Input gradient of the mix + the coupling's backward in one launch (tmg_mix_f32_affine_bwd).  False outside the envelope."""
     B, Hh, Ww, C = dy.shape
-    rc = lib().tmg_mix_f32_affine_bwd(_ptr(dy), _d2o(dy), _ptr(W), _ptr(r), _ptr(t2), _d2o(t2), _ptr(g), _ptr(kappa), _ptr(dto1), _ptr(dtin2),
-                                      _d2o(dtin2), _ptr(dhh), _d2o(dhh), _i64(B * Hh * Ww, C, Hh * Ww), _stream())
-    if rc == -100:
-        return False
-    _chk(rc, "tmg_mix_f32_affine_bwd")
-    return True
+    rc = lib().tmg_mix_f32_affine_bwd(_ptr(dy), _d2(dy), _ptr(W), _ptr(r), _ptr(t2), _d2(t2), _ptr(g), _ptr(kappa), _ptr(dto1), _ptr(dtin2),
+                                      _d2(dtin2), _ptr(dhh), _d2(dhh), _i64(B * Hh * Ww, C, Hh * Ww), _stream())
+    return _launched(rc, "tmg_mix_f32_affine_bwd")
 
 
 def conv_rep_border_fix(dy, w, outs, kappa=None):
@@ -849,35 +818,26 @@ def affine_bwd(gout, yref, rsave, g, gin, dhh, reverse, kappa=None):
 
 def lstm_pointwise_fwd(gates, c_prev, c_next, h_next):
     B, H, W, R4 = gates.shape
-    cd = _d2(c_prev) if c_prev is not None else _i64(0, 0)
-    _chk(lib().tmg_lstm_pointwise_fwd(_ptr(gates), _ptr(c_prev), cd, _ptr(c_next), _ptr(h_next), _i64(B * H * W, R4 // 4), _stream()),
+    _chk(lib().tmg_lstm_pointwise_fwd(_ptr(gates), _ptr(c_prev), _d2(c_prev), _ptr(c_next), _ptr(h_next), _i64(B * H * W, R4 // 4), _stream()),
          "tmg_lstm_pointwise_fwd")
 
 
 def lstm_pointwise_bwd(acts, c_prev, c_next, dh, dc_in, dc_prev):
     B, H, W, R4 = acts.shape
-    cd = _d2(c_prev) if c_prev is not None else _i64(0, 0)
-    _chk(lib().tmg_lstm_pointwise_bwd(_ptr(acts), _ptr(c_prev), cd, _ptr(c_next), _ptr(dh), _ptr(dc_in), _ptr(dc_prev),
+    _chk(lib().tmg_lstm_pointwise_bwd(_ptr(acts), _ptr(c_prev), _d2(c_prev), _ptr(c_next), _ptr(dh), _ptr(dc_in), _ptr(dc_prev),
                                       _i64(B * H * W, R4 // 4), _stream()), "tmg_lstm_pointwise_bwd")
-
-
-def _fl(vals):
-    return (ctypes.c_float * 4)(*vals)
 
 
 def gauss_fwd(hz, zin, zout, logp, mode, clip_mean, limits):
     B, H, W, Ch = zin.shape
-    zo = _d2(zout) if zout is not None else _i64(0, 0)
-    _chk(lib().tmg_gauss_fwd(_ptr(hz), _d2(hz), _ptr(zin), _d2(zin), _ptr(zout), zo, _ptr(logp), _i64(B, H * W, Ch, mode, clip_mean),
-                             _fl(limits), _stream()), "tmg_gauss_fwd")
+    _chk(lib().tmg_gauss_fwd(_ptr(hz), _d2(hz), _ptr(zin), _d2(zin), _ptr(zout), _d2(zout), _ptr(logp), _i64(B, H * W, Ch, mode, clip_mean),
+                             _flts(limits), _stream()), "tmg_gauss_fwd")
 
 
 def gauss_bwd(hz, zin, dzin, g, dzout, dhz, mode, clip_mean, limits):
     B, H, W, Ch = zin.shape
-    di = _d2(dzin) if dzin is not None else _i64(0, 0)
-    do = _d2(dzout) if dzout is not None else _i64(0, 0)
-    _chk(lib().tmg_gauss_bwd(_ptr(hz), _d2(hz), _ptr(zin), _d2(zin), _ptr(dzin), di, _ptr(g), _ptr(dzout), do, _ptr(dhz), _d2(dhz),
-                             _i64(B, H * W, Ch, mode, clip_mean), _fl(limits), _stream()), "tmg_gauss_bwd")
+    _chk(lib().tmg_gauss_bwd(_ptr(hz), _d2(hz), _ptr(zin), _d2(zin), _ptr(dzin), _d2(dzin), _ptr(g), _ptr(dzout), _d2(dzout), _ptr(dhz), _d2(dhz),
+                             _i64(B, H * W, Ch, mode, clip_mean), _flts(limits), _stream()), "tmg_gauss_bwd")
 
 
 def gauss_sample(hz, eps, z1, out, logp, clip_mean, limits, eps_out=None, nonce=None, site=0):
@@ -886,10 +846,9 @@ def gauss_sample(hz, eps, z1, out, logp, clip_mean, limits, eps_out=None, nonce=
     B, Hh, Ww, Co = out.shape
     Ch = hz.shape[3] // 2
     off = Co - Ch
-    zd = lambda t: _d2(t) if t is not None else _i64(0, 0)  # noqa: E731
     od = seg(out)
-    _chk(lib().tmg_gauss_sample(_ptr(hz), _d2(hz), _ptr(eps), zd(eps), _ptr(z1), zd(z1), _ptr(out), _i64(od[1], off), c_i64(0), _ptr(eps_out),
-                                _ptr(logp), _ptr(nonce), _i64(B, Hh * Ww, Ch, clip_mean, site), _fl(limits), _stream()), "tmg_gauss_sample")
+    _chk(lib().tmg_gauss_sample(_ptr(hz), _d2(hz), _ptr(eps), _d2(eps), _ptr(z1), _d2(z1), _ptr(out), _i64(od[1], off), c_i64(0), _ptr(eps_out),
+                                _ptr(logp), _ptr(nonce), _i64(B, Hh * Ww, Ch, clip_mean, site), _flts(limits), _stream()), "tmg_gauss_sample")
 
 
 def gauss_sample_keyed(hz, eps, z1, out, logp, clip_mean, limits, keys, rows_per_key, site=0, eps_out=None):
@@ -898,14 +857,13 @@ def gauss_sample_keyed(hz, eps, z1, out, logp, clip_mean, limits, keys, rows_per
     B, Hh, Ww, Co = out.shape
     Ch = hz.shape[3] // 2
     off = Co - Ch
-    zd = lambda t: _d2(t) if t is not None else _i64(0, 0)  # noqa: E731
     od = seg(out)
     if eps is None and (keys is None or keys.dtype != torch.int64 or not keys.is_cuda or not keys.is_contiguous()
                         or keys.numel() != 2 * (B // max(int(rows_per_key), 1))):
         raise RuntimeError("gauss_sample_keyed needs a contiguous [B / rows_per_key, 2] int64 key table on the device")
-    _chk(lib().tmg_gauss_sample_keyed(_ptr(hz), _d2(hz), _ptr(eps), zd(eps), _ptr(z1), zd(z1), _ptr(out), _i64(od[1], off), c_i64(0),
+    _chk(lib().tmg_gauss_sample_keyed(_ptr(hz), _d2(hz), _ptr(eps), _d2(eps), _ptr(z1), _d2(z1), _ptr(out), _i64(od[1], off), c_i64(0),
                                       _ptr(eps_out), _ptr(logp), _ptr(keys), _i64(B, Hh * Ww, Ch, clip_mean, site, rows_per_key),
-                                      _fl(limits), _stream()), "tmg_gauss_sample_keyed")
+                                      _flts(limits), _stream()), "tmg_gauss_sample_keyed")
 
 
 def ens_accum(y, u, out_mu, out_std, smean, sm2, tmean, tm2, outs, ostrides, k, n_before, m0, t_before, flags):
@@ -952,10 +910,7 @@ def spread2(dy, up):
     """up (contiguous [B,H,W,C]) = dy on the even positions, zeros elsewhere, in one launch (tmg_spread2); False outside the envelope."""
     B, Hh, Ww, C = up.shape
     rc = lib().tmg_spread2(_ptr(dy), _d2(dy), _ptr(up), _i64(B, Hh, Ww, dy.shape[1], dy.shape[2], C), _stream())
-    if rc == -100:
-        return False
-    _chk(rc, "tmg_spread2")
-    return True
+    return _launched(rc, "tmg_spread2")
 
 
 def level_pack(tab, Wz, Wcat, Bz, Kp, NL, NLp, C, ch, Cc):
@@ -998,8 +953,7 @@ def upsample_bwd(dout, din):
 def chan_reduce(x, g, v0, v1, v2, v3, s0, s1, mode, divisor=0):
     """mode 0 with divisor > 0: v0 holds channel SUMS and v0/divisor is subtracted (centred second pass)."""
     B, H, W, C = x.shape
-    gd = _d2(g) if g is not None else _i64(0, 0)
-    _chk(lib().tmg_chan_reduce(_ptr(x), _d2(x), _ptr(g), gd, _ptr(v0), _ptr(v1), _ptr(v2), _ptr(v3), _ptr(s0), _ptr(s1),
+    _chk(lib().tmg_chan_reduce(_ptr(x), _d2(x), _ptr(g), _d2(g), _ptr(v0), _ptr(v1), _ptr(v2), _ptr(v3), _ptr(s0), _ptr(s1),
                                _i64(B * H * W, C, mode, divisor), _stream()), "tmg_chan_reduce")
 
 
@@ -1036,18 +990,15 @@ def bn_finalize(sums, csq, gamma, beta, running_mean, running_var, out, n, eps, 
 
 def masked_add(dst, src=None, ref=None, add=None, accumulate=False):
     B, H, W, n = dst.shape
-    z = _i64(0, 0)
-    _chk(lib().tmg_masked_add(_ptr(src), _d2(src) if src is not None else z, _ptr(ref), _d2(ref) if ref is not None else z, _ptr(add),
-                              _d2(add) if add is not None else z, _ptr(dst), _d2(dst), _i64(B * H * W, n, accumulate), _stream()),
-         "tmg_masked_add")
+    _chk(lib().tmg_masked_add(_ptr(src), _d2(src), _ptr(ref), _d2(ref), _ptr(add), _d2(add), _ptr(dst), _d2(dst),
+                              _i64(B * H * W, n, accumulate), _stream()), "tmg_masked_add")
 
 
 def c1_fwd(inputs, w, out, relu_in=True, w_rows=0, fill4=False, add=None, w_split=0, w_gap=0):
     B, H, W, _ = inputs[0].shape
     ip, idesc, n_in = _segs(inputs)
     Cin = sum(t.shape[3] for t in inputs)
-    ad = _d2(add) if add is not None else _i64(0, 0)
-    _chk(lib().tmg_c1_fwd_add(ip, idesc, c_i64(n_in), _ptr(w), _ptr(add), ad, _ptr(out), _d2(out),
+    _chk(lib().tmg_c1_fwd_add(ip, idesc, c_i64(n_in), _ptr(w), _ptr(add), _d2(add), _ptr(out), _d2(out),
                               _i64(B, H, W, Cin, relu_in, w_rows, fill4, w_split, w_gap), _stream()), "tmg_c1_fwd_add")
 
 
@@ -1056,9 +1007,7 @@ def c1x2_fwd(inputs, w1, w2, out, w_rows, w2_d1_row, add1=None, add2=None, w_spl
     B, H, W, _ = inputs[0].shape
     ip, idesc, n_in = _segs(inputs)
     Cin = sum(t.shape[3] for t in inputs)
-    z = _i64(0, 0)
-    _chk(lib().tmg_c1x2_fwd(ip, idesc, c_i64(n_in), _ptr(w1), _ptr(w2), _ptr(add1), _d2(add1) if add1 is not None else z, _ptr(add2),
-                            _d2(add2) if add2 is not None else z, _ptr(out), _d2(out),
+    _chk(lib().tmg_c1x2_fwd(ip, idesc, c_i64(n_in), _ptr(w1), _ptr(w2), _ptr(add1), _d2(add1), _ptr(add2), _d2(add2), _ptr(out), _d2(out),
                             _i64(B, H, W, Cin, relu_in, w_rows, w_split, w_gap, w2_d1_row), _stream()), "tmg_c1x2_fwd")
 
 
@@ -1067,8 +1016,7 @@ def c1_bwd(inputs, w, dW, dd, dref, gsegs, relu_in=True):
     ip, idesc, n_in = _segs(inputs)
     gp, gdesc, ng = _segs(gsegs)
     Cin = sum(t.shape[3] for t in inputs)
-    rd = _d2(dref) if dref is not None else _i64(0, 0)
-    _chk(lib().tmg_c1_bwd(ip, idesc, c_i64(n_in), _ptr(w), _ptr(dW), _ptr(dd), _d2(dd), _ptr(dref), rd, gp, gdesc, c_i64(ng),
+    _chk(lib().tmg_c1_bwd(ip, idesc, c_i64(n_in), _ptr(w), _ptr(dW), _ptr(dd), _d2(dd), _ptr(dref), _d2(dref), gp, gdesc, c_i64(ng),
                           _i64(B, H, W, Cin, relu_in), _stream()), "tmg_c1_bwd")
 
 
@@ -1097,10 +1045,6 @@ def dense2_bwd(inputs, w1p, w2p, dW1p, dW2p, GD, D, g0, outs, cin_nn, add0=None,
 # ------------------------------------------------------------------------------------------------
 # physics-constrained loss (row F1)
 # ------------------------------------------------------------------------------------------------
-def _flts(vals):
-    return (ctypes.c_float * len(vals))(*[float(v) for v in vals])
-
-
 def phys_fields(u, p, ustar, pstar, dx, dy, rho, k1, k2, scale):
     """Divergence / pressure-Poisson residual fields for 3x3 or 5x5 stencils, scaled or not (tmg_phys_fields).  u: contiguous
     [N,2,H,W]; p: contiguous [N,1,H,W] or None; ustar [N,1,H,W+2] / pstar [N,1,H,W] (either may be None)."""

@@ -22,6 +22,13 @@ def test_library_exports_every_declared_symbol():
     assert sorted(tmg_hip.EXPORTS) == declared
     for name in declared:
         assert hasattr(lib, name), name
+    # the return type the binding reads each export through is the header's: an int64_t workspace size read as int is truncated
+    ret = dict((n, t) for t, n in re.findall(r"\b(int|int64_t)\s+(tmg_\w+)\s*\(", hdr))
+    assert sorted(ret) == declared
+    bound = tmg_hip.lib()
+    for name in declared:
+        assert getattr(bound, name).restype is {"int": ctypes.c_int, "int64_t": ctypes.c_int64}[ret[name]], name
+    assert sorted(n for n in declared if ret[n] == "int64_t") == sorted(tmg_hip.RET_I64) and len(tmg_hip.RET_I64) == 4
 
 
 def test_state_dict_schema_and_seeded_init_match_reference():

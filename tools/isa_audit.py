@@ -2,11 +2,50 @@
 """Per-kernel census of an assembly listing (hipcc -S --cuda-device-only, the flags of tmg_hip.build): MFMAs, global / buffer loads
 and stores, `s_waitcnt vmcnt(0)` (a full drain of the vector-memory queue: in front of a store it serialises the stores behind a
 load in a conditional block), 64-bit vector address additions (v_lshl_add_u64: the fp32 MFMA shares the vector ALUs), scratch.
-usage: tools/isa_audit.py file.s [name-filter]"""
+usage: tools/isa_audit.py file.s [name-filter]
+       tools/isa_audit.py --digest file.s [file.s ...]: one line "<kernel symbol> <sha256 of its instructions> <sha256 of its
+       .amdhsa_ descriptor block>" per kernel, sorted (instructions: label to s_endpgm, comments stripped, local labels .LBB<i>_<j>
+       renumbered in order of appearance) - `diff` of two such listings proves that a host-side change left the device code alone."""
+import hashlib
 import re
 import subprocess
 import sys
 
+
+def digest(paths):
+    out = []
+    for path in paths:
+        lines = open(path).read().split("\n")
+        desc, name = {}, None
+        for ln in lines:
+            m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", ln)
+            if m:
+                name, desc[m.group(1)] = m.group(1), []
+            elif ".end_amdhsa_kernel" in ln:
+                name = None
+            elif name and ".amdhsa_" in ln:
+                desc[name].append(" ".join(ln.split(";")[0].split()))
+        name, body = None, []
+        for ln in lines:
+            m = re.match(r"^(\w+):", ln)
+            if m and m.group(1) in desc:
+                name, body, labels = m.group(1), [], {}
+                continue
+            if name is None:
+                continue
+            ln = " ".join(ln.split(";")[0].split())
+            if ln:
+                body.append(re.sub(r"\.LBB\d+_\d+", lambda k: labels.setdefault(k.group(0), ".L%d" % len(labels)), ln))
+            if ln.startswith("s_endpgm"):
+                h = [hashlib.sha256("\n".join(x).encode()).hexdigest()[:32] for x in (body, desc[name])]
+                out.append("%s %s %s" % (name, h[0], h[1]))
+                name = None
+    print("\n".join(sorted(out)))
+
+
+if sys.argv[1] == "--digest":
+    digest(sys.argv[2:])
+    sys.exit(0)
 txt = open(sys.argv[1]).read().split("\n")
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
 rows, name, body = [], None, []
