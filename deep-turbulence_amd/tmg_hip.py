@@ -39,7 +39,7 @@ EXPORTS = [
     "tmg_gauss_bwd", "tmg_checker", "tmg_upsample_fwd", "tmg_upsample_bwd", "tmg_chan_reduce", "tmg_bn_bwd_apply",
     "tmg_phys_fwd", "tmg_phys_rms", "tmg_phys_bwd", "tmg_conv_wgrad_grouped", "tmg_conv_wgrad_grouped_ws_floats", "tmg_conv_pack_batched", "tmg_masked_add", "tmg_c1x2_fwd", "tmg_c1_fwd", "tmg_c1_bwd", "tmg_dense2_bwd", "tmg_dkappa", "tmg_prof_enable", "tmg_prof_collect", "tmg_mix_f16", "tmg_phys_bwd_dev", "tmg_coupling_fwd", "tmg_coupling_bwd",
     "tmg_conv_wino_pack", "tmg_conv_wino_fwd", "tmg_conv_wino_narrow", "tmg_conv_wino_wgrad", "tmg_conv_wino_wgrad_ws_floats", "tmg_mix_f32", "tmg_lu_fold_fwd", "tmg_lu_fold_bwd", "tmg_lu_fold_bwd_split", "tmg_level_finish", "tmg_conv_wgrad_thin_grouped", "tmg_mix_wgrad_grouped", "tmg_layer_planes", "tmg_conv_wino_wgrad_grouped", "tmg_conv_wino_wgrad_grouped_ws_floats", "tmg_adam_step", "tmg_chan_moments", "tmg_bn_finalize64", "tmg_mix_f32_affine_fwd", "tmg_mix_f32_affine_bwd", "tmg_conv_pack_many", "tmg_pad_halves", "tmg_coupling_fwd_halves", "tmg_coupling_bwd_halves", "tmg_fill_i64", "tmg_conv_wino_pack3", "tmg_conv_wino_fwd3", "tmg_mat_inverse", "tmg_gauss_sample", "tmg_reverse_loss_fwd", "tmg_reverse_loss_bwd", "tmg_sum_terms", "tmg_vec_sum", "tmg_level_pack", "tmg_spread2", "tmg_phys_fields", "tmg_phys_fields_bwd",
-    "tmg_gauss_sample_keyed", "tmg_ens_accum", "tmg_ens_time_finalize",
+    "tmg_gauss_sample_keyed", "tmg_ens_accum", "tmg_ens_time_finalize", "tmg_ens_turb_accum", "tmg_ens_turb_finalize",
 ]
 # Every export returns int except the workspace sizes, which the header declares int64_t (read through a 32-bit return a request of
 # 2^31 floats or more would be truncated and the kernel handed a buffer smaller than it planned for).
@@ -882,6 +882,27 @@ def ens_time_finalize(tmean, tm2, tm_mean, tm_std, rms_mean, rms_std, S, B, HW, 
     """Per member time mean and RMS fluctuation over T steps, then their mean / std over the S members (tmg_ens_time_finalize)."""
     _chk(lib().tmg_ens_time_finalize(_ptr(tmean), _ptr(tm2), _ptr(tm_mean), _ptr(tm_std), _ptr(rms_mean), _ptr(rms_std),
                                      _i64(S, B, HW, C, T), _stream()), "tmg_ens_time_finalize")
+
+
+def ens_turb_accum(y, u, out_mu, out_std, tmean, vmean, vm2, cuv, tvort, outs, ostride, grid, k, n_before, m0, t_before, flags):
+    """The turbulence statistics of the chunk ens_accum folds (same y, u, k, n_before, m0, t_before, flags): vorticity on the grid
+    (dx, dy) into the step state (vmean, vm2) or, flags & 2, as (vort_mean, vort_std) = `outs` with per-case stride ostride; flags & 1
+    advances the members' time co-moment cuv and time-mean vorticity tvort.  Reads the time means ens_accum keeps in tmean as they
+    stand after t_before steps: call it before ens_accum on the chunk (tmg_ens_turb_accum)."""
+    kB, Hh, Ww, Cc = y.shape
+    ptr, ps, co, _ = seg(y)
+    outs = outs if outs is not None else (None,) * 2
+    _chk(lib().tmg_ens_turb_accum(c_vp(ptr), _i64(ps, co), _ptr(u), _ptr(out_mu), _ptr(out_std), _ptr(tmean), _ptr(vmean), _ptr(vm2),
+                                  _ptr(cuv), _ptr(tvort), *[_ptr(t) for t in outs],
+                                  _i64(k, kB // k, Hh, Ww, Cc, n_before, m0, t_before, flags, ostride), _flts(grid), _stream()),
+         "tmg_ens_turb_accum")
+
+
+def ens_turb_finalize(tm2, cuv, tvort, outs, S, B, HW, C, T):
+    """Per member <u'v'>, 0.5 (<u'u'> + <v'v'>) and time-mean vorticity over T steps, then mean / std of each over the S members into
+    outs = (uv_mean, uv_std, tke_mean, tke_std, vort_mean, vort_std) (tmg_ens_turb_finalize)."""
+    _chk(lib().tmg_ens_turb_finalize(_ptr(tm2), _ptr(cuv), _ptr(tvort), *[_ptr(t) for t in outs], _i64(S, B, HW, C, T), _stream()),
+         "tmg_ens_turb_finalize")
 
 
 def reverse_loss_fwd(y, ld, loss, s1, s2):

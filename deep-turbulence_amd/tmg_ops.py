@@ -1549,14 +1549,25 @@ class EnsembleStats:
 
     Feed every step's members in chunks of whole members, in member order (m0 = 0 first), each step's chunks before the next step's.
     Outputs (device tensors): mean, std [B, Tk, C, H, W]; mag_mean, mag_std [B, Tk, H, W]; finalize() adds time_mean_mean,
-    time_mean_std, time_rms_mean, time_rms_std [B, C, H, W]."""
+    time_mean_std, time_rms_mean, time_rms_std [B, C, H, W].
 
-    def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None):
+    grid=(dx, dy) adds the turbulence statistics (tmg_ens_turb_accum / tmg_ens_turb_finalize) of the velocity (channels 0, 1) on a
+    grid of cell size dx along W, dy along H: vort_mean, vort_std [B, Tk, H, W], the members' mean / population std per kept step of the
+    vorticity w = dv/dx - du/dy (3x3 first-derivative stencil of pc/, zero padding); finalize() adds time_uv_mean, time_uv_std (each
+    member's Reynolds shear stress <u'v'> over the time window), time_tke_mean, time_tke_std (its 0.5 (<u'u'> + <v'v'>)) and
+    time_vort_mean, time_vort_std (its time-mean vorticity), all [B, H, W].  The other outputs do not depend on grid."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, grid=None):
         if not (2 <= C <= 4):
             raise ValueError("ensemble statistics need 2 <= C <= 4 channels (the magnitude is formed from channels 0 and 1), got %d" % C)
+        if grid is not None:
+            grid = tuple(float(g) for g in grid)
+            if len(grid) != 2 or not all(math.isfinite(g) and g > 0 for g in grid):
+                raise ValueError("grid needs two positive finite cell sizes (dx, dy), got %s" % (grid,))
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("ensemble statistics run on the HIP path: device %s is not a GPU (there is no CPU path)" % dev)
+        self.grid = grid
         self.S, self.B, self.C, self.H, self.W, self.Tk = int(members), int(B), int(C), int(Hh), int(Ww), int(steps)
         HW = self.H * self.W
         f32 = dict(device=dev, dtype=torch.float32)
@@ -1569,6 +1580,10 @@ class EnsembleStats:
         self.time_state = torch.empty((2, self.S, B, C, HW), **f32)
         self.out = {"mean": torch.empty((B, self.Tk, C, Hh, Ww), **f32), "std": torch.empty((B, self.Tk, C, Hh, Ww), **f32),
                     "mag_mean": torch.empty((B, self.Tk, Hh, Ww), **f32), "mag_std": torch.empty((B, self.Tk, Hh, Ww), **f32)}
+        if grid is not None:
+            self.vort_state = torch.empty((2, B, HW), **f32)                 # the step's (mean, M2) of the vorticity
+            self.turb_state = torch.empty((2, self.S, B, HW), **f32)         # per member: time co-moment of (u, v), time-mean vorticity
+            self.out.update(vort_mean=torch.empty((B, self.Tk, Hh, Ww), **f32), vort_std=torch.empty((B, self.Tk, Hh, Ww), **f32))
         self._n = 0           # members folded into the current step
         self._step = 0        # the step being filled
         self._t = [0] * self.S  # steps folded into each member's time statistics
@@ -1590,9 +1605,14 @@ class EnsembleStats:
         HW = self.H * self.W
         o = self.out
         t = self._step
+        flags = (1 if time else 0) | (2 if last else 0)
+        if self.grid is not None:   # before ens_accum: it reads the members' time means as they stand after t_before steps
+            H.ens_turb_accum(yn, self.u, self.mu, self.sd, self.time_state[0], self.vort_state[0], self.vort_state[1], self.turb_state[0],
+                             self.turb_state[1], (o["vort_mean"][:, t], o["vort_std"][:, t]) if last else None, self.Tk * HW, self.grid, k,
+                             self._n, m0, t_before, flags)
         outs = (o["mean"][:, t], o["std"][:, t], o["mag_mean"][:, t], o["mag_std"][:, t]) if last else None
         H.ens_accum(yn, self.u, self.mu, self.sd, self.step_state[0], self.step_state[1], self.time_state[0], self.time_state[1], outs,
-                    (self.Tk * self.C * HW, self.Tk * HW), k, self._n, m0, t_before, (1 if time else 0) | (2 if last else 0))
+                    (self.Tk * self.C * HW, self.Tk * HW), k, self._n, m0, t_before, flags)
         if time:
             for m in range(m0, m0 + k):
                 self._t[m] += 1
@@ -1612,4 +1632,10 @@ class EnsembleStats:
             self.out[n] = torch.empty(shp, device=self.step_state.device, dtype=torch.float32)
         H.ens_time_finalize(self.time_state[0], self.time_state[1], *[self.out[n] for n in names], self.S, self.B, self.H * self.W,
                             self.C, T)
+        if self.grid is not None:
+            names = ("time_uv_mean", "time_uv_std", "time_tke_mean", "time_tke_std", "time_vort_mean", "time_vort_std")
+            for n in names:
+                self.out[n] = torch.empty((self.B, self.H, self.W), device=self.step_state.device, dtype=torch.float32)
+            H.ens_turb_finalize(self.time_state[1], self.turb_state[0], self.turb_state[1], [self.out[n] for n in names], self.S, self.B,
+                                self.H * self.W, self.C, T)
         return self.out

@@ -93,31 +93,25 @@ def modelPred(args, model, testing_loader, log, samples=1, stride=1, tmax=1):
     return torch.cat(preds, dim=1), torch.cat(targets, dim=0), torch.cat(inputs, dim=0)
 
 
-def modelPredStats(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64):
-    """Ensemble statistics of `samples` roll-outs per test case, computed on the device without forming modelPred's
-    [samples, N, T, C, H, W] tensor.  The roll-outs are modelPred's: fresh seeds from random_(0, 1e8) drawn member by member in
-    modelPred's order (cache=False), states re-anchored half-way to their seed states every 20 steps, fields un-normalised and scaled
-    by the case's inlet velocity u0 (velocities x u0, pressure x u0^2), every `stride`-th of `tmax` steps kept.  The members are
-    folded into TMGlow.sampleEnsemble calls of at most `max_rows` rows, each chunk holding whole members (one member per call when
-    a batch alone exceeds max_rows).
+# modelPredTurbulence's statistics of the target series <- the one-member EnsembleStats output that holds them
+_TARGET_STATS = (("target_time_mean", "time_mean_mean"), ("target_time_rms", "time_rms_mean"), ("target_time_uv", "time_uv_mean"),
+                 ("target_time_tke", "time_tke_mean"), ("target_time_vort", "time_vort_mean"))
 
-    Returns a dict of CPU tensors:
-      mean, std [N, Tk, C, H, W]        mean and population std (ddof 0) over the members, per kept step (Tk = tmax // stride)
-      mag_mean, mag_std [N, Tk, H, W]   the same of the velocity magnitude sqrt(ux^2 + uy^2)
-      time_mean_mean, time_mean_std     mean / std over the members of each member's time mean over the kept steps t_start..Tk-1
-      time_rms_mean, time_rms_std       ... of each member's RMS fluctuation sqrt(mean_t (y - mean_t y)^2) over those steps
-                                        (all four [N, C, H, W]; t_start indexes the kept steps)
-      target [N, T, C, H, W], input [N, T, 3, h, w]   as modelPred returns them."""
+
+def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, turbulence):
+    """The body of modelPredStats and modelPredTurbulence (turbulence: grid = (args.dx, args.dy)): same seed draws in the same order, same
+    folding, same re-anchoring, so that the keys the two share hold identical values under the same host RNG state."""
     import tmg_ops as ops
     core = getattr(model, "module", model)
     core.eval()
     dev = torch.device(args.device) if getattr(args, "device", None) is not None else next(core.parameters()).device
     if dev.type != "cuda" or next(core.parameters()).device.type != "cuda":
-        raise RuntimeError("modelPredStats runs on the HIP path: the model must live on a GPU (there is no CPU path)")
+        raise RuntimeError("%s runs on the HIP path: the model must live on a GPU (there is no CPU path)" % name)
+    grid = (args.dx, args.dy) if turbulence else None
     samples, max_rows = int(samples), int(max_rows)
     nkeep = tmax // stride
     if samples < 1 or nkeep < 1:
-        raise ValueError("modelPredStats needs samples >= 1 and tmax >= stride (samples=%d, tmax=%d, stride=%d)" % (samples, tmax, stride))
+        raise ValueError("%s needs samples >= 1 and tmax >= stride (samples=%d, tmax=%d, stride=%d)" % (name, samples, tmax, stride))
     if not 0 <= t_start < nkeep:
         raise ValueError("t_start=%d outside the %d kept steps" % (t_start, nkeep))
     shp = (1, -1, 1, 1)
@@ -135,7 +129,7 @@ def modelPredStats(args, model, testing_loader, log, samples=1, stride=1, tmax=1
             targets.append(tgt.cpu())
             B, C, Hh, Ww = inp.size(0), tgt.size(2), tgt.size(-2), tgt.size(-1)
             if C != 3:
-                raise ValueError("modelPredStats scales (ux, uy, p) by (u0, u0, u0^2) as modelPred does: 3 target channels, got %d" % C)
+                raise ValueError("%s scales (ux, uy, p) by (u0, u0, u0^2) as modelPred does: 3 target channels, got %d" % (name, C))
             keys = []
             for i in range(samples):                                   # modelPred's seed draws, member by member
                 seeds = torch.LongTensor(B).random_(0, int(1e8))
@@ -146,7 +140,7 @@ def modelPredStats(args, model, testing_loader, log, samples=1, stride=1, tmax=1
             anchors = [[tuple(torch.cat([keys[m0 + j][lv][s] for j in range(k)]) for s in (0, 1)) for lv in range(len(keys[0]))]
                        for m0, k in chunks]
             states = [[(h.clone(), c.clone()) for h, c in a] for a in anchors]
-            st = ops.EnsembleStats(samples, B, C, Hh, Ww, nkeep, dev, out_mu, out_std, u=u.view(B, 3)[:, :C])
+            st = ops.EnsembleStats(samples, B, C, Hh, Ww, nkeep, dev, out_mu, out_std, u=u.view(B, 3)[:, :C], grid=grid)
             for tstep in range(tmax):
                 keep = tstep % stride == 0 and tstep // stride < nkeep
                 for ci, (m0, k) in enumerate(chunks):
@@ -155,9 +149,57 @@ def modelPredStats(args, model, testing_loader, log, samples=1, stride=1, tmax=1
                         st.add(y0, m0, time=tstep // stride >= t_start)
                     if tstep % 20 == 0:
                         states[ci] = [(0.5 * h + 0.5 * hk, 0.5 * c + 0.5 * ck) for (h, c), (hk, ck) in zip(states[ci], anchors[ci])]
-            for name, t in st.finalize().items():
-                outs.setdefault(name, []).append(t.cpu())
-    res = {name: torch.cat(v, dim=0) for name, v in outs.items()}
+            for key, t in st.finalize().items():
+                outs.setdefault(key, []).append(t.cpu())
+            if grid is not None:
+                # the target's own time statistics over the same kept steps: the normalised series as a one-member ensemble
+                if target0.size(1) <= (nkeep - 1) * stride:
+                    raise ValueError("%s: the target series holds %d steps, kept step %d needs step %d"
+                                     % (name, target0.size(1), nkeep - 1, (nkeep - 1) * stride))
+                tn = target0.to(dev)
+                ts = ops.EnsembleStats(1, B, C, Hh, Ww, nkeep - t_start, dev, out_mu, out_std, u=u.view(B, 3)[:, :C], grid=grid)
+                for j in range(t_start, nkeep):
+                    ts.add(tn[:, j * stride].contiguous(memory_format=torch.channels_last), 0)
+                tout = ts.finalize()
+                for key, src in _TARGET_STATS:
+                    outs.setdefault(key, []).append(tout[src].cpu())
+    res = {key: torch.cat(v, dim=0) for key, v in outs.items()}
     res["target"] = torch.cat(targets, dim=0)
     res["input"] = torch.cat(inputs, dim=0)
     return res
+
+
+def modelPredStats(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64):
+    """Ensemble statistics of `samples` roll-outs per test case, computed on the device without forming modelPred's
+    [samples, N, T, C, H, W] tensor.  The roll-outs are modelPred's: fresh seeds from random_(0, 1e8) drawn member by member in
+    modelPred's order (cache=False), states re-anchored half-way to their seed states every 20 steps, fields un-normalised and scaled
+    by the case's inlet velocity u0 (velocities x u0, pressure x u0^2), every `stride`-th of `tmax` steps kept.  The members are
+    folded into TMGlow.sampleEnsemble calls of at most `max_rows` rows, each chunk holding whole members (one member per call when
+    a batch alone exceeds max_rows).
+
+    Returns a dict of CPU tensors:
+      mean, std [N, Tk, C, H, W]        mean and population std (ddof 0) over the members, per kept step (Tk = tmax // stride)
+      mag_mean, mag_std [N, Tk, H, W]   the same of the velocity magnitude sqrt(ux^2 + uy^2)
+      time_mean_mean, time_mean_std     mean / std over the members of each member's time mean over the kept steps t_start..Tk-1
+      time_rms_mean, time_rms_std       ... of each member's RMS fluctuation sqrt(mean_t (y - mean_t y)^2) over those steps
+                                        (all four [N, C, H, W]; t_start indexes the kept steps)
+      target [N, T, C, H, W], input [N, T, 3, h, w]   as modelPred returns them."""
+    return _ensembleStats("modelPredStats", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False)
+
+
+def modelPredTurbulence(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64):
+    """modelPredStats plus the turbulence statistics of the velocity field (channels 0, 1) on the grid (args.dx along W, args.dy
+    along H), still without forming modelPred's [samples, N, T, C, H, W] tensor.  Same roll-outs as modelPredStats: under the same
+    host RNG state the keys both return are identical.
+
+    Returns modelPredStats' dict plus (CPU tensors):
+      vort_mean, vort_std [N, Tk, H, W]       mean / population std over the members of the vorticity w = dv/dx - du/dy (3x3
+                                              first-derivative stencil of pc/, zero padding), per kept step
+      time_uv_mean, time_uv_std [N, H, W]     mean / std over the members of each member's Reynolds shear stress <u'v'> over the
+                                              kept steps t_start..Tk-1
+      time_tke_mean, time_tke_std             ... of each member's turbulent kinetic energy 0.5 (<u'u'> + <v'v'>)
+      time_vort_mean, time_vort_std           ... of each member's time-mean vorticity
+      target_time_mean, target_time_rms [N, C, H, W], target_time_uv, target_time_tke, target_time_vort [N, H, W]
+                                              the same time statistics of the target series over the same steps (target step
+                                              j * stride for kept step j), through the same kernels as a one-member ensemble."""
+    return _ensembleStats("modelPredTurbulence", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, True)

@@ -434,6 +434,22 @@ int tmg_ens_accum(const void* y, const int64_t* y_d, const void* u, const void* 
  * over the S members: tm_mean, tm_std, rms_mean, rms_std [B][C][HW].  dims = {S, B, HW, C, T}. */
 int tmg_ens_time_finalize(const void* tmean, const void* tm2, void* tm_mean, void* tm_std, void* rms_mean, void* rms_std,
                           const int64_t* dims, tmg_stream_t st);
+/* Turbulence statistics of the same chunk (same y, y_d, u, out_mu, out_std, row order and flags as tmg_ens_accum): the vorticity
+ * w = d(yh1)/dx - d(yh0)/dy of every member with the 3x3 first-derivative stencil of pc/ (zero padding, x along W, y along H) is
+ * folded into the step state vmean, vm2 [B][HW] and, on the step's last chunk, written as mean / population std to vort_mean /
+ * vort_std (+ b * dims[9]).  flags & 1: each member's time co-moment cuv += (yh0 - mean0_old) (yh1 - mean1_new) and the time mean
+ * tvort of its vorticity, both [S][B][HW], advance by one step; the running means of channels 0 and 1 are read from tmean
+ * [S][B][C][HW] as tmg_ens_accum left them after t_before steps, so call this BEFORE tmg_ens_accum on the chunk (tmean is not
+ * written here, and not read when t_before = 0).  dims = {k, B, H, W, C, n_before, m0, t_before, flags, per-case stride of the
+ * outputs}; fl = {dx, dy}, positive and finite (else -1). */
+int tmg_ens_turb_accum(const void* y, const int64_t* y_d, const void* u, const void* out_mu, const void* out_std, const void* tmean,
+                       void* vmean, void* vm2, void* cuv, void* tvort, void* vort_mean, void* vort_std, const int64_t* dims,
+                       const float* fl, tmg_stream_t st);
+/* Per member <u'v'> = cuv / T, k = 0.5 (tm2[channel 0] + tm2[channel 1]) / T (tm2 [S][B][C][HW]: the M2 planes of tmg_ens_accum) and
+ * its time-mean vorticity tvort, then the mean and population std of each over the S members, all [B][HW].
+ * dims = {S, B, HW, C, T}. */
+int tmg_ens_turb_finalize(const void* tm2, const void* cuv, const void* tvort, void* uv_mean, void* uv_std, void* tke_mean,
+                          void* tke_std, void* tv_mean, void* tv_std, const int64_t* dims, tmg_stream_t st);
 
 /* The benchmark loss of SURVEY 8-D, generative direction: *loss += fl[0] sum(y^2) + fl[1] sum(logdet) (the caller zeroes *loss;
  * fl = {1 / numel(y), 1 / (B noc H W)}), and its gradient dy = 2 fl[0] *g y, dld[b] = fl[1] *g with the upstream gradient read from
