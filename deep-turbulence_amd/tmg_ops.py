@@ -6,6 +6,7 @@ that are pure bookkeeping (e.g. d(kappa) from <W,dW>+<b,db>) are a handful of sc
 
 All activations are NHWC ([B,H,W,C] contiguous, or channel-slice views of such tensors).
 """
+import collections
 import math
 
 import os
@@ -53,7 +54,7 @@ class _ZeroPool:
             self.cur[key] = (buf, off + need)
         # not a view: a tensor of its own on the chunk's storage - views of one base share a version counter, and an in-place torch
         # op on one carved buffer would invalidate every other one that some autograd node has saved
-        return torch.empty(0, device=device, dtype=torch.float32).set_(buf.untyped_storage(), off, shape)
+        return empty(0, device).set_(buf.untyped_storage(), off, shape)
 
 
 _pool = _ZeroPool()
@@ -66,6 +67,23 @@ def zeros(shape, device):
 
 def zeros_like(t):
     return _pool.zeros(t.shape, t.device)
+
+
+def empty(shape, device):
+    """Uninitialised fp32 buffer on `device`: an activation or gradient that the launch after it writes whole."""
+    return torch.empty(shape, device=device, dtype=torch.float32)
+
+
+def carve(device, *shapes):
+    """One view per shape, back to back in the order given, of ONE zero-filled flat buffer: the parameter gradients of a node for
+    one zeros() call."""
+    sizes = [math.prod(s) for s in shapes]
+    flat = zeros(sum(sizes), device)
+    views, o = [], 0
+    for s, n in zip(shapes, sizes):
+        views.append(flat[o:o + n].view(s))
+        o += n
+    return views
 
 
 # Bumped by every writer of parameter memory that torch's version counters do not see (tmg_optim.HipAdam updates the parameters
@@ -277,7 +295,7 @@ class ConvFn(torch.autograd.Function):
         B, Hin, Win, _ = inputs[0].shape
         Cout = weight.shape[0]
         Ho, Wo = _out_hw(Hin, Win, stride)
-        out = torch.empty((B, Ho, Wo, Cout), device=weight.device, dtype=torch.float32)
+        out = empty((B, Ho, Wo, Cout), weight.device)
         if ksize == 3 and stride == 1 and kappa is None:
             H.conv3x3_auto(list(inputs), weight, Cout, [out], bias=bias, relu_in=relu_in, pad_rep=pad_rep, relu_out=relu_out)
         else:
@@ -321,7 +339,7 @@ class ConvFn(torch.autograd.Function):
                 H.dkappa(weight, dW, bias if ctx.has_bias else weight[:0], db if ctx.has_bias else dW[:0], kappa, dk)
         dins = [None] * ctx.n_in
         if any(ctx.needs_input_grad[4:]):
-            dins = [torch.empty(t.shape, device=t.device, dtype=torch.float32) for t in inputs]
+            dins = [empty(t.shape, t.device) for t in inputs]
             if stride == 1:
                 cin = sum(t.shape[3] for t in inputs)
                 if ksize == 3 and kappa is None:
@@ -339,7 +357,7 @@ class ConvFn(torch.autograd.Function):
                     # = a stride-1 correlation with the flipped taps over dy spread onto the even positions of a zero grid
                     # (4x the minimal MFMA work, but these encoder convs have 8-32 channels: the scalar direct kernel spent
                     # 260 us per call at 0.12 TB/s on them)
-                    up = torch.empty((dy.shape[0], Hin_, Win_, dy.shape[3]), device=dy.device, dtype=torch.float32)
+                    up = empty((dy.shape[0], Hin_, Win_, dy.shape[3]), dy.device)
                     if not H.spread2(dy, up):
                         up.zero_()
                         up[:, ::2, ::2] = dy
@@ -372,7 +390,7 @@ class BNReLUConvFn(torch.autograd.Function):
         x = x if x.stride(3) == 1 else x.contiguous()
         B, Hh, Ww, _ = x.shape
         Cout = weight.shape[0]
-        out = torch.empty((B, Hh, Ww, Cout), device=x.device, dtype=torch.float32)
+        out = empty((B, Hh, Ww, Cout), x.device)
         wpk = H.conv_pack(weight, 0)
         H.conv_fwd([x], wpk, Cout, 3, 1, [out], in_scale=a, in_shift=bsh, relu_in=True)
         ctx.training = training
@@ -388,13 +406,13 @@ class BNReLUConvFn(torch.autograd.Function):
         dW = zeros_like(weight)
         H.conv_wgrad([x], dy, dW, None, 3, 1, in_scale=a, in_shift=bsh, relu_in=True)
         wpk_t = H.conv_pack(weight, 1)
-        G = torch.empty((B, Hh, Ww, C), device=x.device, dtype=torch.float32)
+        G = empty((B, Hh, Ww, C), x.device)
         H.conv_fwd([dy], wpk_t, C, 3, 1, [G])
         s = zeros((3, C), x.device)  # sums of du, du*xhat, and a zero row for the eval-mode call
         s0, s1 = s[0], s[1]
         H.chan_reduce(x, G, a, bsh, mean, rstd, s0, s1, 1)
         dgamma, dbeta = s1, s0
-        dx = torch.empty((B, Hh, Ww, C), device=x.device, dtype=torch.float32)
+        dx = empty((B, Hh, Ww, C), x.device)
         if ctx.training:
             H.bn_bwd_apply(x, G, a, bsh, mean, rstd, gamma, s0, s1, dx, False, divisor=n)
         else:
@@ -418,7 +436,7 @@ class DenseBlockFn(torch.autograd.Function):
         x = x if x.stride(3) == 1 else x.contiguous()
         B, Hh, Ww, c0 = x.shape
         growth = [params[3 * i + 2].shape[0] for i in range(L)]
-        buf = torch.empty((B, Hh, Ww, c0 + sum(growth)), device=x.device, dtype=torch.float32)
+        buf = empty((B, Hh, Ww, c0 + sum(growth)), x.device)
         H.masked_add(buf[..., :c0], src=x)
         # forward and input-gradient operands of all L layers in one launch per 16 (one pack launch per layer and direction otherwise)
         ws = [params[3 * i + 2].contiguous() for i in range(L)]
@@ -466,7 +484,7 @@ class DenseBlockFn(torch.autograd.Function):
             xin, dy = buf[..., :c], dbuf[..., c:c + g]
             dW = zeros_like(weight)
             H.conv_wgrad([xin], dy, dW, None, 3, 1, in_scale=a, in_shift=bsh, relu_in=True)
-            G = torch.empty((B, Hh, Ww, c), device=buf.device, dtype=torch.float32)
+            G = empty((B, Hh, Ww, c), buf.device)
             H.conv_fwd([dy], ctx.packs_t[i], c, 3, 1, [G])
             s = zeros((3, c), buf.device)   # sums of du, du*xhat, and a zero row for the eval-mode call
             H.chan_reduce(xin, G, a, bsh, mean, rstd, s[0], s[1], 1)
@@ -526,9 +544,9 @@ class AffineFn(torch.autograd.Function):
         hh = hh.contiguous()
         B, Hh, Ww, C = x.shape
         ch = C // 2
-        y = torch.empty((B, Hh, Ww, C), device=x.device, dtype=torch.float32)
+        y = empty((B, Hh, Ww, C), x.device)
         H.masked_add(y[..., :ch], src=x[..., :ch])
-        r = torch.empty((B, Hh, Ww, ch), device=x.device, dtype=torch.float32)
+        r = empty((B, Hh, Ww, ch), x.device)
         logdet = zeros(B, x.device)
         H.affine_apply(hh, x[..., ch:], y[..., ch:], r, logdet, reverse)
         ctx.reverse = reverse
@@ -543,7 +561,7 @@ class AffineFn(torch.autograd.Function):
         ch = C // 2
         dx = torch.empty_like(dy)
         H.masked_add(dx[..., :ch], src=dy[..., :ch])
-        dhh = torch.empty((B, Hh, Ww, C), device=dy.device, dtype=torch.float32)
+        dhh = empty((B, Hh, Ww, C), dy.device)
         g = dld.contiguous() if dld is not None else None
         H.affine_bwd(dy[..., ch:], ref[..., ch:], r, g, dx[..., ch:], dhh, ctx.reverse)
         return dhh, dx, None
@@ -559,8 +577,8 @@ class LSTMPointwiseFn(torch.autograd.Function):
         R = R4 // 4
         if c_prev is not None and c_prev.stride(3) != 1:
             c_prev = c_prev.contiguous()
-        c_next = torch.empty((B, Hh, Ww, R), device=acts.device, dtype=torch.float32)
-        h_next = torch.empty((B, Hh, Ww, R), device=acts.device, dtype=torch.float32)
+        c_next = empty((B, Hh, Ww, R), acts.device)
+        h_next = empty((B, Hh, Ww, R), acts.device)
         H.lstm_pointwise_fwd(acts, c_prev, c_next, h_next)
         ctx.has_c = c_prev is not None
         ctx.save_for_backward(acts, c_prev, c_next)
@@ -593,12 +611,12 @@ class ConvLSTMCellFn(torch.autograd.Function):
         R4 = weight.shape[0]
         R = R4 // 4
         dev = weight.device
-        gates = torch.empty((B, Hh, Ww, R4), device=dev, dtype=torch.float32)
+        gates = empty((B, Hh, Ww, R4), dev)
         segs = list(inputs) + [h_cur]
         # the widest contraction of the path (Cin + R -> 4R channels): Winograd F(2x2, 3x3) when the shape is in its envelope
         H.conv3x3_auto(segs, weight, R4, [gates], bias=bias)
-        c_next = torch.empty((B, Hh, Ww, R), device=dev, dtype=torch.float32)
-        h_next = torch.empty((B, Hh, Ww, R), device=dev, dtype=torch.float32)
+        c_next = empty((B, Hh, Ww, R), dev)
+        h_next = empty((B, Hh, Ww, R), dev)
         H.lstm_pointwise_fwd(gates, c_cur, c_next, h_next)
         ctx.n_in = len(inputs)
         ctx.has_c = c_cur is not None
@@ -639,7 +657,7 @@ class ConvLSTMCellFn(torch.autograd.Function):
         dins = [None] * len(segs)
         if last >= 0:
             nch = sum(t.shape[3] for t in segs[:last + 1])
-            dins[:last + 1] = [torch.empty(t.shape, device=t.device, dtype=torch.float32) for t in segs[:last + 1]]
+            dins[:last + 1] = [empty(t.shape, t.device) for t in segs[:last + 1]]
             H.conv3x3_auto([dg], weight, nch, dins[:last + 1], dgrad=True, nvalid=nch)
         return _defer((weight, bias), (dW, db)) + (dins[-1], dc_prev if ctx.has_c else None) + tuple(dins[:-1])
 
@@ -653,7 +671,7 @@ class GaussLogpFn(torch.autograd.Function):
         z2 = z2 if z2.stride(3) == 1 else z2.contiguous()
         B = z2.shape[0]
         logp = zeros(B, z2.device)
-        eps = torch.empty(z2.shape, device=z2.device, dtype=torch.float32) if want_eps else None
+        eps = empty(z2.shape, z2.device) if want_eps else None
         H.gauss_fwd(hz, z2, eps, logp, 0, clip_mean, limits)
         ctx.cfg = (clip_mean, limits)
         ctx.save_for_backward(hz, z2)
@@ -664,7 +682,7 @@ class GaussLogpFn(torch.autograd.Function):
     def backward(ctx, g, _geps):
         hz, z2 = ctx.saved_tensors
         clip_mean, limits = ctx.cfg
-        dz2 = torch.empty(z2.shape, device=z2.device, dtype=torch.float32)
+        dz2 = empty(z2.shape, z2.device)
         dhz = torch.empty_like(hz)
         H.gauss_bwd(hz, z2, None, g.contiguous(), dz2, dhz, 0, clip_mean, limits)
         return dhz, dz2, None, None, None
@@ -679,7 +697,7 @@ class GaussSampleFn(torch.autograd.Function):
         eps = eps.contiguous()
         B = eps.shape[0]
         logp = zeros(B, eps.device)
-        z2 = torch.empty(eps.shape, device=eps.device, dtype=torch.float32)
+        z2 = empty(eps.shape, eps.device)
         H.gauss_fwd(hz, eps, z2, logp, 1, clip_mean, limits)
         ctx.cfg = (clip_mean, limits)
         ctx.save_for_backward(hz, eps)
@@ -725,13 +743,13 @@ class GaussDrawFn(torch.autograd.Function):
         dev = hz.device
         if z1 is not None and z1.stride(3) != 1:
             z1 = z1.contiguous()
-        out = torch.empty((B, Hh, Ww, 2 * Ch if z1 is not None else Ch), device=dev, dtype=torch.float32)
+        out = empty((B, Hh, Ww, 2 * Ch if z1 is not None else Ch), dev)
         logp = zeros(B, dev)
         if eps is not None:
             eps = eps if eps.stride(3) == 1 else eps.contiguous()
             H.gauss_sample(hz, eps, z1, out, logp, clip_mean, limits)
         else:
-            eps = torch.empty((B, Hh, Ww, Ch), device=dev, dtype=torch.float32)
+            eps = empty((B, Hh, Ww, Ch), dev)
             if len(rng) == 3:
                 table, site, rows_per_key = rng
                 H.gauss_sample_keyed(hz, None, z1, out, logp, clip_mean, limits, table, rows_per_key, site=site, eps_out=eps)
@@ -779,7 +797,7 @@ class ReverseLossFn(torch.autograd.Function):
         yn, = ctx.saved_tensors
         n = yn.numel()
         dyn = torch.empty_like(yn)
-        dld = torch.empty(ctx.B, device=yn.device, dtype=torch.float32)
+        dld = empty(ctx.B, yn.device)
         H.reverse_loss_bwd(yn, g.contiguous(), dyn, dld, 1.0 / n, 1.0 / n)
         return dyn.permute(0, 3, 1, 2), dld
 
@@ -797,7 +815,7 @@ class SumTermsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, B, *terms):
         ts = [t.reshape(-1) if t.is_contiguous() else t.contiguous().reshape(-1) for t in terms]
-        out = torch.empty(B, device=ts[0].device, dtype=torch.float32)
+        out = empty(B, ts[0].device)
         H.sum_terms(ts, out)
         ctx.meta = [(t.numel(), t.shape) for t in terms]
         return out
@@ -812,7 +830,7 @@ class SumTermsFn(torch.autograd.Function):
                 outs.append(g)
             elif n == 1:
                 if gs is None:
-                    gs = torch.empty(1, device=g.device, dtype=torch.float32)
+                    gs = empty(1, g.device)
                     H.vec_sum(g, gs)
                 outs.append(gs.view(shape))
             else:
@@ -848,10 +866,10 @@ class CheckerFn(torch.autograd.Function):
         B, Hh, Ww, C = x.shape
         if to_small:
             assert Hh % 2 == 0 and Ww % 2 == 0
-            y = torch.empty((B, Hh // 2, Ww // 2, 4 * C), device=x.device, dtype=torch.float32)
+            y = empty((B, Hh // 2, Ww // 2, 4 * C), x.device)
         else:
             assert C >= 4 and C % 4 == 0
-            y = torch.empty((B, Hh * 2, Ww * 2, C // 4), device=x.device, dtype=torch.float32)
+            y = empty((B, Hh * 2, Ww * 2, C // 4), x.device)
         H.checker(x, y, to_small)
         ctx.to_small = to_small
         return y
@@ -861,9 +879,9 @@ class CheckerFn(torch.autograd.Function):
         dy = dy.contiguous()
         B, Hh, Ww, C = dy.shape
         if ctx.to_small:
-            dx = torch.empty((B, Hh * 2, Ww * 2, C // 4), device=dy.device, dtype=torch.float32)
+            dx = empty((B, Hh * 2, Ww * 2, C // 4), dy.device)
         else:
-            dx = torch.empty((B, Hh // 2, Ww // 2, 4 * C), device=dy.device, dtype=torch.float32)
+            dx = empty((B, Hh // 2, Ww // 2, 4 * C), dy.device)
         H.checker(dy, dx, not ctx.to_small)
         return dx, None
 
@@ -877,7 +895,7 @@ class PadHalvesFn(torch.autograd.Function):
     def forward(ctx, x, ch, pad, to_padded):
         x = x if x.stride(3) == 1 else x.contiguous()
         B, Hh, Ww, _ = x.shape
-        y = torch.empty((B, Hh, Ww, 2 * (ch + pad) if to_padded else 2 * ch), device=x.device, dtype=torch.float32)
+        y = empty((B, Hh, Ww, 2 * (ch + pad) if to_padded else 2 * ch), x.device)
         H.pad_halves(x, y, ch, pad, to_padded)
         ctx.cfg = (ch, pad, to_padded)
         return y
@@ -887,7 +905,7 @@ class PadHalvesFn(torch.autograd.Function):
         ch, pad, to_padded = ctx.cfg
         dy = dy if dy.stride(3) == 1 else dy.contiguous()
         B, Hh, Ww, _ = dy.shape
-        dx = torch.empty((B, Hh, Ww, 2 * ch if to_padded else 2 * (ch + pad)), device=dy.device, dtype=torch.float32)
+        dx = empty((B, Hh, Ww, 2 * ch if to_padded else 2 * (ch + pad)), dy.device)
         H.pad_halves(dy, dx, ch, pad, not to_padded)
         return dx, None, None, None
 
@@ -900,14 +918,14 @@ class UpsampleFn(torch.autograd.Function):
         x = x.contiguous()
         B, Hh, Ww, C = x.shape
         ho, wo = int(math.floor(Hh * scale)), int(math.floor(Ww * scale))
-        y = torch.empty((B, ho, wo, C), device=x.device, dtype=torch.float32)
+        y = empty((B, ho, wo, C), x.device)
         H.upsample_fwd(x, y)
         ctx.in_shape = (B, Hh, Ww, C)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        dx = torch.empty(ctx.in_shape, device=dy.device, dtype=torch.float32)
+        dx = empty(ctx.in_shape, dy.device)
         H.upsample_bwd(dy.contiguous(), dx)
         return dx, None
 
@@ -936,13 +954,13 @@ class CouplingTailFn(torch.autograd.Function):
         nn_in = [x[..., :ch], aux] if mode == 0 else [aux]
         cin = sum(t.shape[3] for t in nn_in)
         w1, w2, wz = w1.contiguous(), w2.contiguous(), wz.contiguous()
-        D = torch.empty((B, Hh, Ww, 4), device=dev, dtype=torch.float32)
+        D = empty((B, Hh, Ww, 4), dev)
         H.c1_fwd(nn_in, w1, D[..., 0:1], relu_in=True, fill4=True)   # writes (d1, 0, 0, 0)
         H.c1_fwd(nn_in + [D], w2, D[..., 1:2], relu_in=True, w_rows=cin + 1)
-        hh = torch.empty((B, Hh, Ww, C), device=dev, dtype=torch.float32)
+        hh = empty((B, Hh, Ww, C), dev)
         H.conv_fwd(nn_in + [D], H.conv_pack(wz, 0, cin + 4), C, 3, 1, [hh], bias=bz, kappa=kappa, relu_in=True, pad_rep=True)
-        y = torch.empty((B, Hh, Ww, C), device=dev, dtype=torch.float32)
-        r = torch.empty((B, Hh, Ww, ch), device=dev, dtype=torch.float32)
+        y = empty((B, Hh, Ww, C), dev)
+        r = empty((B, Hh, Ww, ch), dev)
         logdet = zeros(B, dev)
         H.affine_apply(hh, x[..., ch:], y[..., ch:], r, logdet, reverse, x1=x[..., :ch], y1=y[..., :ch])   # pass-through half in the same launch
         ctx.reverse, ctx.mode, ctx.cin = reverse, mode, cin
@@ -959,23 +977,17 @@ class CouplingTailFn(torch.autograd.Function):
         dev = dy.device
         nn_in = [x[..., :ch], aux] if mode == 0 else [aux]
         # 1. affine
-        dx = torch.empty((B, Hh, Ww, C), device=dev, dtype=torch.float32)
-        dhh = torch.empty((B, Hh, Ww, C), device=dev, dtype=torch.float32)
+        dx = empty((B, Hh, Ww, C), dev)
+        dhh = empty((B, Hh, Ww, C), dev)
         g = dld.contiguous() if dld is not None else None
         H.affine_bwd(dy[..., ch:], (x if reverse else y)[..., ch:], r, g, dx[..., ch:], dhh, reverse)
         # one zero-filled buffer for every parameter gradient of this node
-        n1, n2, nz = cin * 9, (cin + 1) * 9, C * (cin + 2) * 9
-        flat = zeros(n1 + n2 + nz + C + 1, dev)
-        dw1 = flat[:n1].view(1, cin, 3, 3)
-        dw2 = flat[n1:n1 + n2].view(1, cin + 1, 3, 3)
-        dwz = flat[n1 + n2:n1 + n2 + nz].view(C, cin + 2, 3, 3)
-        dbz = flat[n1 + n2 + nz:n1 + n2 + nz + C]
-        dk = flat[n1 + n2 + nz + C:].view(kappa.shape)
+        dw1, dw2, dwz, dbz, dk = carve(dev, (1, cin, 3, 3), (1, cin + 1, 3, 3), (C, cin + 2, 3, 3), (C,), kappa.shape)
         # 2. zero-conv weight / bias / scale gradients
         H.conv_wgrad(nn_in + [D], dhh, dwz, dbz, 3, 1, kappa=kappa, relu_in=True, pad_rep=True, cin_dst=cin + 2)
         H.dkappa(wz, dwz, bz, dbz, kappa, dk)
-        G = [torch.empty(t.shape, device=dev, dtype=torch.float32) for t in nn_in]
-        GD = torch.empty((B, Hh, Ww, 4), device=dev, dtype=torch.float32)
+        G = [empty(t.shape, dev) for t in nn_in]
+        GD = empty((B, Hh, Ww, 4), dev)
         wz_t = H.conv_pack(wz, 1, cin + 4)
         H.conv_fwd([dhh], wz_t, cin + 4, 3, 1, G + [GD], kappa=kappa)
         H.conv_rep_border_fix(dhh, wz_t, G + [GD], kappa=kappa)
@@ -1048,7 +1060,7 @@ def _mix16_ok(C):
 def _mix_fwd(x, Wk, bk, packed=None):
     """y = Wk x + bk per pixel (ActNorm folded into the invertible 1x1 conv).  packed: Wk already in operand order."""
     C = Wk.shape[0]
-    y = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    y = empty(x.shape, x.device)
     if _mix16_ok(C):
         H.mix_f16(x, Wk.contiguous(), bk, y)
         return y
@@ -1079,21 +1091,46 @@ class MixFn(torch.autograd.Function):
         return dx, dW, (db if ctx.has_b else None)
 
 
-def _mix_bwd(x, dy, Wk, dWk, dbk, packed_t=None, defer=None):
-    """Input gradient of _mix_fwd (returned) and weight / bias gradients (accumulated into dWk [C,C], dbk [C]).
-    defer: list collecting (x, dy) instead - the caller runs the weight gradients of a whole level as one grouped launch."""
+def _mix_dgrad(dy, Wk, packed_t=None):
+    """Input gradient of _mix_fwd."""
     C = Wk.shape[0]
-    dx = torch.empty(dy.shape, device=dy.device, dtype=torch.float32)
+    dx = empty(dy.shape, dy.device)
     if _mix16_ok(C):
         H.mix_f16(dy, Wk.contiguous(), None, dx, transposed=True)
     elif not H.mix_f32(dy, Wk.contiguous(), None, dx, transposed=True):
         H.conv_fwd([dy], packed_t if packed_t is not None else H.conv_pack(Wk.reshape(C, C, 1, 1), 1), C, 1, 1, [dx])
-    xs = x if isinstance(x, list) else [x]      # the mix input may be given as channel segments
-    if defer is not None:
-        defer.append((xs, dy))
-    else:
-        H.conv_wgrad(xs, dy, dWk, dbk, 1, 1)
     return dx
+
+
+def _mix_bwd(x, dy, Wk, dWk, dbk):
+    """Input gradient of _mix_fwd (returned) and weight / bias gradients (accumulated into dWk [C,C], dbk [C])."""
+    dx = _mix_dgrad(dy, Wk)
+    H.conv_wgrad([x], dy, dWk, dbk, 1, 1)
+    return dx
+
+
+# One flow level as LevelCouplingFn sees it (built once per forward pass and carried on ctx); w1s .. kps: (w1, w2, wz, bz, kappa) per layer
+_Level = collections.namedtuple("_Level", "NL NLp C ch Cc cin reverse fuse split rec w1s w2s wzs bzs kps")
+# What the per-layer steps of LevelCouplingFn.backward share (see there)
+_LevelBwd = collections.namedtuple("_LevelBwd", "g Wm PZt PMt DH DD quad_last grouped zc_kw wg_in mix_wg dWz dBz dW1 dW2 dWm dbm")
+
+
+def _level(wts, C, Cc, reverse):
+    NL = len(wts) // 5
+    ch = C // 2
+    fuse = 8 <= C <= 32 and ch % 4 == 0 and all(w.is_contiguous() for w in wts)     # narrow levels: see LevelCouplingFn._fwd_fused
+    # Split-halves layout (round 4; generative direction on the levels whose per-layer kernels are bandwidth-bound): between
+    # the layers of the node an activation lives as TWO [B,h,w,C/2] tensors (x1, x2) instead of one [B,h,w,C].  The kernels
+    # that read x1 alone - growth layers, their backward, three weight gradients - then use every byte of the lines they
+    # fetch (a 64-byte pixel of the 16-channel level shares its 128-byte line with the neighbour's other half), and the fused
+    # coupling kernel's x1 patch loads and x2 epilogue loads no longer pull each other's half-used lines through L2 twice.
+    # The node's input and output stay single tensors (addressed as two channel-slice views).
+    split = fuse and reverse and C in (16, 32)
+    # Recompute mode (set_recompute; narrow levels, generative direction - where ~80 % of the per-layer activations of the model
+    # live): nothing per layer is kept; backward rebuilds layer k's input from its output (see _rebuild)
+    rec = _RECOMPUTE[0] and fuse and reverse and C <= 64
+    return _Level(NL, (NL + 3) // 4 * 4, C, ch, Cc, ch + Cc, reverse, fuse, split, rec,
+                  wts[0::5], wts[1::5], wts[2::5], wts[3::5], wts[4::5])
 
 
 class LevelCouplingFn(torch.autograd.Function):
@@ -1113,18 +1150,21 @@ class LevelCouplingFn(torch.autograd.Function):
     inputs: x [B,h,w,C], cond [B,h,w,Cc], Wm [NL,C,C], bm [NL,C] (folded ActNorm + 1x1 per layer, built by
     LSTMFLowBlock._level_mix with autograd), reverse, then (w1, w2, wz, bz, kappa) per layer in layer order.
     outputs: y, logdet [B] (sum of the NL coupling log-dets).
+
+    L: the level (_Level); S: what the steps of backward share (_LevelBwd).  A per-layer step is a call of its own: the layer's tensors
+    are unreferenced when it returns, before the next layer's buffers are allocated.
     """
 
     @staticmethod
-    def _cond_parts(cond, Wzc, Wdc, NL, NLp, C):
+    def _cond_parts(L, cond, Wcat):
         """The conditioning map's share of all NL zero convs (Hc) and of the 2 NL growth layers (Dc; dc_of(k) = layer k's two addends)."""
-        B, Hh, Ww, _ = cond.shape
-        dev = cond.device
-        Hc = torch.empty((B, Hh, Ww, NL * C), device=dev, dtype=torch.float32)
-        H.conv3x3_auto([cond], Wzc, NL * C, [Hc], relu_in=True, pad_rep=True)
-        Dc = torch.empty((B, Hh, Ww, 2 * NLp), device=dev, dtype=torch.float32)
-        H.conv_fwd([cond], H.conv_pack(Wdc, 0), 2 * NLp, 3, 1, [Dc], relu_in=True)
-        if B * Hh * Ww >= int(os.environ.get("TMG_LAYER_PLANES_MIN", 1 << 17)):
+        bhw, dev = cond.shape[:3], cond.device
+        Wzc, Wdc = Wcat[:L.NL * L.C], Wcat[L.NL * L.C:]
+        Hc = empty(bhw + (L.NL * L.C,), dev)
+        H.conv3x3_auto([cond], Wzc, L.NL * L.C, [Hc], relu_in=True, pad_rep=True)
+        Dc = empty(bhw + (2 * L.NLp,), dev)
+        H.conv_fwd([cond], H.conv_pack(Wdc, 0), 2 * L.NLp, 3, 1, [Dc], relu_in=True)
+        if math.prod(bhw) >= int(os.environ.get("TMG_LAYER_PLANES_MIN", 1 << 17)):
             # large images: one float2 plane per layer (every layer reads its addends for every pixel - out of the interleaved
             # tensor that is a full cache line per pixel, more than the growth kernels' real input)
             Dc = H.layer_planes(Dc)
@@ -1134,327 +1174,363 @@ class LevelCouplingFn(torch.autograd.Function):
         return Hc, Dc, dc_of
 
     @staticmethod
-    def _level_operands(wts, NL, NLp, C, ch, Cc, dev):
+    def _level_operands(L, dev):
         """(Wz [NL,C,cin+2,3,3] = stack of the zero-conv weights, Wcat = [Wzc ; Wdc] with Wzc [NL C,Cc,3,3] the conditioning columns
         of all zero convs and Wdc [2 NLp,Cc,3,3] those of the growth layers - output channel 2k / 2k+1 = growth layer 1 / 2 of coupling
         layer k: a layer's two addends share one cache line of Dc -, Bz [NL,C], Kp [NL]) through tmg_level_pack: one launch reading the
         modules' tensors through a device pointer table (round 5: ~10 stack / slice-copy / cat launches per level and direction)."""
-        cin = ch + Cc
-        w1s, w2s, wzs, bzs, kps = wts[0::5], wts[1::5], wts[2::5], wts[3::5], wts[4::5]
-        Wz = torch.empty((NL, C, cin + 2, 3, 3), device=dev, dtype=torch.float32)
-        Wcat = torch.empty((NL * C + 2 * NLp, Cc, 3, 3), device=dev, dtype=torch.float32)
-        Bz = torch.empty((NL, C), device=dev, dtype=torch.float32)
-        Kp = torch.empty(NL, device=dev, dtype=torch.float32)
-        if all(w.is_contiguous() and w.dtype == torch.float32 for w in wts) and os.environ.get("TMG_NO_LEVEL_PACK") is None:
-            tab = H._segment_table([[w.data_ptr() for w in wts[5 * k:5 * k + 5]] for k in range(NL)], dev)
+        NL, NLp, C, ch, Cc, cin = L[:6]
+        layers = list(zip(L.w1s, L.w2s, L.wzs, L.bzs, L.kps))
+        Wz = empty((NL, C, cin + 2, 3, 3), dev)
+        Wcat = empty((NL * C + 2 * NLp, Cc, 3, 3), dev)
+        Bz = empty((NL, C), dev)
+        Kp = empty(NL, dev)
+        if all(w.is_contiguous() and w.dtype == torch.float32 for ws in layers for w in ws) and os.environ.get("TMG_NO_LEVEL_PACK") is None:
+            tab = H._segment_table([[w.data_ptr() for w in ws] for ws in layers], dev)
             H.level_pack(tab, Wz, Wcat, Bz, Kp, NL, NLp, C, ch, Cc)
             return Wz, Wcat, Bz, Kp
-        torch.stack(wzs, out=Wz)
+        torch.stack(L.wzs, out=Wz)
         Wcat[:NL * C] = Wz[:, :, ch:cin].reshape(NL * C, Cc, 3, 3)
         Wdc = Wcat[NL * C:].view(NLp, 2, Cc, 3, 3)
         Wdc[NL:].zero_()
-        Wdc[:NL, 0] = torch.stack(w1s)[:, 0, ch:cin]
-        Wdc[:NL, 1] = torch.stack(w2s)[:, 0, ch:cin]
-        torch.stack(bzs, out=Bz)
-        torch.stack([kp.reshape(()) for kp in kps], out=Kp)
+        Wdc[:NL, 0] = torch.stack(L.w1s)[:, 0, ch:cin]
+        Wdc[:NL, 1] = torch.stack(L.w2s)[:, 0, ch:cin]
+        torch.stack(L.bzs, out=Bz)
+        torch.stack([kp.reshape(()) for kp in L.kps], out=Kp)
         return Wz, Wcat, Bz, Kp
 
     @staticmethod
+    def _growth(L, k, x1, dc_of):
+        """D = (d1, d2, 0, 0) [B,h,w,4]: both growth-1 layers of layer k in one launch (the conditioning parts arrive as add operands)."""
+        D = empty(x1.shape[:3] + (4,), x1.device)
+        add1, add2 = dc_of(k)
+        H.c1x2_fwd([x1], L.w1s[k], L.w2s[k], D, w_rows=L.ch, w2_d1_row=L.cin, add1=add1, add2=add2)
+        return D
+
+    @staticmethod
+    def _fwd_fused(L, k, cur, Wm, bm, PM, Hc, dc_of, logdet):
+        """Layer k of a narrow level -> (its output, what backward keeps of it): zero conv, coupling, log-det and - in the generative
+        direction - the following channel mix are ONE launch (tmg_coupling_fwd) after the growth layers' launch."""
+        C, ch, reverse = L.C, L.ch, L.reverse
+        bhw, dev = Hc.shape[:3], Hc.device
+        tin = cur if reverse else _mix_fwd(cur, Wm[k], bm[k], PM[k])
+        t1 = H._halves(tin)[0]
+        D = LevelCouplingFn._growth(L, k, t1, dc_of)
+        if L.split and k != 0:     # (k = 0 is the node's last layer in this direction: its output is the node's)
+            out = (empty(bhw + (ch,), dev), empty(bhw + (ch,), dev))
+        else:
+            out = empty(bhw + (C,), dev)
+        r = empty(bhw + (ch,), dev)
+        y2 = empty(bhw + (ch,), dev) if reverse else None
+        ok = H.coupling_fwd(tin, out, r, y2, D, Hc[..., k * C:(k + 1) * C], L.wzs[k], L.bzs[k], L.kps[k], Wm[k] if reverse else None,
+                            bm[k] if reverse else None, logdet, reverse, L.cin)
+        assert ok
+        if L.rec:
+            return out, None
+        # the coupling output y: reverse -> (x1 of the input, y2) as two segments (never materialised), forward -> out
+        return out, ((tin, D, r, [t1, y2]) if reverse else (tin, D, r, out, cur))
+
+    @staticmethod
+    def _fwd_wide(L, k, cur, Wm, bm, PM, PZ, Hc, dc_of, logdet, mixaff):
+        """Layer k of a wide level -> (its output, what backward keeps of it): one launch per op."""
+        C, ch, reverse = L.C, L.ch, L.reverse
+        bhw, dev = Hc.shape[:3], Hc.device
+        tin = cur if reverse else _mix_fwd(cur, Wm[k], bm[k], PM[k])
+        x1 = tin[..., :ch]
+        if ch % 4 == 0:
+            D = LevelCouplingFn._growth(L, k, x1, dc_of)
+        else:
+            D = empty(bhw + (4,), dev)
+            add1, add2 = dc_of(k)
+            H.c1_fwd([x1], L.w1s[k], D[..., 0:1], relu_in=True, w_rows=ch, fill4=True, add=add1)
+            H.c1_fwd([x1, D], L.w2s[k], D[..., 1:2], relu_in=True, w_rows=ch + 1, w_split=ch, w_gap=L.Cc, add=add2)
+        hh = empty(bhw + (C,), dev)
+        H.conv_fwd([x1, D], PZ[k], C, 3, 1, [hh], bias=L.bzs[k], kappa=L.kps[k], relu_in=True, pad_rep=True, add=Hc[..., k * C:(k + 1) * C])
+        r = empty(bhw + (ch,), dev)
+        if mixaff:
+            # 64- / 128-channel levels, generative direction: coupling + trailing mix in ONE launch (the coupling is evaluated on
+            # the mix kernel's way in); the coupling output is kept as (x1 of the input, y2), never as a [.., C] tensor
+            y2 = empty(bhw + (ch,), dev)
+            out = empty(bhw + (C,), dev)
+            if H.mix_affine_fwd(tin, hh, Wm[k], bm[k], out, r, y2, logdet):
+                return out, (tin, D, r, [x1, y2])
+        y = empty(bhw + (C,), dev)
+        H.affine_apply(hh, tin[..., ch:], y[..., ch:], r, logdet, reverse, x1=x1, y1=y[..., :ch])
+        return (_mix_fwd(y, Wm[k], bm[k], PM[k]) if reverse else y), (tin, D, r, y) + (() if reverse else (cur,))
+
+    @staticmethod
     def forward(ctx, x, cond, Wm, bm, reverse, *wts):
-        NL = len(wts) // 5
         x = x if x.stride(3) == 1 else x.contiguous()
         cond = cond.contiguous()
-        B, Hh, Ww, C = x.shape
-        Cc = cond.shape[3]
-        ch = C // 2
-        cin = ch + Cc
+        L = _level(wts, x.shape[3], cond.shape[3], reverse)
+        NL, C, ch = L.NL, L.C, L.ch
         dev = x.device
-        NLp = (NL + 3) // 4 * 4
-        w1s, w2s, wzs, bzs, kps = wts[0::5], wts[1::5], wts[2::5], wts[3::5], wts[4::5]
         # parameter-side operands of the whole level (parameter-sized copies, no autograd inside a Function): ONE gather launch
-        Wz, Wcat, Bz, Kp = LevelCouplingFn._level_operands(wts, NL, NLp, C, ch, Cc, dev)
-        Wzc, Wdc = Wcat[:NL * C], Wcat[NL * C:]
-        Hc, Dc, dc_of = LevelCouplingFn._cond_parts(cond, Wzc, Wdc, NL, NLp, C)
-        logdet = zeros(B, dev)
+        Wz, Wcat, Bz, Kp = LevelCouplingFn._level_operands(L, dev)
+        Hc, Dc, dc_of = LevelCouplingFn._cond_parts(L, cond, Wcat)
+        logdet = zeros(x.shape[0], dev)
         # operand packing of every layer's weights in two launches per level instead of two per layer
-        PZ = H.conv_pack_batched(Wz, 0, ch + 4, (ch + 2, ch, Cc))
+        PZ = H.conv_pack_batched(Wz, 0, ch + 4, (ch + 2, ch, L.Cc))
         PM = H.conv_pack_batched(Wm.reshape(NL, C, C, 1, 1), 0)
-        saved = [None] * NL
-        cur = x
-        # narrow levels: zero conv, coupling, log-det and - in the generative direction - the following channel mix are ONE launch
-        # (tmg_coupling_fwd) after the growth layers' launch; wide levels keep one launch per op
-        fuse = 8 <= C <= 32 and ch % 4 == 0 and all(w.is_contiguous() for w in wts)
-        # Split-halves layout (round 4; generative direction on the levels whose per-layer kernels are bandwidth-bound): between
-        # the layers of the node an activation lives as TWO [B,h,w,C/2] tensors (x1, x2) instead of one [B,h,w,C].  The kernels
-        # that read x1 alone - growth layers, their backward, three weight gradients - then use every byte of the lines they
-        # fetch (a 64-byte pixel of the 16-channel level shares its 128-byte line with the neighbour's other half), and the fused
-        # coupling kernel's x1 patch loads and x2 epilogue loads no longer pull each other's half-used lines through L2 twice.
-        # The node's input and output stay single tensors (addressed as two channel-slice views).
-        split = fuse and reverse and C in (16, 32)
         mixaff = (reverse and C in (64, 128) and Wm.is_contiguous() and bm.is_contiguous()
                   and os.environ.get("TMG_NO_MIX_AFFINE") is None)
-        # Recompute mode (set_recompute; narrow levels, generative direction - where ~80 % of the per-layer activations of the model
-        # live): nothing per layer is kept; backward rebuilds layer k's input from its output (see there)
-        rec = _RECOMPUTE[0] and fuse and reverse and C <= 64
+        saved = [None] * NL
+        cur = x
         for k in (range(NL - 1, -1, -1) if reverse else range(NL)):
-            xin = cur
-            if fuse:
-                tin = cur if reverse else _mix_fwd(cur, Wm[k], bm[k], PM[k])
-                t1 = H._halves(tin)[0]
-                D = torch.empty((B, Hh, Ww, 4), device=dev, dtype=torch.float32)
-                H.c1x2_fwd([t1], w1s[k], w2s[k], D, w_rows=ch, w2_d1_row=ch + Cc, add1=dc_of(k)[0], add2=dc_of(k)[1])
-                if split and k != 0:     # (k = 0 is the node's last layer in this direction: its output is the node's)
-                    out = (torch.empty((B, Hh, Ww, ch), device=dev, dtype=torch.float32), torch.empty((B, Hh, Ww, ch), device=dev, dtype=torch.float32))
-                else:
-                    out = torch.empty((B, Hh, Ww, C), device=dev, dtype=torch.float32)
-                r = torch.empty((B, Hh, Ww, ch), device=dev, dtype=torch.float32)
-                y2 = torch.empty((B, Hh, Ww, ch), device=dev, dtype=torch.float32) if reverse else None
-                ok = H.coupling_fwd(tin, out, r, y2, D, Hc[..., k * C:(k + 1) * C], wzs[k], bzs[k], kps[k], Wm[k] if reverse else None,
-                                    bm[k] if reverse else None, logdet, reverse, ch + Cc)
-                assert ok
-                cur = out
-                # the coupling output y: reverse -> (x1 of the input, y2) as two segments (never materialised), forward -> out
-                if not rec:
-                    saved[k] = (xin, tin, D, r, [t1, y2] if reverse else out)
-                continue
-            tin = cur if reverse else _mix_fwd(cur, Wm[k], bm[k], PM[k])
-            x1 = tin[..., :ch]
-            D = torch.empty((B, Hh, Ww, 4), device=dev, dtype=torch.float32)
-            if ch % 4 == 0:
-                # both growth-1 layers in one launch (the conditioning parts arrive as add operands)
-                H.c1x2_fwd([x1], w1s[k], w2s[k], D, w_rows=ch, w2_d1_row=ch + Cc, add1=dc_of(k)[0], add2=dc_of(k)[1])
+            if L.fuse:
+                cur, saved[k] = LevelCouplingFn._fwd_fused(L, k, cur, Wm, bm, PM, Hc, dc_of, logdet)
             else:
-                H.c1_fwd([x1], w1s[k], D[..., 0:1], relu_in=True, w_rows=ch, fill4=True, add=dc_of(k)[0])
-                H.c1_fwd([x1, D], w2s[k], D[..., 1:2], relu_in=True, w_rows=ch + 1, w_split=ch, w_gap=Cc, add=dc_of(k)[1])
-            hh = torch.empty((B, Hh, Ww, C), device=dev, dtype=torch.float32)
-            H.conv_fwd([x1, D], PZ[k], C, 3, 1, [hh], bias=bzs[k], kappa=kps[k], relu_in=True, pad_rep=True, add=Hc[..., k * C:(k + 1) * C])
-            r = torch.empty((B, Hh, Ww, ch), device=dev, dtype=torch.float32)
-            if mixaff:
-                # 64- / 128-channel levels, generative direction: coupling + trailing mix in ONE launch (the coupling is evaluated on
-                # the mix kernel's way in); the coupling output is kept as (x1 of the input, y2), never as a [.., C] tensor
-                y2 = torch.empty((B, Hh, Ww, ch), device=dev, dtype=torch.float32)
-                out = torch.empty((B, Hh, Ww, C), device=dev, dtype=torch.float32)
-                if H.mix_affine_fwd(tin, hh, Wm[k], bm[k], out, r, y2, logdet):
-                    cur = out
-                    saved[k] = (xin, tin, D, r, [x1, y2])
-                    continue
-            y = torch.empty((B, Hh, Ww, C), device=dev, dtype=torch.float32)
-            H.affine_apply(hh, tin[..., ch:], y[..., ch:], r, logdet, reverse, x1=x1, y1=y[..., :ch])
-            cur = _mix_fwd(y, Wm[k], bm[k], PM[k]) if reverse else y
-            saved[k] = (xin, tin, D, r, y)
+                cur, saved[k] = LevelCouplingFn._fwd_wide(L, k, cur, Wm, bm, PM, PZ, Hc, dc_of, logdet, mixaff)
         del Hc, Dc
         # the per-layer activations are module-owned buffers freed layer by layer during backward, hence a plain attribute
         # instead of save_for_backward; the node hands out a VIEW of its last buffer, so the returned tensor (which owns the
         # grad_fn -> ctx reference) is not itself an element of `saved`: no reference cycle when backward never runs
         ctx.saved = saved
-        ctx.rec_out = cur if rec else None      # (recompute mode: the node's own output buffer is all that backward starts from)
-        ctx.fuse = fuse
-        ctx.split = split
-        ctx.meta = (NL, NLp, reverse, ch, Cc)
+        ctx.rec_out = cur if L.rec else None      # (recompute mode: the node's own output buffer is all that backward starts from)
+        ctx.level = L
         ctx.save_for_backward(cond, Wm, bm, Wz, Wcat, Bz, Kp, *wts)
         return cur.view(cur.shape), logdet
 
     @staticmethod
+    def _rebuild(L, R, k):
+        """Recompute mode: layer k's activations (tin, D, r, y) from its output R[-1].  The generative layer k maps tin = [x1 | x2] to
+        out = Wm_k [x1; y2] + bm_k with y2 = x2 e^{-sg} - shift and (shift, sg) functions of x1 and the conditioning map alone
+        (flowAffine.py:102-109, glowConv.py:207-222).  So from out:
+          [x1; y2] = Wm_k^-1 (out - bm_k)                       one 1x1 mix with the inverse (tmg_mat_inverse: fp64, rounded once)
+          D        = growth layers of x1                         tmg_c1x2_fwd, as in the forward pass
+          x2       = (y2 + shift) e^{sg},  r                     tmg_coupling_fwd in its density-direction form, no trailing mix
+        and the layer's input is the previous layer's output: R[-1] on return.  The rest of R: the conditioning shares Hc / Dc of the
+        level, evaluated again, the inverse mixes and a log-det nobody reads."""
+        Hc, dc_of, Winv, binv, ld_dummy, out = R
+        C, ch = L.C, L.ch
+        u = _mix_fwd(out, Winv[k], binv[k])
+        t1 = u[..., :ch]
+        D = LevelCouplingFn._growth(L, k, t1, dc_of)
+        tin = empty(u.shape, u.device)
+        r = empty(t1.shape, u.device)
+        ok = H.coupling_fwd(u, tin, r, None, D, Hc[..., k * C:(k + 1) * C], L.wzs[k], L.bzs[k], L.kps[k], None, None, ld_dummy, False, L.cin)
+        assert ok
+        R[-1] = tin
+        return tin, D, r, [t1, u[..., ch:]]
+
+    @staticmethod
+    def _zero_conv_wgrad(L, S, k, x1D, now=False):
+        """Weight / bias gradient of layer k's zero conv (its x1 | D columns; upstream = the layer's slice of DH): one launch, or -
+        grouped, unless `now` - the inputs recorded for the level's grouped launch, whose per-layer fallback this is too."""
+        if S.grouped and not now:
+            S.wg_in[k] = x1D
+        else:
+            H.conv_wgrad(x1D, S.DH[..., k * L.C:(k + 1) * L.C], S.dWz[k], S.dBz[k], 3, 1, **S.zc_kw)
+
+    @staticmethod
+    def _mix_wgrad(L, S, k, x, dy, now=False):
+        """Weight / bias gradient of layer k's 1x1 mix (x: its input, a tensor or channel segments; dy: the upstream gradient, a tensor
+        or two halves): one launch, or - grouped, unless `now` - the pair recorded for the level's grouped launch."""
+        x = x if isinstance(x, list) else [x]
+        if S.grouped and not now:
+            S.mix_wg[k] = (x, dy)
+        else:
+            H.conv_wgrad(x, dy if torch.is_tensor(dy) else torch.cat(list(dy), 3), S.dWm[k], S.dbm[k], 1, 1)
+
+    @staticmethod
+    def _layer_mix_bwd(L, S, k, x, dy):
+        """Backward of layer k's 1x1 mix on its own: the input gradient (returned), then the weight gradient (now or recorded)."""
+        dx = _mix_dgrad(dy, S.Wm[k], S.PMt[k])
+        LevelCouplingFn._mix_wgrad(L, S, k, x, dy)
+        return dx
+
+    @staticmethod
+    def _growth_bwd(L, S, k, x1, D, G0, GD, dt1, add0):
+        """Both growth-1 layers' backward, ReLU masks and the concat adjoint of layer k in one launch: dt1 (the first half of the
+        layer-input gradient) = add0 (the pass-through half of the coupling's gradient) + G0 + the growth layers' share; (dd1, dd2)
+        go to the layer's channels of DD; the x1 | d1 weight-gradient rows here unless the level's grouped launch writes them."""
+        ch = L.ch
+        dW1, dW2 = (None, None) if S.grouped else (S.dW1[k], S.dW2[k])
+        H.dense2_bwd([x1, D], L.w1s[k], L.w2s[k], dW1, dW2, GD, D, [G0], [dt1], ch, add0=add0, rows1=ch, rows2=ch + 1, split2=ch, gap2=L.Cc,
+                     dd1=S.DD[..., 2 * k:2 * k + 1], dd2=S.DD[..., 2 * k + 1:2 * k + 2], dd_quad=(S.quad_last and k == L.NL - 1))
+
+    @staticmethod
+    def _bwd_fused_generative(L, S, k, dcur, tin, D, r, y):
+        """Narrow level, generative direction (coupling -> mix) -> gradient w.r.t. the layer's input.
+        One launch: mix input gradient -> coupling backward -> zero-conv input gradient (exact replicate adjoint)."""
+        C, ch = L.C, L.ch
+        bhw, dev = D.shape[:3], D.device
+        if L.split and k != L.NL - 1:    # gradient w.r.t. a layer input that lives as two halves: the same layout
+            dtin = (empty(bhw + (ch,), dev), empty(bhw + (ch,), dev))
+        else:                            # (k = NL - 1: the node's own input gradient)
+            dtin = empty(bhw + (C,), dev)
+        G0, GD = empty(bhw + (ch,), dev), empty(bhw + (4,), dev)
+        dhh = S.DH[..., k * C:(k + 1) * C]
+        x1, x2 = H._halves(tin)
+        dt1 = H._halves(dtin)[0]
+        ok = H.coupling_bwd(dcur, x2, r, S.g, S.Wm[k].contiguous(), L.wzs[k], L.kps[k], dhh, dtin, G0, GD, L.cin)
+        assert ok
+        LevelCouplingFn._zero_conv_wgrad(L, S, k, [x1, D])
+        LevelCouplingFn._mix_wgrad(L, S, k, y, dcur)
+        LevelCouplingFn._growth_bwd(L, S, k, x1, D, G0, GD, dt1, dt1)
+        return dtin
+
+    @staticmethod
+    def _bwd_fused_density(L, S, k, dcur, tin, D, r, y, xin):
+        """Narrow level, density direction (mix -> coupling) -> gradient w.r.t. the layer's input.
+        Coupling backward + zero-conv input gradient in one launch (tmg_coupling_bwd in its `fwd` mode: the gradient arrives at the
+        coupling output itself), then the growth layers' backward, then the input gradient of the leading mix (round 4: this
+        direction ran affine_bwd + conv dgrad + border fold per layer before)."""
+        C, ch = L.C, L.ch
+        bhw, dev = D.shape[:3], D.device
+        dtin = empty(bhw + (C,), dev)
+        G0, GD = empty(bhw + (ch,), dev), empty(bhw + (4,), dev)
+        dhh = S.DH[..., k * C:(k + 1) * C]
+        x1, dt1 = tin[..., :ch], dtin[..., :ch]
+        ok = H.coupling_bwd(dcur, y[..., ch:], r, S.g, S.Wm[k].contiguous(), L.wzs[k], L.kps[k], dhh, dtin, G0, GD, L.cin, fwd=True)
+        assert ok
+        LevelCouplingFn._zero_conv_wgrad(L, S, k, [x1, D])
+        LevelCouplingFn._growth_bwd(L, S, k, x1, D, G0, GD, dt1, dt1)
+        return LevelCouplingFn._layer_mix_bwd(L, S, k, xin, dtin)
+
+    @staticmethod
+    def _bwd_wide(L, S, k, dcur, tin, D, r, y, xin=None):
+        """Wide level, either direction -> gradient w.r.t. the layer's input: one launch per op."""
+        C, ch, reverse = L.C, L.ch, L.reverse
+        bhw, dev = D.shape[:3], D.device
+        dtin = empty(bhw + (C,), dev)        # grad w.r.t. the tail input
+        dhh = S.DH[..., k * C:(k + 1) * C]
+        add0 = None
+        if reverse and isinstance(y, list) and C in (64, 128):
+            # the forward pass took the fused coupling + mix launch: its backward in one launch too (mix input gradient with the
+            # coupling's backward on the way out); dto1 = the pass-through half of the gradient, completed by dense2_bwd below
+            dto1 = empty(bhw + (ch,), dev)
+            if H.mix_affine_bwd(dcur, S.Wm[k].contiguous(), r, tin[..., ch:], S.g, L.kps[k], dto1, dtin[..., ch:], dhh):
+                add0 = dto1
+                LevelCouplingFn._mix_wgrad(L, S, k, y, dcur)
+        if add0 is None:
+            dto = LevelCouplingFn._layer_mix_bwd(L, S, k, y, dcur) if reverse else dcur   # grad w.r.t. the tail output y
+            H.affine_bwd(dto[..., ch:], (tin if reverse else y)[..., ch:], r, S.g, dtin[..., ch:], dhh, reverse, kappa=L.kps[k])
+            add0 = dto[..., :ch]
+        x1 = tin[..., :ch]
+        LevelCouplingFn._zero_conv_wgrad(L, S, k, [x1, D])
+        G0, GD = empty(bhw + (ch,), dev), empty(bhw + (4,), dev)
+        wt = S.PZt[k]
+        H.conv_fwd([dhh], wt, ch + 4, 3, 1, [G0, GD])
+        H.conv_rep_border_fix(dhh, wt, [G0, GD])
+        LevelCouplingFn._growth_bwd(L, S, k, x1, D, G0, GD, dtin[..., :ch], add0)
+        return dtin if reverse else LevelCouplingFn._layer_mix_bwd(L, S, k, xin, dtin)
+
+    @staticmethod
+    def _activations(L, R, saved, k):
+        """Layer k's (tin, D, r, y[, xin]) for its backward step: stored (and released from `saved` here), or rebuilt from its output."""
+        if R is not None:
+            return LevelCouplingFn._rebuild(L, R, k)
+        acts, saved[k] = saved[k], None
+        return acts
+
+    @staticmethod
+    def _grouped_wgrads(L, S):
+        """The level's grouped weight-gradient launches with their per-layer fallbacks -> tmpX (the growth layers' rows, for _finish)."""
+        NL, C, ch = L.NL, L.C, L.ch
+        if not H.conv_wgrad_grouped(S.wg_in, S.DH, C, S.dWz, S.dBz, 3, 1, **S.zc_kw):
+            for k in range(NL):
+                LevelCouplingFn._zero_conv_wgrad(L, S, k, S.wg_in[k], now=True)
+        # x1 | d1 rows of the growth-layer weight gradients: same inputs, dy = this layer's (dd1, dd2, 0, 0) quad; row 0 of the
+        # result belongs to w1, row 1 to w2 (its column ch is the d1 input)
+        tmpX = zeros((NL, 4, ch + 4, 3, 3), S.DH.device)
+        if not H.conv_wgrad_grouped(S.wg_in, S.DD, 2, tmpX, None, 3, 1, relu_in=True):
+            for k in range(NL):
+                H.conv_wgrad(S.wg_in[k], S.DD[..., 2 * k:2 * k + 2], tmpX[k][:2], None, 3, 1, relu_in=True)
+        S.wg_in.clear()
+        # the 1x1 mix weight gradients of all layers: same trick, every group with its own upstream gradient tensor
+        gdy = [g_ for _, g_ in S.mix_wg]
+        if any(not torch.is_tensor(g_) for g_ in gdy):      # split-halves layout: every group's upstream gradient as two halves
+            gdy = [H._halves(g_) for g_ in gdy]
+        if not H.conv_wgrad_grouped([a for a, _ in S.mix_wg], None, C, S.dWm.view(NL, C, C, 1, 1), S.dbm, 1, 1, group_dy=gdy):
+            for k in range(NL):
+                LevelCouplingFn._mix_wgrad(L, S, k, *S.mix_wg[k], now=True)
+        S.mix_wg.clear()
+        return tmpX
+
+    @staticmethod
+    def _cond_bwd(L, S, cond, Wcat):
+        """Conditioning side of the whole level: one input-gradient pass (-> Gc = d(cond)), the conditioning columns of the zero-conv
+        weight gradients into dWz, those of the growth layers -> tmpC for level_finish."""
+        NL, NLp, C, ch, Cc, cin = L[:6]
+        dev = cond.device
+        Gc = empty(cond.shape, dev)
+        # zero-conv part (dy = DH) and growth-layer part (dy = DD) of d(cond) as ONE contraction over [DH | DD] (K = NL (C + 4)): the
+        # padding mode of the forward convs does not enter the interior of an input gradient, the replicate fold below adds the ring
+        # terms of the zero convs alone (operand of Wzc by itself)
+        # (Wcat = [Wzc ; Wdc]: rows NL C + 2k / + 2k+1 are the cond columns of w1_k / w2_k - Wdc's own layout)
+        H.conv3x3_auto([S.DH, S.DD], Wcat, Cc, [Gc], dgrad=True)
+        H.conv_rep_border_fix(S.DH, H.conv_pack(Wcat[:NL * C], 1), [Gc])
+        H.masked_add(Gc, src=Gc, ref=cond)
+        H.conv_wgrad([cond], S.DH, S.dWz, None, 3, 1, relu_in=True, pad_rep=True, cin_dst=cin + 2, cin_valid=Cc, ci_off0=ch)
+        tmpC = zeros((NLp, 2, Cc, 3, 3), dev)  # one launch for both growth layers of all layers
+        H.conv_wgrad([cond], S.DD, tmpC.view(2 * NLp, Cc, 3, 3), None, 3, 1, relu_in=True)
+        return Gc, tmpC
+
+    @staticmethod
+    def _finish(L, S, Wz, Bz, Kp, tmpX, tmpC):
+        """One launch: rows of tmpX / tmpC -> dW1 / dW2, and d(kappa_k) = <wz_k, dwz_k> + <bz_k, dbz_k> inside the clamp range
+        (homogeneity of the zero conv in (W, b); the two inner products nearly cancel for small kappa gradients: fp64 sums)."""
+        dK = empty(L.NL, Kp.device)
+        H.level_finish(Wz, S.dWz, Bz, S.dBz, Kp, tmpX, tmpC, S.dW1, S.dW2, dK, zeros(4 * L.NL, Kp.device), L.ch, L.Cc)
+        return dK
+
+    @staticmethod
     def backward(ctx, dy, dld):
-        NL, NLp, reverse, ch, Cc = ctx.meta
+        L = ctx.level
+        NL, NLp, C, ch, Cc, cin = L[:6]
         cond, Wm, bm, Wz, Wcat, Bz, Kp = ctx.saved_tensors[:7]
         wts = ctx.saved_tensors[7:]
-        w1s, w2s, wzs, bzs, kps = wts[0::5], wts[1::5], wts[2::5], wts[3::5], wts[4::5]
         saved = ctx.saved
         if saved is None:
             raise RuntimeError("LevelCouplingFn: the saved activations were released by a previous backward pass "
                                "(a second backward through the same graph is not supported)")
         ctx.saved = None
         dy = dy.contiguous()
-        B, Hh, Ww, C = dy.shape
-        cin = ch + Cc
-        dev = dy.device
-        Wzc, Wdc = Wcat[:NL * C], Wcat[NL * C:]
+        bhw, dev = dy.shape[:3], dy.device
         g = dld.contiguous() if dld is not None else None
-        # stacked native-layout parameter gradients of the whole level, one zero fill
-        n1, n2, nz = cin * 9, (cin + 1) * 9, C * (cin + 2) * 9
-        flat = zeros(NL * (n1 + n2 + nz + C) + NL * C * C + NL * C, dev)
-        o = 0
-        dWz = flat[o:o + NL * nz].view(NL, C, cin + 2, 3, 3); o += NL * nz      # first: 16-byte aligned slices (tmg_level_finish)
-        dW1 = flat[o:o + NL * n1].view(NL, 1, cin, 3, 3); o += NL * n1
-        dW2 = flat[o:o + NL * n2].view(NL, 1, cin + 1, 3, 3); o += NL * n2
-        dBz = flat[o:o + NL * C].view(NL, C); o += NL * C
-        dWm = flat[o:o + NL * C * C].view(NL, C, C); o += NL * C * C
-        dbm = flat[o:o + NL * C].view(NL, C)
-        DH = torch.empty((B, Hh, Ww, NL * C), device=dev, dtype=torch.float32)     # exp(kappa_k) * dhh_k, all layers
+        # stacked native-layout parameter gradients of the whole level, one zero fill; dWz first: 16-byte aligned slices (tmg_level_finish)
+        dWz, dW1, dW2, dBz, dWm, dbm = carve(dev, (NL, C, cin + 2, 3, 3), (NL, 1, cin, 3, 3), (NL, 1, cin + 1, 3, 3), (NL, C), (NL, C, C),
+                                             (NL, C))
+        DH = empty(bhw + (NL * C,), dev)     # exp(kappa_k) * dhh_k, all layers
         # masked gradients w.r.t. the growth channels, COMPACT: channels 2k, 2k + 1 = (dd1_k, dd2_k), 2 NLp channels (round 4: the
         # quad layout (dd1, dd2, 0, 0) per layer made the level-wide conditioning contractions below carry 2 NL zero channels - the
         # weight gradient w.r.t. the conditioning columns 60 output channels for 30, the conditioning input gradient K = NL (C + 4)).
         # Written whole by the per-layer backward kernels (8 bytes per pixel and layer; the LAST layer writes a (dd1, dd2, 0, 0) quad
         # when there is ONE padding layer, which zeroes its two channels; more padding layers are filled): no zero fill at NL = 15
-        DD = torch.empty((B, Hh, Ww, 2 * NLp), device=dev, dtype=torch.float32)
+        DD = empty(bhw + (2 * NLp,), dev)
         quad_last = NLp - NL == 1        # (NL = 15 in the reference's models: one padding layer, zeroed by the last layer's quad store)
         if NLp - NL > 1:
             DD[..., 2 * NL:].zero_()
-        dd_of = lambda k: dict(dd1=DD[..., 2 * k:2 * k + 1], dd2=DD[..., 2 * k + 1:2 * k + 2], dd_quad=(quad_last and k == NL - 1))  # noqa: E731
-        dcur = dy
         # The NL zero-conv weight gradients (x1 | D part) are independent of each other once DH holds every layer's
         # exp(kappa)*dhh: they run as ONE grouped launch after the loop (a few microseconds of MFMA work each otherwise,
         # dominated by launch / pipeline-fill).  Their inputs stay alive until then (NL * C floats per pixel).
         grouped = NL > 1 and ch + 4 <= 132
         PZt = H.conv_pack_batched(Wz, 1, ch + 4, (ch + 2, ch, Cc))          # input-gradient operands of all layers: one launch
         PMt = H.conv_pack_batched(Wm.reshape(NL, C, C, 1, 1), 1)
-        wg_in = [None] * NL
-        mix_wg = [None] * NL if grouped else None   # (input, upstream gradient) of every layer's 1x1 mix
-        rec_out = ctx.rec_out
-        ctx.rec_out = None
-        if rec_out is not None:
-            # Recompute mode: the generative layer k maps tin = [x1 | x2] to out = Wm_k [x1; y2] + bm_k with y2 = x2 e^{-sg} - shift and
-            # (shift, sg) functions of x1 and the conditioning map alone (flowAffine.py:102-109, glowConv.py:207-222).  So from out:
-            #   [x1; y2] = Wm_k^-1 (out - bm_k)                       one 1x1 mix with the inverse (tmg_mat_inverse: fp64, rounded once)
-            #   D        = growth layers of x1                         tmg_c1x2_fwd, as in the forward pass
-            #   x2       = (y2 + shift) e^{sg},  r                     tmg_coupling_fwd in its density-direction form, no trailing mix
-            # and the layer's input is the previous layer's output.  The conditioning shares Hc / Dc of the level are evaluated again.
-            Hc_r, Dc_r, dc_of_r = LevelCouplingFn._cond_parts(cond, Wzc, Wdc, NL, NLp, C)
+        zc_kw = dict(relu_in=True, pad_rep=True, cin_dst=cin + 2, cin_valid=ch + 2, ci_split=ch, ci_off0=0, ci_off1=Cc)
+        # wg_in[k] = [x1, D] of layer k's zero conv; mix_wg[k] = (input, upstream gradient) of its 1x1 mix
+        S = _LevelBwd(g, Wm, PZt, PMt, DH, DD, quad_last, grouped, zc_kw, [None] * NL, [None] * NL if grouped else None, dWz, dBz, dW1, dW2,
+                      dWm, dbm)
+        R = None
+        if ctx.rec_out is not None:     # recompute mode: see _rebuild
+            Hc_r, Dc_r, dc_of_r = LevelCouplingFn._cond_parts(L, cond, Wcat)
             Winv, binv = H.mat_inverse(Wm, bm)
-            ld_dummy = zeros(B, dev)
-        for k in (range(NL) if reverse else range(NL - 1, -1, -1)):
-            if rec_out is not None:
-                u = _mix_fwd(rec_out, Winv[k], binv[k])
-                t1 = u[..., :ch]
-                D = torch.empty((B, Hh, Ww, 4), device=dev, dtype=torch.float32)
-                H.c1x2_fwd([t1], w1s[k], w2s[k], D, w_rows=ch, w2_d1_row=ch + Cc, add1=dc_of_r(k)[0], add2=dc_of_r(k)[1])
-                tin = torch.empty((B, Hh, Ww, C), device=dev, dtype=torch.float32)
-                r = torch.empty((B, Hh, Ww, ch), device=dev, dtype=torch.float32)
-                ok = H.coupling_fwd(u, tin, r, None, D, Hc_r[..., k * C:(k + 1) * C], wzs[k], bzs[k], kps[k], None, None, ld_dummy, False, ch + Cc)
-                assert ok
-                xin, y = tin, [t1, u[..., ch:]]
-                rec_out = tin
-            else:
-                xin, tin, D, r, y = saved[k]
-                saved[k] = None
-            if reverse and ctx.fuse:
-                # one launch: mix input gradient -> coupling backward -> zero-conv input gradient (exact replicate adjoint)
-                if ctx.split and k != NL - 1:    # gradient w.r.t. a layer input that lives as two halves: the same layout
-                    dtin = (torch.empty((B, Hh, Ww, ch), device=dev, dtype=torch.float32), torch.empty((B, Hh, Ww, ch), device=dev, dtype=torch.float32))
-                else:                            # (k = NL - 1: the node's own input gradient)
-                    dtin = torch.empty((B, Hh, Ww, C), device=dev, dtype=torch.float32)
-                G0 = torch.empty((B, Hh, Ww, ch), device=dev, dtype=torch.float32)
-                GD = torch.empty((B, Hh, Ww, 4), device=dev, dtype=torch.float32)
-                dhh = DH[..., k * C:(k + 1) * C]
-                x1, x2 = H._halves(tin)
-                dt1 = H._halves(dtin)[0]
-                ok = H.coupling_bwd(dcur, x2, r, g, Wm[k].contiguous(), wzs[k], kps[k], dhh, dtin, G0, GD, ch + Cc)
-                assert ok
-                if grouped:
-                    wg_in[k] = [x1, D]
-                    mix_wg[k] = (y, dcur)
-                else:
-                    H.conv_wgrad([x1, D], dhh, dWz[k], dBz[k], 3, 1, relu_in=True, pad_rep=True, cin_dst=cin + 2, cin_valid=ch + 2,
-                                 ci_split=ch, ci_off0=0, ci_off1=Cc)
-                    H.conv_wgrad(y, dcur if torch.is_tensor(dcur) else torch.cat(list(dcur), 3), dWm[k], dbm[k], 1, 1)
-                H.dense2_bwd([x1, D], w1s[k], w2s[k], None if grouped else dW1[k], None if grouped else dW2[k], GD, D, [G0], [dt1], ch,
-                             add0=dt1, rows1=ch, rows2=ch + 1, split2=ch, gap2=Cc, **dd_of(k))
-                dcur = dtin
-                del xin, tin, D, r, y
-                continue
-            if (not reverse) and ctx.fuse:
-                # density direction (mix -> coupling): coupling backward + zero-conv input gradient in one launch (tmg_coupling_bwd in its
-                # `fwd` mode: the gradient arrives at the coupling output itself), then the growth layers' backward, then the input
-                # gradient of the leading mix (round 4: this direction ran affine_bwd + conv dgrad + border fold per layer before)
-                mdef = [] if grouped else None
-                dtin = torch.empty((B, Hh, Ww, C), device=dev, dtype=torch.float32)
-                G0 = torch.empty((B, Hh, Ww, ch), device=dev, dtype=torch.float32)
-                GD = torch.empty((B, Hh, Ww, 4), device=dev, dtype=torch.float32)
-                dhh = DH[..., k * C:(k + 1) * C]
-                x1 = tin[..., :ch]
-                ok = H.coupling_bwd(dcur, y[..., ch:], r, g, Wm[k].contiguous(), wzs[k], kps[k], dhh, dtin, G0, GD, ch + Cc, fwd=True)
-                assert ok
-                if grouped:
-                    wg_in[k] = [x1, D]
-                else:
-                    H.conv_wgrad([x1, D], dhh, dWz[k], dBz[k], 3, 1, relu_in=True, pad_rep=True, cin_dst=cin + 2, cin_valid=ch + 2,
-                                 ci_split=ch, ci_off0=0, ci_off1=Cc)
-                H.dense2_bwd([x1, D], w1s[k], w2s[k], None if grouped else dW1[k], None if grouped else dW2[k], GD, D, [G0], [dtin[..., :ch]], ch,
-                             add0=dtin[..., :ch], rows1=ch, rows2=ch + 1, split2=ch, gap2=Cc, **dd_of(k))
-                dcur = _mix_bwd(xin, dtin, Wm[k], dWm[k], dbm[k], PMt[k], mdef)
-                if grouped:
-                    mix_wg[k] = mdef[0]
-                del xin, tin, D, r, y
-                continue
-            mdef = [] if grouped else None
-            dtin = torch.empty((B, Hh, Ww, C), device=dev, dtype=torch.float32)        # grad w.r.t. the tail input
-            dhh = DH[..., k * C:(k + 1) * C]
-            add0 = None
-            if reverse and isinstance(y, list) and C in (64, 128):
-                # the forward pass took the fused coupling + mix launch: its backward in one launch too (mix input gradient with the
-                # coupling's backward on the way out); dto1 = the pass-through half of the gradient, completed by dense2_bwd below
-                dto1 = torch.empty((B, Hh, Ww, ch), device=dev, dtype=torch.float32)
-                if H.mix_affine_bwd(dcur, Wm[k].contiguous(), r, tin[..., ch:], g, kps[k], dto1, dtin[..., ch:], dhh):
-                    add0 = dto1
-                    if mdef is not None:
-                        mdef.append((y, dcur))
-                    else:
-                        H.conv_wgrad(y, dcur, dWm[k], dbm[k], 1, 1)
-            if add0 is None:
-                dto = _mix_bwd(y, dcur, Wm[k], dWm[k], dbm[k], PMt[k], mdef) if reverse else dcur   # grad w.r.t. the tail output y
-                H.affine_bwd(dto[..., ch:], (tin if reverse else y)[..., ch:], r, g, dtin[..., ch:], dhh, reverse, kappa=kps[k])
-                add0 = dto[..., :ch]
-            x1 = tin[..., :ch]
-            if grouped:
-                wg_in[k] = [x1, D]  # weight gradient of this layer's zero conv: deferred, one grouped launch per level
-            else:
-                H.conv_wgrad([x1, D], dhh, dWz[k], dBz[k], 3, 1, relu_in=True, pad_rep=True, cin_dst=cin + 2, cin_valid=ch + 2,
-                             ci_split=ch, ci_off0=0, ci_off1=Cc)
-            G0 = torch.empty((B, Hh, Ww, ch), device=dev, dtype=torch.float32)
-            GD = torch.empty((B, Hh, Ww, 4), device=dev, dtype=torch.float32)
-            wt = PZt[k]
-            H.conv_fwd([dhh], wt, ch + 4, 3, 1, [G0, GD])
-            H.conv_rep_border_fix(dhh, wt, [G0, GD])
-            H.dense2_bwd([x1, D], w1s[k], w2s[k], None if grouped else dW1[k], None if grouped else dW2[k], GD, D, [G0], [dtin[..., :ch]], ch,
-                         add0=add0, rows1=ch, rows2=ch + 1, split2=ch, gap2=Cc, **dd_of(k))
-            dcur = dtin if reverse else _mix_bwd(xin, dtin, Wm[k], dWm[k], dbm[k], PMt[k], mdef)
-            if grouped:
-                mix_wg[k] = mdef[0]
-            del xin, tin, D, r, y
-        tmpX = None
-        if grouped:
-            if not H.conv_wgrad_grouped(wg_in, DH, C, dWz, dBz, 3, 1, relu_in=True, pad_rep=True, cin_dst=cin + 2, cin_valid=ch + 2,
-                                        ci_split=ch, ci_off0=0, ci_off1=Cc):
-                for k in range(NL):
-                    H.conv_wgrad(wg_in[k], DH[..., k * C:(k + 1) * C], dWz[k], dBz[k], 3, 1, relu_in=True, pad_rep=True, cin_dst=cin + 2,
-                                 cin_valid=ch + 2, ci_split=ch, ci_off0=0, ci_off1=Cc)
-            # x1 | d1 rows of the growth-layer weight gradients: same inputs, dy = this layer's (dd1, dd2, 0, 0) quad; row 0 of the
-            # result belongs to w1, row 1 to w2 (its column ch is the d1 input)
-            if tmpX is None:
-                tmpX = zeros((NL, 4, ch + 4, 3, 3), dev)
-            if not H.conv_wgrad_grouped(wg_in, DD, 2, tmpX, None, 3, 1, relu_in=True):
-                for k in range(NL):
-                    H.conv_wgrad(wg_in[k], DD[..., 2 * k:2 * k + 2], tmpX[k][:2], None, 3, 1, relu_in=True)
-            wg_in = None
-            # the 1x1 mix weight gradients of all layers: same trick, every group with its own upstream gradient tensor
-            gdy = [g_ for _, g_ in mix_wg]
-            if any(not torch.is_tensor(g_) for g_ in gdy):      # split-halves layout: every group's upstream gradient as two halves
-                gdy = [H._halves(g_) for g_ in gdy]
-            if not H.conv_wgrad_grouped([a for a, _ in mix_wg], None, C, dWm.view(NL, C, C, 1, 1), dbm, 1, 1, group_dy=gdy):
-                for k in range(NL):
-                    gk = mix_wg[k][1]
-                    H.conv_wgrad(mix_wg[k][0], gk if torch.is_tensor(gk) else torch.cat(list(gk), 3), dWm[k], dbm[k], 1, 1)
-            mix_wg = None
-        # conditioning side of the whole level: one input-gradient pass, three weight-gradient passes
-        Gc = torch.empty(cond.shape, device=dev, dtype=torch.float32)
-        # zero-conv part (dy = DH) and growth-layer part (dy = DD) of d(cond) as ONE contraction over [DH | DD] (K = NL (C + 4)): the
-        # padding mode of the forward convs does not enter the interior of an input gradient, the replicate fold below adds the ring
-        # terms of the zero convs alone (operand of Wzc by itself)
-        # (Wcat = [Wzc ; Wdc]: rows NL C + 2k / + 2k+1 are the cond columns of w1_k / w2_k - Wdc's own layout)
-        H.conv3x3_auto([DH, DD], Wcat, Cc, [Gc], dgrad=True)
-        H.conv_rep_border_fix(DH, H.conv_pack(Wzc, 1), [Gc])
-        H.masked_add(Gc, src=Gc, ref=cond)
-        H.conv_wgrad([cond], DH, dWz, None, 3, 1, relu_in=True, pad_rep=True, cin_dst=cin + 2, cin_valid=Cc, ci_off0=ch)
-        tmpC = zeros((NLp, 2, Cc, 3, 3), dev)  # one launch for both growth layers of all layers
-        H.conv_wgrad([cond], DD, tmpC.view(2 * NLp, Cc, 3, 3), None, 3, 1, relu_in=True)
-        # one launch: rows of tmpX / tmpC -> dW1 / dW2, and d(kappa_k) = <wz_k, dwz_k> + <bz_k, dbz_k> inside the clamp range
-        # (homogeneity of the zero conv in (W, b); the two inner products nearly cancel for small kappa gradients: fp64 sums)
-        dK = torch.empty(NL, device=dev, dtype=torch.float32)
-        H.level_finish(Wz, dWz, Bz, dBz, Kp, tmpX, tmpC, dW1, dW2, dK, zeros(4 * NL, dev), ch, Cc)
+            R = [Hc_r, dc_of_r, Winv, binv, zeros(bhw[0], dev), ctx.rec_out]
+        ctx.rec_out = None
+        if not L.fuse:
+            step = LevelCouplingFn._bwd_wide
+        else:
+            step = LevelCouplingFn._bwd_fused_generative if L.reverse else LevelCouplingFn._bwd_fused_density
+        dcur = dy
+        for k in (range(NL) if L.reverse else range(NL - 1, -1, -1)):
+            dcur = step(L, S, k, dcur, *LevelCouplingFn._activations(L, R, saved, k))
+        tmpX = LevelCouplingFn._grouped_wgrads(L, S) if grouped else None
+        Gc, tmpC = LevelCouplingFn._cond_bwd(L, S, cond, Wcat)
+        dK = LevelCouplingFn._finish(L, S, Wz, Bz, Kp, tmpX, tmpC)
         grads = []
         for k in range(NL):
-            grads += [dW1[k], dW2[k], dWz[k], dBz[k], dK[k].reshape(kps[k].shape)]
+            grads += [dW1[k], dW2[k], dWz[k], dBz[k], dK[k].reshape(L.kps[k].shape)]
         return (dcur, Gc, dWm, dbm, None) + _defer(wts, grads)
 
 
@@ -1471,9 +1547,9 @@ class LevelMixFoldFn(torch.autograd.Function):
         tab, sign_s, perm, iperm, reverse, sgn, hw, K, C = meta
         dev = sign_s.device
         W = torch.empty((K, C, C), device=dev, dtype=torch.float64)     # P L U in fp64, kept for the backward launch
-        Wm = torch.empty((K, C, C), device=dev, dtype=torch.float32)
-        bm = torch.empty((K, C), device=dev, dtype=torch.float32)
-        ld = torch.empty(1, device=dev, dtype=torch.float32)
+        Wm = empty((K, C, C), dev)
+        bm = empty((K, C), dev)
+        ld = empty(1, dev)
         H.lu_fold_fwd(tab, sign_s, perm, iperm, W, Wm, bm, ld, reverse, sgn, hw)
         ctx.meta = meta
         ctx.shapes = [t.shape if t is not None else None for t in params]
@@ -1486,11 +1562,11 @@ class LevelMixFoldFn(torch.autograd.Function):
         tab, sign_s, perm, iperm, reverse, sgn, hw, K, C = ctx.meta
         W = ctx.saved_tensors[0]
         dev = W.device
-        dl = torch.empty((K, C, C), device=dev, dtype=torch.float32)
-        du = torch.empty((K, C, C), device=dev, dtype=torch.float32)
-        dlogs = torch.empty((K, C), device=dev, dtype=torch.float32)
-        da = torch.empty((K, C), device=dev, dtype=torch.float32)
-        db = torch.empty((K, C), device=dev, dtype=torch.float32)
+        dl = empty((K, C, C), dev)
+        du = empty((K, C, C), dev)
+        dlogs = empty((K, C), dev)
+        da = empty((K, C), dev)
+        db = empty((K, C), dev)
         split = dWm is None and dbm is None and dWt is not None and (dWh is not None or K == 1) and (dbt is None) == (dbh is None or K == 1)
         if split:
             dWm, dbm, dWt, dbt = (None if t is None else t.contiguous() for t in (dWh, dbh, dWt, dbt))
@@ -1629,13 +1705,13 @@ class EnsembleStats:
         shp = (self.B, self.C, self.H, self.W)
         names = ("time_mean_mean", "time_mean_std", "time_rms_mean", "time_rms_std")
         for n in names:
-            self.out[n] = torch.empty(shp, device=self.step_state.device, dtype=torch.float32)
+            self.out[n] = empty(shp, self.step_state.device)
         H.ens_time_finalize(self.time_state[0], self.time_state[1], *[self.out[n] for n in names], self.S, self.B, self.H * self.W,
                             self.C, T)
         if self.grid is not None:
             names = ("time_uv_mean", "time_uv_std", "time_tke_mean", "time_tke_std", "time_vort_mean", "time_vort_std")
             for n in names:
-                self.out[n] = torch.empty((self.B, self.H, self.W), device=self.step_state.device, dtype=torch.float32)
+                self.out[n] = empty((self.B, self.H, self.W), self.step_state.device)
             H.ens_turb_finalize(self.time_state[1], self.turb_state[0], self.turb_state[1], [self.out[n] for n in names], self.S, self.B,
                                 self.H * self.W, self.C, T)
         return self.out

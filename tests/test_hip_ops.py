@@ -376,9 +376,9 @@ def test_level_pack_matches_torch_stacks(monkeypatch):
         for _ in range(NL):
             wts += [torch.randn(1, cin, 3, 3, generator=g).to(DEV), torch.randn(1, cin + 1, 3, 3, generator=g).to(DEV),
                     torch.randn(C, cin + 2, 3, 3, generator=g).to(DEV), torch.randn(C, generator=g).to(DEV), torch.randn(1, 1, 1, 1, generator=g).to(DEV)]
-        got = ops.LevelCouplingFn._level_operands(wts, NL, NLp, C, ch, Cc, torch.device(DEV))
+        got = ops.LevelCouplingFn._level_operands(ops._level(wts, C, Cc, False), torch.device(DEV))
         monkeypatch.setenv("TMG_NO_LEVEL_PACK", "1")
-        ref = ops.LevelCouplingFn._level_operands(wts, NL, NLp, C, ch, Cc, torch.device(DEV))
+        ref = ops.LevelCouplingFn._level_operands(ops._level(wts, C, Cc, False), torch.device(DEV))
         monkeypatch.delenv("TMG_NO_LEVEL_PACK")
         for a, b, what in zip(got, ref, ("Wz", "Wcat", "Bz", "Kp")):
             assert torch.equal(a, b), (NL, C, what)
