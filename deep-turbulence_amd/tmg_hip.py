@@ -20,14 +20,14 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmglow_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip"]
+SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip"]
 # Sources compiled WITHOUT the packed-fp32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32): beside MFMAs a packed
 # f32 instruction costs ~13 cycles more than the two scalar ones it replaces (MI355X_MICROARCH.md, cycle constants, 'price of one
 # filler beside MFMAs'), and the compiler SLP-packs adjacent scalar adds / multiplies by itself under -O3.  The matrix-core kernels'
 # files are listed; the vector-ALU kernels (tmg_pointwise.hip, tmg_physics.hip) keep the packed forms, which double their arithmetic
 # rate.  Round 3 measured the switch inside the noise and left the list empty; round 5 on one box, alternating three times: packed
 # everywhere 43.62 / 43.98 / 43.76 ms per step, this list 43.51 / 43.60 / 43.37 (wino + conv + coupling alone 43.64 / 43.52 / 43.58).
-NO_PACKED_F32 = ["tmg_wino.hip", "tmg_conv.hip", "tmg_coupling.hip", "tmg_thin.hip", "tmg_mix16.hip"]
+NO_PACKED_F32 = ["tmg_wino.hip", "tmg_conv.hip", "tmg_coupling.hip", "tmg_thin.hip", "tmg_mix16.hip", "tmg_spectrum.hip"]
 _lib = None
 
 c_i64 = ctypes.c_int64
@@ -40,6 +40,7 @@ EXPORTS = [
     "tmg_phys_fwd", "tmg_phys_rms", "tmg_phys_bwd", "tmg_conv_wgrad_grouped", "tmg_conv_wgrad_grouped_ws_floats", "tmg_conv_pack_batched", "tmg_masked_add", "tmg_c1x2_fwd", "tmg_c1_fwd", "tmg_c1_bwd", "tmg_dense2_bwd", "tmg_dkappa", "tmg_prof_enable", "tmg_prof_collect", "tmg_mix_f16", "tmg_phys_bwd_dev", "tmg_coupling_fwd", "tmg_coupling_bwd",
     "tmg_conv_wino_pack", "tmg_conv_wino_fwd", "tmg_conv_wino_narrow", "tmg_conv_wino_wgrad", "tmg_conv_wino_wgrad_ws_floats", "tmg_mix_f32", "tmg_lu_fold_fwd", "tmg_lu_fold_bwd", "tmg_lu_fold_bwd_split", "tmg_level_finish", "tmg_conv_wgrad_thin_grouped", "tmg_mix_wgrad_grouped", "tmg_layer_planes", "tmg_conv_wino_wgrad_grouped", "tmg_conv_wino_wgrad_grouped_ws_floats", "tmg_adam_step", "tmg_chan_moments", "tmg_bn_finalize64", "tmg_mix_f32_affine_fwd", "tmg_mix_f32_affine_bwd", "tmg_conv_pack_many", "tmg_pad_halves", "tmg_coupling_fwd_halves", "tmg_coupling_bwd_halves", "tmg_fill_i64", "tmg_conv_wino_pack3", "tmg_conv_wino_fwd3", "tmg_mat_inverse", "tmg_gauss_sample", "tmg_reverse_loss_fwd", "tmg_reverse_loss_bwd", "tmg_sum_terms", "tmg_vec_sum", "tmg_level_pack", "tmg_spread2", "tmg_phys_fields", "tmg_phys_fields_bwd",
     "tmg_gauss_sample_keyed", "tmg_ens_accum", "tmg_ens_time_finalize", "tmg_ens_turb_accum", "tmg_ens_turb_finalize",
+    "tmg_spec_rows", "tmg_spec_cols", "tmg_spec_accum", "tmg_spec_finalize",
 ]
 # Every export returns int except the workspace sizes, which the header declares int64_t (read through a 32-bit return a request of
 # 2^31 floats or more would be truncated and the kernel handed a buffer smaller than it planned for).
@@ -903,6 +904,35 @@ def ens_turb_finalize(tm2, cuv, tvort, outs, S, B, HW, C, T):
     outs = (uv_mean, uv_std, tke_mean, tke_std, vort_mean, vort_std) (tmg_ens_turb_finalize)."""
     _chk(lib().tmg_ens_turb_finalize(_ptr(tm2), _ptr(cuv), _ptr(tvort), *[_ptr(t) for t in outs], _i64(S, B, HW, C, T), _stream()),
          "tmg_ens_turb_finalize")
+
+
+def spec_rows(y, u, out_mu, out_std, ft_w, yw, k):
+    """Row transform of a chunk of k members (y: NHWC [k*B, H, W, C] or a channel-slice view; channels 0 and 1 un-normalised on
+    load) into the planar workspace yw [2, k*B, H, W]; ft_w: the operand matrix [2, W, W] (tmg_spec_rows)."""
+    kB, Hh, Ww, Cc = y.shape
+    ptr, ps, co, _ = seg(y)
+    _chk(lib().tmg_spec_rows(c_vp(ptr), _i64(ps, co), _ptr(u), _ptr(out_mu), _ptr(out_std), _ptr(ft_w), _ptr(yw),
+                             _i64(k, kB // k, Hh, Ww, Cc, yw.numel()), _stream()), "tmg_spec_rows")
+
+
+def spec_cols(ft_h, yw, perm, offs, part, n, Hh, Ww, NK):
+    """Column transform of the n images in yw (ft_h: [2, H, H]) and the shell sums of every 16-column tile, in the order of the
+    tiles' shell lists (perm, offs), into part [n, W/16, NK] (tmg_spec_cols)."""
+    _chk(lib().tmg_spec_cols(_ptr(ft_h), _ptr(yw), _ptr(perm), _ptr(offs), _ptr(part), _i64(n, Hh, Ww, NK, yw.numel(), part.numel()),
+                             _flts([0.5 / (float(Hh) * float(Ww)) ** 2]), _stream()), "tmg_spec_cols")
+
+
+def spec_accum(part, smean, sm2, tmean, outs, ostride, k, B, NK, QT, n_before, m0, t_before, flags):
+    """Fold the k members' spectra (part of spec_transform) into the step state (smean, sm2) or, flags & 2, write (spec_mean, spec_std)
+    = `outs` with per-case stride ostride; flags & 1 advances the members' running time means tmean (tmg_spec_accum)."""
+    outs = outs if outs is not None else (None,) * 2
+    _chk(lib().tmg_spec_accum(_ptr(part), _ptr(smean), _ptr(sm2), _ptr(tmean), *[_ptr(t) for t in outs],
+                              _i64(k, B, NK, QT, n_before, m0, t_before, flags, ostride), _stream()), "tmg_spec_accum")
+
+
+def spec_finalize(tmean, tm_mean, tm_std, S, B, NK):
+    """Mean / population std over the S members of their time-mean spectra (tmg_spec_finalize)."""
+    _chk(lib().tmg_spec_finalize(_ptr(tmean), _ptr(tm_mean), _ptr(tm_std), _i64(S, B, NK), _stream()), "tmg_spec_finalize")
 
 
 def reverse_loss_fwd(y, ld, loss, s1, s2):

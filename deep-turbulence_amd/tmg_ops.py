@@ -1715,3 +1715,151 @@ class EnsembleStats:
             H.ens_turb_finalize(self.time_state[1], self.turb_state[0], self.turb_state[1], [self.out[n] for n in names], self.S, self.B,
                                 self.H * self.W, self.C, T)
         return self.out
+
+
+def spectrum_bins(H_, W_, dx, dy):
+    """The shell map of an H x W field on a grid of cell size dx along W, dy along H (fp64, host): signed mode numbers p' (p - H
+    above H // 2), q' likewise, r = sqrt((p' Lmax / Ly)^2 + (q' Lmax / Lx)^2) with Lx = W dx, Ly = H dy, Lmax = max(Lx, Ly), shell
+    s = floor(r + 0.5).  Returns (bins int32 [H, W], k float64 [NK]): NK = 1 + max s, k[s] = s 2 pi / Lmax.  Every mode is kept: the
+    shells sum to 0.5 mean(|z|^2); shell 0 is the mean mode alone."""
+    Hn, Wn = int(H_), int(W_)
+    Lx, Ly = Wn * float(dx), Hn * float(dy)
+    Lmax = max(Lx, Ly)
+    p = torch.arange(Hn, dtype=torch.float64)
+    q = torch.arange(Wn, dtype=torch.float64)
+    p = torch.where(p <= Hn // 2, p, p - Hn) * (Lmax / Ly)
+    q = torch.where(q <= Wn // 2, q, q - Wn) * (Lmax / Lx)
+    r = torch.sqrt(p[:, None] ** 2 + q[None, :] ** 2)
+    bins = torch.floor(r + 0.5).to(torch.int32)
+    k = torch.arange(int(bins.max()) + 1, dtype=torch.float64) * (2.0 * math.pi / Lmax)
+    return bins, k
+
+
+def _spectrum_operand(N, window):
+    """[2, N, N] fp32 (re, im): T[n][m] = w[n] exp(-2 pi i ((n m) mod N) / N), the argument reduced with integers, built in fp64 and
+    rounded once.  w: the periodic Hann window over sqrt(mean(w^2)), or 1."""
+    n = torch.arange(N, dtype=torch.int64)
+    ang = ((n[:, None] * n[None, :]) % N).to(torch.float64) * (-2.0 * math.pi / N)
+    w = torch.ones(N, dtype=torch.float64)
+    if window == "hann":
+        w = 0.5 - 0.5 * torch.cos(2.0 * math.pi * n.to(torch.float64) / N)
+        w = w / torch.sqrt(torch.mean(w * w))
+    return torch.stack((w[:, None] * torch.cos(ang), w[:, None] * torch.sin(ang))).to(torch.float32).contiguous()
+
+
+def _spectrum_lists(bins, NK):
+    """Per 16-column tile of the bin map the tile's modes p * 16 + (q & 15) sorted by shell (stable) and the first list position of
+    every shell: (perm int32 [W/16, 16 H], offs int32 [W/16, NK + 1]).  The column pass sums a shell in this order."""
+    Hn, Wn = bins.shape
+    tiles = bins.view(Hn, Wn // 16, 16).permute(1, 0, 2).reshape(Wn // 16, Hn * 16).to(torch.int64)
+    perm = torch.argsort(tiles, dim=1, stable=True).to(torch.int32)
+    offs = torch.zeros((Wn // 16, NK + 1), dtype=torch.int64)
+    for t in range(Wn // 16):
+        offs[t, 1:] = torch.cumsum(torch.bincount(tiles[t], minlength=NK), 0)
+    return perm.contiguous(), offs.to(torch.int32).contiguous()
+
+
+SPECTRUM_MAX_SHELLS = 8192
+
+
+class EnsembleSpectrum:
+    """On-device shell-binned kinetic-energy spectra E(k) of sampled roll-outs of B cases (tmg_spec_rows / tmg_spec_cols /
+    tmg_spec_accum / tmg_spec_finalize).  Per case, member and kept step: z = g (u + i v) from channels 0 and 1 of the un-normalised
+    field yh = u[b, c] (out_std[c] y + out_mu[c]) (the pressure is ignored), g[y, x] = w_H[y] w_W[x] the periodic Hann window
+    w_N[n] = 0.5 - 0.5 cos(2 pi n / N) over sqrt(mean(w_N^2)) (window=None: g = 1), Z = fft2(z), E2 = 0.5 |Z|^2 / (H W)^2, and
+    E[s] the sum of E2 over shell s of spectrum_bins(H, W, dx, dy).  The transform is a dense DFT on the fp32 matrix pipe with the
+    window folded into its operand matrices; H and W are multiples of 16 up to 512.
+
+    Feeding protocol of EnsembleStats: every step's members in chunks of whole members, in member order, each step's chunks before
+    the next step's.  y: API-shaped [k*B, C, H, W], 2 <= C <= 4.  Outputs (device tensors): spec_mean, spec_std [B, Tk, NK] (mean and
+    population std over the members); finalize() adds time_spec_mean, time_spec_std [B, NK] (mean / std over the members of each
+    member's time mean of E over the steps folded with time=True) and spec_k [NK] (float64, host: the shell centres s 2 pi / Lmax)."""
+
+    def __init__(self, members, B, Hh, Ww, steps, device, out_mu, out_std, u=None, grid=(1.0, 1.0), window="hann"):
+        try:
+            grid = tuple(float(g) for g in grid)
+        except TypeError:
+            raise ValueError("grid needs two positive finite cell sizes (dx, dy), got %r" % (grid,)) from None
+        if len(grid) != 2 or not all(math.isfinite(g) and g > 0 for g in grid):
+            raise ValueError("grid needs two positive finite cell sizes (dx, dy), got %s" % (grid,))
+        if window not in ("hann", None):
+            raise ValueError("window must be 'hann' or None, got %r" % (window,))
+        Hh, Ww = int(Hh), int(Ww)
+        if not all(16 <= n <= 512 and n % 16 == 0 for n in (Hh, Ww)):
+            raise ValueError("spectra need H and W that are a multiple of 16 in [16, 512], got %d x %d" % (Hh, Ww))
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("ensemble spectra run on the HIP path: device %s is not a GPU (there is no CPU path)" % dev)
+        bins, k = spectrum_bins(Hh, Ww, grid[0], grid[1])
+        NK = k.numel()
+        if NK > SPECTRUM_MAX_SHELLS:
+            raise ValueError("grid %s gives %d shells on %d x %d modes, at most %d are supported" % (grid, NK, Hh, Ww, SPECTRUM_MAX_SHELLS))
+        self.grid, self.window = grid, window
+        self.S, self.B, self.H, self.W, self.Tk, self.NK = int(members), int(B), Hh, Ww, int(steps), NK
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.mu = torch.as_tensor(out_mu, **f32).reshape(-1)[:2].contiguous()
+        self.sd = torch.as_tensor(out_std, **f32).reshape(-1)[:2].contiguous()
+        if self.mu.numel() != 2 or self.sd.numel() != 2:
+            raise ValueError("out_mu / out_std need at least 2 entries, got %d / %d" % (self.mu.numel(), self.sd.numel()))
+        self.u = None if u is None else torch.as_tensor(u, **f32).reshape(self.B, -1)[:, :2].contiguous()
+        if self.u is not None and self.u.shape[1] != 2:
+            raise ValueError("u needs at least 2 entries per case")
+        self.k = k
+        self.bins = bins                  # host: the device reads the shell lists derived from it
+        perm, offs = _spectrum_lists(bins, NK)
+        self.perm, self.offs = perm.to(dev), offs.to(dev)
+        self.ft_w = _spectrum_operand(Ww, window).to(dev)
+        self.ft_h = self.ft_w if Hh == Ww else _spectrum_operand(Hh, window).to(dev)
+        self.step_state = torch.empty((2, self.B, NK), **f32)
+        self.time_state = torch.empty((self.S, self.B, NK), **f32)
+        self.out = {"spec_mean": torch.empty((self.B, self.Tk, NK), **f32), "spec_std": torch.empty((self.B, self.Tk, NK), **f32)}
+        self._yw = self._part = None      # workspace of the largest chunk: the planar row transform, the tiles' partial spectra
+        self._n = 0
+        self._step = 0
+        self._t = [0] * self.S
+
+    def add(self, y, m0, time=True):
+        """Fold the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
+        channel-slice; rows member-major)."""
+        yn = y.permute(0, 2, 3, 1)
+        kB = yn.shape[0]
+        if kB % self.B or tuple(yn.shape[1:3]) != (self.H, self.W) or not 2 <= yn.shape[3] <= 4:
+            raise ValueError("chunk shape %s does not hold whole members of [%d, 2..4, %d, %d]" % (tuple(y.shape), self.B, self.H, self.W))
+        k = kB // self.B
+        if m0 != self._n or m0 + k > self.S or self._step >= self.Tk:
+            raise ValueError("members must be fed in order, every step's chunks before the next step's")
+        t_before = self._t[m0]
+        if time and any(self._t[m] != t_before for m in range(m0, m0 + k)):
+            raise ValueError("members of one chunk hold different numbers of time steps")
+        H.check_device(yn)
+        last = m0 + k == self.S
+        QT = self.W // 16
+        if self._yw is None or self._yw.numel() < 2 * kB * self.H * self.W:
+            self._yw = torch.empty(2 * kB * self.H * self.W, device=self.step_state.device, dtype=torch.float32)
+            self._part = torch.empty(kB * QT * self.NK, device=self.step_state.device, dtype=torch.float32)
+        t = self._step
+        flags = (1 if time else 0) | (2 if last else 0)
+        H.spec_rows(yn, self.u, self.mu, self.sd, self.ft_w, self._yw, k)
+        H.spec_cols(self.ft_h, self._yw, self.perm, self.offs, self._part, kB, self.H, self.W, self.NK)
+        o = self.out
+        H.spec_accum(self._part, self.step_state[0], self.step_state[1], self.time_state,
+                     (o["spec_mean"][:, t], o["spec_std"][:, t]) if last else None, self.Tk * self.NK, k, self.B, self.NK, QT, self._n,
+                     m0, t_before, flags)
+        if time:
+            for m in range(m0, m0 + k):
+                self._t[m] += 1
+        self._n = 0 if last else self._n + k
+        self._step += 1 if last else 0
+
+    def finalize(self):
+        """-> dict of the outputs; the time statistics cover the steps folded with time=True."""
+        if self._step != self.Tk:
+            raise RuntimeError("%d of %d steps folded" % (self._step, self.Tk))
+        T = self._t[0]
+        if T < 1 or any(t != T for t in self._t):
+            raise RuntimeError("no time statistics: no step was folded with time=True")
+        for n in ("time_spec_mean", "time_spec_std"):
+            self.out[n] = empty((self.B, self.NK), self.step_state.device)
+        H.spec_finalize(self.time_state, self.out["time_spec_mean"], self.out["time_spec_std"], self.S, self.B, self.NK)
+        self.out["spec_k"] = self.k
+        return self.out

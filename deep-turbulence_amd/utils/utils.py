@@ -98,9 +98,11 @@ _TARGET_STATS = (("target_time_mean", "time_mean_mean"), ("target_time_rms", "ti
                  ("target_time_tke", "time_tke_mean"), ("target_time_vort", "time_vort_mean"))
 
 
-def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, turbulence):
-    """The body of modelPredStats and modelPredTurbulence (turbulence: grid = (args.dx, args.dy)): same seed draws in the same order, same
-    folding, same re-anchoring, so that the keys the two share hold identical values under the same host RNG state."""
+def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, turbulence, spectra=False,
+                   window="hann"):
+    """The body of modelPredStats, modelPredTurbulence (turbulence: grid = (args.dx, args.dy)) and modelPredSpectra (spectra: the same
+    chunks also go through an EnsembleSpectrum with `window`): same seed draws in the same order, same folding, same re-anchoring, so
+    that the keys they share hold identical values under the same host RNG state."""
     import tmg_ops as ops
     core = getattr(model, "module", model)
     core.eval()
@@ -141,16 +143,26 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
                        for m0, k in chunks]
             states = [[(h.clone(), c.clone()) for h, c in a] for a in anchors]
             st = ops.EnsembleStats(samples, B, C, Hh, Ww, nkeep, dev, out_mu, out_std, u=u.view(B, 3)[:, :C], grid=grid)
+            sp = ops.EnsembleSpectrum(samples, B, Hh, Ww, nkeep, dev, out_mu, out_std, u=u.view(B, 3), grid=grid,
+                                      window=window) if spectra else None
             for tstep in range(tmax):
                 keep = tstep % stride == 0 and tstep // stride < nkeep
                 for ci, (m0, k) in enumerate(chunks):
                     y0, _logp, states[ci] = core.sampleEnsemble(inp[:, tstep], states[ci], k)
                     if keep:
                         st.add(y0, m0, time=tstep // stride >= t_start)
+                        if sp is not None:
+                            sp.add(y0, m0, time=tstep // stride >= t_start)
                     if tstep % 20 == 0:
                         states[ci] = [(0.5 * h + 0.5 * hk, 0.5 * c + 0.5 * ck) for (h, c), (hk, ck) in zip(states[ci], anchors[ci])]
             for key, t in st.finalize().items():
                 outs.setdefault(key, []).append(t.cpu())
+            if sp is not None:
+                for key, t in sp.finalize().items():
+                    if key == "spec_k":
+                        spec_k = t
+                    else:
+                        outs.setdefault(key, []).append(t.cpu())
             if grid is not None:
                 # the target's own time statistics over the same kept steps: the normalised series as a one-member ensemble
                 if target0.size(1) <= (nkeep - 1) * stride:
@@ -158,14 +170,25 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
                                      % (name, target0.size(1), nkeep - 1, (nkeep - 1) * stride))
                 tn = target0.to(dev)
                 ts = ops.EnsembleStats(1, B, C, Hh, Ww, nkeep - t_start, dev, out_mu, out_std, u=u.view(B, 3)[:, :C], grid=grid)
+                tsp = ops.EnsembleSpectrum(1, B, Hh, Ww, nkeep - t_start, dev, out_mu, out_std, u=u.view(B, 3), grid=grid,
+                                           window=window) if spectra else None
                 for j in range(t_start, nkeep):
-                    ts.add(tn[:, j * stride].contiguous(memory_format=torch.channels_last), 0)
+                    tj = tn[:, j * stride].contiguous(memory_format=torch.channels_last)
+                    ts.add(tj, 0)
+                    if tsp is not None:
+                        tsp.add(tj, 0)
                 tout = ts.finalize()
                 for key, src in _TARGET_STATS:
                     outs.setdefault(key, []).append(tout[src].cpu())
+                if tsp is not None:
+                    tout = tsp.finalize()
+                    outs.setdefault("target_spec", []).append(tout["spec_mean"].cpu())
+                    outs.setdefault("target_time_spec", []).append(tout["time_spec_mean"].cpu())
     res = {key: torch.cat(v, dim=0) for key, v in outs.items()}
     res["target"] = torch.cat(targets, dim=0)
     res["input"] = torch.cat(inputs, dim=0)
+    if spectra:
+        res["spec_k"] = spec_k
     return res
 
 
@@ -203,3 +226,25 @@ def modelPredTurbulence(args, model, testing_loader, log, samples=1, stride=1, t
                                               the same time statistics of the target series over the same steps (target step
                                               j * stride for kept step j), through the same kernels as a one-member ensemble."""
     return _ensembleStats("modelPredTurbulence", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, True)
+
+
+def modelPredSpectra(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, window="hann"):
+    """modelPredTurbulence plus the shell-binned kinetic-energy spectra E(k) of the velocity field (channels 0, 1) on the grid
+    (args.dx along W, args.dy along H), still without forming modelPred's [samples, N, T, C, H, W] tensor: the 2-D DFT of
+    g (u + i v) of every member and kept step on the device (tmg_ops.EnsembleSpectrum; g: the periodic Hann window over its RMS, or 1
+    for window=None), E2 = 0.5 |Z|^2 / (H W)^2 summed over the shells of tmg_ops.spectrum_bins, so that the shells of one field sum
+    to 0.5 mean(g^2 (u^2 + v^2)).  H and W must be multiples of 16 up to 512.  Same roll-outs as modelPredTurbulence: under the same
+    host RNG state the keys both return are identical.
+
+    Returns modelPredTurbulence's dict plus (CPU tensors):
+      spec_k [NK] float64                    the shell centres s 2 pi / max(W dx, H dy)
+      spec_mean, spec_std [N, Tk, NK]        mean / population std over the members of E, per kept step
+      time_spec_mean, time_spec_std [N, NK]  mean / std over the members of each member's time mean of E over the kept steps
+                                             t_start..Tk-1
+      target_spec [N, Tk - t_start, NK], target_time_spec [N, NK]
+                                             E of the target series at those steps (target step j * stride for kept step j) and its
+                                             time mean, through the same kernels as a one-member ensemble."""
+    if window not in ("hann", None):
+        raise ValueError("window must be 'hann' or None, got %r" % (window,))
+    return _ensembleStats("modelPredSpectra", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, True,
+                          spectra=True, window=window)

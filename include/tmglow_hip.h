@@ -451,6 +451,30 @@ int tmg_ens_turb_accum(const void* y, const int64_t* y_d, const void* u, const v
 int tmg_ens_turb_finalize(const void* tm2, const void* cuv, const void* tvort, void* uv_mean, void* uv_std, void* tke_mean,
                           void* tke_std, void* tv_mean, void* tv_std, const int64_t* dims, tmg_stream_t st);
 
+/* Shell-binned kinetic-energy spectra of the same chunks (tmg_spectrum.hip; no atomics: bitwise reproducible).  Per image (row
+ * j*B + b of the chunk) z = u + i v from channels 0 and 1 of yh = u[b][c] * (out_std[c] * y + out_mu[c]) (u: [B][2] or NULL for 1;
+ * out_mu, out_std: 2 floats), Z = T_H^T z T_W as two dense products on the fp32 matrix pipe, E2 = fl[0] |Z|^2 summed per shell.
+ * T_N: the N-point operand matrix, planes (re, im) of [n][m] floats, T[n][m] = w[n] exp(-2 pi i ((n m) mod N) / N) with the window w
+ * folded in.  H and W: multiples of 16 in [16, 512], else -1.  A workspace smaller than stated below: -4.
+ * tmg_spec_rows: the row transform of a chunk of k members.  y, y_d as tmg_ens_accum (pixel stride, channel offset; C channels,
+ * 2 <= C <= 4, of which 0 and 1 are read); ft = T_W; yw: planar workspace [2][k*B][H][W] (re, im).  dims = {k, B, H, W, C, floats of yw}. */
+int tmg_spec_rows(const void* y, const int64_t* y_d, const void* u, const void* out_mu, const void* out_std, const void* ft, void* yw,
+                  const int64_t* dims, tmg_stream_t st);
+/* tmg_spec_cols: the column transform of the n = k*B images in yw (ft = T_H) and the shell sums of every 16-column tile in the fixed
+ * order of a host-built list: perm [W/16][16 H] int32 holds the tile's mode indices p * 16 + (q & 15) sorted by shell, offs
+ * [W/16][NK + 1] int32 the first list position of every shell; part [n][W/16][NK] receives the tiles' partial spectra.
+ * dims = {n, H, W, NK, floats of yw, floats of part}; fl = {0.5 / (H W)^2}; NK > 8192: -2. */
+int tmg_spec_cols(const void* ft, const void* yw, const void* perm, const void* offs, void* part, const int64_t* dims, const float* fl,
+                  tmg_stream_t st);
+/* tmg_spec_accum: E[s] of member m0 + j, case b = sum over the QT tiles of part (in tile order), folded as tmg_ens_accum folds a
+ * channel: step state smean, sm2 [B][NK] holding n_before members; flags & 1: each member's running time mean tmean [S][B][NK]
+ * (holding t_before steps) advances; flags & 2: the step's last chunk, mean and population std go to mean_out / std_out
+ * (+ b * dims[8]) instead of the step state.  dims = {k, B, NK, QT, n_before, m0, t_before, flags, per-case stride of the outputs}. */
+int tmg_spec_accum(const void* part, void* smean, void* sm2, void* tmean, void* mean_out, void* std_out, const int64_t* dims,
+                   tmg_stream_t st);
+/* tmg_spec_finalize: mean and population std over the S members of their time means: tm_mean, tm_std [B][NK].  dims = {S, B, NK}. */
+int tmg_spec_finalize(const void* tmean, void* tm_mean, void* tm_std, const int64_t* dims, tmg_stream_t st);
+
 /* The benchmark loss of SURVEY 8-D, generative direction: *loss += fl[0] sum(y^2) + fl[1] sum(logdet) (the caller zeroes *loss;
  * fl = {1 / numel(y), 1 / (B noc H W)}), and its gradient dy = 2 fl[0] *g y, dld[b] = fl[1] *g with the upstream gradient read from
  * device memory.  y, dy: n contiguous floats, 16-byte aligned.  dims = {n, B}.  Replaces the pow / mean / div / add chain the
