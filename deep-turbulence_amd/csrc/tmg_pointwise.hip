@@ -27,8 +27,10 @@ static inline int grid_for(size_t n, int cap = 4096) {
 __global__ __launch_bounds__(256) void affine_apply_kernel(const float* __restrict__ hh, int hs, int ho, const float* x2, int xs,
                                                            int xo, float* y2, int ys, int yo, float* __restrict__ rsave,
                                                            float* __restrict__ logdet, int pix_per_img, int Ch, int reverse, int vec,
-                                                           const float* x1, int x1s, float* y1, int y1s) {
+                                                           const float* x1, int x1s, float* y1, int y1s, int hpair) {
     // x1 / y1 (optional): the pass-through half of the coupling, copied here instead of in a launch of its own
+    // hpair: every (shift_j, r_j) pair of hh is 8-byte aligned (the launcher checks pointer, stride and offset); otherwise - a view
+    // with an odd channel offset or an odd pixel stride - the scalar path reads the pair as two floats
     __shared__ float red[4];
     const int b = blockIdx.y;
     const size_t base = (size_t)b * pix_per_img;
@@ -60,7 +62,8 @@ __global__ __launch_bounds__(256) void affine_apply_kernel(const float* __restri
     for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
         const size_t pix = base + i / Ch;
         const int j = i % Ch;
-        const float2 h2 = *reinterpret_cast<const float2*>(hh + pix * hs + ho + 2 * j);
+        const float* hp = hh + pix * hs + ho + 2 * j;
+        const float2 h2 = hpair ? *reinterpret_cast<const float2*>(hp) : make_float2(hp[0], hp[1]);
         const float r = h2.y;
         const float sg = 2.f * r / (1.f + fabsf(r));
         const float xv = x2[pix * xs + xo + j];
@@ -78,10 +81,11 @@ __global__ __launch_bounds__(256) void affine_apply_kernel(const float* __restri
 
 // gout: grad w.r.t. op output half; yref: forward -> op OUTPUT y2, reverse -> op INPUT y2.
 // gin: grad w.r.t. op input half; dhh: [npix][C] interleaved (da, dr).  g: per-sample grad on logdet.
+// dpair: every (da_j, dr_j) pair of dhh is 8-byte aligned (checked by the launcher); otherwise it is written as two floats.
 __global__ void affine_bwd_kernel(const float* gout, int gs, int go, const float* __restrict__ yref, int rs_, int ro,
                                   const float* __restrict__ rsave, const float* __restrict__ g, float* gin, int is, int io,
                                   float* __restrict__ dhh, int ds, int dof, int pix_per_img, int Ch, size_t npix, int reverse,
-                                  const float* __restrict__ kappa) {
+                                  const float* __restrict__ kappa, int dpair) {
     const float hsc = out_scale_of(kappa);   // kappa given: dhh is written pre-multiplied by exp(clamp(kappa))
     const size_t total = npix * Ch;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -107,7 +111,10 @@ __global__ void affine_bwd_kernel(const float* gout, int gs, int go, const float
             dsg = 2.f * go_ * yv + 2.f * gb;
         }
         gin[pix * is + io + j] = gi;
-        *reinterpret_cast<float2*>(dhh + pix * ds + dof + 2 * j) = make_float2(da * hsc, hsc * dsg / (den * den));
+        float* dp = dhh + pix * ds + dof + 2 * j;
+        const float2 d2 = make_float2(da * hsc, hsc * dsg / (den * den));
+        if (dpair) *reinterpret_cast<float2*>(dp) = d2;
+        else { dp[0] = d2.x; dp[1] = d2.y; }
     }
 }
 
@@ -118,6 +125,35 @@ __global__ void affine_bwd_kernel(const float* gout, int gs, int go, const float
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
+// One hidden channel of the forward and of the backward pass.  The scalar kernels and the float4 kernels both call these two, and
+// every fused multiply-add in them is written out with contraction switched off: left to the compiler, the float4 kernel (its four
+// channels unrolled and packed in pairs) fused the other product of gf cp + gi gg than the scalar kernel did, and the two kernels
+// differed in the last bit of c_next.  (The fused forms are the ones the compiler chose for the scalar kernels.)
+struct LstmF1 { float cn, hn; };
+struct LstmB1 { float r0, r1, r2, r3, dp; };
+__device__ __forceinline__ LstmF1 lstm_fwd1(float ai, float af, float ao, float ag, float cp) {
+#pragma clang fp contract(off)
+    const float gi = sigmoidf_(ai), gf = sigmoidf_(af), go = sigmoidf_(ao), gg = tanhf(ag);
+    LstmF1 o;
+    o.cn = fmaf(gi, gg, gf * cp);
+    o.hn = go * tanhf(o.cn);
+    return o;
+}
+// pre-activation gate gradients (i, f, o, g) and the gradient of the previous cell state
+__device__ __forceinline__ LstmB1 lstm_bwd1(float ai, float af, float ao, float ag, float cp, float cnx, float dhv, float dci) {
+#pragma clang fp contract(off)
+    const float gi = sigmoidf_(ai), gf = sigmoidf_(af), go = sigmoidf_(ao), gg = tanhf(ag);
+    const float tc = tanhf(cnx);
+    const float dc = fmaf(dhv * go, fmaf(-tc, tc, 1.f), dci);
+    LstmB1 o;
+    o.r0 = dc * gg * gi * (1.f - gi);
+    o.r1 = dc * cp * gf * (1.f - gf);
+    o.r2 = dhv * tc * go * (1.f - go);
+    o.r3 = dc * gi * fmaf(-gg, gg, 1.f);
+    o.dp = dc * gf;
+    return o;
+}
+
 __global__ void lstm_pointwise_fwd_kernel(const float* __restrict__ gates, const float* __restrict__ c_prev, int cps, int cpo,
                                           float* __restrict__ c_next, float* __restrict__ h_next, int R, size_t npix) {
     const size_t total = npix * R;
@@ -125,32 +161,17 @@ __global__ void lstm_pointwise_fwd_kernel(const float* __restrict__ gates, const
         const size_t pix = i / R;
         const int j = i % R;
         const float* gp = gates + pix * 4 * R + j;
-        const float gi = sigmoidf_(gp[0]), gf = sigmoidf_(gp[R]), go = sigmoidf_(gp[2 * R]), gg = tanhf(gp[3 * R]);
-        const float cp = c_prev ? c_prev[pix * cps + cpo + j] : 0.f;
-        const float cn = gf * cp + gi * gg;
-        c_next[pix * R + j] = cn;
-        h_next[pix * R + j] = go * tanhf(cn);
+        const LstmF1 e = lstm_fwd1(gp[0], gp[R], gp[2 * R], gp[3 * R], c_prev ? c_prev[pix * cps + cpo + j] : 0.f);
+        c_next[pix * R + j] = e.cn;
+        h_next[pix * R + j] = e.hn;
     }
 }
 
 // The same, four consecutive hidden channels per thread (float4 loads / stores, 32-bit index arithmetic): R and the c_prev stride /
-// offset multiples of 4, 16-byte aligned tensors, fewer than 2^31 quads (the launcher checks).  Element for element the arithmetic
-// of the scalar kernel.  Rq = R / 4.
+// offset multiples of 4, 16-byte aligned tensors, fewer than 2^31 quads (the launcher checks).  Bit for bit the values of the
+// scalar kernels, and only because every kernel here calls lstm_fwd1 / lstm_bwd1 (contraction off, explicit fmaf): keep the formulas
+// there, not inlined in a kernel (tests/test_pointwise_kernels.py::test_lstm_vec_equals_scalar).  Rq = R / 4.
 #define TMG_F4(V) {(V).x, (V).y, (V).z, (V).w}
-struct LstmB1 { float r0, r1, r2, r3, dp; };
-// one hidden channel of lstm_pointwise_bwd_kernel: pre-activation gate gradients (i, f, o, g) and the gradient of the previous cell state
-__device__ __forceinline__ LstmB1 lstm_bwd1(float ai, float af, float ao, float ag, float cp, float cnx, float dhv, float dci) {
-    const float gi = sigmoidf_(ai), gf = sigmoidf_(af), go = sigmoidf_(ao), gg = tanhf(ag);
-    const float tc = tanhf(cnx);
-    const float dc = dci + dhv * go * (1.f - tc * tc);
-    LstmB1 o;
-    o.r0 = dc * gg * gi * (1.f - gi);
-    o.r1 = dc * cp * gf * (1.f - gf);
-    o.r2 = dhv * tc * go * (1.f - go);
-    o.r3 = dc * gi * (1.f - gg * gg);
-    o.dp = dc * gf;
-    return o;
-}
 __global__ __launch_bounds__(256) void lstm_pointwise_fwd4_kernel(const float* __restrict__ gates, const float* __restrict__ c_prev, int cps, int cpo,
                                            float* __restrict__ c_next, float* __restrict__ h_next, int Rq, unsigned npix) {
     const unsigned total = npix * (unsigned)Rq;
@@ -166,9 +187,9 @@ __global__ __launch_bounds__(256) void lstm_pointwise_fwd4_kernel(const float* _
         float cn[4], hn[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float gi = sigmoidf_(ai[e]), gf = sigmoidf_(af[e]), go = sigmoidf_(ao[e]), gg = tanhf(ag[e]);
-            cn[e] = gf * cp[e] + gi * gg;
-            hn[e] = go * tanhf(cn[e]);
+            const LstmF1 r = lstm_fwd1(ai[e], af[e], ao[e], ag[e], cp[e]);
+            cn[e] = r.cn;
+            hn[e] = r.hn;
         }
         *reinterpret_cast<float4*>(c_next + (size_t)pix * R + j) = make_float4(cn[0], cn[1], cn[2], cn[3]);
         *reinterpret_cast<float4*>(h_next + (size_t)pix * R + j) = make_float4(hn[0], hn[1], hn[2], hn[3]);
@@ -211,16 +232,13 @@ __global__ void lstm_pointwise_bwd_kernel(float* __restrict__ acts, const float*
         const size_t pix = i / R;
         const int j = i % R;
         float* gp = acts + pix * 4 * R + j;
-        const float gi = sigmoidf_(gp[0]), gf = sigmoidf_(gp[R]), go = sigmoidf_(gp[2 * R]), gg = tanhf(gp[3 * R]);
-        const float cp = c_prev ? c_prev[pix * cps + cpo + j] : 0.f;
-        const float tc = tanhf(c_next[pix * R + j]);
-        const float dhv = dh ? dh[pix * R + j] : 0.f;
-        const float dc = (dc_in ? dc_in[pix * R + j] : 0.f) + dhv * go * (1.f - tc * tc);
-        gp[0] = dc * gg * gi * (1.f - gi);
-        gp[R] = dc * cp * gf * (1.f - gf);
-        gp[2 * R] = dhv * tc * go * (1.f - go);
-        gp[3 * R] = dc * gi * (1.f - gg * gg);
-        if (dc_prev) dc_prev[pix * R + j] = dc * gf;     // null: the previous cell state carries no gradient (nothing to write)
+        const LstmB1 e = lstm_bwd1(gp[0], gp[R], gp[2 * R], gp[3 * R], c_prev ? c_prev[pix * cps + cpo + j] : 0.f, c_next[pix * R + j],
+                                   dh ? dh[pix * R + j] : 0.f, dc_in ? dc_in[pix * R + j] : 0.f);
+        gp[0] = e.r0;
+        gp[R] = e.r1;
+        gp[2 * R] = e.r2;
+        gp[3 * R] = e.r3;
+        if (dc_prev) dc_prev[pix * R + j] = e.dp;     // null: the previous cell state carries no gradient (nothing to write)
     }
 }
 
@@ -1512,6 +1530,9 @@ extern "C" int tmg_affine_apply_pass(const void* hh, const int64_t* hh_d, const 
     int vec = ((Ch & 3) == 0) && (((hh_d[0] | hh_d[1] | x_d[0] | x_d[1] | y_d[0] | y_d[1]) & 3) == 0) &&
               (((((uintptr_t)hh) | ((uintptr_t)x2) | ((uintptr_t)y2) | ((uintptr_t)rsave)) & 15) == 0);
     if (x1 && (((x1_d[0] | y1_d[0]) & 3) || ((((uintptr_t)x1) | ((uintptr_t)y1)) & 15))) vec = 0;
+    // the scalar path reads (shift_j, r_j) as one float2 only where every pair is 8-byte aligned: a channel-slice view whose offset
+    // (folded into the pointer by the Python binding) or pixel stride is odd is read float by float
+    const int hpair = (((hh_d[0] | hh_d[1]) & 1) == 0) && ((((uintptr_t)hh) & 7) == 0);
     const size_t per = (size_t)ppi * (vec ? Ch / 4 : Ch);
     int gx = (int)((per + 1023) / 1024);  // >= 4 items per thread
     if (gx > 64) gx = 64;
@@ -1519,7 +1540,8 @@ extern "C" int tmg_affine_apply_pass(const void* hh, const int64_t* hh_d, const 
     TmgProf prof(TMG_PROF_AFF, 4.0 * B * (double)ppi * Ch * (x1 ? 7 : 5), st);
     hipLaunchKernelGGL(affine_apply_kernel, dim3(gx, B), dim3(256), 0, st, (const float*)hh, (int)hh_d[0], (int)hh_d[1],
                        (const float*)x2, (int)x_d[0], (int)x_d[1], (float*)y2, (int)y_d[0], (int)y_d[1], (float*)rsave, (float*)logdet,
-                       ppi, Ch, (int)dims[3], vec, (const float*)x1, x1 ? (int)x1_d[0] : 0, x1 ? (float*)y1 : nullptr, x1 ? (int)y1_d[0] : 0);
+                       ppi, Ch, (int)dims[3], vec, (const float*)x1, x1 ? (int)x1_d[0] : 0, x1 ? (float*)y1 : nullptr, x1 ? (int)y1_d[0] : 0,
+                       hpair);
     TMG_CHECK_LAUNCH();
     return 0;
 }
@@ -1542,9 +1564,10 @@ extern "C" int tmg_affine_bwd_scaled(const void* gout, const int64_t* go_d, cons
     const int B = (int)dims[0], ppi = (int)dims[1], Ch = (int)dims[2];
     const size_t npix = (size_t)B * ppi;
     TmgProf prof(TMG_PROF_AFFB, 4.0 * (double)npix * Ch * 6, st);   // reads gout, yref, r; writes gin, dhh (2 Ch)
+    const int dpair = (((dh_d[0] | dh_d[1]) & 1) == 0) && ((((uintptr_t)dhh) & 7) == 0);   // float2 stores of (da_j, dr_j) are aligned
     hipLaunchKernelGGL(affine_bwd_kernel, dim3(grid_for(npix * Ch)), dim3(256), 0, st, (const float*)gout, (int)go_d[0], (int)go_d[1],
                        (const float*)yref, (int)yr_d[0], (int)yr_d[1], (const float*)rsave, (const float*)g, (float*)gin, (int)gi_d[0],
-                       (int)gi_d[1], (float*)dhh, (int)dh_d[0], (int)dh_d[1], ppi, Ch, npix, (int)dims[3], (const float*)kappa);
+                       (int)gi_d[1], (float*)dhh, (int)dh_d[0], (int)dh_d[1], ppi, Ch, npix, (int)dims[3], (const float*)kappa, dpair);
     TMG_CHECK_LAUNCH();
     return 0;
 }

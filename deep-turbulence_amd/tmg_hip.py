@@ -1072,7 +1072,9 @@ def c1_bwd(inputs, w, dW, dd, dref, gsegs, relu_in=True):
 
 
 def dkappa(w, dw, b, db, kappa, dk):
-    _chk(lib().tmg_dkappa(_ptr(w), _ptr(dw), c_i64(w.numel()), _ptr(b), _ptr(db), c_i64(b.numel()), _ptr(kappa), _ptr(dk), _stream()),
+    """dk += <w, dw> + <b, db> when kappa lies inside its clamp range (b / db None: a convolution without bias)."""
+    _chk(lib().tmg_dkappa(_ptr(w), _ptr(dw), c_i64(w.numel()), _ptr(b), _ptr(db), c_i64(b.numel() if b is not None else 0), _ptr(kappa),
+                          _ptr(dk), _stream()),
          "tmg_dkappa")
 
 

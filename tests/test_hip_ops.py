@@ -1,5 +1,7 @@
 """GPU parity of every HIP primitive against a plain PyTorch fp32/fp64 CPU reference of the same op.
-Runs through the C ABI (ctypes -> libtmglow_hip.so)."""
+Runs through the C ABI (ctypes -> libtmglow_hip.so).  The bandwidth-bound kernels (affine, LSTM pointwise, Gaussian, channel
+reductions / BatchNorm pieces, masked add, checker, ...) are tested kernel by kernel, on every dispatch path and launch-plan edge,
+in test_pointwise_kernels.py; the fused coupling and mix kernels in test_coupling_kernels.py."""
 import math
 
 import pytest
