@@ -20,7 +20,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmglow_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip"]
+SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip"]
 # Sources compiled WITHOUT the packed-fp32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32): beside MFMAs a packed
 # f32 instruction costs ~13 cycles more than the two scalar ones it replaces (MI355X_MICROARCH.md, cycle constants, 'price of one
 # filler beside MFMAs'), and the compiler SLP-packs adjacent scalar adds / multiplies by itself under -O3.  The matrix-core kernels'
@@ -41,6 +41,7 @@ EXPORTS = [
     "tmg_conv_wino_pack", "tmg_conv_wino_fwd", "tmg_conv_wino_narrow", "tmg_conv_wino_wgrad", "tmg_conv_wino_wgrad_ws_floats", "tmg_mix_f32", "tmg_lu_fold_fwd", "tmg_lu_fold_bwd", "tmg_lu_fold_bwd_split", "tmg_level_finish", "tmg_conv_wgrad_thin_grouped", "tmg_mix_wgrad_grouped", "tmg_layer_planes", "tmg_conv_wino_wgrad_grouped", "tmg_conv_wino_wgrad_grouped_ws_floats", "tmg_adam_step", "tmg_chan_moments", "tmg_bn_finalize64", "tmg_mix_f32_affine_fwd", "tmg_mix_f32_affine_bwd", "tmg_conv_pack_many", "tmg_pad_halves", "tmg_coupling_fwd_halves", "tmg_coupling_bwd_halves", "tmg_fill_i64", "tmg_conv_wino_pack3", "tmg_conv_wino_fwd3", "tmg_mat_inverse", "tmg_gauss_sample", "tmg_reverse_loss_fwd", "tmg_reverse_loss_bwd", "tmg_sum_terms", "tmg_vec_sum", "tmg_level_pack", "tmg_spread2", "tmg_phys_fields", "tmg_phys_fields_bwd",
     "tmg_gauss_sample_keyed", "tmg_ens_accum", "tmg_ens_time_finalize", "tmg_ens_turb_accum", "tmg_ens_turb_finalize",
     "tmg_spec_rows", "tmg_spec_cols", "tmg_spec_accum", "tmg_spec_finalize",
+    "tmg_ens_score_store", "tmg_ens_score_step",
 ]
 # Every export returns int except the workspace sizes, which the header declares int64_t (read through a 32-bit return a request of
 # 2^31 floats or more would be truncated and the kernel handed a buffer smaller than it planned for).
@@ -904,6 +905,28 @@ def ens_turb_finalize(tm2, cuv, tvort, outs, S, B, HW, C, T):
     outs = (uv_mean, uv_std, tke_mean, tke_std, vort_mean, vort_std) (tmg_ens_turb_finalize)."""
     _chk(lib().tmg_ens_turb_finalize(_ptr(tm2), _ptr(cuv), _ptr(tvort), *[_ptr(t) for t in outs], _i64(S, B, HW, C, T), _stream()),
          "tmg_ens_turb_finalize")
+
+
+def ens_score_store(y, xs, k, m0):
+    """Copy one chunk of k members (y: NHWC [k*B, H, W, C] or a channel-slice view, rows member-major) into rows m0 .. m0 + k - 1 of
+    the planar member buffer xs [S, B, C, HW], values unchanged (tmg_ens_score_store)."""
+    kB, Hh, Ww, Cc = y.shape
+    ptr, ps, co, _ = seg(y)
+    _chk(lib().tmg_ens_score_store(c_vp(ptr), _i64(ps, co), _ptr(xs), _i64(k, kB // k, Hh * Ww, Cc, xs.shape[0], m0), _stream()),
+         "tmg_ens_score_store")
+
+
+def ens_score_step(xs, target, scale, crps, crps_fair, hist, tmeans, ostrides, t_before, flags):
+    """Score one kept step whose S members are in xs [S, B, C, HW] against target (NHWC [B, H, W, C] or a channel-slice view): CRPS and
+    fair CRPS times scale [B, C] into crps / crps_fair, the targets' ranks into the int32 histogram hist, with the per-case strides
+    ostrides = (scores, histogram); flags & 1 advances the running time means tmeans = (tcrps, tcrps_fair) that hold t_before steps
+    (tmg_ens_score_step)."""
+    S, B, Cc, HW = xs.shape
+    ptr, ps, co, _ = seg(target)
+    tmeans = tmeans if tmeans is not None else (None,) * 2
+    _chk(lib().tmg_ens_score_step(_ptr(xs), c_vp(ptr), _i64(ps, co), _ptr(scale), _ptr(crps), _ptr(crps_fair), _ptr(hist),
+                                  *[_ptr(t) for t in tmeans], _i64(*ostrides), _i64(S, B, HW, Cc, t_before, flags), _stream()),
+         "tmg_ens_score_step")
 
 
 def spec_rows(y, u, out_mu, out_std, ft_w, yw, k):

@@ -1717,6 +1717,108 @@ class EnsembleStats:
         return self.out
 
 
+SCORES_MAX_MEMBERS = 1024
+
+
+class EnsembleScores:
+    """On-device calibration scores of sampled roll-outs of B cases against the target (tmg_ens_score_store / tmg_ens_score_step).
+    For case b, kept step t, channel c and pixel p, with the members x_1..x_S (raw normalised model outputs), the normalised target
+    y, a = u[b, c] out_std[c] > 0 and the un-normalised xh = u (out_std x + out_mu), yh likewise:
+      crps      = (1/S) sum_m |xh_m - yh| - (1 / (2 S^2)) sum_m sum_n |xh_m - xh_n|       the ensemble CRPS
+      crps_fair = the same with 1 / (2 S (S - 1)) on the pair term (S = 1: crps)
+      rank      = #{m : x_m < y}, strict: a member equal to the target is not below it
+    out_mu cancels in every term and a > 0 keeps the order, so the kernels work on the raw values and multiply by a once; out_mu is
+    not an input.  rank_hist[b, t, c, r] counts the pixels of rank r = 0..S.
+
+    Feeding protocol of EnsembleStats: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
+    chunks before the next step's; every chunk comes with the step's target, and the last chunk's is the one that is scored.
+    Outputs (device tensors): crps, crps_fair [B, Tk, C, H, W]; rank_hist [B, Tk, C, S + 1] int64; finalize() adds time_crps,
+    time_crps_fair [B, C, H, W] (running means over the steps folded with time=True) and time_rank_hist [B, C, S + 1] int64 (the sum
+    of rank_hist over those steps)."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_std, u=None):
+        if not (2 <= C <= 4):
+            raise ValueError("ensemble scores need 2 <= C <= 4 channels, got %d" % C)
+        if not (1 <= int(members) <= SCORES_MAX_MEMBERS):
+            raise ValueError("ensemble scores need 1 <= members <= %d, got %d" % (SCORES_MAX_MEMBERS, int(members)))
+        sd = torch.as_tensor(out_std, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
+        if sd.numel() != C:
+            raise ValueError("out_std needs %d entries, got %d" % (C, sd.numel()))
+        if not bool((torch.isfinite(sd) & (sd > 0)).all()):
+            raise ValueError("out_std must be finite and strictly positive (the scores scale with u * out_std), got %s" % sd.tolist())
+        if u is not None:
+            u = torch.as_tensor(u, dtype=torch.float32).detach().reshape(B, C).cpu()
+            if not bool((torch.isfinite(u) & (u > 0)).all()):
+                raise ValueError("u must be finite and strictly positive (the scores scale with u * out_std)")
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("ensemble scores run on the HIP path: device %s is not a GPU (there is no CPU path)" % dev)
+        self.S, self.B, self.C, self.H, self.W, self.Tk = int(members), int(B), int(C), int(Hh), int(Ww), int(steps)
+        HW = self.H * self.W
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.scale = (sd.view(1, C).expand(self.B, C) if u is None else u * sd.view(1, C)).to(dev).contiguous()
+        self.xs = torch.empty((self.S, self.B, C, HW), **f32)
+        self.time_state = torch.empty((2, self.B, C, HW), **f32)
+        self.hist = torch.zeros((self.B, self.Tk, C, self.S + 1), device=dev, dtype=torch.int32)
+        self.out = {"crps": torch.empty((self.B, self.Tk, C, Hh, Ww), **f32), "crps_fair": torch.empty((self.B, self.Tk, C, Hh, Ww), **f32)}
+        self._n = 0           # members stored for the current step
+        self._step = 0        # the step being filled
+        self._t = [0] * self.S  # timed steps every member has been fed for
+        self._timed = []      # the steps whose scores went into the time means
+
+    def add(self, y, m0, target, time=True):
+        """Store the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
+        channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride rule.  The step's
+        last chunk scores the step against its target."""
+        yn = y.permute(0, 2, 3, 1)
+        kB = yn.shape[0]
+        if kB % self.B or tuple(yn.shape[1:]) != (self.H, self.W, self.C):
+            raise ValueError("chunk shape %s does not hold whole members of [%d, %d, %d, %d]" % (tuple(y.shape), self.B, self.C, self.H, self.W))
+        if target is None or tuple(target.shape) != (self.B, self.C, self.H, self.W):
+            raise ValueError("target shape %s is not [%d, %d, %d, %d]" % (None if target is None else tuple(target.shape), self.B, self.C,
+                                                                          self.H, self.W))
+        k = kB // self.B
+        if m0 != self._n or m0 + k > self.S or self._step >= self.Tk:
+            raise ValueError("members must be fed in order, every step's chunks before the next step's")
+        t_before = self._t[m0]
+        if time and any(self._t[m] != t_before for m in range(m0, m0 + k)):
+            raise ValueError("members of one chunk hold different numbers of time steps")
+        H.check_device(yn)
+        tn = target.permute(0, 2, 3, 1)
+        H.check_act(tn)
+        H.check_device(tn)
+        last = m0 + k == self.S
+        H.ens_score_store(yn, self.xs, k, m0)
+        if last:
+            HW = self.H * self.W
+            t = self._step
+            o = self.out
+            H.ens_score_step(self.xs, tn, self.scale, o["crps"][:, t], o["crps_fair"][:, t], self.hist[:, t],
+                             (self.time_state[0], self.time_state[1]), (self.Tk * self.C * HW, self.Tk * self.C * (self.S + 1)),
+                             t_before, 1 if time else 0)
+            if time:
+                self._timed.append(t)
+        if time:
+            for m in range(m0, m0 + k):
+                self._t[m] += 1
+        self._n = 0 if last else self._n + k
+        self._step += 1 if last else 0
+
+    def finalize(self):
+        """-> dict of the outputs; the time statistics cover the steps folded with time=True."""
+        if self._step != self.Tk:
+            raise RuntimeError("%d of %d steps folded" % (self._step, self.Tk))
+        T = self._t[0]
+        if T < 1 or any(t != T for t in self._t) or len(self._timed) != T:
+            raise RuntimeError("no time statistics: no step was folded with time=True")
+        shp = (self.B, self.C, self.H, self.W)
+        self.out["rank_hist"] = self.hist.to(torch.int64)
+        self.out["time_crps"] = self.time_state[0].view(shp)
+        self.out["time_crps_fair"] = self.time_state[1].view(shp)
+        self.out["time_rank_hist"] = self.out["rank_hist"][:, self._timed].sum(dim=1)
+        return self.out
+
+
 def spectrum_bins(H_, W_, dx, dy):
     """The shell map of an H x W field on a grid of cell size dx along W, dy along H (fp64, host): signed mode numbers p' (p - H
     above H // 2), q' likewise, r = sqrt((p' Lmax / Ly)^2 + (q' Lmax / Lx)^2) with Lx = W dx, Ly = H dy, Lmax = max(Lx, Ly), shell

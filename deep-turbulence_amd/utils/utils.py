@@ -99,9 +99,10 @@ _TARGET_STATS = (("target_time_mean", "time_mean_mean"), ("target_time_rms", "ti
 
 
 def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, turbulence, spectra=False,
-                   window="hann"):
-    """The body of modelPredStats, modelPredTurbulence (turbulence: grid = (args.dx, args.dy)) and modelPredSpectra (spectra: the same
-    chunks also go through an EnsembleSpectrum with `window`): same seed draws in the same order, same folding, same re-anchoring, so
+                   window="hann", scores=False):
+    """The body of modelPredStats, modelPredTurbulence (turbulence: grid = (args.dx, args.dy)), modelPredSpectra (spectra: the same
+    chunks also go through an EnsembleSpectrum with `window`) and modelPredScores (scores: the same chunks also go through an
+    EnsembleScores with the step's normalised target): same seed draws in the same order, same folding, same re-anchoring, so
     that the keys they share hold identical values under the same host RNG state."""
     import tmg_ops as ops
     core = getattr(model, "module", model)
@@ -132,6 +133,9 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
             B, C, Hh, Ww = inp.size(0), tgt.size(2), tgt.size(-2), tgt.size(-1)
             if C != 3:
                 raise ValueError("%s scales (ux, uy, p) by (u0, u0, u0^2) as modelPred does: 3 target channels, got %d" % (name, C))
+            if scores and target0.size(1) <= (nkeep - 1) * stride:
+                raise ValueError("%s: the target series holds %d steps, kept step %d needs step %d"
+                                 % (name, target0.size(1), nkeep - 1, (nkeep - 1) * stride))
             keys = []
             for i in range(samples):                                   # modelPred's seed draws, member by member
                 seeds = torch.LongTensor(B).random_(0, int(1e8))
@@ -145,14 +149,19 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
             st = ops.EnsembleStats(samples, B, C, Hh, Ww, nkeep, dev, out_mu, out_std, u=u.view(B, 3)[:, :C], grid=grid)
             sp = ops.EnsembleSpectrum(samples, B, Hh, Ww, nkeep, dev, out_mu, out_std, u=u.view(B, 3), grid=grid,
                                       window=window) if spectra else None
+            sc = ops.EnsembleScores(samples, B, C, Hh, Ww, nkeep, dev, out_std, u=u.view(B, 3)[:, :C]) if scores else None
+            tnorm = target0.to(dev) if scores else None                # the normalised series; one step at a time goes channels-last
             for tstep in range(tmax):
                 keep = tstep % stride == 0 and tstep // stride < nkeep
+                tj = tnorm[:, tstep].contiguous(memory_format=torch.channels_last) if keep and scores else None
                 for ci, (m0, k) in enumerate(chunks):
                     y0, _logp, states[ci] = core.sampleEnsemble(inp[:, tstep], states[ci], k)
                     if keep:
                         st.add(y0, m0, time=tstep // stride >= t_start)
                         if sp is not None:
                             sp.add(y0, m0, time=tstep // stride >= t_start)
+                        if sc is not None:
+                            sc.add(y0, m0, tj, time=tstep // stride >= t_start)
                     if tstep % 20 == 0:
                         states[ci] = [(0.5 * h + 0.5 * hk, 0.5 * c + 0.5 * ck) for (h, c), (hk, ck) in zip(states[ci], anchors[ci])]
             for key, t in st.finalize().items():
@@ -163,6 +172,9 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
                         spec_k = t
                     else:
                         outs.setdefault(key, []).append(t.cpu())
+            if sc is not None:
+                for key, t in sc.finalize().items():
+                    outs.setdefault(key, []).append(t.cpu())
             if grid is not None:
                 # the target's own time statistics over the same kept steps: the normalised series as a one-member ensemble
                 if target0.size(1) <= (nkeep - 1) * stride:
@@ -248,3 +260,20 @@ def modelPredSpectra(args, model, testing_loader, log, samples=1, stride=1, tmax
         raise ValueError("window must be 'hann' or None, got %r" % (window,))
     return _ensembleStats("modelPredSpectra", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, True,
                           spectra=True, window=window)
+
+
+def modelPredScores(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64):
+    """modelPredStats plus the ensemble's calibration scores against the target the loader carries, still without forming modelPred's
+    [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleScores).  The target of kept step j is series step j * stride.  Same roll-outs
+    as modelPredStats: under the same host RNG state the keys both return are identical.
+
+    Returns modelPredStats' dict plus (CPU tensors), with xh_1..xh_S the un-normalised members and yh the un-normalised target:
+      crps [N, Tk, C, H, W]             the ensemble CRPS per pixel and kept step,
+                                        (1/S) sum_m |xh_m - yh| - (1 / (2 S^2)) sum_m sum_n |xh_m - xh_n|
+      crps_fair [N, Tk, C, H, W]        the same with 1 / (2 S (S - 1)) on the pair term (samples = 1: crps = |xh_1 - yh|)
+      rank_hist [N, Tk, C, S + 1]       int64: the number of pixels whose target has rank r = #{m : xh_m < yh} (strict), r = 0..S
+                                        (the Talagrand histogram; flat for a calibrated ensemble)
+      time_crps, time_crps_fair [N, C, H, W]   the means of crps / crps_fair over the kept steps t_start..Tk-1
+      time_rank_hist [N, C, S + 1]      int64: the sum of rank_hist over those steps."""
+    return _ensembleStats("modelPredScores", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False,
+                          scores=True)

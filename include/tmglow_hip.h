@@ -451,6 +451,24 @@ int tmg_ens_turb_accum(const void* y, const int64_t* y_d, const void* u, const v
 int tmg_ens_turb_finalize(const void* tm2, const void* cuv, const void* tvort, void* uv_mean, void* uv_std, void* tke_mean,
                           void* tke_std, void* tv_mean, void* tv_std, const int64_t* dims, tmg_stream_t st);
 
+/* Ensemble calibration scores against the target (tmg_scores.hip; no float atomics, int32 adds for the histogram only: bitwise
+ * reproducible).  Both work on the raw normalised fields: the un-normalisation's offset cancels in every term and its scale
+ * a = u[b][c] * out_std[c] > 0 multiplies the scores once at the end.
+ * tmg_ens_score_store copies one chunk of k members into rows m0 .. m0 + k - 1 of the planar member buffer xs [S][B][C][HW], values
+ * unchanged.  y, y_d and the row order as tmg_ens_accum (row j*B + b = member m0 + j, case b).  dims = {k, B, HW, C, S, m0};
+ * 2 <= C <= 4, m0 + k <= S, else -1; S > 1024 or sizes beyond the index ranges: -2. */
+int tmg_ens_score_store(const void* y, const int64_t* y_d, void* xs, const int64_t* dims, tmg_stream_t st);
+/* tmg_ens_score_step scores one kept step once all S members are stored.  target: [B][HW] pixels of C fp32 channels, pixel stride
+ * t_d[0], channel offset t_d[1] (normalised, as the members); scale: [B][C], the a above.  Per (case b, channel c, pixel) with target
+ * value y: rank = #{m : x_m < y} (strict), crps = a ((1/S) sum_m |x_m - y| - sum_{m<n} |x_m - x_n| / S^2) and crps_fair with
+ * S (S - 1) for S^2 (S = 1: no pair term), written at + b * o_d[0] + c * HW of crps / crps_fair.  hist: int32 bins, zero-filled by
+ * the caller, case b and channel c at + b * o_d[1] + c * (S + 1); every pixel adds 1 to bin `rank` (integer adds: any order gives
+ * the same sums).  flags & 1: the running time means tcrps, tcrps_fair [B][C][HW], which hold t_before steps, advance by this step
+ * in place (with t_before = 0 they are not read).  dims = {S, B, HW, C, t_before, flags}; S > 1024 (the block's LDS histogram): -2;
+ * a null pointer among xs, target, scale, crps, crps_fair, hist, or among the time means with flags & 1: -3. */
+int tmg_ens_score_step(const void* xs, const void* target, const int64_t* t_d, const void* scale, void* crps, void* crps_fair,
+                       void* hist, void* tcrps, void* tcrps_fair, const int64_t* o_d, const int64_t* dims, tmg_stream_t st);
+
 /* Shell-binned kinetic-energy spectra of the same chunks (tmg_spectrum.hip; no atomics: bitwise reproducible).  Per image (row
  * j*B + b of the chunk) z = u + i v from channels 0 and 1 of yh = u[b][c] * (out_std[c] * y + out_mu[c]) (u: [B][2] or NULL for 1;
  * out_mu, out_std: 2 floats), Z = T_H^T z T_W as two dense products on the fp32 matrix pipe, E2 = fl[0] |Z|^2 summed per shell.
