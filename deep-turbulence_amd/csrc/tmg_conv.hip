@@ -1529,8 +1529,19 @@ static inline int ilog2_ceil(int v) {
     return l;
 }
 
+// Launch-plan query (tmg_conv_fwd_plan): the launchers below fill `plan` from their own template arguments and the ConvP they
+// would launch with, and return in place of the launch - what a test reads is what the launch runs.
+// plan: {kernel (0 conv_fwd_kernel, 1 conv_mfma_kernel), MT, NTW, WM, WN, TW_log2, TH, tiles_x, tiles_y, KCH, nchunks, grid_x, grid_y,
+//        lds_bytes, vec4, ovec4 (conv_mfma_kernel stores scalars: 0)}
+static void fill_fwd_plan(int64_t* plan, int kernel, int MT, int NTW, int WM, int WN, const ConvP& p, int gx, int gy, size_t lds_bytes) {
+    const int64_t v[16] = {kernel, MT, NTW, WM, WN, p.TW_log2, p.TH, p.tiles_x, p.tiles_y, p.KCH, (p.Cin_pad + p.KCH - 1) / p.KCH, gx, gy,
+                           (int64_t)lds_bytes, p.vec4, kernel == 0 ? p.ovec4 : 0};
+    for (int i = 0; i < 16; ++i) plan[i] = v[i];
+}
+
 template <int MT, int NTW, int WM, int WN>
-static int launch_conv(const ConvP& p, int gy, size_t lds_bytes, hipStream_t st) {
+static int launch_conv(const ConvP& p, int gy, size_t lds_bytes, hipStream_t st, int64_t* plan) {
+    if (plan) { fill_fwd_plan(plan, 1, MT, NTW, WM, WN, p, p.B * p.tiles_x * p.tiles_y, gy, lds_bytes); return 0; }
     TMG_LDS_OPTIN((&conv_mfma_kernel<MT, NTW, WM, WN>));
     dim3 grid(p.B * p.tiles_x * p.tiles_y, gy, 1);
     const int kid = (WM == 4 ? NTW - 1 : (WM == 2 ? NTW + 1 : NTW + 3));
@@ -1541,7 +1552,8 @@ static int launch_conv(const ConvP& p, int gy, size_t lds_bytes, hipStream_t st)
 }
 
 template <int MT, int NTW, int WM, int WN>
-static int launch_fwd(const ConvP& p, int G, int gy, size_t lds_bytes, hipStream_t st) {
+static int launch_fwd(const ConvP& p, int G, int gy, size_t lds_bytes, hipStream_t st, int64_t* plan) {
+    if (plan) { fill_fwd_plan(plan, 0, MT, NTW, WM, WN, p, G, gy, lds_bytes); return 0; }
     TMG_LDS_OPTIN((&conv_fwd_kernel<MT, NTW, WM, WN>));
     const int kid = p.ksize == 1 ? 31 : 11 + (WM == 8 ? NTW - 1 : (WM == 4 ? NTW + 1 : NTW + 3));
     ProfScope prof(kid, 2.0 * p.B * p.Hout * p.Wout * (double)p.Cout * p.Cin * p.ksize * p.ksize, st);
@@ -1551,7 +1563,7 @@ static int launch_fwd(const ConvP& p, int G, int gy, size_t lds_bytes, hipStream
 }
 
 // Tile / chunk plan and launch of conv_fwd_kernel; -100 when the shape is not eligible (caller falls back to conv_mfma_kernel).
-static int conv_fwd_lean(ConvP p, hipStream_t st) {
+static int conv_fwd_lean(ConvP p, hipStream_t st, int64_t* plan) {
     if (p.stride != 1 || !p.vec4 || (p.Cin & 3) || (long)p.Hin * p.Win >= (1 << 24) || (long)p.B * p.Hout >= (1 << 24) ||
         p.Wout >= (1 << 24) || (long)p.B * p.Hout * p.Wout >= (1L << 32))
         return -100;
@@ -1602,9 +1614,9 @@ static int conv_fwd_lean(ConvP p, hipStream_t st) {
         const size_t lds_bytes = 2 * (size_t)PHPW * (kch + 8) * 4;
 #define TMG_FWD_CASE(NTW_, WM_, WN_)                                                                   \
         if (NTW == NTW_ && WM == WM_ && WN == WN_) {                                                   \
-            if (MT == 4) return launch_fwd<4, NTW_, WM_, WN_>(p, G, gy, lds_bytes, st);                \
-            if (MT == 2) return launch_fwd<2, NTW_, WM_, WN_>(p, G, gy, lds_bytes, st);                \
-            return launch_fwd<1, NTW_, WM_, WN_>(p, G, gy, lds_bytes, st);                             \
+            if (MT == 4) return launch_fwd<4, NTW_, WM_, WN_>(p, G, gy, lds_bytes, st, plan);                \
+            if (MT == 2) return launch_fwd<2, NTW_, WM_, WN_>(p, G, gy, lds_bytes, st, plan);                \
+            return launch_fwd<1, NTW_, WM_, WN_>(p, G, gy, lds_bytes, st, plan);                             \
         }
         TMG_FWD_CASE(1, 8, 1) TMG_FWD_CASE(2, 8, 1) TMG_FWD_CASE(3, 8, 1) TMG_FWD_CASE(4, 8, 1)
         TMG_FWD_CASE(3, 4, 2) TMG_FWD_CASE(4, 4, 2) TMG_FWD_CASE(3, 2, 4) TMG_FWD_CASE(4, 2, 4)
@@ -1694,12 +1706,11 @@ extern "C" int tmg_conv_fwd(const void* const* in_ptrs, const int64_t* in_desc, 
                             dims, st);
 }
 
-// As tmg_conv_fwd with an extra tensor `add` ({stride, off}, Cout channels) summed into the accumulator before the bias
-// and the exp(kappa) scale:  out = [relu]((conv + add + bias) * scale).
-extern "C" int tmg_conv_fwd_add(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* wpk, const void* bias,
-                                const void* kappa, const void* in_scale, const void* in_shift, const void* add,
-                                const int64_t* add_desc, void* const* out_ptrs, const int64_t* out_desc, int64_t nout,
-                                const int64_t* dims, hipStream_t st) {
+// Shared body of tmg_conv_fwd_add (plan == null: launches) and tmg_conv_fwd_plan (fills plan, launches nothing).
+static int conv_fwd_impl(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* wpk, const void* bias,
+                         const void* kappa, const void* in_scale, const void* in_shift, const void* add,
+                         const int64_t* add_desc, void* const* out_ptrs, const int64_t* out_desc, int64_t nout,
+                         const int64_t* dims, hipStream_t st, int64_t* plan) {
     ConvP p;
     const TmgD2 ad = tmg_opt_d2(add, add_desc);
     p.add = TmgSeg{(const float*)add, ad.stride, ad.off, 0};
@@ -1719,7 +1730,7 @@ extern "C" int tmg_conv_fwd_add(const void* const* in_ptrs, const int64_t* in_de
     if (tmg_decode_out(p.out, out_ptrs, out_desc, nout).csum != p.Cout) return -4;   // (the kernels store scalars where a segment is not float4-addressable)
 
     {
-        const int rc = conv_fwd_lean(p, st);
+        const int rc = conv_fwd_lean(p, st, plan);
         if (rc != -100) return rc;
     }
 
@@ -1767,9 +1778,9 @@ extern "C" int tmg_conv_fwd_add(const void* const* in_ptrs, const int64_t* in_de
 
 #define TMG_CONV_CASE(NTW_, WM_, WN_)                                                                  \
     if (NTW == NTW_ && WM == WM_ && WN == WN_) {                                                       \
-        if (MT == 4) return launch_conv<4, NTW_, WM_, WN_>(p, gy, lds_bytes, st);                      \
-        if (MT == 2) return launch_conv<2, NTW_, WM_, WN_>(p, gy, lds_bytes, st);                      \
-        return launch_conv<1, NTW_, WM_, WN_>(p, gy, lds_bytes, st);                                   \
+        if (MT == 4) return launch_conv<4, NTW_, WM_, WN_>(p, gy, lds_bytes, st, plan);                      \
+        if (MT == 2) return launch_conv<2, NTW_, WM_, WN_>(p, gy, lds_bytes, st, plan);                      \
+        return launch_conv<1, NTW_, WM_, WN_>(p, gy, lds_bytes, st, plan);                                   \
     }
     TMG_CONV_CASE(1, 4, 1)
     TMG_CONV_CASE(2, 4, 1)
@@ -1783,8 +1794,37 @@ extern "C" int tmg_conv_fwd_add(const void* const* in_ptrs, const int64_t* in_de
     return -7;
 }
 
+// As tmg_conv_fwd with an extra tensor `add` ({stride, off}, Cout channels) summed into the accumulator before the bias
+// and the exp(kappa) scale:  out = [relu]((conv + add + bias) * scale).
+extern "C" int tmg_conv_fwd_add(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* wpk, const void* bias,
+                                const void* kappa, const void* in_scale, const void* in_shift, const void* add,
+                                const int64_t* add_desc, void* const* out_ptrs, const int64_t* out_desc, int64_t nout,
+                                const int64_t* dims, hipStream_t st) {
+    return conv_fwd_impl(in_ptrs, in_desc, nseg, wpk, bias, kappa, in_scale, in_shift, add, add_desc, out_ptrs, out_desc, nout, dims, st,
+                         nullptr);
+}
+
+// The launch plan of tmg_conv_fwd_add for these arguments (see fill_fwd_plan): nothing is launched and no pointer is dereferenced;
+// returns the code the launch would return.
+extern "C" int tmg_conv_fwd_plan(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* wpk, const void* bias,
+                                 const void* kappa, const void* in_scale, const void* in_shift, const void* add,
+                                 const int64_t* add_desc, void* const* out_ptrs, const int64_t* out_desc, int64_t nout,
+                                 const int64_t* dims, hipStream_t st, int64_t* plan) {
+    if (!plan) return -3;
+    for (int i = 0; i < 16; ++i) plan[i] = -1;
+    return conv_fwd_impl(in_ptrs, in_desc, nseg, wpk, bias, kappa, in_scale, in_shift, add, add_desc, out_ptrs, out_desc, nout, dims, st,
+                         plan);
+}
+
 template <int NP, int NCO, bool LEAN>
-static int launch_wgrad(const WgradP& p, dim3 grid, size_t lds_bytes, hipStream_t st) {
+static int launch_wgrad(const WgradP& p, dim3 grid, size_t lds_bytes, hipStream_t st, int64_t* plan, size_t ws_floats) {
+    if (plan) {
+        // {NP, NCO, LEAN, ksplit, MPIX, TH, TW_log2, CITG, PPG, gx, gy, gz, slab path, lds_bytes, ws_floats}
+        const int64_t v[15] = {NP, NCO, LEAN ? 1 : 0, p.ksplit, p.MPIX, p.TH, p.TW_log2, p.CITG, p.PPG, grid.x, grid.y, grid.z, p.ws ? 1 : 0,
+                               (int64_t)lds_bytes, (int64_t)ws_floats};
+        for (int i = 0; i < 15; ++i) plan[i] = v[i];
+        return 0;
+    }
     TMG_LDS_OPTIN((&conv_wgrad_kernel<NP, NCO, LEAN>));
     const int nco_i = NCO == 1 ? 0 : (NCO == 2 ? 1 : 2);
     const int kid = NP == 3 ? 8 + nco_i : (NP == 8 ? 28 + nco_i : 19 + ((NP - 5) / 2) * 3 + nco_i);
@@ -1924,7 +1964,7 @@ extern "C" int64_t tmg_conv_wgrad_ws_floats(const int64_t* dims) {
 static int wgrad_impl(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* in_scale,
                       const void* in_shift, const void* dy, const int64_t* dy_desc, void* dW, void* dbias,
                       const void* kappa, void* ws, int64_t ws_floats, const int64_t* dims, hipStream_t st,
-                      const long long* gtab, int ngroups, int dy_goff, long long dw_gstride, int db_gstride) {
+                      const long long* gtab, int ngroups, int dy_goff, long long dw_gstride, int db_gstride, int64_t* plan = nullptr) {
     WgradP p;
     p.nseg = (int)nseg;
     p.vec4 = tmg_decode_in(p.in, in_ptrs, in_desc, nseg).vec4;   // (neither the segment count nor the channel sum is tested here)
@@ -1972,14 +2012,15 @@ static int wgrad_impl(const void* const* in_ptrs, const int64_t* in_desc, int64_
     int lrc = -7;
 #define TMG_WG_CASE(NP_, NCO_)                                                                    \
     if (pl.NP == NP_ && pl.NCO == NCO_)                                                           \
-        lrc = p.fstage ? launch_wgrad<NP_, NCO_, true>(p, grid, pl.lds_bytes, st) : launch_wgrad<NP_, NCO_, false>(p, grid, pl.lds_bytes, st);
+        lrc = p.fstage ? launch_wgrad<NP_, NCO_, true>(p, grid, pl.lds_bytes, st, plan, pl.ws_floats)                       \
+                       : launch_wgrad<NP_, NCO_, false>(p, grid, pl.lds_bytes, st, plan, pl.ws_floats);
     TMG_WG_CASE(3, 1) TMG_WG_CASE(3, 2) TMG_WG_CASE(3, 4)
     TMG_WG_CASE(5, 1) TMG_WG_CASE(5, 2)
     TMG_WG_CASE(7, 1) TMG_WG_CASE(7, 2)
     TMG_WG_CASE(8, 1) TMG_WG_CASE(8, 2)
     TMG_WG_CASE(9, 1) TMG_WG_CASE(9, 2)
 #undef TMG_WG_CASE
-    if (lrc != 0) return lrc;
+    if (lrc != 0 || plan) return lrc;
     if (p.ws) {
         const int items = pl.gy * pl.gz * (pl.ksplit ? 1 : 4) * pl.NP * pl.NCO * 64;
         int xchunk = 32;
@@ -1996,6 +2037,18 @@ extern "C" int tmg_conv_wgrad(const void* const* in_ptrs, const int64_t* in_desc
                               const void* in_shift, const void* dy, const int64_t* dy_desc, void* dW, void* dbias,
                               const void* kappa, void* ws, int64_t ws_floats, const int64_t* dims, hipStream_t st) {
     return wgrad_impl(in_ptrs, in_desc, nseg, in_scale, in_shift, dy, dy_desc, dW, dbias, kappa, ws, ws_floats, dims, st, nullptr, 1, 0, 0, 0);
+}
+
+// The launch plan of tmg_conv_wgrad (ngroups = 1) or of a grouped launch of `ngroups` such contractions for these arguments (see
+// launch_wgrad): nothing is launched and no pointer is dereferenced; returns the code the launch would return.
+extern "C" int tmg_conv_wgrad_plan(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* in_scale,
+                                   const void* in_shift, const void* dy, const int64_t* dy_desc, void* dW, void* dbias,
+                                   const void* kappa, void* ws, int64_t ws_floats, const int64_t* dims, hipStream_t st, int64_t ngroups,
+                                   int64_t* plan) {
+    if (!plan || ngroups < 1) return -3;
+    for (int i = 0; i < 15; ++i) plan[i] = -1;
+    return wgrad_impl(in_ptrs, in_desc, nseg, in_scale, in_shift, dy, dy_desc, dW, dbias, kappa, ws, ws_floats, dims, st, nullptr,
+                      (int)ngroups, 0, 0, 0, plan);
 }
 
 // `ngroups` identically shaped weight-gradient contractions in ONE launch (the per-layer coupling convolutions of a flow
@@ -2022,11 +2075,22 @@ extern "C" int64_t tmg_conv_wgrad_grouped_ws_floats(const int64_t* dims, int64_t
     return (int64_t)((size_t)gx * gy * pl.gz * (pl.ksplit ? 1 : 4) * pl.NP * pl.NCO * 256 + (size_t)gx * gy * 64);
 }
 
-// Replicate-padding fold for the 3x3 input gradient (see conv_rep_border_fix_kernel).
-// dims: [B,H,W,Cdy,Cx]; dy_desc: [stride, off]; w: the mode-1 packed weights of the SAME conv (tmg_conv_pack)
-extern "C" int tmg_conv_rep_border_fix(const void* dy, const int64_t* dy_desc, const void* w, const void* kappa,
-                                       void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims,
-                                       hipStream_t st) {
+// plan: {mfma (0: conv_rep_border_fix_kernel, 1: conv_rep_border_mfma_kernel<NT>), NT, ksplit S, tiles t0, blocks}
+template <int NT>
+static int launch_border_mfma(const BorderMP& m, int blocks, hipStream_t st, int64_t* plan) {
+    if (plan) {
+        const int64_t v[5] = {1, NT, m.ksplit, m.tile0[16], blocks};
+        for (int i = 0; i < 5; ++i) plan[i] = v[i];
+        return 0;
+    }
+    hipLaunchKernelGGL(conv_rep_border_mfma_kernel<NT>, dim3(blocks), dim3(256), 0, st, m);
+    TMG_CHECK_LAUNCH();
+    return 0;
+}
+
+// Shared body of tmg_conv_rep_border_fix (plan == null: launches) and tmg_conv_rep_border_plan.
+static int rep_border_impl(const void* dy, const int64_t* dy_desc, const void* w, const void* kappa, void* const* out_ptrs,
+                           const int64_t* out_desc, int64_t nout, const int64_t* dims, hipStream_t st, int64_t* plan) {
     BorderP p;
     p.dy = (const float*)dy; p.dy_stride = (int)dy_desc[0]; p.dy_off = (int)dy_desc[1];
     p.B = (int)dims[0]; p.H = (int)dims[1]; p.W = (int)dims[2]; p.Cdy = (int)dims[3]; p.Cx = (int)dims[4];
@@ -2061,23 +2125,43 @@ extern "C" int tmg_conv_rep_border_fix(const void* dy, const int64_t* dy_desc, c
         const long items = (long)t0 * S;
         const int blocks = (int)((items + 3) / 4 < 4096 ? (items + 3) / 4 : 4096);
         switch (p.Npad >> 4) {
-            case 1: hipLaunchKernelGGL(conv_rep_border_mfma_kernel<1>, dim3(blocks), dim3(256), 0, st, m); break;
-            case 2: hipLaunchKernelGGL(conv_rep_border_mfma_kernel<2>, dim3(blocks), dim3(256), 0, st, m); break;
-            case 3: hipLaunchKernelGGL(conv_rep_border_mfma_kernel<3>, dim3(blocks), dim3(256), 0, st, m); break;
-            case 4: hipLaunchKernelGGL(conv_rep_border_mfma_kernel<4>, dim3(blocks), dim3(256), 0, st, m); break;
-            case 5: hipLaunchKernelGGL(conv_rep_border_mfma_kernel<5>, dim3(blocks), dim3(256), 0, st, m); break;
-            case 6: hipLaunchKernelGGL(conv_rep_border_mfma_kernel<6>, dim3(blocks), dim3(256), 0, st, m); break;
-            case 7: hipLaunchKernelGGL(conv_rep_border_mfma_kernel<7>, dim3(blocks), dim3(256), 0, st, m); break;
-            default: hipLaunchKernelGGL(conv_rep_border_mfma_kernel<8>, dim3(blocks), dim3(256), 0, st, m); break;
+            case 1: return launch_border_mfma<1>(m, blocks, st, plan);
+            case 2: return launch_border_mfma<2>(m, blocks, st, plan);
+            case 3: return launch_border_mfma<3>(m, blocks, st, plan);
+            case 4: return launch_border_mfma<4>(m, blocks, st, plan);
+            case 5: return launch_border_mfma<5>(m, blocks, st, plan);
+            case 6: return launch_border_mfma<6>(m, blocks, st, plan);
+            case 7: return launch_border_mfma<7>(m, blocks, st, plan);
+            default: return launch_border_mfma<8>(m, blocks, st, plan);
         }
-        TMG_CHECK_LAUNCH();
-        return 0;
     }
     const size_t total = (size_t)p.B * p.nborder * p.Cx;
     const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    if (plan) {
+        const int64_t v[5] = {0, 0, 1, 0, blocks};
+        for (int i = 0; i < 5; ++i) plan[i] = v[i];
+        return 0;
+    }
     hipLaunchKernelGGL(conv_rep_border_fix_kernel, dim3(blocks), dim3(256), 0, st, p);
     TMG_CHECK_LAUNCH();
     return 0;
+}
+
+// Replicate-padding fold for the 3x3 input gradient (see conv_rep_border_fix_kernel): ADDS the fold onto the outputs' contents.
+// dims: [B,H,W,Cdy,Cx]; dy_desc: [stride, off]; w: the mode-1 packed weights of the SAME conv (tmg_conv_pack)
+extern "C" int tmg_conv_rep_border_fix(const void* dy, const int64_t* dy_desc, const void* w, const void* kappa,
+                                       void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims,
+                                       hipStream_t st) {
+    return rep_border_impl(dy, dy_desc, w, kappa, out_ptrs, out_desc, nout, dims, st, nullptr);
+}
+
+// The launch plan of tmg_conv_rep_border_fix for these arguments: nothing is launched, no pointer is dereferenced.
+extern "C" int tmg_conv_rep_border_plan(const void* dy, const int64_t* dy_desc, const void* w, const void* kappa,
+                                        void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims,
+                                        hipStream_t st, int64_t* plan) {
+    if (!plan) return -3;
+    for (int i = 0; i < 5; ++i) plan[i] = -1;
+    return rep_border_impl(dy, dy_desc, w, kappa, out_ptrs, out_desc, nout, dims, st, plan);
 }
 
 // dims: [B,Hin,Win,Hout,Wout,Cin,Cout,ksize,stride,accumulate]; dy_desc/dx_desc: [stride, off]

@@ -43,6 +43,9 @@ EXPORTS = [
     "tmg_spec_rows", "tmg_spec_cols", "tmg_spec_accum", "tmg_spec_finalize",
     "tmg_ens_score_store", "tmg_ens_score_step",
 ]
+# Launch-plan queries of the direct convolution launchers (conv_fwd_plan / conv_wgrad_plan / conv_rep_border_plan below): they launch
+# nothing, so they are listed apart from the operations above.
+PLAN_EXPORTS = ["tmg_conv_fwd_plan", "tmg_conv_wgrad_plan", "tmg_conv_rep_border_plan"]
 # Every export returns int except the workspace sizes, which the header declares int64_t (read through a 32-bit return a request of
 # 2^31 floats or more would be truncated and the kernel handed a buffer smaller than it planned for).
 RET_I64 = ("tmg_conv_wgrad_ws_floats", "tmg_conv_wgrad_grouped_ws_floats", "tmg_conv_wino_wgrad_ws_floats",
@@ -54,7 +57,7 @@ def build(force=False, verbose=False):
     source or a header changed, all stale ones in parallel), then one link."""
     from concurrent.futures import ThreadPoolExecutor
     inc = os.path.join(os.path.dirname(_HERE), "include")
-    headers = [os.path.join(CSRC, "tmg_common.h"), os.path.join(inc, "tmglow_hip.h")]
+    headers = [os.path.join(CSRC, "tmg_common.h"), os.path.join(inc, "tmglow_hip.h"), os.path.join(inc, "tmglow_hip_plan.h")]
     hmt = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -105,6 +108,9 @@ def lib():
         for name in EXPORTS:
             getattr(_lib, name).restype = c_i64 if name in RET_I64 else ctypes.c_int
         _lib.tmg_prof_name.restype = ctypes.c_char_p
+        for name in PLAN_EXPORTS:
+            getattr(_lib, name).restype = ctypes.c_int
+            getattr(_lib, name).argtypes = PLAN_ARGTYPES[name]
     return _lib
 
 
@@ -786,6 +792,92 @@ def conv_rep_border_fix(dy, w, outs, kappa=None):
     Cx = sum(t.shape[3] for t in outs)
     _chk(lib().tmg_conv_rep_border_fix(_ptr(dy), _d2(dy), _ptr(w), _ptr(kappa), op, odesc, c_i64(n_out), _i64(B, H, W, Cdy, Cx),
                                        _stream()), "tmg_conv_rep_border_fix")
+
+
+# Launch-plan queries (tmg_conv_fwd_plan / tmg_conv_wgrad_plan / tmg_conv_rep_border_plan): which kernel instance, tiling and grid the
+# launcher would use.  Nothing is launched and no pointer is dereferenced, so they run without a device.  An activation is a tensor (as
+# in the launching wrappers) or a descriptor ((B, H, W), address, pixel stride, channels) standing for one; an optional operand that
+# only has to be present or absent (bias, kappa, in_scale, ws, dbias) may be any true value.
+FWD_PLAN_FIELDS = ("kernel", "MT", "NTW", "WM", "WN", "TW_log2", "TH", "tiles_x", "tiles_y", "KCH", "nchunks", "grid_x", "grid_y",
+                   "lds_bytes", "vec4", "ovec4")
+WGRAD_PLAN_FIELDS = ("NP", "NCO", "LEAN", "ksplit", "MPIX", "TH", "TW_log2", "CITG", "PPG", "gx", "gy", "gz", "slab", "lds_bytes",
+                     "ws_floats")
+BORDER_PLAN_FIELDS = ("mfma", "NT", "S", "tiles", "blocks")
+PLAN_ARGTYPES = {
+    "tmg_conv_fwd_plan": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],
+    "tmg_conv_wgrad_plan": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp],
+    "tmg_conv_rep_border_plan": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],
+}
+
+
+def _pseg(t):
+    """(shape[:3], address, pixel stride, channels) of a tensor or of a descriptor of one."""
+    if isinstance(t, torch.Tensor):
+        B, H, W, C = t.shape
+        d = seg(t)
+        return (B, H, W), d[0], d[1], d[3]
+    shp, addr, stride, n = t
+    return tuple(shp), int(addr), int(stride), int(n)
+
+
+def _psegs(ts):
+    d = [_pseg(t) for t in ts]
+    return (c_vp * len(d))(*[x[1] for x in d]), (c_i64 * (3 * len(d)))(*[v for x in d for v in (x[2], 0, x[3])]), len(d), d
+
+
+def _pp(t):
+    """Address of an optional operand: a tensor's, a descriptor's, an integer, or 16 for any other true value."""
+    if t is None or t is False:
+        return c_vp(0)
+    if isinstance(t, torch.Tensor):
+        return c_vp(t.data_ptr())
+    if isinstance(t, tuple):
+        return c_vp(int(t[1]))
+    return c_vp(16 if t is True else int(t))
+
+
+def _plan_call(name, fields, *args):
+    buf = (c_i64 * len(fields))()
+    rc = getattr(lib(), name)(*(args + (buf,)))
+    out = dict(zip(fields, [int(v) for v in buf]))
+    out["rc"] = int(rc)
+    return out
+
+
+def conv_fwd_plan(inputs, Cout, ksize, stride, outs, bias=None, kappa=None, in_scale=None, in_shift=None, relu_in=False,
+                  pad_rep=False, relu_out=False, accumulate=False, add=None):
+    """The launch plan of conv_fwd with these arguments: a dict of FWD_PLAN_FIELDS plus "rc", the code the launch would return."""
+    ip, idesc, n_in, di = _psegs(inputs)
+    op, odesc, n_out, do = _psegs(outs)
+    (B, Hin, Win), (_, Hout, Wout) = di[0][0], do[0][0]
+    Cin = sum(x[3] for x in di)
+    dims = _i64(B, Hin, Win, Hout, Wout, ksize, stride, Cin, Cout, relu_in, pad_rep, relu_out, accumulate)
+    ad = _i64(_pseg(add)[2], 0) if add is not None else _i64(0, 0)
+    return _plan_call("tmg_conv_fwd_plan", FWD_PLAN_FIELDS, ip, idesc, n_in, c_vp(16), _pp(bias), _pp(kappa), _pp(in_scale),
+                      _pp(in_shift), _pp(add), ad, op, odesc, n_out, dims, None)
+
+
+def conv_wgrad_plan(inputs, dy, ksize, stride, dbias=None, kappa=None, in_scale=None, in_shift=None, relu_in=False, pad_rep=False,
+                    use_ws=True, cin_dst=0, cin_valid=0, ci_split=0, ci_off0=0, ci_off1=0, ngroups=1):
+    """The launch plan of conv_wgrad's direct kernel (tmg_conv_wgrad; ngroups > 1: of a grouped launch) with these arguments: a dict
+    of WGRAD_PLAN_FIELDS plus "rc".  use_ws stands for a workspace of the size the library asks for."""
+    ip, idesc, n_in, di = _psegs(inputs)
+    (B, Hin, Win) = di[0][0]
+    (_, Hout, Wout), dyp, dys, Cout = _pseg(dy)
+    Cin = sum(x[3] for x in di)
+    dims = _i64(B, Hin, Win, Hout, Wout, ksize, stride, Cin, Cout, relu_in, pad_rep, cin_dst, cin_valid, ci_split, ci_off0, ci_off1)
+    need = lib().tmg_conv_wgrad_grouped_ws_floats(dims, c_i64(ngroups)) if ngroups > 1 else lib().tmg_conv_wgrad_ws_floats(dims)
+    return _plan_call("tmg_conv_wgrad_plan", WGRAD_PLAN_FIELDS, ip, idesc, n_in, _pp(in_scale), _pp(in_shift), c_vp(dyp), _i64(dys, 0),
+                      c_vp(16), _pp(dbias), _pp(kappa), c_vp(16 if use_ws else 0), c_i64(need if use_ws else 0), dims, None, c_i64(ngroups))
+
+
+def conv_rep_border_plan(dy, outs):
+    """The launch plan of conv_rep_border_fix(dy, w, outs): a dict of BORDER_PLAN_FIELDS plus "rc"."""
+    (B, H, W), dyp, dys, Cdy = _pseg(dy)
+    op, odesc, n_out, do = _psegs(outs)
+    Cx = sum(x[3] for x in do)
+    return _plan_call("tmg_conv_rep_border_plan", BORDER_PLAN_FIELDS, c_vp(dyp), _i64(dys, 0), c_vp(16), c_vp(0), op, odesc, n_out,
+                      _i64(B, H, W, Cdy, Cx), None)
 
 
 def conv_dgrad_direct(dy, w, dx, ksize, stride, accumulate=False):

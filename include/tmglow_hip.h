@@ -121,6 +121,10 @@ int64_t tmg_conv_wgrad_ws_floats(const int64_t* dims);
 int tmg_conv_rep_border_fix(const void* dy, const int64_t* dy_desc, const void* w, const void* kappa, void* const* out_ptrs,
                             const int64_t* out_desc, int64_t nout, const int64_t* dims, tmg_stream_t st);
 
+/* Launch-plan queries of the three launchers above (tmg_conv_fwd_plan, tmg_conv_wgrad_plan, tmg_conv_rep_border_plan): diagnostic
+ * entry points that launch nothing, declared in a header of their own. */
+#include "tmglow_hip_plan.h"
+
 /* Direct input gradient for strided convs (encoder stride-2 convs, tmGlow.py:154-156,180-182).
  * dims = {B,Hin,Win,Hout,Wout,Cin,Cout,ksize,stride,accumulate} */
 int tmg_conv_dgrad_direct(const void* dy, const int64_t* dy_desc, const void* w, void* dx, const int64_t* dx_desc,

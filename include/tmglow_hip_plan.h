@@ -1,0 +1,24 @@
+/* Launch-plan queries of libtmglow_hip.so's direct convolution launchers.  Included by tmglow_hip.h (which defines tmg_stream_t): do not
+ * include it on its own.  The operations are declared in tmglow_hip.h; these entry points compute nothing. */
+#ifndef TMGLOW_HIP_PLAN_H
+#define TMGLOW_HIP_PLAN_H
+
+/* Launch-plan queries of the three launchers above: the arguments of the launch plus `plan`; nothing is launched, no pointer is
+ * dereferenced and no device is needed (without one the planners assume 256 compute units); the return value is the code the launch
+ * would return.  The launchers themselves fill `plan`, immediately before the point where they would launch.
+ *   tmg_conv_fwd_plan: plan[16] = {kernel (0 conv_fwd_kernel, 1 conv_mfma_kernel), MT, NTW, WM, WN, TW_log2, TH, tiles_x, tiles_y, KCH,
+ *     nchunks, grid_x, grid_y, lds_bytes, vec4, ovec4}
+ *   tmg_conv_wgrad_plan (ngroups > 1: the plan of tmg_conv_wgrad_grouped): plan[15] = {NP, NCO, LEAN, ksplit, MPIX, TH, TW_log2, CITG,
+ *     PPG, gx, gy, gz, slab path (ws accepted), lds_bytes, ws_floats}
+ *   tmg_conv_rep_border_plan: plan[5] = {mfma (0 scalar kernel, 1 matrix-core kernel), NT, ksplit S, 16-pixel tiles, blocks} */
+int tmg_conv_fwd_plan(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* wpk, const void* bias,
+                      const void* kappa, const void* in_scale, const void* in_shift, const void* add, const int64_t* add_desc,
+                      void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, tmg_stream_t st,
+                      int64_t* plan);
+int tmg_conv_wgrad_plan(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* in_scale,
+                        const void* in_shift, const void* dy, const int64_t* dy_desc, void* dW, void* dbias, const void* kappa,
+                        void* ws, int64_t ws_floats, const int64_t* dims, tmg_stream_t st, int64_t ngroups, int64_t* plan);
+int tmg_conv_rep_border_plan(const void* dy, const int64_t* dy_desc, const void* w, const void* kappa, void* const* out_ptrs,
+                             const int64_t* out_desc, int64_t nout, const int64_t* dims, tmg_stream_t st, int64_t* plan);
+
+#endif
