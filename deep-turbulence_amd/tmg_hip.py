@@ -20,14 +20,14 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmglow_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip"]
+SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip"]
 # Sources compiled WITHOUT the packed-fp32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32): beside MFMAs a packed
 # f32 instruction costs ~13 cycles more than the two scalar ones it replaces (MI355X_MICROARCH.md, cycle constants, 'price of one
 # filler beside MFMAs'), and the compiler SLP-packs adjacent scalar adds / multiplies by itself under -O3.  The matrix-core kernels'
 # files are listed; the vector-ALU kernels (tmg_pointwise.hip, tmg_physics.hip) keep the packed forms, which double their arithmetic
 # rate.  Round 3 measured the switch inside the noise and left the list empty; round 5 on one box, alternating three times: packed
 # everywhere 43.62 / 43.98 / 43.76 ms per step, this list 43.51 / 43.60 / 43.37 (wino + conv + coupling alone 43.64 / 43.52 / 43.58).
-NO_PACKED_F32 = ["tmg_wino.hip", "tmg_conv.hip", "tmg_coupling.hip", "tmg_thin.hip", "tmg_mix16.hip", "tmg_spectrum.hip"]
+NO_PACKED_F32 = ["tmg_wino.hip", "tmg_conv.hip", "tmg_coupling.hip", "tmg_thin.hip", "tmg_mix16.hip", "tmg_spectrum.hip", "tmg_tspec.hip"]
 _lib = None
 
 c_i64 = ctypes.c_int64
@@ -46,6 +46,8 @@ EXPORTS = [
 # Launch-plan queries of the direct convolution launchers (conv_fwd_plan / conv_wgrad_plan / conv_rep_border_plan below): they launch
 # nothing, so they are listed apart from the operations above.
 PLAN_EXPORTS = ["tmg_conv_fwd_plan", "tmg_conv_wgrad_plan", "tmg_conv_rep_border_plan"]
+# The temporal power spectra (csrc/tmg_tspec.hip), declared in include/tmglow_hip_tspec.h: tspec_store / tspec_block / tspec_finalize below.
+TSPEC_EXPORTS = ["tmg_tspec_store", "tmg_tspec_block", "tmg_tspec_finalize"]
 # Every export returns int except the workspace sizes, which the header declares int64_t (read through a 32-bit return a request of
 # 2^31 floats or more would be truncated and the kernel handed a buffer smaller than it planned for).
 RET_I64 = ("tmg_conv_wgrad_ws_floats", "tmg_conv_wgrad_grouped_ws_floats", "tmg_conv_wino_wgrad_ws_floats",
@@ -57,7 +59,8 @@ def build(force=False, verbose=False):
     source or a header changed, all stale ones in parallel), then one link."""
     from concurrent.futures import ThreadPoolExecutor
     inc = os.path.join(os.path.dirname(_HERE), "include")
-    headers = [os.path.join(CSRC, "tmg_common.h"), os.path.join(inc, "tmglow_hip.h"), os.path.join(inc, "tmglow_hip_plan.h")]
+    headers = [os.path.join(CSRC, "tmg_common.h"), os.path.join(inc, "tmglow_hip.h"), os.path.join(inc, "tmglow_hip_plan.h"),
+               os.path.join(inc, "tmglow_hip_tspec.h")]
     hmt = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -111,6 +114,8 @@ def lib():
         for name in PLAN_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
             getattr(_lib, name).argtypes = PLAN_ARGTYPES[name]
+        for name in TSPEC_EXPORTS:
+            getattr(_lib, name).restype = ctypes.c_int
     return _lib
 
 
@@ -1048,6 +1053,29 @@ def spec_accum(part, smean, sm2, tmean, outs, ostride, k, B, NK, QT, n_before, m
 def spec_finalize(tmean, tm_mean, tm_std, S, B, NK):
     """Mean / population std over the S members of their time-mean spectra (tmg_spec_finalize)."""
     _chk(lib().tmg_spec_finalize(_ptr(tmean), _ptr(tm_mean), _ptr(tm_std), _i64(S, B, NK), _stream()), "tmg_spec_finalize")
+
+
+def tspec_store(y, u, out_mu, out_std, ring, k, m0, slot):
+    """Un-normalise one chunk of k members (y: NHWC [k*B, H, W, C] or a channel-slice view, rows member-major) into rows m0 .. m0 + k - 1
+    of slot `slot` of the planar ring [16, S, B, C, HW] (tmg_tspec_store)."""
+    kB, Hh, Ww, Cc = y.shape
+    ptr, ps, co, _ = seg(y)
+    _chk(lib().tmg_tspec_store(c_vp(ptr), _i64(ps, co), _ptr(u), _ptr(out_mu), _ptr(out_std), _ptr(ring),
+                               _i64(k, kB // k, Hh * Ww, Cc, ring.shape[1], m0, slot), _stream()), "tmg_tspec_store")
+
+
+def tspec_block(tm, ring, acc, Tn, NF, n0, nb, first):
+    """Fold the nb <= 16 valid slots of ring [16, S, B, C, HW], which hold steps n0 .. n0 + nb - 1, into acc [2 NF + 1, S, B, C, HW] with
+    rows n0 .. n0 + nb - 1 of the operand tm [Tn, RP]; first: acc is written, else added to (tmg_tspec_block)."""
+    _chk(lib().tmg_tspec_block(_ptr(tm), _ptr(ring), _ptr(acc), _i64(ring[0].numel(), Tn, NF, n0, nb, 1 if first else 0), _stream()),
+         "tmg_tspec_block")
+
+
+def tspec_finalize(acc, cst, psd_mean, psd_std, S, B, C, HW, NF, Tn):
+    """P_k of every member from acc and the constants cst [3, NF] = (Re G_k, Im G_k, c_k / Tn^2), then mean / population std over the S
+    members into psd_mean / psd_std [B, NF, C, H, W] (tmg_tspec_finalize)."""
+    _chk(lib().tmg_tspec_finalize(_ptr(acc), _ptr(cst), _ptr(psd_mean), _ptr(psd_std), _i64(S, B, C, HW, NF), _flts([1.0 / float(Tn)]),
+                                  _stream()), "tmg_tspec_finalize")
 
 
 def reverse_loss_fwd(y, ld, loss, s1, s2):

@@ -1965,3 +1965,143 @@ class EnsembleSpectrum:
         H.spec_finalize(self.time_state, self.out["time_spec_mean"], self.out["time_spec_std"], self.S, self.B, self.NK)
         self.out["spec_k"] = self.k
         return self.out
+
+
+def _tspec_window(Tn, window):
+    """fp64 [Tn]: the periodic Hann window w_n = 0.5 - 0.5 cos(2 pi n / Tn) over sqrt(mean(w^2)), or ones."""
+    n = torch.arange(Tn, dtype=torch.float64)
+    if window != "hann":
+        return torch.ones(Tn, dtype=torch.float64)
+    w = 0.5 - 0.5 * torch.cos(2.0 * math.pi * n / Tn)
+    return w / torch.sqrt(torch.mean(w * w))
+
+
+def _tspec_operand(Tn, NF, window):
+    """The host-built constants of the temporal DFT, fp64 rounded once to fp32, the argument reduced with integers as (k n) mod Tn:
+    tm [Tn, RP] (RP = 2 NF + 1 rounded up to 16): tm[n, k] = g_n cos(2 pi k n / Tn), tm[n, NF + k] = -g_n sin(2 pi k n / Tn),
+    tm[n, 2 NF] = 1 (the plain sum that gives xbar), the padding columns zero; cst [3, NF] = (Re G_k, Im G_k, c_k / Tn^2) with
+    G_k = sum_n g_n exp(-2 pi i k n / Tn) (parts below 1e-9 Tn, fp64 noise of a sum that vanishes, set to zero) and c_k = 1 at k = 0 and at the Nyquist bin of an even Tn, else 2."""
+    Tn, NF = int(Tn), int(NF)
+    R = 2 * NF + 1
+    RP = (R + 15) // 16 * 16
+    g = _tspec_window(Tn, window)
+    n = torch.arange(Tn, dtype=torch.int64)
+    k = torch.arange(NF, dtype=torch.int64)
+    ang = ((n[:, None] * k[None, :]) % Tn).to(torch.float64) * (2.0 * math.pi / Tn)
+    re, im = g[:, None] * torch.cos(ang), -g[:, None] * torch.sin(ang)
+    tm = torch.zeros((Tn, RP), dtype=torch.float64)
+    tm[:, :NF], tm[:, NF:2 * NF], tm[:, 2 * NF] = re, im, 1.0
+    ck = torch.full((NF,), 2.0, dtype=torch.float64)
+    ck[0] = 1.0
+    if Tn % 2 == 0 and NF > Tn // 2:
+        ck[Tn // 2] = 1.0
+    G = torch.stack((re.sum(0), im.sum(0)))
+    G[G.abs() < 1e-9 * Tn] = 0.0        # sums that vanish analytically (Hann: every k >= 2) hold fp64 rounding noise: exact zeros
+    cst = torch.cat((G, (ck / float(Tn) ** 2)[None]))
+    return tm.to(torch.float32).contiguous(), cst.to(torch.float32).contiguous()
+
+
+TSPEC_BLOCK = 16      # steps per ring pass (csrc/tmg_tspec.hip)
+
+
+class EnsembleTimeSpectrum:
+    """On-device temporal power spectra of sampled roll-outs of B cases (tmg_tspec_store / tmg_tspec_block / tmg_tspec_finalize).
+    For case b, member m, channel c and pixel p, with xh_n = u[b, c] (out_std[c] y + out_mu[c]) at the fed steps n = 0 .. Tn - 1:
+      xbar = mean_n xh_n
+      g_n  = periodic Hann w_n = 0.5 - 0.5 cos(2 pi n / Tn) over sqrt(mean_n w_n^2)           (window=None: g_n = 1)
+      d_n  = g_n (xh_n - xbar)
+      X_k  = sum_n d_n exp(-2 pi i k n / Tn),   k = 0 .. NF - 1,   NF = min(nfreq, Tn // 2 + 1)
+      P_k  = c_k |X_k|^2 / Tn^2,   c_k = 1 for k = 0 and (Tn even and k = Tn / 2), else 2
+    so that sum_{k = 0}^{Tn // 2} P_k = mean_n d_n^2.  The average over the members plays the role of Welch's segment average.
+    The steps are gathered 16 at a time in a planar ring and folded by a dense DFT on the fp32 matrix pipe; the state is
+    (2 NF + 1 + 16) * 4 bytes per element of [members, B, C, H, W].  H and W are any positive sizes.
+
+    `steps` is Tn: there are no per-step outputs, so only the steps of the time window are fed.  Feeding protocol of EnsembleStats:
+    every step's members in chunks of whole members, in member order (m0 = 0 first), each step's chunks before the next step's.
+    finalize() returns psd_mean, psd_std [B, NF, C, H, W] (device; mean and population std of P_k over the members) and psd_freq [NF]
+    (float64, host: k / (Tn dt), dt the time between two fed steps).
+
+    Argument errors are ValueError in this order: C, steps, nfreq, window, dt, members, the entries of out_mu / out_std, the shape of
+    u; a device that is not a GPU comes last (RuntimeError)."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, nfreq=32, window="hann", dt=1.0):
+        if not (2 <= C <= 4):
+            raise ValueError("temporal spectra need 2 <= C <= 4 channels, got %d" % C)
+        if int(steps) < 2:
+            raise ValueError("temporal spectra need steps >= 2 (the window of the transform), got %d" % int(steps))
+        if int(nfreq) < 1:
+            raise ValueError("temporal spectra need nfreq >= 1, got %d" % int(nfreq))
+        if window not in ("hann", None):
+            raise ValueError("window must be 'hann' or None, got %r" % (window,))
+        try:
+            dt = float(dt)
+        except (TypeError, ValueError):
+            raise ValueError("dt needs a positive finite time between two fed steps, got %r" % (dt,)) from None
+        if not (math.isfinite(dt) and dt > 0):
+            raise ValueError("dt needs a positive finite time between two fed steps, got %r" % (dt,))
+        if int(members) < 1 or int(B) < 1 or int(Hh) < 1 or int(Ww) < 1:
+            raise ValueError("temporal spectra need members, B, H and W >= 1, got %d, %d, %d x %d" % (int(members), int(B), int(Hh), int(Ww)))
+        mu = torch.as_tensor(out_mu, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
+        sd = torch.as_tensor(out_std, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
+        if mu.numel() != C or sd.numel() != C:
+            raise ValueError("out_mu / out_std need %d entries, got %d / %d" % (C, mu.numel(), sd.numel()))
+        if u is not None:
+            u = torch.as_tensor(u, dtype=torch.float32).detach()
+            if u.numel() != int(B) * C:
+                raise ValueError("u needs %d x %d entries, got %d" % (int(B), C, u.numel()))
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("temporal spectra run on the HIP path: device %s is not a GPU (there is no CPU path)" % dev)
+        self.S, self.B, self.C, self.H, self.W, self.Tn = int(members), int(B), int(C), int(Hh), int(Ww), int(steps)
+        self.NF = min(int(nfreq), self.Tn // 2 + 1)
+        self.window, self.dt = window, dt
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.mu, self.sd = mu.to(dev).contiguous(), sd.to(dev).contiguous()
+        self.u = None if u is None else u.to(dev).reshape(self.B, C).contiguous()
+        tm, cst = _tspec_operand(self.Tn, self.NF, window)
+        self.tm, self.cst = tm.to(dev), cst.to(dev)
+        HW = self.H * self.W
+        self.ring = torch.empty((TSPEC_BLOCK, self.S, self.B, C, HW), **f32)
+        self.acc = torch.empty((2 * self.NF + 1, self.S, self.B, C, HW), **f32)
+        self.freq = torch.arange(self.NF, dtype=torch.float64) / (self.Tn * dt)
+        self.out = None
+        self._n = 0           # members stored for the current step
+        self._step = 0        # the step being filled
+
+    def _fold(self, n0, nb):
+        H.tspec_block(self.tm, self.ring, self.acc, self.Tn, self.NF, n0, nb, n0 == 0)
+
+    def add(self, y, m0):
+        """Store the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
+        channel-slice; rows member-major); the last chunk of every 16th step folds the ring into the accumulator."""
+        yn = y.permute(0, 2, 3, 1)
+        kB = yn.shape[0]
+        if kB < 1 or kB % self.B or tuple(yn.shape[1:]) != (self.H, self.W, self.C):
+            raise ValueError("chunk shape %s does not hold whole members of [%d, %d, %d, %d]" % (tuple(y.shape), self.B, self.C, self.H, self.W))
+        k = kB // self.B
+        if m0 != self._n or m0 + k > self.S or self._step >= self.Tn:
+            raise ValueError("members must be fed in order, every step's chunks before the next step's")
+        H.check_device(yn)
+        H.tspec_store(yn, self.u, self.mu, self.sd, self.ring, k, m0, self._step % TSPEC_BLOCK)
+        if m0 + k < self.S:
+            self._n += k
+            return
+        self._n = 0
+        self._step += 1
+        if self._step % TSPEC_BLOCK == 0:
+            self._fold(self._step - TSPEC_BLOCK, TSPEC_BLOCK)
+
+    def finalize(self):
+        """-> dict of psd_mean, psd_std (device) and psd_freq (host)."""
+        if self._step != self.Tn or self._n != 0:
+            raise RuntimeError("%d of %d steps fed" % (self._step, self.Tn))
+        if self.out is None:
+            nb = self.Tn % TSPEC_BLOCK
+            if nb:
+                self._fold(self.Tn - nb, nb)
+            shp = (self.B, self.NF, self.C, self.H, self.W)
+            dev = self.acc.device
+            self.out = {"psd_mean": empty(shp, dev), "psd_std": empty(shp, dev), "psd_freq": self.freq}
+            H.tspec_finalize(self.acc, self.cst, self.out["psd_mean"], self.out["psd_std"], self.S, self.B, self.C, self.H * self.W,
+                             self.NF, self.Tn)
+        return self.out

@@ -4,6 +4,7 @@ utils/utils.py:55-148): `<name><id>.zip` holding `torchModel<id>.pth` = {'epoch'
 tests/test_boundary_cpu.py)."""
 import io
 import json
+import math
 import os
 import zipfile
 
@@ -99,11 +100,12 @@ _TARGET_STATS = (("target_time_mean", "time_mean_mean"), ("target_time_rms", "ti
 
 
 def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, turbulence, spectra=False,
-                   window="hann", scores=False):
+                   window="hann", scores=False, tspec=None):
     """The body of modelPredStats, modelPredTurbulence (turbulence: grid = (args.dx, args.dy)), modelPredSpectra (spectra: the same
-    chunks also go through an EnsembleSpectrum with `window`) and modelPredScores (scores: the same chunks also go through an
-    EnsembleScores with the step's normalised target): same seed draws in the same order, same folding, same re-anchoring, so
-    that the keys they share hold identical values under the same host RNG state."""
+    chunks also go through an EnsembleSpectrum with `window`), modelPredScores (scores: the same chunks also go through an
+    EnsembleScores with the step's normalised target) and modelPredTimeSpectra (tspec = (nfreq, window, dt between kept steps): the
+    chunks of the kept steps from t_start on also go through an EnsembleTimeSpectrum): same seed draws in the same order, same
+    folding, same re-anchoring, so that the keys they share hold identical values under the same host RNG state."""
     import tmg_ops as ops
     core = getattr(model, "module", model)
     core.eval()
@@ -117,6 +119,9 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
         raise ValueError("%s needs samples >= 1 and tmax >= stride (samples=%d, tmax=%d, stride=%d)" % (name, samples, tmax, stride))
     if not 0 <= t_start < nkeep:
         raise ValueError("t_start=%d outside the %d kept steps" % (t_start, nkeep))
+    if tspec is not None and nkeep - t_start < 2:
+        raise ValueError("%s needs at least 2 kept steps from t_start on, got %d (tmax=%d, stride=%d, t_start=%d)"
+                         % (name, nkeep - t_start, tmax, stride, t_start))
     shp = (1, -1, 1, 1)
     in_std, in_mu = core.in_std.to(dev).view(shp), core.in_mu.to(dev).view(shp)
     out_std, out_mu = core.out_std.to(dev), core.out_mu.to(dev)
@@ -133,7 +138,7 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
             B, C, Hh, Ww = inp.size(0), tgt.size(2), tgt.size(-2), tgt.size(-1)
             if C != 3:
                 raise ValueError("%s scales (ux, uy, p) by (u0, u0, u0^2) as modelPred does: 3 target channels, got %d" % (name, C))
-            if scores and target0.size(1) <= (nkeep - 1) * stride:
+            if (scores or tspec is not None) and target0.size(1) <= (nkeep - 1) * stride:
                 raise ValueError("%s: the target series holds %d steps, kept step %d needs step %d"
                                  % (name, target0.size(1), nkeep - 1, (nkeep - 1) * stride))
             keys = []
@@ -150,6 +155,8 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
             sp = ops.EnsembleSpectrum(samples, B, Hh, Ww, nkeep, dev, out_mu, out_std, u=u.view(B, 3), grid=grid,
                                       window=window) if spectra else None
             sc = ops.EnsembleScores(samples, B, C, Hh, Ww, nkeep, dev, out_std, u=u.view(B, 3)[:, :C]) if scores else None
+            tsp_t = ops.EnsembleTimeSpectrum(samples, B, C, Hh, Ww, nkeep - t_start, dev, out_mu, out_std, u=u.view(B, 3)[:, :C],
+                                             nfreq=tspec[0], window=tspec[1], dt=tspec[2]) if tspec is not None else None
             tnorm = target0.to(dev) if scores else None                # the normalised series; one step at a time goes channels-last
             for tstep in range(tmax):
                 keep = tstep % stride == 0 and tstep // stride < nkeep
@@ -162,6 +169,8 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
                             sp.add(y0, m0, time=tstep // stride >= t_start)
                         if sc is not None:
                             sc.add(y0, m0, tj, time=tstep // stride >= t_start)
+                        if tsp_t is not None and tstep // stride >= t_start:
+                            tsp_t.add(y0, m0)
                     if tstep % 20 == 0:
                         states[ci] = [(0.5 * h + 0.5 * hk, 0.5 * c + 0.5 * ck) for (h, c), (hk, ck) in zip(states[ci], anchors[ci])]
             for key, t in st.finalize().items():
@@ -175,6 +184,19 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
             if sc is not None:
                 for key, t in sc.finalize().items():
                     outs.setdefault(key, []).append(t.cpu())
+            if tsp_t is not None:
+                for key, t in tsp_t.finalize().items():
+                    if key == "psd_freq":
+                        psd_freq = t
+                    else:
+                        outs.setdefault(key, []).append(t.cpu())
+                # the target series over the same kept steps through the same kernels: a one-member ensemble
+                tn = target0.to(dev)
+                tts = ops.EnsembleTimeSpectrum(1, B, C, Hh, Ww, nkeep - t_start, dev, out_mu, out_std, u=u.view(B, 3)[:, :C],
+                                               nfreq=tspec[0], window=tspec[1], dt=tspec[2])
+                for j in range(t_start, nkeep):
+                    tts.add(tn[:, j * stride].contiguous(memory_format=torch.channels_last), 0)
+                outs.setdefault("target_psd", []).append(tts.finalize()["psd_mean"].cpu())
             if grid is not None:
                 # the target's own time statistics over the same kept steps: the normalised series as a one-member ensemble
                 if target0.size(1) <= (nkeep - 1) * stride:
@@ -201,6 +223,8 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
     res["input"] = torch.cat(inputs, dim=0)
     if spectra:
         res["spec_k"] = spec_k
+    if tspec is not None:
+        res["psd_freq"] = psd_freq
     return res
 
 
@@ -277,3 +301,33 @@ def modelPredScores(args, model, testing_loader, log, samples=1, stride=1, tmax=
       time_rank_hist [N, C, S + 1]      int64: the sum of rank_hist over those steps."""
     return _ensembleStats("modelPredScores", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False,
                           scores=True)
+
+
+def modelPredTimeSpectra(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, nfreq=32, window="hann",
+                         dt=None):
+    """modelPredStats plus the temporal power spectra of every member's series at every pixel over the kept steps t_start..Tk-1
+    (Tn = Tk - t_start >= 2 of them), still without forming modelPred's [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleTimeSpectrum):
+    the frequency content of the roll-outs - shedding behind the cylinders, the flapping shear layer behind the step - beside the
+    target's.  Same roll-outs as modelPredStats: under the same host RNG state the keys both return are identical.
+
+    With xh_n the un-normalised value at kept step t_start + n, xbar its mean over the window, g the periodic Hann window over its
+    RMS (window=None: 1), d_n = g_n (xh_n - xbar) and X_k = sum_n d_n exp(-2 pi i k n / Tn):
+      P_k = c_k |X_k|^2 / Tn^2, k = 0 .. NF - 1, NF = min(nfreq, Tn // 2 + 1); c_k = 1 at k = 0 and at the Nyquist bin of an even Tn,
+      else 2, so that the bins 0 .. Tn // 2 of one series sum to mean_n d_n^2.
+    The average over the members stands where Welch's segment average stands for a single signal.
+
+    Returns modelPredStats' dict plus (CPU tensors):
+      psd_mean, psd_std [N, NF, C, H, W]   mean / population std over the members of P_k
+      psd_freq [NF] float64                k / Tn, cycles per kept step, when dt is None; else k / (Tn stride dt) with dt the time
+                                           between two model steps (the reference's args carry no time step)
+      target_psd [N, NF, C, H, W]          P_k of the target series at steps j * stride, j = t_start..Tk-1, through the same kernels
+                                           as a one-member ensemble; raises when the series is too short."""
+    if window not in ("hann", None):
+        raise ValueError("window must be 'hann' or None, got %r" % (window,))
+    if int(nfreq) < 1:
+        raise ValueError("nfreq must be >= 1, got %d" % int(nfreq))
+    step_dt = 1.0 if dt is None else float(stride) * float(dt)
+    if not (math.isfinite(step_dt) and step_dt > 0):
+        raise ValueError("dt must be a positive finite time between two model steps, got %r" % (dt,))
+    return _ensembleStats("modelPredTimeSpectra", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False,
+                          tspec=(int(nfreq), window, step_dt))
