@@ -646,8 +646,21 @@ static int wino_fwd_setup(P& p, const void* const* in_ptrs, const int64_t* in_de
 // dims = {B, H, W, Cin, Cout, relu_in, pad_replicate}; in_desc / out_desc = {stride, off, n} per segment (<= 3 each).
 // Envelope: float4-addressable segments, Cin % 4 == 0, Cout % 4 == 0, Cout >= 64; returns -100 outside it (the caller
 // uses tmg_conv_fwd).
-extern "C" int tmg_conv_wino_fwd(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* U, const void* bias,
-                                 void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, hipStream_t st) {
+// Launch-plan queries (tmg_conv_wino_fwd_plan / _fwd3_plan / _narrow_plan): the launchers below fill `plan` from the WinoP / WinoNP they
+// are about to pass, immediately before the point where they would launch, and return without launching.
+// plan: {kernel (0 wino_fwd_kernel, 1 wino_fwdp_kernel, 2 wino_fwd3_kernel, 3 wino_nn_kernel), NPW (wino_nn_kernel: NTN), Cin_pad, nchunks,
+//        16-channel groups of the last chunk, Npad / 16, tiles_x, tiles_y, ntiles, grid_x, grid_y, largest tile count of one block, lds_bytes}
+#define TMG_WINO_FWD_PLAN_N 13
+template <typename P>
+static void fill_wino_fwd_plan(int64_t* plan, int kernel, int npw, const P& p, int gx, int gy, size_t lds_bytes) {
+    const int64_t v[TMG_WINO_FWD_PLAN_N] = {kernel, npw, p.Cin_pad, p.nchunks, (p.Cin_pad - 32 * (p.nchunks - 1) + 15) / 16, p.Npad / 16, p.tiles_x,
+                                            p.tiles_y, p.ntiles, gx, gy, (p.ntiles + gx - 1) / gx, (int64_t)lds_bytes};
+    for (int i = 0; i < TMG_WINO_FWD_PLAN_N; ++i) plan[i] = v[i];
+}
+
+// Shared body of tmg_conv_wino_fwd (plan == null: launches) and tmg_conv_wino_fwd_plan (fills plan, launches nothing).
+static int wino_fwd_impl(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* U, const void* bias,
+                         void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, hipStream_t st, int64_t* plan) {
     WinoP p;
     const int rc = wino_fwd_setup(p, in_ptrs, in_desc, nseg, U, bias, out_ptrs, out_desc, nout, dims, 16, false);
     if (rc != 1) return rc;
@@ -656,18 +669,17 @@ extern "C" int tmg_conv_wino_fwd(const void* const* in_ptrs, const int64_t* in_d
     const int gy = (ntt + 8 * npw - 1) / (8 * npw);
     const int G = tmg_persistent_grid(gy, p.ntiles);
     const size_t lds_bytes = (size_t)(2 * 180 * 40 + 16 * 32 * 40) * sizeof(float);
+    const size_t ldsp = (size_t)(2 * 16 * 32 * 40) * sizeof(float);      // wino_fwdp_kernel, two V buffers: all 160 KB of the CU
+    if (plan) { fill_wino_fwd_plan(plan, npw == 1 ? 1 : 0, npw, p, G, gy, npw == 1 ? ldsp : lds_bytes); return 0; }
     TmgProf prof(TMG_PROF_WINO, 2.0 * p.B * p.Hin * p.Win * (double)p.Cout * p.Cin * 9, st);   // algorithmic (direct) flops
     // Producer-wave form (round 6) for the contractions with <= 128 output channels (one n-tile per wave: 100 registers, twelve waves
     // fit): 0.592 -> 0.551 ms (40 -> 104 at 128^2), 0.157 -> 0.146, 0.051 -> 0.049 (profiles/r6_ab_wino_producer_waves.txt).  Two
     // n-tiles per wave need 221 registers with the four-deep U ring; at the 168 that twelve waves leave, a two-deep ring measured 2.375 ms
     // against 2.294 for the gate conv and a three-deep one spills: the wide shapes stay on wino_fwd_kernel<2>.  The one-tile producer
     // form for every shape (two blocks per pixel tile above 128 channels) measured 2.355 ms.
-    if (npw == 1) {
-        const size_t ldsp = (size_t)(2 * 16 * 32 * 40) * sizeof(float);      // two V buffers: all 160 KB of the CU
-        const int gyp = (ntt + 7) / 8;
-        const int Gp = tmg_persistent_grid(gyp, p.ntiles);
+    if (npw == 1) {          // (gy and G above are this form's: one n-tile per wave, 8 per block row)
         TMG_LDS_OPTIN((&wino_fwdp_kernel<1>));
-        hipLaunchKernelGGL(wino_fwdp_kernel<1>, dim3(Gp, gyp, 1), dim3(768), ldsp, st, p);
+        hipLaunchKernelGGL(wino_fwdp_kernel<1>, dim3(G, gy, 1), dim3(768), ldsp, st, p);
         TMG_CHECK_LAUNCH();
         return 0;
     }
@@ -675,6 +687,21 @@ extern "C" int tmg_conv_wino_fwd(const void* const* in_ptrs, const int64_t* in_d
     hipLaunchKernelGGL(wino_fwd_kernel<2>, dim3(G, gy, 1), dim3(512), lds_bytes, st, p);
     TMG_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int tmg_conv_wino_fwd(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* U, const void* bias,
+                                 void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, hipStream_t st) {
+    return wino_fwd_impl(in_ptrs, in_desc, nseg, U, bias, out_ptrs, out_desc, nout, dims, st, nullptr);
+}
+
+// The launch plan of tmg_conv_wino_fwd for these arguments (see fill_wino_fwd_plan): nothing is launched and no pointer is dereferenced;
+// the return value is the code the launch would return (a declined query leaves the plan at -1).
+extern "C" int tmg_conv_wino_fwd_plan(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* U, const void* bias,
+                                      void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, hipStream_t st,
+                                      int64_t* plan) {
+    if (!plan) return -3;
+    for (int i = 0; i < TMG_WINO_FWD_PLAN_N; ++i) plan[i] = -1;
+    return wino_fwd_impl(in_ptrs, in_desc, nseg, U, bias, out_ptrs, out_desc, nout, dims, st, plan);
 }
 
 // =================================================================================================================================
@@ -1047,8 +1074,8 @@ __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd3_kernel(WinoP 
 }
 
 // tmg_conv_wino_fwd with the operand of tmg_conv_wino_pack3 (same arguments, same envelope).
-extern "C" int tmg_conv_wino_fwd3(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* U, const void* bias,
-                                  void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, hipStream_t st) {
+static int wino_fwd3_impl(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* U, const void* bias,
+                          void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, hipStream_t st, int64_t* plan) {
     WinoP p;
     const int rc = wino_fwd_setup(p, in_ptrs, in_desc, nseg, U, bias, out_ptrs, out_desc, nout, dims, 32, false);
     if (rc != 1) return rc;
@@ -1057,6 +1084,7 @@ extern "C" int tmg_conv_wino_fwd3(const void* const* in_ptrs, const int64_t* in_
     const int gy = (ntt + 8 * npw - 1) / (8 * npw);
     const int G = tmg_persistent_grid(gy, p.ntiles);
     const size_t lds_bytes = (size_t)(2 * 180 * 40) * sizeof(float) + (size_t)16 * 3 * 4 * 512;
+    if (plan) { fill_wino_fwd_plan(plan, 2, npw, p, G, gy, lds_bytes); return 0; }
     TmgProf prof(TMG_PROF_WINO, 2.0 * p.B * p.Hin * p.Win * (double)p.Cout * p.Cin * 9, st);   // algorithmic (direct) flops
     if (npw == 1) {
         TMG_LDS_OPTIN((&wino_fwd3_kernel<1>));
@@ -1067,6 +1095,20 @@ extern "C" int tmg_conv_wino_fwd3(const void* const* in_ptrs, const int64_t* in_
     }
     TMG_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int tmg_conv_wino_fwd3(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* U, const void* bias,
+                                  void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, hipStream_t st) {
+    return wino_fwd3_impl(in_ptrs, in_desc, nseg, U, bias, out_ptrs, out_desc, nout, dims, st, nullptr);
+}
+
+// The launch plan of tmg_conv_wino_fwd3 for these arguments (as tmg_conv_wino_fwd_plan).
+extern "C" int tmg_conv_wino_fwd3_plan(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* U, const void* bias,
+                                       void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, hipStream_t st,
+                                       int64_t* plan) {
+    if (!plan) return -3;
+    for (int i = 0; i < TMG_WINO_FWD_PLAN_N; ++i) plan[i] = -1;
+    return wino_fwd3_impl(in_ptrs, in_desc, nseg, U, bias, out_ptrs, out_desc, nout, dims, st, plan);
 }
 
 // =================================================================================================================================
@@ -1096,7 +1138,7 @@ struct WinoNP {
 // commit / issue first and multiply afterwards, waves 4-7 multiply first and commit / issue before the barrier - each wave's staging
 // instructions issue while its SIMD partner's MFMAs keep the pipe busy.  Same LDS hazards as before: the stage after this one is
 // committed to the buffer nobody reads in this round, at any point between the two barriers.  Measured (tools/bench_wino.py, one box,
-// TMG_WN_NOSKEW=1 for the form without): 256 -> 40 at 128^2 1.259 -> 1.173 ms, 240 -> 32 0.935 -> 0.863, 480 -> 32 at 64^2 0.428 -> 0.408;
+// SKEW = 0 for the form without; the run-time switch that selected it is gone, only SKEW = 1 is instantiated): 256 -> 40 at 128^2 1.259 -> 1.173 ms, 240 -> 32 0.935 -> 0.863, 480 -> 32 at 64^2 0.428 -> 0.408;
 // pairing the waves as (w, w ^ 1) instead: 1.222 / 0.902 (waves w and w + 4 are the ones that share a SIMD).  The same change in
 // wino_fwd_kernel, whose rounds also hold the all-thread input transform, lost 2-5 % and is not in the tree.
 template <int NTN, int SKEW = 1>
@@ -1356,8 +1398,9 @@ __global__ __launch_bounds__(512, 1) void wino_nn_kernel(WinoNP p) {
 }
 
 template <int NTN>
-static int launch_wino_nn(const WinoNP& p, int G, hipStream_t st) {
+static int launch_wino_nn(const WinoNP& p, int G, hipStream_t st, int64_t* plan) {
     const size_t lds_bytes = (size_t)(2 * 180 * 40 + 16 * 32 * (NTN * 16 + (NTN < 3 ? 4 : 0))) * sizeof(float);
+    if (plan) { fill_wino_fwd_plan(plan, 3, NTN, p, G, 1, lds_bytes); return 0; }
     TMG_LDS_OPTIN((&wino_nn_kernel<NTN>));
     TmgProf prof(TMG_PROF_WINO, 2.0 * p.B * p.Hin * p.Win * (double)p.Cout * p.Cin * 9, st);
     hipLaunchKernelGGL((wino_nn_kernel<NTN>), dim3(G), dim3(512), lds_bytes, st, p);
@@ -1365,21 +1408,35 @@ static int launch_wino_nn(const WinoNP& p, int G, hipStream_t st) {
     return 0;
 }
 
-// The Winograd contraction for FEW output channels (Cout <= 64) and many input channels: same operand format and descriptors as
+// The Winograd contraction for FEW output channels (Cout <= 48) and many input channels: same operand format and descriptors as
 // tmg_conv_wino_fwd, up to 3 output segments (out_desc = {stride, off, n} each), dims = {B,H,W,Cin,Cout,relu_in,pad_replicate,relu_out}.
 // Returns -100 outside its envelope (float4-addressable operands, channel counts multiples of 4, Cin >= 64, Cout <= 48).
-extern "C" int tmg_conv_wino_narrow(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* U, const void* bias,
-                                    void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, hipStream_t st) {
+static int wino_narrow_impl(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* U, const void* bias,
+                            void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, hipStream_t st, int64_t* plan) {
     WinoNP p;
     const int rc = wino_fwd_setup(p, in_ptrs, in_desc, nseg, U, bias, out_ptrs, out_desc, nout, dims, 16, true);
     if (rc != 1) return rc;
     p.relu_out = (int)dims[7];
     const int G = tmg_persistent_grid(1, p.ntiles);
     switch (p.Npad >> 4) {
-        case 1: return launch_wino_nn<1>(p, G, st);
-        case 2: return launch_wino_nn<2>(p, G, st);
-        default: return launch_wino_nn<3>(p, G, st);
+        case 1: return launch_wino_nn<1>(p, G, st, plan);
+        case 2: return launch_wino_nn<2>(p, G, st, plan);
+        default: return launch_wino_nn<3>(p, G, st, plan);
     }
+}
+
+extern "C" int tmg_conv_wino_narrow(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* U, const void* bias,
+                                    void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, hipStream_t st) {
+    return wino_narrow_impl(in_ptrs, in_desc, nseg, U, bias, out_ptrs, out_desc, nout, dims, st, nullptr);
+}
+
+// The launch plan of tmg_conv_wino_narrow for these arguments (as tmg_conv_wino_fwd_plan; NPW holds NTN).
+extern "C" int tmg_conv_wino_narrow_plan(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* U, const void* bias,
+                                         void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, hipStream_t st,
+                                         int64_t* plan) {
+    if (!plan) return -3;
+    for (int i = 0; i < TMG_WINO_FWD_PLAN_N; ++i) plan[i] = -1;
+    return wino_narrow_impl(in_ptrs, in_desc, nseg, U, bias, out_ptrs, out_desc, nout, dims, st, plan);
 }
 
 // =================================================================================================================================
@@ -1760,10 +1817,20 @@ extern "C" int64_t tmg_conv_wino_wgrad_ws_floats(const int64_t* dims) {
     return (int64_t)pl.ws_floats;
 }
 
+static inline int wino_wgrad_reduce_groups(int gx) { return gx >= 64 ? 16 : (gx >= 32 ? 8 : 4); }
+
+// plan (tmg_conv_wino_wgrad_plan): {CIT, NCO, DB, gx, gy, gz, bpg, NG of wino_wgrad_reduce_kernel, ntiles, lds_bytes, ws_floats}
+#define TMG_WINO_WG_PLAN_N 11
 template <int CIT, int NCO>
-static int launch_wino_wgrad(const WinoWP& p, const WinoWPlan& pl, hipStream_t st) {
+static int launch_wino_wgrad(const WinoWP& p, const WinoWPlan& pl, hipStream_t st, int64_t* plan) {
     constexpr size_t one = (size_t)(180 * (CIT * 16 + 8) + 128 * (NCO * 16 + 8)) * sizeof(float);
     constexpr bool DB = 2 * one <= 160 * 1024;       // two tile buffers where they fit (see the kernel)
+    if (plan) {
+        const int64_t v[TMG_WINO_WG_PLAN_N] = {CIT, NCO, DB ? 1 : 0, pl.gx, pl.gy, pl.gz, p.bpg, wino_wgrad_reduce_groups(pl.gx), p.ntiles,
+                                               (int64_t)(DB ? 2 * one : (one < 8192 ? 8192 : one)), (int64_t)pl.ws_floats};
+        for (int i = 0; i < TMG_WINO_WG_PLAN_N; ++i) plan[i] = v[i];
+        return 0;
+    }
     const double ngr = p.gtab ? (double)(pl.gy / (p.bpg > 0 ? p.bpg : 1)) : 1.0;      // (a grouped launch: every group's flops)
     TmgProf prof(TMG_PROF_WINO_WG, ngr * 2.0 * p.B * p.Hin * p.Win * (double)p.Cout * p.Cin * 9, st);
     const size_t lds = DB ? 2 * one : (one < 8192 ? 8192 : one);
@@ -1775,7 +1842,7 @@ static int launch_wino_wgrad(const WinoWP& p, const WinoWPlan& pl, hipStream_t s
 
 static int wino_wgrad_impl(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* dy, const int64_t* dy_desc,
                            void* dW, void* dbias, void* ws, int64_t ws_floats, const int64_t* dims, hipStream_t st, const long long* gtab,
-                           int ngroups, int dy_goff, long long dw_gstride, int db_gstride) {
+                           int ngroups, int dy_goff, long long dw_gstride, int db_gstride, int64_t* plan = nullptr) {
     WinoWP p;
     p.nseg = (int)nseg;
     if (p.nseg < 1 || p.nseg > TMG_MAX_IN_SEG) return -3;
@@ -1801,12 +1868,12 @@ static int wino_wgrad_impl(const void* const* in_ptrs, const int64_t* in_desc, i
     if (p.ntiles <= 0) return 0;
     if ((long long)p.B * p.Hin * p.Win >= (1LL << 31)) return -100;      // 32-bit pixel indices in the kernels
     int rc = -7;
-#define TMG_WW_CASE(C_, N_) if (pl.CIT == C_ && pl.NCO == N_) rc = launch_wino_wgrad<C_, N_>(p, pl, st);
+#define TMG_WW_CASE(C_, N_) if (pl.CIT == C_ && pl.NCO == N_) rc = launch_wino_wgrad<C_, N_>(p, pl, st, plan);
     TMG_WW_CASE(2, 2) TMG_WW_CASE(2, 3) TMG_WW_CASE(2, 4) TMG_WW_CASE(3, 2) TMG_WW_CASE(3, 3) TMG_WW_CASE(3, 4) TMG_WW_CASE(4, 2) TMG_WW_CASE(4, 3)
     TMG_WW_CASE(4, 4)
 #undef TMG_WW_CASE
-    if (rc != 0) return rc;
-    const int ng = pl.gx >= 64 ? 16 : (pl.gx >= 32 ? 8 : 4);
+    if (rc != 0 || plan) return rc;
+    const int ng = wino_wgrad_reduce_groups(pl.gx);
     if (ng == 16) {
         TMG_LDS_OPTIN((&wino_wgrad_reduce_kernel<16>));
         hipLaunchKernelGGL(wino_wgrad_reduce_kernel<16>, dim3(pl.gy * pl.gz * pl.CIT * pl.NCO), dim3(1024), 15 * 64 * 37 * sizeof(float), st,
@@ -1844,6 +1911,16 @@ extern "C" int tmg_conv_wino_wgrad_grouped(const void* const* in_ptrs, const int
     if (ngroups < 1 || !gtab) return -3;
     return wino_wgrad_impl(in_ptrs, in_desc, nseg, dy, dy_desc, dW, dbias, ws, ws_floats, dims, st, (const long long*)gtab, (int)ngroups,
                            (int)gdims[0], (long long)gdims[1], (int)gdims[2]);
+}
+
+// The launch plan of tmg_conv_wino_wgrad (ngroups = 1) or of a tmg_conv_wino_wgrad_grouped launch of `ngroups` such contractions for these
+// arguments (see launch_wino_wgrad): nothing is launched, no pointer is dereferenced; the return value is the launch's code.
+extern "C" int tmg_conv_wino_wgrad_plan(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* dy, const int64_t* dy_desc,
+                                        void* dW, void* dbias, void* ws, int64_t ws_floats, const int64_t* dims, hipStream_t st, int64_t ngroups,
+                                        int64_t* plan) {
+    if (!plan || ngroups < 1) return -3;
+    for (int i = 0; i < TMG_WINO_WG_PLAN_N; ++i) plan[i] = -1;
+    return wino_wgrad_impl(in_ptrs, in_desc, nseg, dy, dy_desc, dW, dbias, ws, ws_floats, dims, st, nullptr, (int)ngroups, 0, 0, 0, plan);
 }
 
 extern "C" int64_t tmg_conv_wino_wgrad_grouped_ws_floats(const int64_t* dims, int64_t ngroups) {

@@ -43,9 +43,11 @@ EXPORTS = [
     "tmg_spec_rows", "tmg_spec_cols", "tmg_spec_accum", "tmg_spec_finalize",
     "tmg_ens_score_store", "tmg_ens_score_step",
 ]
-# Launch-plan queries of the direct convolution launchers (conv_fwd_plan / conv_wgrad_plan / conv_rep_border_plan below): they launch
-# nothing, so they are listed apart from the operations above.
-PLAN_EXPORTS = ["tmg_conv_fwd_plan", "tmg_conv_wgrad_plan", "tmg_conv_rep_border_plan"]
+# Launch-plan queries of the convolution launchers, direct (conv_fwd_plan / conv_wgrad_plan / conv_rep_border_plan below) and Winograd
+# (conv_wino_fwd_plan / conv_wino_fwd3_plan / conv_wino_narrow_plan / conv_wino_wgrad_plan): they launch nothing, so they are listed apart
+# from the operations above.
+PLAN_EXPORTS = ["tmg_conv_fwd_plan", "tmg_conv_wgrad_plan", "tmg_conv_rep_border_plan", "tmg_conv_wino_fwd_plan", "tmg_conv_wino_fwd3_plan",
+                "tmg_conv_wino_narrow_plan", "tmg_conv_wino_wgrad_plan"]
 # The temporal power spectra (csrc/tmg_tspec.hip), declared in include/tmglow_hip_tspec.h: tspec_store / tspec_block / tspec_finalize below.
 TSPEC_EXPORTS = ["tmg_tspec_store", "tmg_tspec_block", "tmg_tspec_finalize"]
 # Every export returns int except the workspace sizes, which the header declares int64_t (read through a 32-bit return a request of
@@ -799,7 +801,7 @@ def conv_rep_border_fix(dy, w, outs, kappa=None):
                                        _stream()), "tmg_conv_rep_border_fix")
 
 
-# Launch-plan queries (tmg_conv_fwd_plan / tmg_conv_wgrad_plan / tmg_conv_rep_border_plan): which kernel instance, tiling and grid the
+# Launch-plan queries (tmg_conv_fwd_plan / tmg_conv_wgrad_plan / tmg_conv_rep_border_plan, tmg_conv_wino_*_plan): which kernel instance, tiling and grid the
 # launcher would use.  Nothing is launched and no pointer is dereferenced, so they run without a device.  An activation is a tensor (as
 # in the launching wrappers) or a descriptor ((B, H, W), address, pixel stride, channels) standing for one; an optional operand that
 # only has to be present or absent (bias, kappa, in_scale, ws, dbias) may be any true value.
@@ -812,7 +814,15 @@ PLAN_ARGTYPES = {
     "tmg_conv_fwd_plan": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],
     "tmg_conv_wgrad_plan": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp],
     "tmg_conv_rep_border_plan": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],
+    "tmg_conv_wino_fwd_plan": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],
+    "tmg_conv_wino_fwd3_plan": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],
+    "tmg_conv_wino_narrow_plan": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],
+    "tmg_conv_wino_wgrad_plan": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp],
 }
+WINO_FWD_PLAN_FIELDS = ("kernel", "NPW", "Cin_pad", "nchunks", "last_groups", "ntt", "tiles_x", "tiles_y", "ntiles", "grid_x", "grid_y",
+                        "max_tiles", "lds_bytes")
+WINO_KERNELS = ("wino_fwd_kernel", "wino_fwdp_kernel", "wino_fwd3_kernel", "wino_nn_kernel")     # plan field "kernel"
+WINO_WGRAD_PLAN_FIELDS = ("CIT", "NCO", "DB", "gx", "gy", "gz", "bpg", "NG", "ntiles", "lds_bytes", "ws_floats")
 
 
 def _pseg(t):
@@ -883,6 +893,46 @@ def conv_rep_border_plan(dy, outs):
     Cx = sum(x[3] for x in do)
     return _plan_call("tmg_conv_rep_border_plan", BORDER_PLAN_FIELDS, c_vp(dyp), _i64(dys, 0), c_vp(16), c_vp(0), op, odesc, n_out,
                       _i64(B, H, W, Cdy, Cx), None)
+
+
+def _wino_fwd_plan(name, inputs, Cout, outs, bias, *flags):
+    ip, idesc, n_in, di = _psegs(inputs)
+    op, odesc, n_out, do = _psegs(outs)
+    (B, Hin, Win) = di[0][0]
+    Cin = sum(x[3] for x in di)
+    return _plan_call(name, WINO_FWD_PLAN_FIELDS, ip, idesc, n_in, c_vp(16), _pp(bias), op, odesc, n_out,
+                      _i64(B, Hin, Win, Cin, Cout, *flags), None)
+
+
+def conv_wino_fwd_plan(inputs, Cout, outs, bias=None, relu_in=False, pad_rep=False):
+    """The launch plan of conv_wino_fwd with these arguments: a dict of WINO_FWD_PLAN_FIELDS plus "rc", the code the launch would return
+    (-100: outside the envelope, conv_wino_fwd returns False)."""
+    return _wino_fwd_plan("tmg_conv_wino_fwd_plan", inputs, Cout, outs, bias, relu_in, pad_rep)
+
+
+def conv_wino_fwd3_plan(inputs, Cout, outs, bias=None, relu_in=False, pad_rep=False):
+    """The launch plan of conv_wino_fwd3 (as conv_wino_fwd_plan)."""
+    return _wino_fwd_plan("tmg_conv_wino_fwd3_plan", inputs, Cout, outs, bias, relu_in, pad_rep)
+
+
+def conv_wino_narrow_plan(inputs, Cout, outs, bias=None, relu_in=False, pad_rep=False, relu_out=False):
+    """The launch plan of conv_wino_narrow (as conv_wino_fwd_plan; "NPW" holds NTN)."""
+    return _wino_fwd_plan("tmg_conv_wino_narrow_plan", inputs, Cout, outs, bias, relu_in, pad_rep, relu_out)
+
+
+def conv_wino_wgrad_plan(inputs, dy, dbias=None, relu_in=False, pad_rep=False, cin_dst=0, cin_valid=0, ci_split=0, ci_off0=0, ci_off1=0,
+                         ngroups=1, use_ws=True):
+    """The launch plan of conv_wino_wgrad (ngroups > 1: of conv_wgrad_grouped's Winograd launch of that many groups, dy standing for ONE
+    group's channels) with these arguments: a dict of WINO_WGRAD_PLAN_FIELDS plus "rc".  use_ws stands for a workspace of the size the
+    library asks for."""
+    ip, idesc, n_in, di = _psegs(inputs)
+    (B, Hin, Win) = di[0][0]
+    _, dyp, dys, Cout = _pseg(dy)
+    Cin = sum(x[3] for x in di)
+    wd = _i64(B, Hin, Win, Cin, Cout, relu_in, pad_rep, cin_dst, cin_valid, ci_split, ci_off0, ci_off1)
+    need = lib().tmg_conv_wino_wgrad_grouped_ws_floats(wd, c_i64(ngroups)) if ngroups > 1 else lib().tmg_conv_wino_wgrad_ws_floats(wd)
+    return _plan_call("tmg_conv_wino_wgrad_plan", WINO_WGRAD_PLAN_FIELDS, ip, idesc, n_in, c_vp(dyp), _i64(dys, 0), c_vp(16), _pp(dbias),
+                      c_vp(16 if use_ws else 0), c_i64(need if use_ws else 0), wd, None, c_i64(ngroups))
 
 
 def conv_dgrad_direct(dy, w, dx, ksize, stride, accumulate=False):

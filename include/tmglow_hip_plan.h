@@ -1,4 +1,4 @@
-/* Launch-plan queries of libtmglow_hip.so's direct convolution launchers.  Included by tmglow_hip.h (which defines tmg_stream_t): do not
+/* Launch-plan queries of libtmglow_hip.so's convolution launchers, direct and Winograd.  Included by tmglow_hip.h (which defines tmg_stream_t): do not
  * include it on its own.  The operations are declared in tmglow_hip.h; these entry points compute nothing. */
 #ifndef TMGLOW_HIP_PLAN_H
 #define TMGLOW_HIP_PLAN_H
@@ -20,5 +20,24 @@ int tmg_conv_wgrad_plan(const void* const* in_ptrs, const int64_t* in_desc, int6
                         void* ws, int64_t ws_floats, const int64_t* dims, tmg_stream_t st, int64_t ngroups, int64_t* plan);
 int tmg_conv_rep_border_plan(const void* dy, const int64_t* dy_desc, const void* w, const void* kappa, void* const* out_ptrs,
                              const int64_t* out_desc, int64_t nout, const int64_t* dims, tmg_stream_t st, int64_t* plan);
+
+/* The same for the Winograd launchers (tmg_wino.hip):
+ *   tmg_conv_wino_fwd_plan, tmg_conv_wino_fwd3_plan, tmg_conv_wino_narrow_plan: plan[13] = {kernel (0 wino_fwd_kernel, 1 wino_fwdp_kernel,
+ *     2 wino_fwd3_kernel, 3 wino_nn_kernel), NPW (wino_nn_kernel: NTN), Cin_pad, nchunks, 16-channel groups of the last 32-channel chunk,
+ *     Npad / 16, tiles_x, tiles_y, ntiles, grid_x, grid_y, largest tile count of one block, lds_bytes}
+ *   tmg_conv_wino_wgrad_plan (ngroups > 1: the plan of tmg_conv_wino_wgrad_grouped): plan[11] = {CIT, NCO, DB (two tile buffers), gx, gy,
+ *     gz, bpg (block rows per group), NG of wino_wgrad_reduce_kernel, ntiles, lds_bytes, ws_floats} */
+int tmg_conv_wino_fwd_plan(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* U, const void* bias,
+                           void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, tmg_stream_t st,
+                           int64_t* plan);
+int tmg_conv_wino_fwd3_plan(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* U, const void* bias,
+                            void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, tmg_stream_t st,
+                            int64_t* plan);
+int tmg_conv_wino_narrow_plan(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* U, const void* bias,
+                              void* const* out_ptrs, const int64_t* out_desc, int64_t nout, const int64_t* dims, tmg_stream_t st,
+                              int64_t* plan);
+int tmg_conv_wino_wgrad_plan(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* dy, const int64_t* dy_desc,
+                             void* dW, void* dbias, void* ws, int64_t ws_floats, const int64_t* dims, tmg_stream_t st, int64_t ngroups,
+                             int64_t* plan);
 
 #endif
