@@ -20,7 +20,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmglow_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip"]
+SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip"]
 # Sources compiled WITHOUT the packed-fp32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32): beside MFMAs a packed
 # f32 instruction costs ~13 cycles more than the two scalar ones it replaces (MI355X_MICROARCH.md, cycle constants, 'price of one
 # filler beside MFMAs'), and the compiler SLP-packs adjacent scalar adds / multiplies by itself under -O3.  The matrix-core kernels'
@@ -50,6 +50,8 @@ PLAN_EXPORTS = ["tmg_conv_fwd_plan", "tmg_conv_wgrad_plan", "tmg_conv_rep_border
                 "tmg_conv_wino_narrow_plan", "tmg_conv_wino_wgrad_plan"]
 # The temporal power spectra (csrc/tmg_tspec.hip), declared in include/tmglow_hip_tspec.h: tspec_store / tspec_block / tspec_finalize below.
 TSPEC_EXPORTS = ["tmg_tspec_store", "tmg_tspec_block", "tmg_tspec_finalize"]
+# The prediction intervals (csrc/tmg_quant.hip), declared in include/tmglow_hip_quant.h: ens_quant_step below.
+QUANT_EXPORTS = ["tmg_ens_quant_step"]
 # Every export returns int except the workspace sizes, which the header declares int64_t (read through a 32-bit return a request of
 # 2^31 floats or more would be truncated and the kernel handed a buffer smaller than it planned for).
 RET_I64 = ("tmg_conv_wgrad_ws_floats", "tmg_conv_wgrad_grouped_ws_floats", "tmg_conv_wino_wgrad_ws_floats",
@@ -62,7 +64,7 @@ def build(force=False, verbose=False):
     from concurrent.futures import ThreadPoolExecutor
     inc = os.path.join(os.path.dirname(_HERE), "include")
     headers = [os.path.join(CSRC, "tmg_common.h"), os.path.join(inc, "tmglow_hip.h"), os.path.join(inc, "tmglow_hip_plan.h"),
-               os.path.join(inc, "tmglow_hip_tspec.h")]
+               os.path.join(inc, "tmglow_hip_tspec.h"), os.path.join(inc, "tmglow_hip_quant.h")]
     hmt = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -116,7 +118,7 @@ def lib():
         for name in PLAN_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
             getattr(_lib, name).argtypes = PLAN_ARGTYPES[name]
-        for name in TSPEC_EXPORTS:
+        for name in TSPEC_EXPORTS + QUANT_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
     return _lib
 
@@ -1074,6 +1076,24 @@ def ens_score_step(xs, target, scale, crps, crps_fair, hist, tmeans, ostrides, t
     _chk(lib().tmg_ens_score_step(_ptr(xs), c_vp(ptr), _i64(ps, co), _ptr(scale), _ptr(crps), _ptr(crps_fair), _ptr(hist),
                                   *[_ptr(t) for t in tmeans], _i64(*ostrides), _i64(S, B, HW, Cc, t_before, flags), _stream()),
          "tmg_ens_score_step")
+
+
+def ens_quant_step(xs, target, u, out_mu, out_std, lo, hi, w, thr, ex, quant, exceed, taggs, ostrides, t_before, flags):
+    """Order statistics of one kept step whose S members are in xs [S, B, C, HW]: the Q levels (lo, hi, w) (host sequences: ranks
+    and the fp32 weight between them) un-normalised by u [B, C] or None, out_mu, out_std into quant; the K thresholds ex = ((channel,
+    1 for > / 0 for <), ..) with the raw values thr [B, K] (device) as exceedance probabilities into exceed; per-case strides ostrides
+    = (quant, exceed).  flags & 1 advances the time aggregates taggs = (tquant, tbelow int32, texceed int32) that hold t_before steps;
+    flags & 2: target (NHWC [B, H, W, C] or a channel-slice view) is given and tbelow counts the steps with target < quantile
+    (tmg_ens_quant_step)."""
+    S, B, Cc, HW = xs.shape
+    ptr, ps, co, _ = seg(target) if target is not None else (0, 0, 0, 0)
+    taggs = taggs if taggs is not None else (None,) * 3
+    lohi = [int(v) for pair in zip(lo, hi) for v in pair]
+    exf = [int(v) for e in ex for v in e]
+    _chk(lib().tmg_ens_quant_step(_ptr(xs), c_vp(ptr), _i64(ps, co), _ptr(u), _ptr(out_mu), _ptr(out_std), _i64(*lohi),
+                                  _flts([float(v) for v in w]), _ptr(thr), _i64(*exf) if exf else None, _ptr(quant), _ptr(exceed),
+                                  *[_ptr(t) for t in taggs], _i64(*ostrides), _i64(S, B, HW, Cc, len(lohi) // 2, len(exf) // 2, t_before, flags),
+                                  _stream()), "tmg_ens_quant_step")
 
 
 def spec_rows(y, u, out_mu, out_std, ft_w, yw, k):

@@ -8,6 +8,7 @@ All activations are NHWC ([B,H,W,C] contiguous, or channel-slice views of such t
 """
 import collections
 import math
+import numbers
 
 import os
 import threading
@@ -1817,6 +1818,169 @@ class EnsembleScores:
         self.out["time_crps_fair"] = self.time_state[1].view(shp)
         self.out["time_rank_hist"] = self.out["rank_hist"][:, self._timed].sum(dim=1)
         return self.out
+
+
+def quantile_levels(S, levels):
+    """The host level table of EnsembleQuantiles, numpy's method="linear" in fp64: for every probability q of `levels` the virtual
+    index h = q (S - 1), lo = min(floor(h), S - 1), hi = min(lo + 1, S - 1) and the weight w = float32(h - lo), so that the quantile is
+    x_(lo) + w (x_(hi) - x_(lo)) over the order statistics x_(0) <= .. <= x_(S-1).  -> (lo, hi, w): int64, int64, float32 arrays."""
+    import numpy as np
+    S = int(S)
+    q = np.asarray(levels, dtype=np.float64).reshape(-1)
+    if S < 1 or not bool(np.all(np.isfinite(q) & (q >= 0) & (q <= 1))):
+        raise ValueError("quantile levels must be finite and in [0, 1] and S >= 1, got S=%d, levels=%s" % (S, q.tolist()))
+    h = q * (S - 1)
+    lo = np.minimum(np.floor(h), S - 1).astype(np.int64)
+    hi = np.minimum(lo + 1, S - 1)
+    return lo, hi, (h - lo).astype(np.float32)
+
+
+QUANT_MAX_LEVELS = 8
+QUANT_MAX_EXCEED = 4
+
+
+def quantile_args(levels, exceed, C):
+    """The checks of EnsembleQuantiles' levels and exceed arguments for C channels -> (levels as floats, exceed as tuples)."""
+    lv = [float(q) for q in levels]
+    if not (1 <= len(lv) <= QUANT_MAX_LEVELS) or not all(math.isfinite(q) and 0.0 <= q <= 1.0 for q in lv):
+        raise ValueError("levels must be 1 to %d finite probabilities in [0, 1], got %s" % (QUANT_MAX_LEVELS, lv))
+    ex = [tuple(e) for e in exceed]
+    if len(ex) > QUANT_MAX_EXCEED:
+        raise ValueError("exceed takes at most %d entries, got %d" % (QUANT_MAX_EXCEED, len(ex)))
+    for e in ex:
+        if len(e) != 3 or isinstance(e[0], bool) or not isinstance(e[0], numbers.Integral) or not 0 <= e[0] < C \
+                or e[2] not in (">", "<") or isinstance(e[1], bool) or not isinstance(e[1], numbers.Real) or not math.isfinite(e[1]):
+            raise ValueError("exceed entries are (channel in 0..%d, finite value, '>' or '<'), got %r" % (C - 1, e))
+    return lv, ex
+
+
+class EnsembleQuantiles:
+    """On-device prediction intervals of sampled roll-outs of B cases (tmg_ens_score_store / tmg_ens_quant_step): per case b, kept
+    step t, channel c and pixel p the quantiles of the S members at the probability `levels` (numpy's method="linear": exact order
+    statistics, ties broken by member index, then one fp32 interpolation, see quantile_levels), un-normalised as
+    u[b, c] (out_std[c] q + out_mu[c]); and for every entry (channel, value, ">" | "<") of `exceed` the share of the members of that
+    channel whose un-normalised value is strictly above / below `value` (physical units; (0, 0.0, "<") is the reverse-flow
+    probability).  u out_std > 0 keeps the order, so the kernel selects on the raw normalised values and compares them with the
+    thresholds (value / u - out_mu) / out_std, formed in fp64 and rounded once.  Non-finite members are not supported: the outputs
+    of a pixel that holds one are unspecified.
+
+    Feeding protocol of EnsembleScores: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
+    chunks before the next step's.  The target is optional, but given for every step or for none; the last chunk's is the one used.
+    Outputs (device tensors): quant [B, Tk, Q, C, H, W]; exceed_prob [B, Tk, K, H, W] (K > 0); finalize() adds, over the steps folded
+    with time=True (Tn of them), time_quant [B, Q, C, H, W] (the running mean of quant), with a target time_below_count int64 (the
+    steps whose normalised target was strictly under the normalised quantile) and below_frac = time_below_count / Tn, with K > 0
+    time_exceed_count [B, K, H, W] int64 (member counts summed over the steps) and time_exceed_prob = count / (S Tn); and levels [Q]
+    float64 as given."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, levels=(0.05, 0.5, 0.95), exceed=()):
+        if not (2 <= C <= 4):
+            raise ValueError("ensemble quantiles need 2 <= C <= 4 channels, got %d" % C)
+        if int(steps) < 1:
+            raise ValueError("ensemble quantiles need steps >= 1, got %d" % int(steps))
+        lv, ex = quantile_args(levels, exceed, C)
+        if not (1 <= int(members) <= SCORES_MAX_MEMBERS):
+            raise ValueError("ensemble quantiles need 1 <= members <= %d, got %d" % (SCORES_MAX_MEMBERS, int(members)))
+        sd = torch.as_tensor(out_std, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
+        mu = torch.as_tensor(out_mu, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
+        if sd.numel() != C or mu.numel() != C:
+            raise ValueError("out_mu / out_std need %d entries, got %d / %d" % (C, mu.numel(), sd.numel()))
+        if not bool((torch.isfinite(sd) & (sd > 0)).all()):
+            raise ValueError("out_std must be finite and strictly positive (u * out_std > 0 keeps the members' order), got %s" % sd.tolist())
+        if not bool(torch.isfinite(mu).all()):
+            raise ValueError("out_mu must be finite, got %s" % mu.tolist())
+        if u is not None:
+            u = torch.as_tensor(u, dtype=torch.float32).detach().reshape(B, C).cpu()
+            if not bool((torch.isfinite(u) & (u > 0)).all()):
+                raise ValueError("u must be finite and strictly positive (u * out_std > 0 keeps the members' order)")
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("ensemble quantiles run on the HIP path: device %s is not a GPU (there is no CPU path)" % dev)
+        self.S, self.B, self.C, self.H, self.W, self.Tk = int(members), int(B), int(C), int(Hh), int(Ww), int(steps)
+        self.levels = lv
+        self.lo, self.hi, self.w = quantile_levels(self.S, lv)
+        self.Q, self.K = len(lv), len(ex)
+        HW = self.H * self.W
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.mu, self.sd = mu.to(dev).contiguous(), sd.to(dev).contiguous()
+        self.u = None if u is None else u.to(dev).contiguous()
+        self.xs = torch.empty((self.S, self.B, C, HW), **f32)
+        self.tquant = torch.empty((self.B, self.Q, C, HW), **f32)
+        self.tbelow = torch.empty((self.B, self.Q, C, HW), device=dev, dtype=torch.int32)
+        self.out = {"quant": torch.empty((self.B, self.Tk, self.Q, C, Hh, Ww), **f32)}
+        self.ex = [(int(e[0]), 1 if e[2] == ">" else 0) for e in ex]
+        self.thr = self.texceed = None
+        if self.K:
+            # the raw threshold of case b: (value / sc - out_mu) / out_std in fp64, rounded once
+            scd = torch.ones(self.B, C, dtype=torch.float64) if u is None else u.double()
+            thr = torch.stack([(float(e[1]) / scd[:, e[0]] - mu.double()[e[0]]) / sd.double()[e[0]] for e in ex], 1)
+            self.thr = thr.to(torch.float32).to(dev).contiguous()
+            self.texceed = torch.empty((self.B, self.K, HW), device=dev, dtype=torch.int32)
+            self.out["exceed_prob"] = torch.empty((self.B, self.Tk, self.K, Hh, Ww), **f32)
+        self._n = 0           # members stored for the current step
+        self._step = 0        # the step being filled
+        self._t = [0] * self.S  # timed steps every member has been fed for
+        self._scored = None   # whether the steps come with a target: the first step decides
+
+    def add(self, y, m0, target=None, time=True):
+        """Store the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
+        channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride rule, or None.  The
+        step's last chunk selects the step's quantiles."""
+        yn = y.permute(0, 2, 3, 1)
+        kB = yn.shape[0]
+        if kB % self.B or tuple(yn.shape[1:]) != (self.H, self.W, self.C):
+            raise ValueError("chunk shape %s does not hold whole members of [%d, %d, %d, %d]" % (tuple(y.shape), self.B, self.C, self.H, self.W))
+        if target is not None and tuple(target.shape) != (self.B, self.C, self.H, self.W):
+            raise ValueError("target shape %s is not [%d, %d, %d, %d]" % (tuple(target.shape), self.B, self.C, self.H, self.W))
+        k = kB // self.B
+        if m0 != self._n or m0 + k > self.S or self._step >= self.Tk:
+            raise ValueError("members must be fed in order, every step's chunks before the next step's")
+        t_before = self._t[m0]
+        if time and any(self._t[m] != t_before for m in range(m0, m0 + k)):
+            raise ValueError("members of one chunk hold different numbers of time steps")
+        H.check_device(yn)
+        tn = None
+        if target is not None:
+            tn = target.permute(0, 2, 3, 1)
+            H.check_act(tn)
+            H.check_device(tn)
+        last = m0 + k == self.S
+        if last:
+            if self._scored is None:
+                self._scored = tn is not None
+            if self._scored != (tn is not None):
+                raise ValueError("the target is given for every step or for none")
+        H.ens_score_store(yn, self.xs, k, m0)
+        if last:
+            HW = self.H * self.W
+            t = self._step
+            o = self.out
+            H.ens_quant_step(self.xs, tn, self.u, self.mu, self.sd, self.lo, self.hi, self.w, self.thr, self.ex, o["quant"][:, t],
+                             o["exceed_prob"][:, t] if self.K else None, (self.tquant, self.tbelow, self.texceed),
+                             (self.Tk * self.Q * self.C * HW, self.Tk * self.K * HW), t_before, (1 if time else 0) | (2 if tn is not None else 0))
+        if time:
+            for m in range(m0, m0 + k):
+                self._t[m] += 1
+        self._n = 0 if last else self._n + k
+        self._step += 1 if last else 0
+
+    def finalize(self):
+        """-> dict of the outputs; the time aggregates cover the steps folded with time=True."""
+        if self._step != self.Tk:
+            raise RuntimeError("%d of %d steps folded" % (self._step, self.Tk))
+        T = self._t[0]
+        if T < 1 or any(t != T for t in self._t):
+            raise RuntimeError("no time statistics: no step was folded with time=True")
+        shp = (self.B, self.Q, self.C, self.H, self.W)
+        o = self.out
+        o["time_quant"] = self.tquant.view(shp)
+        if self._scored:
+            o["time_below_count"] = self.tbelow.view(shp).to(torch.int64)
+            o["below_frac"] = (o["time_below_count"].double() / float(T)).to(torch.float32)
+        if self.K:
+            o["time_exceed_count"] = self.texceed.view(self.B, self.K, self.H, self.W).to(torch.int64)
+            o["time_exceed_prob"] = (o["time_exceed_count"].double() / (float(self.S) * float(T))).to(torch.float32)
+        o["levels"] = torch.tensor(self.levels, dtype=torch.float64)
+        return o
 
 
 def spectrum_bins(H_, W_, dx, dy):

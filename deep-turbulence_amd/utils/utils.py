@@ -100,11 +100,12 @@ _TARGET_STATS = (("target_time_mean", "time_mean_mean"), ("target_time_rms", "ti
 
 
 def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, turbulence, spectra=False,
-                   window="hann", scores=False, tspec=None):
+                   window="hann", scores=False, tspec=None, quant=None):
     """The body of modelPredStats, modelPredTurbulence (turbulence: grid = (args.dx, args.dy)), modelPredSpectra (spectra: the same
     chunks also go through an EnsembleSpectrum with `window`), modelPredScores (scores: the same chunks also go through an
     EnsembleScores with the step's normalised target) and modelPredTimeSpectra (tspec = (nfreq, window, dt between kept steps): the
-    chunks of the kept steps from t_start on also go through an EnsembleTimeSpectrum): same seed draws in the same order, same
+    chunks of the kept steps from t_start on also go through an EnsembleTimeSpectrum) and modelPredQuantiles (quant = (levels, exceed):
+    the same chunks also go through an EnsembleQuantiles with the step's normalised target): same seed draws in the same order, same
     folding, same re-anchoring, so that the keys they share hold identical values under the same host RNG state."""
     import tmg_ops as ops
     core = getattr(model, "module", model)
@@ -138,7 +139,7 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
             B, C, Hh, Ww = inp.size(0), tgt.size(2), tgt.size(-2), tgt.size(-1)
             if C != 3:
                 raise ValueError("%s scales (ux, uy, p) by (u0, u0, u0^2) as modelPred does: 3 target channels, got %d" % (name, C))
-            if (scores or tspec is not None) and target0.size(1) <= (nkeep - 1) * stride:
+            if (scores or tspec is not None or quant is not None) and target0.size(1) <= (nkeep - 1) * stride:
                 raise ValueError("%s: the target series holds %d steps, kept step %d needs step %d"
                                  % (name, target0.size(1), nkeep - 1, (nkeep - 1) * stride))
             keys = []
@@ -157,10 +158,12 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
             sc = ops.EnsembleScores(samples, B, C, Hh, Ww, nkeep, dev, out_std, u=u.view(B, 3)[:, :C]) if scores else None
             tsp_t = ops.EnsembleTimeSpectrum(samples, B, C, Hh, Ww, nkeep - t_start, dev, out_mu, out_std, u=u.view(B, 3)[:, :C],
                                              nfreq=tspec[0], window=tspec[1], dt=tspec[2]) if tspec is not None else None
-            tnorm = target0.to(dev) if scores else None                # the normalised series; one step at a time goes channels-last
+            qt = ops.EnsembleQuantiles(samples, B, C, Hh, Ww, nkeep, dev, out_mu, out_std, u=u.view(B, 3)[:, :C], levels=quant[0],
+                                       exceed=quant[1]) if quant is not None else None
+            tnorm = target0.to(dev) if scores or qt is not None else None                # the normalised series; one step at a time goes channels-last
             for tstep in range(tmax):
                 keep = tstep % stride == 0 and tstep // stride < nkeep
-                tj = tnorm[:, tstep].contiguous(memory_format=torch.channels_last) if keep and scores else None
+                tj = tnorm[:, tstep].contiguous(memory_format=torch.channels_last) if keep and tnorm is not None else None
                 for ci, (m0, k) in enumerate(chunks):
                     y0, _logp, states[ci] = core.sampleEnsemble(inp[:, tstep], states[ci], k)
                     if keep:
@@ -171,6 +174,8 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
                             sc.add(y0, m0, tj, time=tstep // stride >= t_start)
                         if tsp_t is not None and tstep // stride >= t_start:
                             tsp_t.add(y0, m0)
+                        if qt is not None:
+                            qt.add(y0, m0, tj, time=tstep // stride >= t_start)
                     if tstep % 20 == 0:
                         states[ci] = [(0.5 * h + 0.5 * hk, 0.5 * c + 0.5 * ck) for (h, c), (hk, ck) in zip(states[ci], anchors[ci])]
             for key, t in st.finalize().items():
@@ -184,6 +189,12 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
             if sc is not None:
                 for key, t in sc.finalize().items():
                     outs.setdefault(key, []).append(t.cpu())
+            if qt is not None:
+                for key, t in qt.finalize().items():
+                    if key == "levels":
+                        q_levels = t
+                    else:
+                        outs.setdefault(key, []).append(t.cpu())
             if tsp_t is not None:
                 for key, t in tsp_t.finalize().items():
                     if key == "psd_freq":
@@ -225,6 +236,8 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
         res["spec_k"] = spec_k
     if tspec is not None:
         res["psd_freq"] = psd_freq
+    if quant is not None:
+        res["levels"] = q_levels
     return res
 
 
@@ -331,3 +344,36 @@ def modelPredTimeSpectra(args, model, testing_loader, log, samples=1, stride=1, 
         raise ValueError("dt must be a positive finite time between two model steps, got %r" % (dt,))
     return _ensembleStats("modelPredTimeSpectra", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False,
                           tspec=(int(nfreq), window, step_dt))
+
+
+def modelPredQuantiles(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, levels=(0.05, 0.5, 0.95),
+                       exceed=()):
+    """modelPredStats plus the ensemble's prediction band and exceedance probabilities per pixel, still without forming modelPred's
+    [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleQuantiles): exact order statistics of the members, so the band is right where
+    the members' marginals are skewed or bimodal (behind a bluff body) and mean +- k std is not.  The target of kept step j is series
+    step j * stride; a series that is too short raises.  Channel scales (u0, u0, u0^2).  Same roll-outs as modelPredStats: under the
+    same host RNG state the keys both return are identical.
+
+    levels: 1 to 8 probabilities in [0, 1] (any order, duplicates allowed).  exceed: up to 4 tuples (channel, value, ">" | "<") with
+    value in physical units; (0, 0.0, "<") is the reverse-flow probability P(ux < 0), which locates the recirculation and
+    reattachment behind the step and the wake behind the cylinders.
+
+    Returns modelPredStats' dict plus (CPU tensors), with Q levels, K thresholds, S = samples and Tn = Tk - t_start timed steps:
+      quant [N, Tk, Q, C, H, W]         the un-normalised quantiles of the members per kept step (numpy's method="linear")
+      time_quant [N, Q, C, H, W]        the mean of quant over the kept steps t_start..Tk-1
+      time_below_count [N, Q, C, H, W]  int64: the number of those steps at which the target is strictly under the quantile
+      below_frac [N, Q, C, H, W]        time_below_count / Tn
+      exceed_prob [N, Tk, K, H, W]      the share of the members strictly above (">") / below ("<") the threshold, per kept step
+      time_exceed_count [N, K, H, W]    int64: the member counts summed over those steps
+      time_exceed_prob [N, K, H, W]     time_exceed_count / (S Tn)                       (the three exceed keys only when K > 0)
+      levels [Q] float64                the levels as given.
+
+    What below_frac should be.  For a calibrated ensemble the target is exchangeable with the members, so it falls under the order
+    statistic x_(r) (r = 0..S-1) with probability P(y < x_(r)) = (r + 1) / (S + 1) - not r / (S - 1).  A level that falls on a member
+    (w = 0 in tmg_ops.quantile_levels, rank lo) should therefore show below_frac near (lo + 1) / (S + 1), not q: the median of S = 5
+    members gives 0.5, but level 0 gives 1 / 6 and level 1 gives 5 / 6.  A level between two members is approximately the linear
+    interpolation ((lo + 1) + w) / (S + 1) of its two neighbours."""
+    import tmg_ops as ops
+    levels, exceed = ops.quantile_args(levels, exceed, 3)
+    return _ensembleStats("modelPredQuantiles", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False,
+                          quant=(tuple(levels), tuple(exceed)))
