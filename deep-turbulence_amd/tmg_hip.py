@@ -20,7 +20,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmglow_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip"]
+SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip"]
 # Sources compiled WITHOUT the packed-fp32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32): beside MFMAs a packed
 # f32 instruction costs ~13 cycles more than the two scalar ones it replaces (MI355X_MICROARCH.md, cycle constants, 'price of one
 # filler beside MFMAs'), and the compiler SLP-packs adjacent scalar adds / multiplies by itself under -O3.  The matrix-core kernels'
@@ -52,6 +52,9 @@ PLAN_EXPORTS = ["tmg_conv_fwd_plan", "tmg_conv_wgrad_plan", "tmg_conv_rep_border
 TSPEC_EXPORTS = ["tmg_tspec_store", "tmg_tspec_block", "tmg_tspec_finalize"]
 # The prediction intervals (csrc/tmg_quant.hip), declared in include/tmglow_hip_quant.h: ens_quant_step below.
 QUANT_EXPORTS = ["tmg_ens_quant_step"]
+# The energy score and member distances (csrc/tmg_gram.hip), declared in include/tmglow_hip_gram.h: ens_gram_plan / ens_gram_step /
+# ens_gram_traj below.
+GRAM_EXPORTS = ["tmg_ens_gram_plan", "tmg_ens_gram_step", "tmg_ens_gram_traj"]
 # Every export returns int except the workspace sizes, which the header declares int64_t (read through a 32-bit return a request of
 # 2^31 floats or more would be truncated and the kernel handed a buffer smaller than it planned for).
 RET_I64 = ("tmg_conv_wgrad_ws_floats", "tmg_conv_wgrad_grouped_ws_floats", "tmg_conv_wino_wgrad_ws_floats",
@@ -64,7 +67,8 @@ def build(force=False, verbose=False):
     from concurrent.futures import ThreadPoolExecutor
     inc = os.path.join(os.path.dirname(_HERE), "include")
     headers = [os.path.join(CSRC, "tmg_common.h"), os.path.join(inc, "tmglow_hip.h"), os.path.join(inc, "tmglow_hip_plan.h"),
-               os.path.join(inc, "tmglow_hip_tspec.h"), os.path.join(inc, "tmglow_hip_quant.h")]
+               os.path.join(inc, "tmglow_hip_tspec.h"), os.path.join(inc, "tmglow_hip_quant.h"),
+               os.path.join(inc, "tmglow_hip_gram.h")]
     hmt = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -118,7 +122,7 @@ def lib():
         for name in PLAN_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
             getattr(_lib, name).argtypes = PLAN_ARGTYPES[name]
-        for name in TSPEC_EXPORTS + QUANT_EXPORTS:
+        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
     return _lib
 
@@ -1094,6 +1098,42 @@ def ens_quant_step(xs, target, u, out_mu, out_std, lo, hi, w, thr, ex, quant, ex
                                   _flts([float(v) for v in w]), _ptr(thr), _i64(*exf) if exf else None, _ptr(quant), _ptr(exceed),
                                   *[_ptr(t) for t in taggs], _i64(*ostrides), _i64(S, B, HW, Cc, len(lohi) // 2, len(exf) // 2, t_before, flags),
                                   _stream()), "tmg_ens_quant_step")
+
+
+def ens_gram_plan(S, B, C, HW):
+    """The launch plan of ens_gram_step for S members of [B, C, HW] (tmg_ens_gram_plan; nothing is launched) -> dict: P pixel slices of
+    SL pixels, L the fmaf terms of one partial (L P >= HW), NT row macro-tiles of 64 rows over the S + 1 rows, pairs = the NT (NT + 1) / 2
+    macro-tile pairs (I, J), I <= J, in workspace order, part the floats of one partial, ws the workspace floats."""
+    plan = (c_i64 * 7)()
+    _chk(lib().tmg_ens_gram_plan(_i64(S, B, C, HW), plan), "tmg_ens_gram_plan")
+    P, L, NP, ws, SL, NT, part = [int(v) for v in plan]
+    pairs = [(i, j) for i in range(NT) for j in range(i, NT)]
+    assert len(pairs) == NP
+    return {"P": P, "L": L, "pairs": pairs, "ws": ws, "SL": SL, "NT": NT, "part": part}
+
+
+def ens_gram_step(xs, target, a2, groups, r, ws, traj, outf, outi, t, t_before, flags):
+    """Energy score and member distances of one kept step whose S members are in xs [S, B, C, HW], against target (NHWC [B, H, W, C] or
+    a channel-slice view) as row S: the members' mean into r [B, C, HW], the Gram partials into the workspace ws (>= ens_gram_plan's
+    floats), then per case and channel group (groups: tuples of channels; a2 [B, C]: the squared scales) the step's scores into
+    outf [5, B, Tk, Gn] / outi [2, B, Tk, Gn] int64 at step t; flags & 1 adds the squared distances to traj [B, Gn, S + 1, S + 1],
+    which holds t_before steps (tmg_ens_gram_step)."""
+    S, B, Cc, HW = xs.shape
+    ptr, ps, co, _ = seg(target)
+    grp = [-1] * 16
+    for g, chs in enumerate(groups):
+        for k, ch in enumerate(chs):
+            grp[4 * g + k] = int(ch)
+    _chk(lib().tmg_ens_gram_step(_ptr(xs), c_vp(ptr), _i64(ps, co), _ptr(a2), _i64(*grp), _ptr(r), _ptr(ws), c_i64(ws.numel()),
+                                 _ptr(traj), _ptr(outf), _ptr(outi), _i64(S, B, HW, Cc, len(groups), outf.shape[2], t, t_before, flags),
+                                 _stream()), "tmg_ens_gram_step")
+
+
+def ens_gram_traj(traj, outf, outi):
+    """The scores and argmins of ens_gram_step on sqrt(traj), traj [B, Gn, S + 1, S + 1], into outf [5, B, Gn] / outi [2, B, Gn] int64
+    (tmg_ens_gram_traj)."""
+    B, Gn, R, _ = traj.shape
+    _chk(lib().tmg_ens_gram_traj(_ptr(traj), _ptr(outf), _ptr(outi), _i64(R - 1, B, Gn), _stream()), "tmg_ens_gram_traj")
 
 
 def spec_rows(y, u, out_mu, out_std, ft_w, yw, k):

@@ -1983,6 +1983,144 @@ class EnsembleQuantiles:
         return o
 
 
+def energy_groups(groups, C):
+    """The checks of EnsembleEnergy's groups argument for C channels: non-empty tuples of distinct channels in 0..C-1, every channel in
+    at most one group -> the groups as a tuple of tuples of ints."""
+    try:
+        gs = tuple(tuple(g) for g in groups)
+    except TypeError:
+        raise ValueError("groups must be tuples of channels, got %r" % (groups,))
+    seen = set()
+    if not gs:
+        raise ValueError("groups must hold at least one group of channels, got %r" % (groups,))
+    for g in gs:
+        if not g:
+            raise ValueError("groups must be non-empty tuples of channels, got %r" % (groups,))
+        for ch in g:
+            if isinstance(ch, bool) or not isinstance(ch, numbers.Integral) or not 0 <= ch < C or int(ch) in seen:
+                raise ValueError("groups hold distinct channels in 0..%d, each in at most one group, got %r" % (C - 1, groups))
+            seen.add(int(ch))
+    return tuple(tuple(int(ch) for ch in g) for g in gs)
+
+
+ENERGY_STEP_KEYS = ("energy_score", "energy_score_fair", "target_dist_mean", "pair_dist_mean", "nearest_dist")
+
+
+class EnsembleEnergy:
+    """On-device energy score and member distances of sampled roll-outs of B cases against the target (tmg_ens_score_store /
+    tmg_ens_gram_step): the score of every member as ONE vector over the pixels, which no per-pixel score can see.  For case b and
+    kept step t, with the rows x_0..x_{S-1} (raw normalised members) and x_S = y (the normalised target), a_c = u[b, c] out_std[c] > 0
+    and the channel groups g (tuples of channels that share a unit; default for 3 channels ((0, 1), (2,)): velocity and pressure):
+      d2_g[m, n] = sum_{c in g} a_c^2 sum_p (x_m - x_n)^2,  dist = sqrt(d2)            the distance of two fields in physical units
+      target_dist_mean = (1/S) sum_{m<S} dist[m, S],  pair_dist_mean = (2/S^2) sum_{m<n<S} dist[m, n]
+      energy_score = target_dist_mean - pair_dist_mean / 2; energy_score_fair: 1 / (S (S - 1)) for 1 / S^2 (S = 1: the pair term is 0)
+      medoid = argmin_{m<S} sum_{n<S} dist[m, n],  nearest = argmin_{m<S} dist[m, S] (ties: the lowest member), nearest_dist
+    out_mu cancels in every term and is not an input.  The kernels form d2 from the Gram matrix of the rows centred about the members'
+    mean (csrc/tmg_gram.hip), on the fp32 matrix pipe.
+
+    Feeding protocol of EnsembleScores: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
+    chunks before the next step's; every chunk comes with the step's target, and the last chunk's is the one that is scored.
+    Outputs (device tensors, Gn groups): energy_score, energy_score_fair, target_dist_mean, pair_dist_mean, nearest_dist [B, Tk, Gn]
+    float32; medoid, nearest [B, Tk, Gn] int64; finalize() adds, over the steps folded with time=True, time_energy_score,
+    time_energy_score_fair [B, Gn] (the means of the per-step scores), traj_dist2 [B, Gn, S + 1, S + 1] (the sum of d2: the squared
+    distance between whole roll-outs, space and time as one vector; symmetric, zero diagonal, the target last), traj_energy_score,
+    traj_energy_score_fair [B, Gn] and traj_medoid, traj_nearest [B, Gn] int64 (the same formulas on sqrt(traj_dist2))."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_std, u=None, groups=None):
+        if not (2 <= C <= 4):
+            raise ValueError("ensemble energy scores need 2 <= C <= 4 channels, got %d" % C)
+        if not (1 <= int(members) <= SCORES_MAX_MEMBERS):
+            raise ValueError("ensemble energy scores need 1 <= members <= %d, got %d" % (SCORES_MAX_MEMBERS, int(members)))
+        sd = torch.as_tensor(out_std, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
+        if sd.numel() != C:
+            raise ValueError("out_std needs %d entries, got %d" % (C, sd.numel()))
+        if not bool((torch.isfinite(sd) & (sd > 0)).all()):
+            raise ValueError("out_std must be finite and strictly positive (the distances scale with u * out_std), got %s" % sd.tolist())
+        if u is not None:
+            u = torch.as_tensor(u, dtype=torch.float32).detach().reshape(B, C).cpu()
+            if not bool((torch.isfinite(u) & (u > 0)).all()):
+                raise ValueError("u must be finite and strictly positive (the distances scale with u * out_std)")
+        if groups is None:
+            groups = ((0, 1), (2,)) if C == 3 else (tuple(range(C)),)
+        self.groups = energy_groups(groups, C)
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("ensemble energy scores run on the HIP path: device %s is not a GPU (there is no CPU path)" % dev)
+        self.S, self.B, self.C, self.H, self.W, self.Tk = int(members), int(B), int(C), int(Hh), int(Ww), int(steps)
+        HW = self.H * self.W
+        Gn = len(self.groups)
+        f32 = dict(device=dev, dtype=torch.float32)
+        # a_c^2 = (u out_std)^2 in fp64 from the fp32 factors, rounded once
+        a = sd.double().view(1, C).expand(self.B, C) if u is None else u.double() * sd.double().view(1, C)
+        self.a2 = (a * a).to(torch.float32).to(dev).contiguous()
+        self.plan = H.ens_gram_plan(self.S, self.B, C, HW)
+        self.xs = torch.empty((self.S, self.B, C, HW), **f32)
+        self.r = torch.empty((self.B, C, HW), **f32)
+        self.ws = torch.empty((self.plan["ws"],), **f32)
+        self.traj = torch.empty((self.B, Gn, self.S + 1, self.S + 1), **f32)
+        self.outf = torch.empty((5, self.B, self.Tk, Gn), **f32)
+        self.outi = torch.empty((2, self.B, self.Tk, Gn), device=dev, dtype=torch.int64)
+        self.out = dict(zip(ENERGY_STEP_KEYS, self.outf))
+        self.out["medoid"], self.out["nearest"] = self.outi[0], self.outi[1]
+        self._n = 0           # members stored for the current step
+        self._step = 0        # the step being filled
+        self._t = [0] * self.S  # timed steps every member has been fed for
+        self._timed = []      # the steps whose distances went into traj_dist2
+
+    def add(self, y, m0, target, time=True):
+        """Store the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
+        channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride rule.  The step's
+        last chunk scores the step against its target."""
+        yn = y.permute(0, 2, 3, 1)
+        kB = yn.shape[0]
+        if kB % self.B or tuple(yn.shape[1:]) != (self.H, self.W, self.C):
+            raise ValueError("chunk shape %s does not hold whole members of [%d, %d, %d, %d]" % (tuple(y.shape), self.B, self.C, self.H, self.W))
+        if target is None or tuple(target.shape) != (self.B, self.C, self.H, self.W):
+            raise ValueError("target shape %s is not [%d, %d, %d, %d]" % (None if target is None else tuple(target.shape), self.B, self.C,
+                                                                          self.H, self.W))
+        k = kB // self.B
+        if m0 != self._n or m0 + k > self.S or self._step >= self.Tk:
+            raise ValueError("members must be fed in order, every step's chunks before the next step's")
+        t_before = self._t[m0]
+        if time and any(self._t[m] != t_before for m in range(m0, m0 + k)):
+            raise ValueError("members of one chunk hold different numbers of time steps")
+        H.check_device(yn)
+        tn = target.permute(0, 2, 3, 1)
+        H.check_act(tn)
+        H.check_device(tn)
+        last = m0 + k == self.S
+        H.ens_score_store(yn, self.xs, k, m0)
+        if last:
+            H.ens_gram_step(self.xs, tn, self.a2, self.groups, self.r, self.ws, self.traj, self.outf, self.outi, self._step, t_before,
+                            1 if time else 0)
+            if time:
+                self._timed.append(self._step)
+        if time:
+            for m in range(m0, m0 + k):
+                self._t[m] += 1
+        self._n = 0 if last else self._n + k
+        self._step += 1 if last else 0
+
+    def finalize(self):
+        """-> dict of the outputs; the time statistics cover the steps folded with time=True."""
+        if self._step != self.Tk:
+            raise RuntimeError("%d of %d steps folded" % (self._step, self.Tk))
+        T = self._t[0]
+        if T < 1 or any(t != T for t in self._t) or len(self._timed) != T:
+            raise RuntimeError("no time statistics: no step was folded with time=True")
+        o = self.out
+        Gn = len(self.groups)
+        tf = torch.empty((5, self.B, Gn), device=self.traj.device, dtype=torch.float32)
+        ti = torch.empty((2, self.B, Gn), device=self.traj.device, dtype=torch.int64)
+        H.ens_gram_traj(self.traj, tf, ti)
+        o["traj_dist2"] = self.traj
+        o["traj_energy_score"], o["traj_energy_score_fair"] = tf[0], tf[1]
+        o["traj_medoid"], o["traj_nearest"] = ti[0], ti[1]
+        o["time_energy_score"] = o["energy_score"][:, self._timed].double().mean(dim=1).to(torch.float32)
+        o["time_energy_score_fair"] = o["energy_score_fair"][:, self._timed].double().mean(dim=1).to(torch.float32)
+        return o
+
+
 def spectrum_bins(H_, W_, dx, dy):
     """The shell map of an H x W field on a grid of cell size dx along W, dy along H (fp64, host): signed mode numbers p' (p - H
     above H // 2), q' likewise, r = sqrt((p' Lmax / Ly)^2 + (q' Lmax / Lx)^2) with Lx = W dx, Ly = H dy, Lmax = max(Lx, Ly), shell

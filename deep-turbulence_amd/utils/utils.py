@@ -100,12 +100,13 @@ _TARGET_STATS = (("target_time_mean", "time_mean_mean"), ("target_time_rms", "ti
 
 
 def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, turbulence, spectra=False,
-                   window="hann", scores=False, tspec=None, quant=None):
+                   window="hann", scores=False, tspec=None, quant=None, energy=None):
     """The body of modelPredStats, modelPredTurbulence (turbulence: grid = (args.dx, args.dy)), modelPredSpectra (spectra: the same
     chunks also go through an EnsembleSpectrum with `window`), modelPredScores (scores: the same chunks also go through an
     EnsembleScores with the step's normalised target) and modelPredTimeSpectra (tspec = (nfreq, window, dt between kept steps): the
     chunks of the kept steps from t_start on also go through an EnsembleTimeSpectrum) and modelPredQuantiles (quant = (levels, exceed):
-    the same chunks also go through an EnsembleQuantiles with the step's normalised target): same seed draws in the same order, same
+    the same chunks also go through an EnsembleQuantiles with the step's normalised target) and modelPredEnergy (energy = the channel
+    groups: the same chunks also go through an EnsembleEnergy with the step's normalised target): same seed draws in the same order, same
     folding, same re-anchoring, so that the keys they share hold identical values under the same host RNG state."""
     import tmg_ops as ops
     core = getattr(model, "module", model)
@@ -139,7 +140,7 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
             B, C, Hh, Ww = inp.size(0), tgt.size(2), tgt.size(-2), tgt.size(-1)
             if C != 3:
                 raise ValueError("%s scales (ux, uy, p) by (u0, u0, u0^2) as modelPred does: 3 target channels, got %d" % (name, C))
-            if (scores or tspec is not None or quant is not None) and target0.size(1) <= (nkeep - 1) * stride:
+            if (scores or tspec is not None or quant is not None or energy is not None) and target0.size(1) <= (nkeep - 1) * stride:
                 raise ValueError("%s: the target series holds %d steps, kept step %d needs step %d"
                                  % (name, target0.size(1), nkeep - 1, (nkeep - 1) * stride))
             keys = []
@@ -160,7 +161,8 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
                                              nfreq=tspec[0], window=tspec[1], dt=tspec[2]) if tspec is not None else None
             qt = ops.EnsembleQuantiles(samples, B, C, Hh, Ww, nkeep, dev, out_mu, out_std, u=u.view(B, 3)[:, :C], levels=quant[0],
                                        exceed=quant[1]) if quant is not None else None
-            tnorm = target0.to(dev) if scores or qt is not None else None                # the normalised series; one step at a time goes channels-last
+            en = ops.EnsembleEnergy(samples, B, C, Hh, Ww, nkeep, dev, out_std, u=u.view(B, 3)[:, :C], groups=energy) if energy is not None else None
+            tnorm = target0.to(dev) if scores or qt is not None or en is not None else None                # the normalised series; one step at a time goes channels-last
             for tstep in range(tmax):
                 keep = tstep % stride == 0 and tstep // stride < nkeep
                 tj = tnorm[:, tstep].contiguous(memory_format=torch.channels_last) if keep and tnorm is not None else None
@@ -176,6 +178,8 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
                             tsp_t.add(y0, m0)
                         if qt is not None:
                             qt.add(y0, m0, tj, time=tstep // stride >= t_start)
+                        if en is not None:
+                            en.add(y0, m0, tj, time=tstep // stride >= t_start)
                     if tstep % 20 == 0:
                         states[ci] = [(0.5 * h + 0.5 * hk, 0.5 * c + 0.5 * ck) for (h, c), (hk, ck) in zip(states[ci], anchors[ci])]
             for key, t in st.finalize().items():
@@ -195,6 +199,9 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
                         q_levels = t
                     else:
                         outs.setdefault(key, []).append(t.cpu())
+            if en is not None:
+                for key, t in en.finalize().items():
+                    outs.setdefault(key, []).append(t.cpu())
             if tsp_t is not None:
                 for key, t in tsp_t.finalize().items():
                     if key == "psd_freq":
@@ -238,6 +245,8 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
         res["psd_freq"] = psd_freq
     if quant is not None:
         res["levels"] = q_levels
+    if energy is not None:
+        res["energy_groups"] = tuple(energy)
     return res
 
 
@@ -377,3 +386,40 @@ def modelPredQuantiles(args, model, testing_loader, log, samples=1, stride=1, tm
     levels, exceed = ops.quantile_args(levels, exceed, 3)
     return _ensembleStats("modelPredQuantiles", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False,
                           quant=(tuple(levels), tuple(exceed)))
+
+
+def modelPredEnergy(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, groups=((0, 1), (2,))):
+    """modelPredStats plus the ensemble's energy score and the distances between the members as whole fields, still without forming
+    modelPred's [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleEnergy).  Every other score here is per pixel and does not change when
+    the pixels of every member are shuffled independently; the energy score is the multivariate generalisation of the CRPS and scores
+    each member as one vector over the pixels.  The target of kept step j is series step j * stride; a series that is too short
+    raises.  Channel scales (u0, u0, u0^2).  Same roll-outs as modelPredStats: under the same host RNG state the keys both return are
+    identical.
+
+    groups: tuples of channels that share a unit, each channel in at most one group; the default is velocity (0, 1) and pressure (2,).
+    With xh_0..xh_{S-1} the un-normalised members, xh_S the un-normalised target and |.|_g the Euclidean norm over the pixels and the
+    channels of group g, dist[m, n] = |xh_m - xh_n|_g.
+
+    Returns modelPredStats' dict plus (CPU tensors; Gn groups, S = samples, kept steps t_start..Tk-1 are the timed ones):
+      target_dist_mean [N, Tk, Gn]      (1/S) sum_m dist[m, S]: the mean distance of a member to the target
+      pair_dist_mean [N, Tk, Gn]        (1/S^2) sum_m sum_n dist[m, n]: the mean distance of two members (m = n counted, as in crps)
+      energy_score [N, Tk, Gn]          target_dist_mean - pair_dist_mean / 2; lower is better, a proper score of the whole field
+      energy_score_fair [N, Tk, Gn]     the same with 1 / (S (S - 1)) on the pair sum (samples = 1: energy_score = dist[0, S])
+      medoid [N, Tk, Gn] int64          argmin_m sum_n dist[m, n]: the representative member, the one to plot
+      nearest [N, Tk, Gn] int64, nearest_dist [N, Tk, Gn]   the member closest to the target and its distance (ties: the lowest member)
+      time_energy_score, time_energy_score_fair [N, Gn]     the means of the two scores over the timed steps
+      traj_dist2 [N, Gn, S + 1, S + 1]  the sum of dist^2 over the timed steps: the squared distance between whole roll-outs, space and
+                                        time as one vector; symmetric, zero diagonal, the target as the last row and column
+      traj_energy_score, traj_energy_score_fair [N, Gn], traj_medoid, traj_nearest [N, Gn] int64
+                                        the same formulas on sqrt(traj_dist2)
+      energy_groups                     the groups as given.
+
+    What to read from target_dist_mean against pair_dist_mean.  For a calibrated ensemble the target is exchangeable with the members,
+    so the expected member-to-target distance equals the expected member-to-member distance: compare target_dist_mean with
+    pair_dist_mean S / (S - 1) (the pair mean without its S zero terms m = n).  A target that is much further from the members than
+    they are from each other means an over-confident (under-dispersive) or biased ensemble; members further apart than the target is
+    from them mean an over-dispersive one."""
+    import tmg_ops as ops
+    groups = ops.energy_groups(groups, 3)
+    return _ensembleStats("modelPredEnergy", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False,
+                          energy=groups)
