@@ -20,7 +20,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmglow_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip"]
+SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip"]
 # Sources compiled WITHOUT the packed-fp32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32): beside MFMAs a packed
 # f32 instruction costs ~13 cycles more than the two scalar ones it replaces (MI355X_MICROARCH.md, cycle constants, 'price of one
 # filler beside MFMAs'), and the compiler SLP-packs adjacent scalar adds / multiplies by itself under -O3.  The matrix-core kernels'
@@ -55,6 +55,9 @@ QUANT_EXPORTS = ["tmg_ens_quant_step"]
 # The energy score and member distances (csrc/tmg_gram.hip), declared in include/tmglow_hip_gram.h: ens_gram_plan / ens_gram_step /
 # ens_gram_traj below.
 GRAM_EXPORTS = ["tmg_ens_gram_plan", "tmg_ens_gram_step", "tmg_ens_gram_traj"]
+# The structure functions and the variogram score (csrc/tmg_sfun.hip), declared in include/tmglow_hip_sfun.h: ens_sfun_plan /
+# ens_sfun_step below.
+SFUN_EXPORTS = ["tmg_ens_sfun_plan", "tmg_ens_sfun_step"]
 # Every export returns int except the workspace sizes, which the header declares int64_t (read through a 32-bit return a request of
 # 2^31 floats or more would be truncated and the kernel handed a buffer smaller than it planned for).
 RET_I64 = ("tmg_conv_wgrad_ws_floats", "tmg_conv_wgrad_grouped_ws_floats", "tmg_conv_wino_wgrad_ws_floats",
@@ -68,7 +71,7 @@ def build(force=False, verbose=False):
     inc = os.path.join(os.path.dirname(_HERE), "include")
     headers = [os.path.join(CSRC, "tmg_common.h"), os.path.join(inc, "tmglow_hip.h"), os.path.join(inc, "tmglow_hip_plan.h"),
                os.path.join(inc, "tmglow_hip_tspec.h"), os.path.join(inc, "tmglow_hip_quant.h"),
-               os.path.join(inc, "tmglow_hip_gram.h")]
+               os.path.join(inc, "tmglow_hip_gram.h"), os.path.join(inc, "tmglow_hip_sfun.h")]
     hmt = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -122,7 +125,7 @@ def lib():
         for name in PLAN_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
             getattr(_lib, name).argtypes = PLAN_ARGTYPES[name]
-        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS:
+        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS + SFUN_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
     return _lib
 
@@ -1134,6 +1137,35 @@ def ens_gram_traj(traj, outf, outi):
     (tmg_ens_gram_traj)."""
     B, Gn, R, _ = traj.shape
     _chk(lib().tmg_ens_gram_traj(_ptr(traj), _ptr(outf), _ptr(outi), _i64(R - 1, B, Gn), _stream()), "tmg_ens_gram_traj")
+
+
+def ens_sfun_plan(S, B, C, H, W, lags):
+    """The launch plan of ens_sfun_step for S members of [B, C, H, W] and the lags [(dx, dy), ..] (tmg_ens_sfun_plan; nothing is
+    launched) -> dict: P pixel slices of SL pixels (pixel i W + j), threads = 256 (thread t walks the pixels t, t + 256, .. of its
+    slice), Lc the fp32 additions along the longest path inside one partial, R = S + 1 rows, ws the workspace floats, and per lag
+    off / jmax / ilo / ihi / N: the pair (p, p + off) is counted at pixel p when j < jmax and ilo <= i < ihi, N of them."""
+    lags = [(int(dx), int(dy)) for dx, dy in lags]
+    L = len(lags)
+    plan = (c_i64 * 88)()
+    _chk(lib().tmg_ens_sfun_plan(_i64(S, B, C, H, W, L), _i64(*[v for l in lags for v in l]) if L else None, plan), "tmg_ens_sfun_plan")
+    P, Lc, ws, SL, threads, Lq, R = [int(v) for v in plan[:7]]
+    assert Lq == L
+    per = [[int(v) for v in plan[8 + 5 * l:13 + 5 * l]] for l in range(L)]
+    return {"P": P, "Lc": Lc, "ws": ws, "SL": SL, "threads": threads, "L": L, "R": R, "lags": lags,
+            "off": [q[0] for q in per], "jmax": [q[1] for q in per], "ilo": [q[2] for q in per], "ihi": [q[3] for q in per],
+            "N": [q[4] for q in per]}
+
+
+def ens_sfun_step(xs, target, lags, ws, mom, vsum, tmom, tvar, H, W, t_before, flags):
+    """Raw structure-function and variogram sums of one kept step whose S members are in xs [S, B, C, H W], against target (NHWC
+    [B, H, W, C] or a channel-slice view) as row S, at the lags [(dx, dy), ..]: mom [3, B, C, L, S + 1] (the sums of the increments'
+    squares, cubes and fourth powers), vsum [B, C, L]; flags & 1 adds them to tmom / tvar, which hold t_before steps; ws: the
+    workspace (>= ens_sfun_plan's floats) (tmg_ens_sfun_step)."""
+    S, B, Cc, HW = xs.shape
+    ptr, ps, co, _ = seg(target)
+    _chk(lib().tmg_ens_sfun_step(_ptr(xs), c_vp(ptr), _i64(ps, co), _i64(*[int(v) for l in lags for v in l]), _ptr(ws), c_i64(ws.numel()),
+                                 _ptr(mom), _ptr(vsum), _ptr(tmom), _ptr(tvar), _i64(S, B, Cc, H, W, len(lags), t_before, flags),
+                                 _stream()), "tmg_ens_sfun_step")
 
 
 def spec_rows(y, u, out_mu, out_std, ft_w, yw, k):

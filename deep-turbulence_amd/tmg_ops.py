@@ -2121,6 +2121,200 @@ class EnsembleEnergy:
         return o
 
 
+STRUCTURE_MAX_LAGS = 16
+STRUCTURE_MAX_LAG = 64
+
+
+def structure_lags(lags, H, W):
+    """The checks of EnsembleStructure's lags argument for an H x W field -> the lags as a tuple of (dx, dy) int pairs.  A lag is
+    l = (dx, dy) in pixels, dx along W and dy along H, in canonical form: dx >= 0, and dy > 0 when dx == 0; 0 <= dx <= 64, |dy| <= 64,
+    dx < W, |dy| < H; distinct, 1 <= L <= 16 of them.  None: (1, 0), (2, 0), .. in powers of two up to min(32, W // 2), then the same
+    along H.  A lag that breaks a rule raises ValueError naming it."""
+    H, W = int(H), int(W)
+    if lags is None:
+        lags = [(1 << k, 0) for k in range(6) if (1 << k) <= min(32, W // 2)] + [(0, 1 << k) for k in range(6) if (1 << k) <= min(32, H // 2)]
+        if not lags:
+            raise ValueError("lags: a %d x %d field holds no default lag" % (H, W))
+    try:
+        ls = [tuple(l) for l in lags]
+    except TypeError:
+        raise ValueError("lags must be (dx, dy) pairs, got %r" % (lags,))
+    if not 1 <= len(ls) <= STRUCTURE_MAX_LAGS:
+        raise ValueError("lags must hold 1 to %d (dx, dy) pairs, got %d" % (STRUCTURE_MAX_LAGS, len(ls)))
+    seen = set()
+    for l in ls:
+        if len(l) != 2 or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in l):
+            raise ValueError("lag %r is not a pair of integers (dx, dy)" % (l,))
+        dx, dy = int(l[0]), int(l[1])
+        if dx < 0 or (dx == 0 and dy <= 0):
+            raise ValueError("lag %r is not in canonical form: dx >= 0, and dy > 0 when dx == 0" % (l,))
+        if dx > STRUCTURE_MAX_LAG or abs(dy) > STRUCTURE_MAX_LAG:
+            raise ValueError("lag %r is beyond %d pixels" % (l, STRUCTURE_MAX_LAG))
+        if dx >= W or abs(dy) >= H:
+            raise ValueError("lag %r has no pair in a %d x %d field" % (l, H, W))
+        if (dx, dy) in seen:
+            raise ValueError("lag %r is listed twice" % (l,))
+        seen.add((dx, dy))
+    return tuple((int(l[0]), int(l[1])) for l in ls)
+
+
+class EnsembleStructure:
+    """On-device structure functions and variogram score of sampled roll-outs of B cases against the target (tmg_ens_score_store /
+    tmg_ens_sfun_step): the dependence between neighbouring pixels of one member.  Permute the members independently at every pixel
+    and every per-pixel score stays bit-identical; the increments do not.
+
+    Setting.  Case b, kept step t, channel c.  Rows x_0..x_{S-1} are the raw normalised members.  Row x_S = y is the normalised target.
+    a_c = u[b,c] * out_std[c] > 0.  out_mu cancels and is not an input.
+    Lags.  A lag is l = (dx, dy) in pixels, dx along W and dy along H.  Lags are in canonical form: dx >= 0, and dy > 0 when dx == 0.
+    0 <= dx <= 64, |dy| <= 64, dx < W, |dy| < H.  Lags are distinct, with 1 <= L <= 16 of them.  The pairs of a lag are all pixels
+    p = (i, j) for which p' = (i + dy, j + dx) lies in the field.  N_l = (H - |dy|) (W - dx) >= 1.  D_m(p) = x_m(p') - x_m(p).
+    Raw moment sums.  Per row m = 0..S and lag: M_q[m] = sum_p D_m(p)^q for q = 2, 3, 4, in fp32.
+    Raw variogram sum.  Per lag, of order 1/2: s_m(p) = sqrtf(|D_m(p)|); sbar(p) = (s_0 + .. + s_{S-1}, added sequentially in member
+    order in fp32) * fl(1/S); V_l = sum_p (s_S(p) - sbar(p))^2.
+    Physical outputs.  Formed from the raw sums in fp64 and rounded once to float32:
+      sf2, sf3, sf4 [B, Tk, C, L, S+1] = a_c^q M_q / N_l, with the target's row last.
+      sf2_mean, sf2_std [B, Tk, C, L]: mean and population std over the members, target excluded.
+      vario_lag[b,t,c,l] = w_l a_c V_l / N_l.  vario_score[b,t,c] = sum_l vario_lag.  The weights w_l are positive and finite, default 1.
+    Time statistics.  Over the steps folded with time=True, the raw sums are added up on the device: tmom [3, B, C, L, S+1] and
+    tvar [B, C, L], one fp32 addition per step, written rather than read at the first timed step.
+      time_sf2, time_sf3, time_sf4 [B, C, L, S+1] = a^q tmom / (T N_l).  time_skew = time_sf3 / time_sf2^1.5.
+      time_flat = time_sf4 / time_sf2^2.  Both are 0 where time_sf2 == 0.  time_vario_lag [B, C, L] and time_vario_score [B, C].
+    Lag outputs.  lags is int64 [L, 2].  lag_dist is float64 [L] = hypot(dx * grid_dx, dy * grid_dy).
+    Not supported.  Non-finite members, as in EnsembleQuantiles.
+
+    Feeding protocol of EnsembleEnergy: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
+    chunks before the next step's; every chunk comes with the step's target, and the last chunk's is the one that is scored.  The raw
+    device buffers: xs [S, B, C, HW], ws (the workspace), mom [Tk, 3, B, C, L, S+1] and vsum [Tk, B, C, L] (step t writes its own
+    plane), tmom [3, B, C, L, S+1], tvar [B, C, L]."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_std, u=None, lags=None, weights=None, grid=(1.0, 1.0)):
+        if not (2 <= C <= 4):
+            raise ValueError("ensemble structure functions need 2 <= C <= 4 channels, got %d" % C)
+        if not (1 <= int(members) <= SCORES_MAX_MEMBERS):
+            raise ValueError("ensemble structure functions need 1 <= members <= %d, got %d" % (SCORES_MAX_MEMBERS, int(members)))
+        sd = torch.as_tensor(out_std, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
+        if sd.numel() != C:
+            raise ValueError("out_std needs %d entries, got %d" % (C, sd.numel()))
+        if not bool((torch.isfinite(sd) & (sd > 0)).all()):
+            raise ValueError("out_std must be finite and strictly positive (the increments scale with u * out_std), got %s" % sd.tolist())
+        if u is not None:
+            u = torch.as_tensor(u, dtype=torch.float32).detach().reshape(B, C).cpu()
+            if not bool((torch.isfinite(u) & (u > 0)).all()):
+                raise ValueError("u must be finite and strictly positive (the increments scale with u * out_std)")
+        self.lags = structure_lags(lags, Hh, Ww)
+        L = len(self.lags)
+        if weights is None:
+            w = torch.ones(L, dtype=torch.float64)
+        else:
+            w = torch.as_tensor(weights, dtype=torch.float64).detach().reshape(-1).cpu()
+            if w.numel() != L or not bool((torch.isfinite(w) & (w > 0)).all()):
+                raise ValueError("weights must be %d positive finite numbers, one per lag, got %r" % (L, weights))
+        try:
+            gx, gy = float(grid[0]), float(grid[1])
+        except (TypeError, IndexError, ValueError):
+            raise ValueError("grid must be the cell sizes (dx, dy), got %r" % (grid,))
+        if not (0 < gx < float("inf") and 0 < gy < float("inf")):
+            raise ValueError("grid must be positive finite cell sizes (dx, dy), got %r" % (grid,))
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("ensemble structure functions run on the HIP path: device %s is not a GPU (there is no CPU path)" % dev)
+        self.S, self.B, self.C, self.H, self.W, self.Tk = int(members), int(B), int(C), int(Hh), int(Ww), int(steps)
+        self.L = L
+        HW = self.H * self.W
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.a = (sd.double().view(1, C).expand(self.B, C) if u is None else u.double() * sd.double().view(1, C)).contiguous()   # fp64, host
+        self.w = w
+        self.lag_dist = torch.tensor([math.hypot(dx * gx, dy * gy) for dx, dy in self.lags], dtype=torch.float64)
+        self.plan = H.ens_sfun_plan(self.S, self.B, C, self.H, self.W, self.lags)
+        R = self.S + 1
+        self.xs = torch.empty((self.S, self.B, C, HW), **f32)
+        self.ws = torch.empty((self.plan["ws"],), **f32)
+        self.mom = torch.empty((self.Tk, 3, self.B, C, L, R), **f32)
+        self.vsum = torch.empty((self.Tk, self.B, C, L), **f32)
+        self.tmom = torch.empty((3, self.B, C, L, R), **f32)
+        self.tvar = torch.empty((self.B, C, L), **f32)
+        self._n = 0           # members stored for the current step
+        self._step = 0        # the step being filled
+        self._t = [0] * self.S  # timed steps every member has been fed for
+        self._timed = []      # the steps whose sums went into tmom / tvar
+
+    def add(self, y, m0, target, time=True):
+        """Store the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
+        channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride rule.  The step's
+        last chunk forms the step's sums against its target."""
+        yn = y.permute(0, 2, 3, 1)
+        kB = yn.shape[0]
+        if kB % self.B or tuple(yn.shape[1:]) != (self.H, self.W, self.C):
+            raise ValueError("chunk shape %s does not hold whole members of [%d, %d, %d, %d]" % (tuple(y.shape), self.B, self.C, self.H, self.W))
+        if target is None or tuple(target.shape) != (self.B, self.C, self.H, self.W):
+            raise ValueError("target shape %s is not [%d, %d, %d, %d]" % (None if target is None else tuple(target.shape), self.B, self.C,
+                                                                          self.H, self.W))
+        k = kB // self.B
+        if m0 != self._n or m0 + k > self.S or self._step >= self.Tk:
+            raise ValueError("members must be fed in order, every step's chunks before the next step's")
+        t_before = self._t[m0]
+        if time and any(self._t[m] != t_before for m in range(m0, m0 + k)):
+            raise ValueError("members of one chunk hold different numbers of time steps")
+        H.check_device(yn)
+        tn = target.permute(0, 2, 3, 1)
+        H.check_act(tn)
+        H.check_device(tn)
+        last = m0 + k == self.S
+        H.ens_score_store(yn, self.xs, k, m0)
+        if last:
+            H.ens_sfun_step(self.xs, tn, self.lags, self.ws, self.mom[self._step], self.vsum[self._step], self.tmom, self.tvar,
+                            self.H, self.W, t_before, 1 if time else 0)
+            if time:
+                self._timed.append(self._step)
+        if time:
+            for m in range(m0, m0 + k):
+                self._t[m] += 1
+        self._n = 0 if last else self._n + k
+        self._step += 1 if last else 0
+
+    def finalize(self):
+        """-> dict of the outputs; the time statistics cover the steps folded with time=True."""
+        if self._step != self.Tk:
+            raise RuntimeError("%d of %d steps folded" % (self._step, self.Tk))
+        T = self._t[0]
+        if T < 1 or any(t != T for t in self._t) or len(self._timed) != T:
+            raise RuntimeError("no time statistics: no step was folded with time=True")
+        dev = self.mom.device
+        f32 = torch.float32
+        a = self.a.to(dev)                                                   # [B, C] fp64
+        n = torch.tensor(self.plan["N"], dtype=torch.float64, device=dev)    # [L]
+        w = self.w.to(dev)
+        S = self.S
+        o = {}
+        mom = self.mom.double()                                              # [Tk, 3, B, C, L, R]
+        sf = []
+        for q in (2, 3, 4):
+            v = (a ** q).view(1, self.B, self.C, 1, 1) * mom[:, q - 2] / n.view(1, 1, 1, -1, 1)
+            sf.append(v.permute(1, 0, 2, 3, 4).contiguous())                 # [B, Tk, C, L, R]
+            o["sf%d" % q] = sf[-1].to(f32)
+        mem = sf[0][..., :S]
+        mean = mem.mean(-1)
+        o["sf2_mean"] = mean.to(f32)
+        o["sf2_std"] = ((mem - mean.unsqueeze(-1)) ** 2).mean(-1).sqrt().to(f32)
+        vl = (w.view(1, 1, 1, -1) * a.view(1, self.B, self.C, 1) * self.vsum.double() / n.view(1, 1, 1, -1)).permute(1, 0, 2, 3).contiguous()
+        o["vario_lag"] = vl.to(f32)
+        o["vario_score"] = vl.sum(-1).to(f32)
+        tm = self.tmom.double()                                              # [3, B, C, L, R]
+        ts = [(a ** q).view(self.B, self.C, 1, 1) * tm[q - 2] / (T * n.view(1, 1, -1, 1)) for q in (2, 3, 4)]
+        for q in (2, 3, 4):
+            o["time_sf%d" % q] = ts[q - 2].to(f32)
+        nz = ts[0] != 0
+        den = torch.where(nz, ts[0], torch.ones_like(ts[0]))
+        o["time_skew"] = torch.where(nz, ts[1] / den ** 1.5, torch.zeros_like(den)).to(f32)
+        o["time_flat"] = torch.where(nz, ts[2] / den ** 2, torch.zeros_like(den)).to(f32)
+        tv = w.view(1, 1, -1) * a.view(self.B, self.C, 1) * self.tvar.double() / (T * n.view(1, 1, -1))
+        o["time_vario_lag"] = tv.to(f32)
+        o["time_vario_score"] = tv.sum(-1).to(f32)
+        o["lags"] = torch.tensor(self.lags, dtype=torch.int64).reshape(-1, 2)
+        o["lag_dist"] = self.lag_dist
+        return o
+
+
 def spectrum_bins(H_, W_, dx, dy):
     """The shell map of an H x W field on a grid of cell size dx along W, dy along H (fp64, host): signed mode numbers p' (p - H
     above H // 2), q' likewise, r = sqrt((p' Lmax / Ly)^2 + (q' Lmax / Lx)^2) with Lx = W dx, Ly = H dy, Lmax = max(Lx, Ly), shell

@@ -100,13 +100,15 @@ _TARGET_STATS = (("target_time_mean", "time_mean_mean"), ("target_time_rms", "ti
 
 
 def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, turbulence, spectra=False,
-                   window="hann", scores=False, tspec=None, quant=None, energy=None):
+                   window="hann", scores=False, tspec=None, quant=None, energy=None, structure=None):
     """The body of modelPredStats, modelPredTurbulence (turbulence: grid = (args.dx, args.dy)), modelPredSpectra (spectra: the same
     chunks also go through an EnsembleSpectrum with `window`), modelPredScores (scores: the same chunks also go through an
     EnsembleScores with the step's normalised target) and modelPredTimeSpectra (tspec = (nfreq, window, dt between kept steps): the
     chunks of the kept steps from t_start on also go through an EnsembleTimeSpectrum) and modelPredQuantiles (quant = (levels, exceed):
     the same chunks also go through an EnsembleQuantiles with the step's normalised target) and modelPredEnergy (energy = the channel
-    groups: the same chunks also go through an EnsembleEnergy with the step's normalised target): same seed draws in the same order, same
+    groups: the same chunks also go through an EnsembleEnergy with the step's normalised target) and modelPredStructure (structure =
+    (lags, weights): the same chunks also go through an EnsembleStructure with the step's normalised target and grid = (args.dx,
+    args.dy)): same seed draws in the same order, same
     folding, same re-anchoring, so that the keys they share hold identical values under the same host RNG state."""
     import tmg_ops as ops
     core = getattr(model, "module", model)
@@ -127,7 +129,7 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
     shp = (1, -1, 1, 1)
     in_std, in_mu = core.in_std.to(dev).view(shp), core.in_mu.to(dev).view(shp)
     out_std, out_mu = core.out_std.to(dev), core.out_mu.to(dev)
-    outs, targets, inputs = {}, [], []
+    outs, targets, inputs, sf_lags = {}, [], [], {}
     with torch.no_grad():
         for mbIdx, (input0, target0, u0) in enumerate(testing_loader):
             log.log('Running mini-batch {:d}/{:d}'.format(mbIdx + 1, len(testing_loader)))
@@ -140,7 +142,7 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
             B, C, Hh, Ww = inp.size(0), tgt.size(2), tgt.size(-2), tgt.size(-1)
             if C != 3:
                 raise ValueError("%s scales (ux, uy, p) by (u0, u0, u0^2) as modelPred does: 3 target channels, got %d" % (name, C))
-            if (scores or tspec is not None or quant is not None or energy is not None) and target0.size(1) <= (nkeep - 1) * stride:
+            if (scores or tspec is not None or quant is not None or energy is not None or structure is not None) and target0.size(1) <= (nkeep - 1) * stride:
                 raise ValueError("%s: the target series holds %d steps, kept step %d needs step %d"
                                  % (name, target0.size(1), nkeep - 1, (nkeep - 1) * stride))
             keys = []
@@ -162,7 +164,9 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
             qt = ops.EnsembleQuantiles(samples, B, C, Hh, Ww, nkeep, dev, out_mu, out_std, u=u.view(B, 3)[:, :C], levels=quant[0],
                                        exceed=quant[1]) if quant is not None else None
             en = ops.EnsembleEnergy(samples, B, C, Hh, Ww, nkeep, dev, out_std, u=u.view(B, 3)[:, :C], groups=energy) if energy is not None else None
-            tnorm = target0.to(dev) if scores or qt is not None or en is not None else None                # the normalised series; one step at a time goes channels-last
+            sfn = ops.EnsembleStructure(samples, B, C, Hh, Ww, nkeep, dev, out_std, u=u.view(B, 3)[:, :C], lags=structure[0],
+                                        weights=structure[1], grid=(args.dx, args.dy)) if structure is not None else None
+            tnorm = target0.to(dev) if scores or qt is not None or en is not None or sfn is not None else None                # the normalised series; one step at a time goes channels-last
             for tstep in range(tmax):
                 keep = tstep % stride == 0 and tstep // stride < nkeep
                 tj = tnorm[:, tstep].contiguous(memory_format=torch.channels_last) if keep and tnorm is not None else None
@@ -180,6 +184,8 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
                             qt.add(y0, m0, tj, time=tstep // stride >= t_start)
                         if en is not None:
                             en.add(y0, m0, tj, time=tstep // stride >= t_start)
+                        if sfn is not None:
+                            sfn.add(y0, m0, tj, time=tstep // stride >= t_start)
                     if tstep % 20 == 0:
                         states[ci] = [(0.5 * h + 0.5 * hk, 0.5 * c + 0.5 * ck) for (h, c), (hk, ck) in zip(states[ci], anchors[ci])]
             for key, t in st.finalize().items():
@@ -202,6 +208,12 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
             if en is not None:
                 for key, t in en.finalize().items():
                     outs.setdefault(key, []).append(t.cpu())
+            if sfn is not None:
+                for key, t in sfn.finalize().items():
+                    if key in ("lags", "lag_dist"):
+                        sf_lags[key] = t
+                    else:
+                        outs.setdefault(key, []).append(t.cpu())
             if tsp_t is not None:
                 for key, t in tsp_t.finalize().items():
                     if key == "psd_freq":
@@ -247,6 +259,7 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
         res["levels"] = q_levels
     if energy is not None:
         res["energy_groups"] = tuple(energy)
+    res.update(sf_lags)
     return res
 
 
@@ -423,3 +436,34 @@ def modelPredEnergy(args, model, testing_loader, log, samples=1, stride=1, tmax=
     groups = ops.energy_groups(groups, 3)
     return _ensembleStats("modelPredEnergy", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False,
                           energy=groups)
+
+
+def modelPredStructure(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, lags=None, weights=None):
+    """modelPredStats plus the structure functions of every member and of the target and the ensemble's variogram score, still without
+    forming modelPred's [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleStructure, grid = (args.dx, args.dy)).  This is the
+    dependence between neighbouring pixels of ONE member: permute the members independently at every pixel and every per-pixel score
+    (crps, rank_hist, quant) stays bit-identical, and the energy score barely moves; the increments D(p) = x(p + l) - x(p) at a pixel
+    lag l = (dx, dy) (dx along W, dy along H) see it.  The target of kept step j is series step j * stride; a series that is too short
+    raises.  Channel scales a = (u0, u0, u0^2) * out_std.  Same roll-outs as modelPredStats: under the same host RNG state the keys both
+    return are identical.
+
+    lags: up to 16 distinct (dx, dy) with dx >= 0, and dy > 0 when dx == 0, 0 <= dx <= 64, |dy| <= 64, dx < W, |dy| < H; None: (1, 0),
+    (2, 0), .. in powers of two up to min(32, W // 2), then the same along H.  weights: one positive finite w_l per lag, default 1.
+
+    Returns modelPredStats' dict plus (CPU tensors; L lags, S = samples, kept steps t_start..Tk-1 are the T timed ones, N_l the pairs
+    of lag l):
+      sf2, sf3, sf4 [N, Tk, C, L, S+1]  the structure functions <D^q> = a^q sum_p D^q / N_l of every member, the target's row last
+      sf2_mean, sf2_std [N, Tk, C, L]   mean and population std of sf2 over the members, target excluded
+      vario_lag [N, Tk, C, L]           w_l a sum_p (sqrt|D_target| - mean_m sqrt|D_m|)^2 / N_l: the variogram score of order 1/2
+                                        (Scheuerer & Hamill 2015) per lag, in physical units; lower is better
+      vario_score [N, Tk, C]            its sum over the lags
+      time_sf2, time_sf3, time_sf4 [N, C, L, S+1]   the same averages over the timed steps as well
+      time_skew, time_flat [N, C, L, S+1]           time_sf3 / time_sf2^1.5 and time_sf4 / time_sf2^2 (0 where time_sf2 == 0): the
+                                        increment skewness and flatness, the standard measures of intermittency (3 for Gaussian increments)
+      time_vario_lag [N, C, L], time_vario_score [N, C]   the means of vario_lag / vario_score over the timed steps
+      lags [L, 2] int64, lag_dist [L] float64       the lags and their lengths hypot(dx args.dx, dy args.dy)."""
+    if lags is not None:
+        import tmg_ops as ops
+        lags = ops.structure_lags(lags, 65, 65)                           # the rules that do not depend on the field; the field's come with it
+    return _ensembleStats("modelPredStructure", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False,
+                          structure=(lags, weights))
