@@ -1839,9 +1839,10 @@ static int c1_tile(int W, int H, int* twl) {
 // fill4 = 1: out points at channel 0 of a 16-byte aligned 4-channel pixel and (value,0,0,0) is stored
 // Both growth-1 layers in one launch (see c1x2_fwd_kernel).  dims: [B,H,W,Cin,relu_in,w_rows,w_split,w_gap,w2_d1_row];
 // add1_d / add2_d / out_d = [stride, off]; out receives (d1, d2, 0, 0) per pixel as one float4 (16-byte aligned, off 0).
-extern "C" int tmg_c1x2_fwd(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* w1, const void* w2,
-                            const void* add1, const int64_t* add1_d, const void* add2, const int64_t* add2_d, void* out,
-                            const int64_t* out_d, const int64_t* dims, hipStream_t st) {
+// Shared body of tmg_c1x2_fwd (plan == null: launches) and tmg_c1x2_fwd_plan.
+static int c1x2_fwd_impl(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* w1, const void* w2,
+                         const void* add1, const int64_t* add1_d, const void* add2, const int64_t* add2_d, void* out,
+                         const int64_t* out_d, const int64_t* dims, hipStream_t st, int64_t* plan) {
     C1X2P p;
     p.nseg = (int)nseg;
     p.vec4 = tmg_decode_in(p.in, in_ptrs, in_desc, nseg).vec4;
@@ -1859,9 +1860,10 @@ extern "C" int tmg_c1x2_fwd(const void* const* in_ptrs, const int64_t* in_desc, 
     c1_tile(p.Win, p.Hin, &p.TW_log2);
     // threads per pixel (see the kernel): by the number of 256-pixel tiles the image offers
     int CG = 1;
+    long t256;
     {
         const int tw = 1 << p.TW_log2, th = 256 >> p.TW_log2;
-        const long t256 = (long)p.B * ((p.Win + tw - 1) / tw) * ((p.Hin + th - 1) / th);
+        t256 = (long)p.B * ((p.Win + tw - 1) / tw) * ((p.Hin + th - 1) / th);
         const int Cq = (p.Cin + 3) / 4;
         // (measured at config M: 4 threads per pixel take the 64- and 128-channel levels from 19 / 32 us to 15; 2 per pixel on the
         // 1 024 tiles of the 32-channel level lose 5 us against one)
@@ -1879,6 +1881,12 @@ extern "C" int tmg_c1x2_fwd(const void* const* in_ptrs, const int64_t* in_desc, 
     size_t lds_floats = (size_t)(TH + 4) * (TW + 4) * (p.KCH + 4) + 18 * p.KCH;
     const size_t d1_floats = 2 * (size_t)(((TH + 2) * (TW + 2) + 3) & ~3);
     if (lds_floats < d1_floats) lds_floats = d1_floats;
+    if (plan) {
+        const int64_t v[12] = {CG, p.TW_log2, TH, p.tiles_x, p.tiles_y, t256, p.KCH, (Cpad + p.KCH - 1) / p.KCH, 2 * (TW + 2) + 2 * TH,
+                               (int64_t)p.B * p.tiles_x * p.tiles_y, (int64_t)(lds_floats * 4), p.vec4};
+        for (int i = 0; i < 12; ++i) plan[i] = v[i];
+        return 0;
+    }
     TmgProf prof(TMG_PROF_C1X2, 4.0 * p.B * (double)p.Hin * p.Win * (p.Cin + 4 + (p.add1 ? 1 : 0) + (p.add2 ? 1 : 0)), st);   // input once, D written
     const dim3 grid(p.B * p.tiles_x * p.tiles_y);
     if (CG == 1) {
@@ -1895,14 +1903,25 @@ extern "C" int tmg_c1x2_fwd(const void* const* in_ptrs, const int64_t* in_desc, 
     return 0;
 }
 
-extern "C" int tmg_c1_fwd(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* w, void* out,
-                          const int64_t* out_d, const int64_t* dims, hipStream_t st) {
-    return tmg_c1_fwd_add(in_ptrs, in_desc, nseg, w, nullptr, nullptr, out, out_d, dims, st);
+extern "C" int tmg_c1x2_fwd(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* w1, const void* w2,
+                            const void* add1, const int64_t* add1_d, const void* add2, const int64_t* add2_d, void* out,
+                            const int64_t* out_d, const int64_t* dims, hipStream_t st) {
+    return c1x2_fwd_impl(in_ptrs, in_desc, nseg, w1, w2, add1, add1_d, add2, add2_d, out, out_d, dims, st, nullptr);
 }
 
-// As tmg_c1_fwd plus a per-pixel scalar `add` ({stride, off}) summed onto the result.
-extern "C" int tmg_c1_fwd_add(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* w, const void* add,
-                              const int64_t* add_d, void* out, const int64_t* out_d, const int64_t* dims, hipStream_t st) {
+// The launch plan of tmg_c1x2_fwd for these arguments: nothing is launched, no pointer is dereferenced.
+// plan: {CG, TW_log2, TH, tiles_x, tiles_y, t256, KCH, nchunks, nring, grid, lds_bytes, vec4}
+extern "C" int tmg_c1x2_fwd_plan(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* w1, const void* w2,
+                                 const void* add1, const int64_t* add1_d, const void* add2, const int64_t* add2_d, void* out,
+                                 const int64_t* out_d, const int64_t* dims, hipStream_t st, int64_t* plan) {
+    if (!plan) return -1;
+    for (int i = 0; i < 12; ++i) plan[i] = -1;
+    return c1x2_fwd_impl(in_ptrs, in_desc, nseg, w1, w2, add1, add1_d, add2, add2_d, out, out_d, dims, st, plan);
+}
+
+// Shared body of tmg_c1_fwd_add (plan == null: launches) and tmg_c1_fwd_plan.
+static int c1_fwd_impl(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* w, const void* add,
+                       const int64_t* add_d, void* out, const int64_t* out_d, const int64_t* dims, hipStream_t st, int64_t* plan) {
     C1P p;
     p.nseg = (int)nseg;
     p.vec4 = tmg_decode_in(p.in, in_ptrs, in_desc, nseg).vec4;
@@ -1922,10 +1941,36 @@ extern "C" int tmg_c1_fwd_add(const void* const* in_ptrs, const int64_t* in_desc
     const int Cpad = (p.Cin + 3) & ~3;
     p.KCH = Cpad < 32 ? Cpad : 32;
     const size_t lds_bytes = ((size_t)(TH + 2) * (TW + 2) * (p.KCH + 4) + 9 * p.KCH) * 4;
+    if (plan) {
+        const int64_t v[9] = {p.TW_log2, TH, p.tiles_x, p.tiles_y, p.KCH, (Cpad + p.KCH - 1) / p.KCH, (int64_t)p.B * p.tiles_x * p.tiles_y,
+                              (int64_t)lds_bytes, p.vec4};
+        for (int i = 0; i < 9; ++i) plan[i] = v[i];
+        return 0;
+    }
     TMG_LDS_OPTIN((&c1_fwd_kernel));
     hipLaunchKernelGGL(c1_fwd_kernel, dim3(p.B * p.tiles_x * p.tiles_y), dim3(256), lds_bytes, st, p);
     TMG_CHECK_LAUNCH();
     return 0;
+}
+
+// As tmg_c1_fwd plus a per-pixel scalar `add` ({stride, off}) summed onto the result.
+extern "C" int tmg_c1_fwd_add(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* w, const void* add,
+                              const int64_t* add_d, void* out, const int64_t* out_d, const int64_t* dims, hipStream_t st) {
+    return c1_fwd_impl(in_ptrs, in_desc, nseg, w, add, add_d, out, out_d, dims, st, nullptr);
+}
+
+extern "C" int tmg_c1_fwd(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* w, void* out,
+                          const int64_t* out_d, const int64_t* dims, hipStream_t st) {
+    return c1_fwd_impl(in_ptrs, in_desc, nseg, w, nullptr, nullptr, out, out_d, dims, st, nullptr);
+}
+
+// The launch plan of tmg_c1_fwd_add for these arguments: nothing is launched, no pointer is dereferenced.
+// plan: {TW_log2, TH, tiles_x, tiles_y, KCH, nchunks, grid, lds_bytes, vec4}
+extern "C" int tmg_c1_fwd_plan(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* w, const void* add,
+                               const int64_t* add_d, void* out, const int64_t* out_d, const int64_t* dims, hipStream_t st, int64_t* plan) {
+    if (!plan) return -1;
+    for (int i = 0; i < 9; ++i) plan[i] = -1;
+    return c1_fwd_impl(in_ptrs, in_desc, nseg, w, add, add_d, out, out_d, dims, st, plan);
 }
 
 // dims: [B,H,W,Cin,relu_in]; dd_d/dref_d = [stride, off]; g segments accumulate (+=); dW accumulates atomically

@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256) void wgrad_thin_kernel(ThinP p) {
 }
 
 template <int SL, int CS, int TH>
-static int launch_thin(ThinP p, int G, hipStream_t st) {
+static int launch_thin(ThinP p, int G, hipStream_t st, int64_t* plan) {
     constexpr int lds_bytes = ((TH + 2) * 19 * CS + TH * 64) * 4;
     p.tiles_x = (p.W + 15) / 16;
     p.tiles_y = (p.H + TH - 1) / TH;
@@ -155,6 +155,11 @@ static int launch_thin(ThinP p, int G, hipStream_t st) {
     if (P >= 8) P &= ~7;
     p.G = G; p.P = P;
     static_assert(lds_bytes <= 64 * 1024, "above 64 KB the kernel would need the per-device LDS opt-in (TMG_LDS_OPTIN)");
+    if (plan) {
+        const int64_t v[11] = {SL, CS, TH, p.dyc, p.tiles_x, p.tiles_y, p.ntiles, P, (P & 7) == 0, (int64_t)P * G, lds_bytes};
+        for (int i = 0; i < 11; ++i) plan[i] = v[i];
+        return 0;
+    }
     hipLaunchKernelGGL((wgrad_thin_kernel<SL, CS, TH>), dim3(P * G), dim3(256), lds_bytes, st, p);
     TMG_CHECK_LAUNCH();
     return 0;
@@ -164,8 +169,8 @@ static int launch_thin(ThinP p, int G, hipStream_t st) {
 // shared tensor, group g at channels [4 g, 4 g + 4)).  dims = {B, H, W, Cin, relu_in}.  dW [G][4][Cin][3][3] is ACCUMULATED into
 // (float atomics: zero it first).  Supported: Cin in {12, 20, 36, 68} (channel halves 8 / 16 / 32 / 64 plus the 4 growth channels),
 // every segment a multiple of 4 channels with 16-byte aligned pixels; otherwise -100 (nothing launched; use tmg_conv_wgrad_grouped).
-extern "C" int tmg_conv_wgrad_thin_grouped(const void* gtab, int64_t G, const int64_t* seg_channels, int64_t nseg, const void* dy,
-                                           int64_t dy_stride, void* dW, const int64_t* dims, hipStream_t st) {
+static int thin_impl(const void* gtab, int64_t G, const int64_t* seg_channels, int64_t nseg, const void* dy, int64_t dy_stride, void* dW,
+                     const int64_t* dims, hipStream_t st, int64_t* plan) {
     ThinP p;
     p.gtab = (const long long*)gtab; p.dy = (const float*)dy; p.dys = (int)dy_stride; p.dW = (float*)dW;
     p.B = (int)dims[0]; p.H = (int)dims[1]; p.W = (int)dims[2]; p.relu_in = (int)dims[4];
@@ -175,12 +180,26 @@ extern "C" int tmg_conv_wgrad_thin_grouped(const void* gtab, int64_t G, const in
     for (int i = 0; i < nseg; ++i)
         if (seg_channels[i] & 3) return -100;
     switch (Cin) {
-        case 12: return launch_thin<2, 12, 16>(p, (int)G, st);
-        case 20: return launch_thin<3, 20, 16>(p, (int)G, st);
-        case 36: return launch_thin<6, 36, 16>(p, (int)G, st);
-        case 68: return launch_thin<10, 68, 8>(p, (int)G, st);
+        case 12: return launch_thin<2, 12, 16>(p, (int)G, st, plan);
+        case 20: return launch_thin<3, 20, 16>(p, (int)G, st, plan);
+        case 36: return launch_thin<6, 36, 16>(p, (int)G, st, plan);
+        case 68: return launch_thin<10, 68, 8>(p, (int)G, st, plan);
         default: return -100;
     }
+}
+
+extern "C" int tmg_conv_wgrad_thin_grouped(const void* gtab, int64_t G, const int64_t* seg_channels, int64_t nseg, const void* dy,
+                                           int64_t dy_stride, void* dW, const int64_t* dims, hipStream_t st) {
+    return thin_impl(gtab, G, seg_channels, nseg, dy, dy_stride, dW, dims, st, nullptr);
+}
+
+// The launch plan of tmg_conv_wgrad_thin_grouped for these arguments: nothing is launched, no pointer is dereferenced.
+// plan: {SL, CS, TH, dyc, tiles_x, tiles_y, ntiles, P, xcd (P % 8 == 0: the XCD-aware block order), grid, lds_bytes}
+extern "C" int tmg_conv_wgrad_thin_grouped_plan(const void* gtab, int64_t G, const int64_t* seg_channels, int64_t nseg, const void* dy,
+                                                int64_t dy_stride, void* dW, const int64_t* dims, hipStream_t st, int64_t* plan) {
+    if (!plan) return -1;
+    for (int i = 0; i < 11; ++i) plan[i] = -1;
+    return thin_impl(gtab, G, seg_channels, nseg, dy, dy_stride, dW, dims, st, plan);
 }
 
 // =================================================================================================================================
@@ -299,7 +318,7 @@ __global__ __launch_bounds__(256) void mix_wgrad_kernel(MixWgP p) {
 // gtab as for tmg_conv_wgrad_grouped with every group's own upstream gradient (row entries 12 / 13: pointer, pixel stride); all
 // tensors pixel-linear NHWC (address = pointer + pixel * stride + channel).  dims = {npix, C}.  dW [G][C][C] and db [G][C] (nullable) are
 // ACCUMULATED into (zero them first).  C in {16, 32} (the levels whose mixes are bandwidth kernels); otherwise -100 (nothing launched).
-extern "C" int tmg_mix_wgrad_grouped(const void* gtab, int64_t G, void* dW, void* db, const int64_t* dims, hipStream_t st) {
+static int mix_wgrad_impl(const void* gtab, int64_t G, void* dW, void* db, const int64_t* dims, hipStream_t st, int64_t* plan) {
     MixWgP p;
     p.gtab = (const long long*)gtab; p.dW = (float*)dW; p.db = (float*)db; p.npix = dims[0]; p.C = (int)dims[1]; p.G = (int)G;
     if (G < 1 || !gtab || p.npix < 1) return -100;
@@ -310,10 +329,28 @@ extern "C" int tmg_mix_wgrad_grouped(const void* gtab, int64_t G, void* dW, void
     if (P > maxp) P = maxp;
     if (P < 1) P = 1;
     p.P = (int)P;
+    if (plan) {
+        const int64_t CT = p.C / 16, U = CT == 2 ? 4 : 8;
+        const int64_t v[5] = {CT, U, P, ((p.npix + P - 1) / P + 16 * U - 1) / (16 * U) * (16 * U), P * G};   // per: as in the kernel
+        for (int i = 0; i < 5; ++i) plan[i] = v[i];
+        return 0;
+    }
     if (p.C == 16) hipLaunchKernelGGL(mix_wgrad_kernel<1>, dim3((unsigned)(P * G)), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(mix_wgrad_kernel<2>, dim3((unsigned)(P * G)), dim3(256), 0, st, p);
     TMG_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int tmg_mix_wgrad_grouped(const void* gtab, int64_t G, void* dW, void* db, const int64_t* dims, hipStream_t st) {
+    return mix_wgrad_impl(gtab, G, dW, db, dims, st, nullptr);
+}
+
+// The launch plan of tmg_mix_wgrad_grouped for these arguments: nothing is launched, no pointer is dereferenced.
+// plan: {CT (16-channel tiles per side), U (pixel quads in flight per wave), P, per (pixels per partition), grid}
+extern "C" int tmg_mix_wgrad_grouped_plan(const void* gtab, int64_t G, void* dW, void* db, const int64_t* dims, hipStream_t st, int64_t* plan) {
+    if (!plan) return -1;
+    for (int i = 0; i < 5; ++i) plan[i] = -1;
+    return mix_wgrad_impl(gtab, G, dW, db, dims, st, plan);
 }
 
 // =================================================================================================================================
@@ -344,11 +381,14 @@ __global__ __launch_bounds__(256) void layer_planes_kernel(const float* __restri
     }
 }
 
-// src [npix][CP] contiguous (CP a multiple of 4), dst [CP / 2][npix][2].
+// src [npix][CP] contiguous (CP a multiple of 4, 4 <= CP <= 512; from CP = 256 on the staging rows need the LDS opt-in), dst [CP / 2][npix][2];
+// -1 otherwise (nothing launched).
 extern "C" int tmg_layer_planes(const void* src, void* dst, int64_t npix, int64_t CP, hipStream_t st) {
     if (npix < 1 || CP < 4 || (CP & 3) || CP > 512) return -1;
     const long long blocks = (npix + 63) / 64;
-    hipLaunchKernelGGL(layer_planes_kernel, dim3((unsigned)blocks), dim3(256), (size_t)64 * (CP + 2) * 4, st, (const float*)src, (float*)dst,
+    const size_t lds_bytes = (size_t)64 * (CP + 2) * 4;     // CP = 512: 131 584 bytes
+    if (lds_bytes > 64 * 1024) TMG_LDS_OPTIN((&layer_planes_kernel));
+    hipLaunchKernelGGL(layer_planes_kernel, dim3((unsigned)blocks), dim3(256), lds_bytes, st, (const float*)src, (float*)dst,
                        (long long)npix, (int)CP);
     TMG_CHECK_LAUNCH();
     return 0;

@@ -44,10 +44,12 @@ EXPORTS = [
     "tmg_ens_score_store", "tmg_ens_score_step",
 ]
 # Launch-plan queries of the convolution launchers, direct (conv_fwd_plan / conv_wgrad_plan / conv_rep_border_plan below) and Winograd
-# (conv_wino_fwd_plan / conv_wino_fwd3_plan / conv_wino_narrow_plan / conv_wino_wgrad_plan): they launch nothing, so they are listed apart
-# from the operations above.
+# (conv_wino_fwd_plan / conv_wino_fwd3_plan / conv_wino_narrow_plan / conv_wino_wgrad_plan), and of the growth-layer forwards and the thin /
+# mix weight gradients (c1x2_fwd_plan / c1_fwd_plan / conv_wgrad_thin_grouped_plan / mix_wgrad_grouped_plan): they launch nothing, so
+# they are listed apart from the operations above.
 PLAN_EXPORTS = ["tmg_conv_fwd_plan", "tmg_conv_wgrad_plan", "tmg_conv_rep_border_plan", "tmg_conv_wino_fwd_plan", "tmg_conv_wino_fwd3_plan",
-                "tmg_conv_wino_narrow_plan", "tmg_conv_wino_wgrad_plan"]
+                "tmg_conv_wino_narrow_plan", "tmg_conv_wino_wgrad_plan", "tmg_c1x2_fwd_plan", "tmg_c1_fwd_plan",
+                "tmg_conv_wgrad_thin_grouped_plan", "tmg_mix_wgrad_grouped_plan"]
 # The temporal power spectra (csrc/tmg_tspec.hip), declared in include/tmglow_hip_tspec.h: tspec_store / tspec_block / tspec_finalize below.
 TSPEC_EXPORTS = ["tmg_tspec_store", "tmg_tspec_block", "tmg_tspec_finalize"]
 # The prediction intervals (csrc/tmg_quant.hip), declared in include/tmglow_hip_quant.h: ens_quant_step below.
@@ -595,6 +597,64 @@ def _pixel_linear(t):
     return t.stride(3) == 1 and (Hh == 1 or t.stride(1) == t.stride(2) * Ww) and (B == 1 or t.stride(0) == t.stride(2) * Ww * Hh)
 
 
+def _group_rows(group_inputs, group_dy=None):
+    """Rows of the grouped launches' device table: per group 3 input segments {pointer incl. the view's channel offset, pixel stride, 0,
+    channels} (unused ones zero), then the group's own upstream gradient {pointer, pixel stride, pointer 2, pixel stride 2}: zeros
+    without one, the second pair zero for ONE tensor, both filled for a (half 1, half 2) pair."""
+    first = group_inputs[0]
+    n_in = len(first)
+    dy_pairs = group_dy is not None and isinstance(group_dy[0], (tuple, list))
+    rows = []
+    for segs in group_inputs:
+        # same shapes in every group; the pixel strides may differ (a group's row of the device table carries its own: the first and
+        # last layer of a level's node address channel-slice views of [.., C] tensors, the others [.., C/2] tensors of their own)
+        assert len(segs) == n_in and all(a.shape == b.shape and a.stride(2) % 4 == b.stride(2) % 4 for a, b in zip(segs, first))
+        row = []
+        for t in segs:
+            row += list(seg(t))  # (pointer incl. the view's channel offset, pixel stride, 0, channels)
+        row += [0, 0, 0, 0] * (3 - n_in)
+        if group_dy is None:
+            row += [0, 0, 0, 0]
+        elif dy_pairs:
+            a, b = group_dy[len(rows)]
+            row += [seg(a)[0], seg(a)[1], seg(b)[0], seg(b)[1]]
+        else:
+            row += [seg(group_dy[len(rows)])[0], seg(group_dy[len(rows)])[1], 0, 0]
+        rows.append(row)
+    return rows
+
+
+def conv_wgrad_thin_grouped(group_inputs, dy, dy_group_channels, dW, relu_in=False, gtab=None):
+    """The thin grouped 3x3 weight gradient (tmg_conv_wgrad_thin_grouped) called directly: group_inputs[g] a list of <= 3 NHWC
+    segments, dy the shared upstream gradient with dy_group_channels (4 or 2) channels per group, dW [G, 4, Cin, 3, 3] accumulated
+    into.  Returns the library's code: 0 launched, -100 outside the kernel's envelope (nothing launched)."""
+    first = group_inputs[0]
+    B, Hin, Win, _ = first[0].shape
+    # the part of the envelope the library cannot see (the segments' addresses live in the device table): float4-addressable pixels
+    if not all(t.stride(2) % 4 == 0 and t.data_ptr() % 16 == 0 for segs in group_inputs for t in segs):
+        return -100
+    if gtab is None:
+        gtab = _segment_table(_group_rows(group_inputs), dy.device)
+    return lib().tmg_conv_wgrad_thin_grouped(_ptr(gtab), c_i64(len(group_inputs)), _i64(*[t.shape[3] for t in first]), c_i64(len(first)),
+                                             _ptr(dy), c_i64(dy.stride(2)), _ptr(dW),
+                                             _i64(B, Hin, Win, sum(t.shape[3] for t in first), relu_in, int(dy_group_channels)), _stream())
+
+
+def mix_wgrad_grouped(group_inputs, group_dy, dW, dbias, gtab=None):
+    """The streaming weight gradient of the 1x1 mixes (tmg_mix_wgrad_grouped) called directly: group_dy[g] one [B,H,W,C] tensor or a
+    (half 1, half 2) pair per group; dW [G, C, C] and dbias [G, C] (or None) accumulated into.  Returns the library's code: 0 launched,
+    -100 outside the kernel's envelope (nothing launched)."""
+    first = group_inputs[0]
+    B, Hin, Win, _ = first[0].shape
+    pairs = isinstance(group_dy[0], (tuple, list))
+    assert all(_pixel_linear(t) for segs in group_inputs for t in segs)
+    assert all(_pixel_linear(t) for e in group_dy for t in (e if pairs else (e,)))
+    if gtab is None:
+        gtab = _segment_table(_group_rows(group_inputs, group_dy), dW.device)
+    return lib().tmg_mix_wgrad_grouped(_ptr(gtab), c_i64(len(group_inputs)), _ptr(dW), _ptr(dbias),
+                                       _i64(B * Hin * Win, sum(t.shape[3] for t in first)), _stream())
+
+
 def conv_wgrad_grouped(group_inputs, dy, dy_group_channels, dW, dbias, ksize, stride, relu_in=False, pad_rep=False, cin_dst=0,
                        cin_valid=0, ci_split=0, ci_off0=0, ci_off1=0, group_dy=None):
     """One launch for len(group_inputs) identically shaped weight gradients.  group_inputs[g]: list of <= 3 NHWC segments;
@@ -620,24 +680,7 @@ def conv_wgrad_grouped(group_inputs, dy, dy_group_channels, dW, dbias, ksize, st
     Cg = int(dy_group_channels)
     ip, idesc, n_in = _segs(first)
     Cin = sum(t.shape[3] for t in first)
-    rows = []
-    for segs in group_inputs:
-        # same shapes in every group; the pixel strides may differ (a group's row of the device table carries its own: the first and
-        # last layer of a level's node address channel-slice views of [.., C] tensors, the others [.., C/2] tensors of their own)
-        assert len(segs) == n_in and all(a.shape == b.shape and a.stride(2) % 4 == b.stride(2) % 4 for a, b in zip(segs, first))
-        row = []
-        for t in segs:
-            row += list(seg(t))  # (pointer incl. the view's channel offset, pixel stride, 0, channels)
-        row += [0, 0, 0, 0] * (3 - n_in)
-        if group_dy is None:
-            row += [0, 0, 0, 0]
-        elif dy_pairs:
-            a, b = group_dy[len(rows)]
-            row += [seg(a)[0], seg(a)[1], seg(b)[0], seg(b)[1]]
-        else:
-            row += [seg(group_dy[len(rows)])[0], seg(group_dy[len(rows)])[1], 0, 0]
-        rows.append(row)
-    gtab = _segment_table(rows, dy.device)
+    gtab = _segment_table(_group_rows(group_inputs, group_dy), dy.device)
     if group_dy is None and ksize == 3 and stride == 1 and Cin >= 20 and Cg >= 32:
         # the wide levels' per-layer zero-conv weight gradients: Winograd F(3x3, 2x2), all layers of the level in one launch
         wd = _i64(B, Hin, Win, Cin, Cg, relu_in, pad_rep, cin_dst, cin_valid, ci_split, ci_off0, ci_off1)
@@ -654,7 +697,7 @@ def conv_wgrad_grouped(group_inputs, dy, dy_group_channels, dW, dbias, ksize, st
             and all(_pixel_linear(t) for segs in group_inputs for t in segs)
             and all(_pixel_linear(t) for e in group_dy for t in (e if dy_pairs else (e,)))):
         # the 1x1 mixes' weight gradients: streaming GEMM over the pixels, operands straight from global memory
-        rc = lib().tmg_mix_wgrad_grouped(_ptr(gtab), c_i64(G), _ptr(dW), _ptr(dbias), _i64(B * Hin * Win, Cin), _stream())
+        rc = mix_wgrad_grouped(group_inputs, group_dy, dW, dbias, gtab=gtab)
         if _launched(rc, "tmg_mix_wgrad_grouped"):
             return True
     if dy_pairs:    # outside the streaming kernel's envelope after all: the general kernels read one tensor per group
@@ -666,8 +709,7 @@ def conv_wgrad_grouped(group_inputs, dy, dy_group_channels, dW, dbias, ksize, st
             and all(t.stride(2) % 4 == 0 and t.data_ptr() % 16 == 0 for segs in group_inputs for t in segs)):
         # four output rows per group (the growth-1 layers; dy: (dd1, dd2, 0, 0) quads or compact (dd1, dd2) pairs): 4x4x1 MFMA blocks
         # instead of 16x16 tiles that would be 2/16 used
-        rc = lib().tmg_conv_wgrad_thin_grouped(_ptr(gtab), c_i64(G), _i64(*[t.shape[3] for t in first]), c_i64(n_in), _ptr(dy),
-                                               c_i64(dy.stride(2)), _ptr(dW), _i64(B, Hin, Win, Cin, relu_in, Cg), _stream())
+        rc = conv_wgrad_thin_grouped(group_inputs, dy, Cg, dW, relu_in=relu_in, gtab=gtab)
         if _launched(rc, "tmg_conv_wgrad_thin_grouped"):
             return True
     dims = _i64(B, Hin, Win, Hout, Wout, ksize, stride, Cin, Cg, relu_in, pad_rep, cin_dst, cin_valid, ci_split, ci_off0, ci_off1)
@@ -810,7 +852,8 @@ def conv_rep_border_fix(dy, w, outs, kappa=None):
                                        _stream()), "tmg_conv_rep_border_fix")
 
 
-# Launch-plan queries (tmg_conv_fwd_plan / tmg_conv_wgrad_plan / tmg_conv_rep_border_plan, tmg_conv_wino_*_plan): which kernel instance, tiling and grid the
+# Launch-plan queries (tmg_conv_fwd_plan / tmg_conv_wgrad_plan / tmg_conv_rep_border_plan, tmg_conv_wino_*_plan, tmg_c1x2_fwd_plan / tmg_c1_fwd_plan /
+# tmg_conv_wgrad_thin_grouped_plan / tmg_mix_wgrad_grouped_plan): which kernel instance, tiling and grid the
 # launcher would use.  Nothing is launched and no pointer is dereferenced, so they run without a device.  An activation is a tensor (as
 # in the launching wrappers) or a descriptor ((B, H, W), address, pixel stride, channels) standing for one; an optional operand that
 # only has to be present or absent (bias, kappa, in_scale, ws, dbias) may be any true value.
@@ -827,7 +870,15 @@ PLAN_ARGTYPES = {
     "tmg_conv_wino_fwd3_plan": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],
     "tmg_conv_wino_narrow_plan": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],
     "tmg_conv_wino_wgrad_plan": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp],
+    "tmg_c1x2_fwd_plan": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "tmg_c1_fwd_plan": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "tmg_conv_wgrad_thin_grouped_plan": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp],
+    "tmg_mix_wgrad_grouped_plan": [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
 }
+C1X2_PLAN_FIELDS = ("CG", "TW_log2", "TH", "tiles_x", "tiles_y", "t256", "KCH", "nchunks", "nring", "grid", "lds_bytes", "vec4")
+C1_PLAN_FIELDS = ("TW_log2", "TH", "tiles_x", "tiles_y", "KCH", "nchunks", "grid", "lds_bytes", "vec4")
+THIN_PLAN_FIELDS = ("SL", "CS", "TH", "dyc", "tiles_x", "tiles_y", "ntiles", "P", "xcd", "grid", "lds_bytes")
+MIX_WGRAD_PLAN_FIELDS = ("CT", "U", "P", "per", "grid")
 WINO_FWD_PLAN_FIELDS = ("kernel", "NPW", "Cin_pad", "nchunks", "last_groups", "ntt", "tiles_x", "tiles_y", "ntiles", "grid_x", "grid_y",
                         "max_tiles", "lds_bytes")
 WINO_KERNELS = ("wino_fwd_kernel", "wino_fwdp_kernel", "wino_fwd3_kernel", "wino_nn_kernel")     # plan field "kernel"
@@ -942,6 +993,41 @@ def conv_wino_wgrad_plan(inputs, dy, dbias=None, relu_in=False, pad_rep=False, c
     need = lib().tmg_conv_wino_wgrad_grouped_ws_floats(wd, c_i64(ngroups)) if ngroups > 1 else lib().tmg_conv_wino_wgrad_ws_floats(wd)
     return _plan_call("tmg_conv_wino_wgrad_plan", WINO_WGRAD_PLAN_FIELDS, ip, idesc, n_in, c_vp(dyp), _i64(dys, 0), c_vp(16), _pp(dbias),
                       c_vp(16 if use_ws else 0), c_i64(need if use_ws else 0), wd, None, c_i64(ngroups))
+
+
+def c1x2_fwd_plan(inputs, out, add1=None, add2=None, w_rows=0, w2_d1_row=0, w_split=0, w_gap=0, relu_in=True):
+    """The launch plan of c1x2_fwd with these arguments: a dict of C1X2_PLAN_FIELDS plus "rc"."""
+    ip, idesc, n_in, di = _psegs(inputs)
+    (B, Hh, Ww) = di[0][0]
+    Cin = sum(x[3] for x in di)
+    _, op, ostr, _ = _pseg(out)
+    d2 = lambda t: _i64(_pseg(t)[2], 0) if t is not None else _i64(0, 0)      # noqa: E731
+    return _plan_call("tmg_c1x2_fwd_plan", C1X2_PLAN_FIELDS, ip, idesc, n_in, c_vp(16), c_vp(16), _pp(add1), d2(add1), _pp(add2), d2(add2),
+                      c_vp(op), _i64(ostr, 0), _i64(B, Hh, Ww, Cin, relu_in, w_rows, w_split, w_gap, w2_d1_row), None)
+
+
+def c1_fwd_plan(inputs, out, add=None, w_rows=0, fill4=False, w_split=0, w_gap=0, relu_in=True):
+    """The launch plan of c1_fwd with these arguments: a dict of C1_PLAN_FIELDS plus "rc"."""
+    ip, idesc, n_in, di = _psegs(inputs)
+    (B, Hh, Ww) = di[0][0]
+    Cin = sum(x[3] for x in di)
+    _, op, ostr, _ = _pseg(out)
+    ad = _i64(_pseg(add)[2], 0) if add is not None else _i64(0, 0)
+    return _plan_call("tmg_c1_fwd_plan", C1_PLAN_FIELDS, ip, idesc, n_in, c_vp(16), _pp(add), ad, c_vp(op), _i64(ostr, 0),
+                      _i64(B, Hh, Ww, Cin, relu_in, w_rows, fill4, w_split, w_gap), None)
+
+
+def conv_wgrad_thin_grouped_plan(shape3, seg_channels, G, dy_addr, dy_stride, dyc, relu_in=True):
+    """The launch plan of conv_wgrad_thin_grouped: G groups of inputs [B, H, W, sum(seg_channels)] (shape3 = (B, H, W)), the shared
+    dy at address dy_addr with pixel stride dy_stride and dyc channels per group: a dict of THIN_PLAN_FIELDS plus "rc" (-100: declined)."""
+    B, Hh, Ww = shape3
+    return _plan_call("tmg_conv_wgrad_thin_grouped_plan", THIN_PLAN_FIELDS, c_vp(16), c_i64(G), _i64(*seg_channels), c_i64(len(seg_channels)),
+                      c_vp(int(dy_addr)), c_i64(dy_stride), c_vp(16), _i64(B, Hh, Ww, sum(seg_channels), relu_in, dyc), None)
+
+
+def mix_wgrad_grouped_plan(npix, C, G, db=True):
+    """The launch plan of mix_wgrad_grouped for G groups of npix pixels and C channels: a dict of MIX_WGRAD_PLAN_FIELDS plus "rc"."""
+    return _plan_call("tmg_mix_wgrad_grouped_plan", MIX_WGRAD_PLAN_FIELDS, c_vp(16), c_i64(G), c_vp(16), _pp(db), _i64(npix, C), None)
 
 
 def conv_dgrad_direct(dy, w, dx, ksize, stride, accumulate=False):

@@ -371,7 +371,8 @@ int tmg_mix_wgrad_grouped(const void* gtab, int64_t G, void* dW, void* db, const
 
 /* [npix][CP] -> [CP/2][npix][2]: the level-wide conditioning addends of the growth-1 convs (channel 2k / 2k+1 = coupling layer k,
  * flowAffine.py:73-75 with the conditioning part of the dense block's input split off) as one pixel-contiguous float2 plane per layer, so
- * that each layer's launch reads 8 bytes per pixel instead of a whole line of the interleaved tensor.  CP a multiple of 4. */
+ * that each layer's launch reads 8 bytes per pixel instead of a whole line of the interleaved tensor.  CP a multiple of 4, 4 <= CP <= 512
+ * (64 (CP + 2) floats of LDS: above 64 KB, i.e. from CP = 256 on, the launcher opts the kernel in); -1 otherwise, nothing launched. */
 int tmg_layer_planes(const void* src, void* dst, int64_t npix, int64_t CP, tmg_stream_t st);
 
 /* Parameter-gradient epilogue of a level's NL plain coupling layers, one launch: d(kappa_k) = (<Wz_k, dWz_k> + <bz_k, dBz_k>) inside the

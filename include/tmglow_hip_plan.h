@@ -1,4 +1,4 @@
-/* Launch-plan queries of libtmglow_hip.so's convolution launchers, direct and Winograd.  Included by tmglow_hip.h (which defines tmg_stream_t): do not
+/* Launch-plan queries of libtmglow_hip.so's convolution launchers, direct and Winograd, and of the growth-layer forwards and the thin / mix weight gradients.  Included by tmglow_hip.h (which defines tmg_stream_t): do not
  * include it on its own.  The operations are declared in tmglow_hip.h; these entry points compute nothing. */
 #ifndef TMGLOW_HIP_PLAN_H
 #define TMGLOW_HIP_PLAN_H
@@ -39,5 +39,21 @@ int tmg_conv_wino_narrow_plan(const void* const* in_ptrs, const int64_t* in_desc
 int tmg_conv_wino_wgrad_plan(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* dy, const int64_t* dy_desc,
                              void* dW, void* dbias, void* ws, int64_t ws_floats, const int64_t* dims, tmg_stream_t st, int64_t ngroups,
                              int64_t* plan);
+
+/* The same for the growth-layer forwards (tmg_pointwise.hip) and the thin / mix weight gradients (tmg_thin.hip):
+ *   tmg_c1x2_fwd_plan: plan[12] = {CG (threads per pixel), TW_log2, TH, tiles_x, tiles_y, t256 (256-pixel tiles, which select CG), KCH,
+ *     nchunks, nring (ring pixels of a tile's d1 region), grid, lds_bytes, vec4}
+ *   tmg_c1_fwd_plan (the plan of tmg_c1_fwd_add): plan[9] = {TW_log2, TH, tiles_x, tiles_y, KCH, nchunks, grid, lds_bytes, vec4}
+ *   tmg_conv_wgrad_thin_grouped_plan: plan[11] = {SL, CS, TH, dyc, tiles_x, tiles_y, ntiles, P, xcd (P % 8 == 0: the XCD-aware block
+ *     order), grid, lds_bytes}
+ *   tmg_mix_wgrad_grouped_plan: plan[5] = {CT, U, P, per (pixels per partition), grid} */
+int tmg_c1x2_fwd_plan(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* w1, const void* w2, const void* add1,
+                      const int64_t* add1_d, const void* add2, const int64_t* add2_d, void* out, const int64_t* out_d, const int64_t* dims,
+                      tmg_stream_t st, int64_t* plan);
+int tmg_c1_fwd_plan(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* w, const void* add,
+                    const int64_t* add_d, void* out, const int64_t* out_d, const int64_t* dims, tmg_stream_t st, int64_t* plan);
+int tmg_conv_wgrad_thin_grouped_plan(const void* gtab, int64_t G, const int64_t* seg_channels, int64_t nseg, const void* dy,
+                                     int64_t dy_stride, void* dW, const int64_t* dims, tmg_stream_t st, int64_t* plan);
+int tmg_mix_wgrad_grouped_plan(const void* gtab, int64_t G, void* dW, void* db, const int64_t* dims, tmg_stream_t st, int64_t* plan);
 
 #endif

@@ -55,6 +55,10 @@ def _header_params(name):
     ("tmg_conv_fwd_plan", "tmg_conv_fwd_add", ["int64_t *"]),
     ("tmg_conv_wgrad_plan", "tmg_conv_wgrad", ["int64_t", "int64_t *"]),
     ("tmg_conv_rep_border_plan", "tmg_conv_rep_border_fix", ["int64_t *"]),
+    ("tmg_c1x2_fwd_plan", "tmg_c1x2_fwd", ["int64_t *"]),
+    ("tmg_c1_fwd_plan", "tmg_c1_fwd_add", ["int64_t *"]),
+    ("tmg_conv_wgrad_thin_grouped_plan", "tmg_conv_wgrad_thin_grouped", ["int64_t *"]),
+    ("tmg_mix_wgrad_grouped_plan", "tmg_mix_wgrad_grouped", ["int64_t *"]),
 ])
 def test_plan_exports_and_signatures(plan_fn, launch_fn, extra):
     import ctypes

@@ -994,6 +994,9 @@ def test_thin_grouped_weight_gradient(shape):
     Ds = [torch.randn(B, Hh, Ww, 4, generator=g).to(DEV) for _ in range(G)]
     DD = torch.randn(B, Hh, Ww, 4 * G, generator=g).to(DEV)
     groups = [[x[..., :ch], d] for x, d in zip(xs, Ds)]
+    # the thin kernel is the one taken (a declined launch falls through to the general kernel, which would then be compared with itself)
+    plan = H.conv_wgrad_thin_grouped_plan((B, Hh, Ww), (ch, 4), G, DD.data_ptr(), DD.stride(2), 4, relu_in=True)
+    assert plan["rc"] == 0 and plan["CS"] == ch + 4 and plan["grid"] == plan["P"] * G, plan
     res = {}
     for mode in ("thin", "general"):
         os.environ.pop("TMG_NO_THIN_WGRAD", None)
@@ -1096,6 +1099,9 @@ def test_mix_weight_gradient_grouped_kernel(shape):
     y2s = [torch.randn(B, Hh, Ww, ch, generator=g).to(DEV) for _ in range(G)]
     douts = [torch.randn(B, Hh, Ww, C_, generator=g).to(DEV) for _ in range(G)]
     ins = [[t[..., :ch], y2] for t, y2 in zip(tins, y2s)]
+    # the streaming kernel is the one taken (a declined launch falls through to the general kernel)
+    plan = H.mix_wgrad_grouped_plan(B * Hh * Ww, C_, G)
+    assert plan["rc"] == 0 and plan["CT"] == C_ // 16 and plan["grid"] == plan["P"] * G, plan
     res = {}
     for mode in ("stream", "general"):
         os.environ.pop("TMG_NO_MIX_WGRAD_KERNEL", None)

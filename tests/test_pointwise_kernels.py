@@ -62,10 +62,16 @@ sqrt(K) u of the sum of the |terms|.
   running statistics: 9 u (+ the statistic's own bound) of the two terms.  bn_bwd_apply: (12 + sqrt K) u of
     gamma rstd (|g| + sum|du| / n + (|x| + |mean|) rstd sum|du xhat| / n).
   dkappa, vec_sum: (1 + sqrt K) u of the sum of |terms|.  masked_add, spread2, checker, rsave, y1: exact.
-Observed on an MI355X (largest share of each bound; LAB_NOTES.md, "The bandwidth-bound kernels against fp64 on every dispatch path"):
-affine y2 0.23, logdet 0.04, affine_bwd gin 0.19, dhh 0.26, lstm c_next 0.12, h_next 0.06, gate gradients 0.06, dc_prev 0.06, from the
-one device run so far, which ended at test_lstm_vec_equals_scalar (fixed since, see lstm_fwd1 in tmg_pointwise.hip); the tests below
-that one have not run on a device yet and their shares are still to be recorded."""
+Observed on an MI355X (largest share of each bound, from the SHARE lines of a run of the whole GPU suite, every test of this file
+passing; LAB_NOTES.md, "The bandwidth-bound kernels against fp64 on every dispatch path"): affine y2 0.2278, logdet 0.0357,
+affine_bwd gin 0.1971, dhh 0.2669; lstm c_next 0.1335, h_next 0.0673, gate gradients 0.0564, dc_prev 0.0576; gauss zout 0.1990,
+logp 0.0545, dzout 0.1973, dhz 0.2161; chan_reduce sum 0.0438, sum sq 0.0592, centred sum 0.0246, centred sq 0.0495, bn-relu sum du
+0.0285, sum du xhat 0.0314; chan_moments sum 0.0000, sum sq 0.2357; bn_finalize mean 0.0395, var 0.0531, rstd 0.0395, a 0.0425, bsh
+0.0227, running_mean 0.0280, running_var 0.0189; bn_finalize64 mean 0.4808, var 0.4959, rstd 0.1972, a 0.2240, bsh 0.1292,
+running_mean 0.1062, running_var 0.0812, under cancellation mean 0.2001, var 0.4840, rstd 0.1246 (the fp32 two-pass variance there:
+0.0000 of its own bound, 0.6636 of the 2 u bound it is not held to); n = 1: rstd 0.1149, running_mean 0.0790, running_var 0.0526;
+bn_bwd_apply dx 0.0562 / 0.0510 (accumulate 0 / 1); dkappa 0.0139, vec_sum 0.0139.  The whole file has run on a device since the
+first version of this text (which ended at test_lstm_vec_equals_scalar): that test and everything after it pass."""
 import math
 
 import pytest
