@@ -20,7 +20,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmglow_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip"]
+SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip"]
 # Sources compiled WITHOUT the packed-fp32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32): beside MFMAs a packed
 # f32 instruction costs ~13 cycles more than the two scalar ones it replaces (MI355X_MICROARCH.md, cycle constants, 'price of one
 # filler beside MFMAs'), and the compiler SLP-packs adjacent scalar adds / multiplies by itself under -O3.  The matrix-core kernels'
@@ -60,6 +60,9 @@ GRAM_EXPORTS = ["tmg_ens_gram_plan", "tmg_ens_gram_step", "tmg_ens_gram_traj"]
 # The structure functions and the variogram score (csrc/tmg_sfun.hip), declared in include/tmglow_hip_sfun.h: ens_sfun_plan /
 # ens_sfun_step below.
 SFUN_EXPORTS = ["tmg_ens_sfun_plan", "tmg_ens_sfun_step"]
+# The event verification: Brier, reliability, ROC, fractions skill score (csrc/tmg_event.hip), declared in
+# include/tmglow_hip_event.h: ens_event_plan / ens_event_count / ens_event_step below.
+EVENT_EXPORTS = ["tmg_ens_event_plan", "tmg_ens_event_count", "tmg_ens_event_step"]
 # Every export returns int except the workspace sizes, which the header declares int64_t (read through a 32-bit return a request of
 # 2^31 floats or more would be truncated and the kernel handed a buffer smaller than it planned for).
 RET_I64 = ("tmg_conv_wgrad_ws_floats", "tmg_conv_wgrad_grouped_ws_floats", "tmg_conv_wino_wgrad_ws_floats",
@@ -73,7 +76,8 @@ def build(force=False, verbose=False):
     inc = os.path.join(os.path.dirname(_HERE), "include")
     headers = [os.path.join(CSRC, "tmg_common.h"), os.path.join(inc, "tmglow_hip.h"), os.path.join(inc, "tmglow_hip_plan.h"),
                os.path.join(inc, "tmglow_hip_tspec.h"), os.path.join(inc, "tmglow_hip_quant.h"),
-               os.path.join(inc, "tmglow_hip_gram.h"), os.path.join(inc, "tmglow_hip_sfun.h")]
+               os.path.join(inc, "tmglow_hip_gram.h"), os.path.join(inc, "tmglow_hip_sfun.h"),
+               os.path.join(inc, "tmglow_hip_event.h")]
     hmt = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -127,7 +131,7 @@ def lib():
         for name in PLAN_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
             getattr(_lib, name).argtypes = PLAN_ARGTYPES[name]
-        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS + SFUN_EXPORTS:
+        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS + SFUN_EXPORTS + EVENT_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
     return _lib
 
@@ -1252,6 +1256,50 @@ def ens_sfun_step(xs, target, lags, ws, mom, vsum, tmom, tvar, H, W, t_before, f
     _chk(lib().tmg_ens_sfun_step(_ptr(xs), c_vp(ptr), _i64(ps, co), _i64(*[int(v) for l in lags for v in l]), _ptr(ws), c_i64(ws.numel()),
                                  _ptr(mom), _ptr(vsum), _ptr(tmom), _ptr(tvar), _i64(S, B, Cc, H, W, len(lags), t_before, flags),
                                  _stream()), "tmg_ens_sfun_step")
+
+
+EVENT_PLAN_FIELDS = ("TH", "TW", "halo", "NTY", "NTX", "lds", "threads", "ws", "pitch", "rows", "blocks")
+
+
+def ens_event_plan(S, B, H, W, K, scales):
+    """The launch plan of ens_event_step's neighbourhood kernel for S members of B cases of [H, W], K events and the odd widths
+    `scales` (tmg_ens_event_plan; nothing is launched) -> dict: one block per TH x TW tile of one (case, event) plane, NTY x NTX tiles,
+    halo = the largest w // 2 (the block loads its tile plus that many pixels on every side, zeros outside the field), two LDS
+    tables of `rows` rows of `pitch` ints (summed-area tables with a zero row and column), lds bytes per block, threads, ws = 0
+    workspace, blocks = NTY NTX K B."""
+    scales = [int(w) for w in scales]
+    plan = (c_i64 * 12)()
+    _chk(lib().tmg_ens_event_plan(_i64(S, B, H, W, K, len(scales)), _i64(*scales) if scales else None, plan), "tmg_ens_event_plan")
+    out = {k: int(v) for k, v in zip(EVENT_PLAN_FIELDS, plan)}
+    out["scales"] = scales
+    return out
+
+
+def ens_event_count(y, thr, ev, cnt, S, k, m0):
+    """Count one chunk of k members (y: NHWC [k*B, H, W, C] or a channel-slice view, rows member-major) against the K events ev =
+    ((channel, 1 for > / 0 for <), ..) with the raw thresholds thr [B, K] (device) into cnt [B, K, HW] int32: m0 = 0 writes, later
+    chunks add (tmg_ens_event_count)."""
+    kB, Hh, Ww, Cc = y.shape
+    ptr, ps, co, _ = seg(y)
+    evf = [int(v) for e in ev for v in e]
+    _chk(lib().tmg_ens_event_count(c_vp(ptr), _i64(ps, co), _ptr(thr), _i64(*evf) if evf else None, _ptr(cnt),
+                                   _i64(k, kB // k, Hh * Ww, Cc, S, m0, len(ev)), _stream()), "tmg_ens_event_count")
+
+
+def ens_event_step(cnt, target, thr, ev, scales, rel_count, rel_hit, fss_raw, tsum, ostrides, S, t_before, flags):
+    """Verify one kept step whose member counts are in cnt [B, K, HW] int32 against target (NHWC [B, H, W, C] or a channel-slice
+    view): the reliability tables into rel_count / rel_hit (int32, [K, S + 1] per case) and the raw fractions-skill sums (A, Bx, Cc)
+    per width of `scales` into fss_raw (int64, [K, NS, 3] per case), with the per-case strides ostrides = (tables, raw sums); the
+    step's planes are zeroed first.  flags & 1 advances the per-pixel sums tsum [4, B, K, HW] int32 (n, o, n^2, n o) that hold
+    t_before steps (tmg_ens_event_step)."""
+    B, Hh, Ww, Cc = target.shape
+    ptr, ps, co, _ = seg(target)
+    evf = [int(v) for e in ev for v in e]
+    scales = [int(w) for w in scales]
+    _chk(lib().tmg_ens_event_step(_ptr(cnt), c_vp(ptr), _i64(ps, co), _ptr(thr), _i64(*evf) if evf else None,
+                                  _i64(*scales) if scales else None, _ptr(rel_count), _ptr(rel_hit), _ptr(fss_raw), _ptr(tsum),
+                                  _i64(*ostrides), _i64(S, B, Hh, Ww, Cc, len(ev), len(scales), t_before, flags), _stream()),
+         "tmg_ens_event_step")
 
 
 def spec_rows(y, u, out_mu, out_std, ft_w, yw, k):

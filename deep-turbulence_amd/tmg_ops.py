@@ -1854,6 +1854,15 @@ def quantile_args(levels, exceed, C):
     return lv, ex
 
 
+def raw_thresholds(entries, B, C, mu, sd, u=None):
+    """The raw thresholds of the entries (channel, value, direction) for B cases: thr[b, k] = (value / u[b, c] - out_mu[c]) / out_std[c]
+    in fp64, rounded once to fp32 (mu, sd: [C] fp32 CPU tensors, u: [B, C] fp32 CPU tensor or None for 1).  With u out_std > 0,
+    comparing raw normalised values with thr is comparing physical values with `value`.  -> [B, K] fp32 CPU tensor."""
+    scd = torch.ones(B, C, dtype=torch.float64) if u is None else u.double()
+    thr = torch.stack([(float(e[1]) / scd[:, e[0]] - mu.double()[e[0]]) / sd.double()[e[0]] for e in entries], 1)
+    return thr.to(torch.float32)
+
+
 class EnsembleQuantiles:
     """On-device prediction intervals of sampled roll-outs of B cases (tmg_ens_score_store / tmg_ens_quant_step): per case b, kept
     step t, channel c and pixel p the quantiles of the S members at the probability `levels` (numpy's method="linear": exact order
@@ -1910,10 +1919,7 @@ class EnsembleQuantiles:
         self.ex = [(int(e[0]), 1 if e[2] == ">" else 0) for e in ex]
         self.thr = self.texceed = None
         if self.K:
-            # the raw threshold of case b: (value / sc - out_mu) / out_std in fp64, rounded once
-            scd = torch.ones(self.B, C, dtype=torch.float64) if u is None else u.double()
-            thr = torch.stack([(float(e[1]) / scd[:, e[0]] - mu.double()[e[0]]) / sd.double()[e[0]] for e in ex], 1)
-            self.thr = thr.to(torch.float32).to(dev).contiguous()
+            self.thr = raw_thresholds(ex, self.B, C, mu, sd, u).to(dev).contiguous()
             self.texceed = torch.empty((self.B, self.K, HW), device=dev, dtype=torch.int32)
             self.out["exceed_prob"] = torch.empty((self.B, self.Tk, self.K, Hh, Ww), **f32)
         self._n = 0           # members stored for the current step
@@ -1980,6 +1986,214 @@ class EnsembleQuantiles:
             o["time_exceed_count"] = self.texceed.view(self.B, self.K, self.H, self.W).to(torch.int64)
             o["time_exceed_prob"] = (o["time_exceed_count"].double() / (float(self.S) * float(T))).to(torch.float32)
         o["levels"] = torch.tensor(self.levels, dtype=torch.float64)
+        return o
+
+
+EVENT_MAX_EVENTS = QUANT_MAX_EXCEED
+EVENT_MAX_SCALES = 8
+EVENT_MAX_WIDTH = 33
+EVENT_DEFAULT_SCALES = (1, 3, 5, 9, 17, 33)
+
+
+def event_args(events, scales, C):
+    """The checks of EnsembleEvents' events and scales arguments for C channels.  events: the rules and messages of quantile_args'
+    exceed entries (channel in 0..C-1, finite value, '>' or '<'; at most 4), and at least one of them.  scales: 1 to 8 distinct odd
+    integers in 1..33 (no bools, no floats); the first offending entry is named.  -> (events as tuples, scales as a tuple of ints)."""
+    _, ev = quantile_args((0.5,), events, C)
+    if len(ev) < 1:
+        raise ValueError("events needs at least one entry (channel, value, '>' or '<')")
+    sc = list(scales)
+    if not (1 <= len(sc) <= EVENT_MAX_SCALES):
+        raise ValueError("scales takes 1 to %d neighbourhood widths, got %d" % (EVENT_MAX_SCALES, len(sc)))
+    for i, w in enumerate(sc):
+        if isinstance(w, bool) or not isinstance(w, numbers.Integral) or not 1 <= w <= EVENT_MAX_WIDTH or w % 2 != 1:
+            raise ValueError("scales are odd integers in 1..%d, got %r" % (EVENT_MAX_WIDTH, w))
+        if w in sc[:i]:
+            raise ValueError("scales must be distinct, got %r twice" % (w,))
+    return ev, tuple(int(w) for w in sc)
+
+
+def event_table_scores(cnt, hit, S):
+    """The scores of reliability tables (cnt, hit: int64 CPU tensors [..., S + 1]; bin j holds the pixels with j of S members in the
+    event, hit those of them at which the target is in the event), in fp64 -> dict of fp64 tensors [...] and, for obs_freq / the
+    ROC curve, [..., S + 1] / [..., S + 2].  N = sum cnt.  Empty bins add nothing; roc_area is NaN without an event or a non-event."""
+    S = int(S)
+    j = torch.arange(S + 1, dtype=torch.int64)
+    N = cnt.sum(-1)
+    nd = N.double()
+    num = (cnt * (j * j) - 2 * S * (hit * j) + S * S * hit).sum(-1)           # exact: S^2 N < 2^63
+    out = {"brier": num.double() / (float(S * S) * nd)}
+    nh = hit.sum(-1)
+    ob = nh.double() / nd
+    out["base_rate"] = ob
+    out["fcst_rate"] = (cnt * j).sum(-1).double() / (float(S) * nd)
+    c, h = cnt.double(), hit.double()
+    full = cnt > 0
+    oj = torch.where(full, h / torch.where(full, c, torch.ones_like(c)), torch.zeros_like(c))
+    fj = j.double() / float(S)
+    out["brier_rel"] = (c * (fj - oj) ** 2).sum(-1) / nd
+    out["brier_res"] = (c * (oj - ob.unsqueeze(-1)) ** 2).sum(-1) / nd
+    out["brier_unc"] = ob * (1.0 - ob)
+    out["obs_freq"] = torch.where(full, oj, torch.full_like(oj, float("nan")))
+    # the rule "yes when n >= j", j = 0..S+1: the sums over the bins i >= j, then a zero
+    tail = lambda v: torch.cat([v.flip(-1).cumsum(-1).flip(-1), torch.zeros_like(v[..., :1])], -1)     # noqa: E731
+    hr = tail(hit).double() / nh.double().unsqueeze(-1)
+    fr = tail(cnt - hit).double() / (N - nh).double().unsqueeze(-1)
+    out["roc_hit_rate"], out["roc_false_rate"] = hr, fr
+    out["roc_area"] = ((fr[..., :-1] - fr[..., 1:]) * (hr[..., :-1] + hr[..., 1:])).sum(-1) * 0.5
+    return out
+
+
+def event_fss(raw, S):
+    """The fractions skill score of the raw sums raw [..., 3] = (A, Bx, Cc) (int64 CPU tensor): 1 - (A - 2 S Bx + S^2 Cc) /
+    (A + S^2 Cc), the integers exact, one fp64 division; NaN when the denominator is 0.  -> fp64 [...]."""
+    S = int(S)
+    A, Bx, Cc = raw[..., 0], raw[..., 1], raw[..., 2]
+    return 1.0 - (A - 2 * S * Bx + S * S * Cc).double() / (A + S * S * Cc).double()
+
+
+EVENT_STEP_KEYS = ("brier", "brier_rel", "brier_res", "brier_unc", "base_rate", "fcst_rate", "roc_area")
+EVENT_TIME_KEYS = ("brier", "brier_rel", "brier_res", "brier_unc", "base_rate", "roc_area")
+
+
+class EnsembleEvents:
+    """On-device probabilistic event verification of sampled roll-outs of B cases against the target (tmg_ens_event_count /
+    tmg_ens_event_step).  An event k is (channel, value, ">" | "<"), strict, in physical units ((0, 0.0, "<") is reverse flow); it
+    is decided on the raw normalised values against the raw threshold of raw_thresholds (u out_std > 0 keeps the order).  Per case b,
+    kept step t, event k and pixel p: n = the number of the S members in the event (the forecast probability is n / S) and o = 1
+    when the target is in it.  rel_count[j] counts the pixels with n = j and rel_hit[j] those of them with o = 1; the Brier score,
+    its Murphy decomposition (brier = brier_rel - brier_res + brier_unc, exact here because the forecast takes only S + 1 values),
+    base_rate, fcst_rate and the ROC area (the rule "yes when n >= j"; NaN without an event or a non-event) are formed from the two
+    tables on the host in fp64 and rounded once.  For every odd width w of `scales`, with Nf / No the sums of n / o over the w x w box
+    centred on a pixel (zeros outside the field), fss_raw = (sum Nf^2, sum Nf No, sum No^2) and fss = 1 - (A - 2 S Bx + S^2 Cc) /
+    (A + S^2 Cc), the fractions skill score of Roberts & Lean (2008); NaN when the denominator is 0.
+
+    The counts fold chunk by chunk: no member buffer [S][..] is kept.  The device memory of this class is O(B K HW) (the counts and
+    four running sums per pixel, int32) plus the tables, not O(S B C HW).
+
+    Feeding protocol of EnsembleQuantiles: every step's members in chunks of whole members, in member order (m0 = 0 first), each
+    step's chunks before the next step's; every chunk comes with the step's target, and the last chunk's is the one that is used.
+    Outputs (device tensors): rel_count, rel_hit [B, Tk, K, S + 1] int64; brier, brier_rel, brier_res, brier_unc, base_rate,
+    fcst_rate, roc_area [B, Tk, K]; fss_raw [B, Tk, K, NS, 3] int64; fss [B, Tk, K, NS]; finalize() adds, over the steps folded with
+    time=True (Tn of them), time_rel_count, time_rel_hit [B, K, S + 1] int64 (the tables summed: pooled over steps and pixels),
+    time_rel_obs_freq [B, K, S + 1] (NaN in empty bins), time_roc_hit_rate, time_roc_false_rate [B, K, S + 2], time_brier,
+    time_brier_rel, time_brier_res, time_brier_unc, time_base_rate, time_roc_area [B, K] (the same formulas on the summed tables),
+    time_fss [B, K, NS] (from the summed raw sums, not a mean of ratios), time_fss_uniform = 0.5 + time_base_rate / 2 [B, K],
+    time_event_count, time_obs_count [B, K, H, W] int64 (sum_t n, sum_t o), time_brier_map [B, K, H, W] = (sum n^2 - 2 S sum n o +
+    S^2 sum o) / (S^2 Tn), and event_scales [NS] int64 as given."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, events=((0, 0.0, "<"),), scales=EVENT_DEFAULT_SCALES):
+        if not (2 <= C <= 4):
+            raise ValueError("ensemble events need 2 <= C <= 4 channels, got %d" % C)
+        if int(steps) < 1:
+            raise ValueError("ensemble events need steps >= 1, got %d" % int(steps))
+        ev, sc = event_args(events, scales, C)
+        if not (1 <= int(members) <= SCORES_MAX_MEMBERS):
+            raise ValueError("ensemble events need 1 <= members <= %d, got %d" % (SCORES_MAX_MEMBERS, int(members)))
+        sd = torch.as_tensor(out_std, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
+        mu = torch.as_tensor(out_mu, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
+        if sd.numel() != C or mu.numel() != C:
+            raise ValueError("out_mu / out_std need %d entries, got %d / %d" % (C, mu.numel(), sd.numel()))
+        if not bool((torch.isfinite(sd) & (sd > 0)).all()):
+            raise ValueError("out_std must be finite and strictly positive (u * out_std > 0 keeps the members' order), got %s" % sd.tolist())
+        if not bool(torch.isfinite(mu).all()):
+            raise ValueError("out_mu must be finite, got %s" % mu.tolist())
+        if u is not None:
+            u = torch.as_tensor(u, dtype=torch.float32).detach().reshape(B, C).cpu()
+            if not bool((torch.isfinite(u) & (u > 0)).all()):
+                raise ValueError("u must be finite and strictly positive (u * out_std > 0 keeps the members' order)")
+        S, Tk, HW, wmax = int(members), int(steps), int(Hh) * int(Ww), max(sc)
+        if int(B) < 1 or HW < 1:
+            raise ValueError("ensemble events need B, H, W >= 1, got %d, %d, %d" % (B, Hh, Ww))
+        if S * S * Tk >= 2 ** 31:
+            raise ValueError("S^2 Tk = %d^2 * %d does not stay under 2^31 (the int32 per-pixel sums)" % (S, Tk))
+        if S * S * wmax ** 4 * HW * Tk >= 2 ** 63:
+            raise ValueError("S^2 w_max^4 HW Tk = %d^2 * %d^4 * %d * %d does not stay under 2^63 (the int64 raw sums)" % (S, wmax, HW, Tk))
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("ensemble events run on the HIP path: device %s is not a GPU (there is no CPU path)" % dev)
+        self.S, self.B, self.C, self.H, self.W, self.Tk = S, int(B), int(C), int(Hh), int(Ww), Tk
+        self.events, self.scales = ev, sc
+        self.K, self.NS = len(ev), len(sc)
+        self.ev = [(int(e[0]), 1 if e[2] == ">" else 0) for e in ev]
+        self.thr = raw_thresholds(ev, self.B, C, mu, sd, u).to(dev).contiguous()
+        self.plan = H.ens_event_plan(S, self.B, self.H, self.W, self.K, sc)
+        i32 = dict(device=dev, dtype=torch.int32)
+        self.cnt = torch.empty((self.B, self.K, HW), **i32)
+        self.tsum = torch.empty((4, self.B, self.K, HW), **i32)
+        self.rel = torch.empty((2, self.B, Tk, self.K, S + 1), **i32)
+        self.fss_raw = torch.empty((self.B, Tk, self.K, self.NS, 3), device=dev, dtype=torch.int64)
+        self._n = 0           # members counted for the current step
+        self._step = 0        # the step being filled
+        self._t = [0] * S     # timed steps every member has been fed for
+        self._timed = []      # the steps that went into the time aggregates
+
+    def add(self, y, m0, target, time=True):
+        """Count the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
+        channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride rule.  The step's
+        last chunk verifies the step against its target."""
+        yn = y.permute(0, 2, 3, 1)
+        kB = yn.shape[0]
+        if kB % self.B or tuple(yn.shape[1:]) != (self.H, self.W, self.C):
+            raise ValueError("chunk shape %s does not hold whole members of [%d, %d, %d, %d]" % (tuple(y.shape), self.B, self.C, self.H, self.W))
+        if target is None or tuple(target.shape) != (self.B, self.C, self.H, self.W):
+            raise ValueError("target shape %s is not [%d, %d, %d, %d]" % (None if target is None else tuple(target.shape), self.B, self.C,
+                                                                          self.H, self.W))
+        k = kB // self.B
+        if m0 != self._n or m0 + k > self.S or self._step >= self.Tk:
+            raise ValueError("members must be fed in order, every step's chunks before the next step's")
+        t_before = self._t[m0]
+        if time and any(self._t[m] != t_before for m in range(m0, m0 + k)):
+            raise ValueError("members of one chunk hold different numbers of time steps")
+        H.check_device(yn)
+        tn = target.permute(0, 2, 3, 1)
+        H.check_act(tn)
+        H.check_device(tn)
+        last = m0 + k == self.S
+        H.ens_event_count(yn, self.thr, self.ev, self.cnt, self.S, k, m0)
+        if last:
+            t = self._step
+            H.ens_event_step(self.cnt, tn, self.thr, self.ev, self.scales, self.rel[0, :, t], self.rel[1, :, t], self.fss_raw[:, t],
+                             self.tsum, (self.Tk * self.K * (self.S + 1), self.Tk * self.K * self.NS * 3), self.S, t_before,
+                             1 if time else 0)
+            if time:
+                self._timed.append(t)
+        if time:
+            for m in range(m0, m0 + k):
+                self._t[m] += 1
+        self._n = 0 if last else self._n + k
+        self._step += 1 if last else 0
+
+    def finalize(self):
+        """-> dict of the outputs; the time aggregates cover the steps folded with time=True."""
+        if self._step != self.Tk:
+            raise RuntimeError("%d of %d steps folded" % (self._step, self.Tk))
+        T = self._t[0]
+        if T < 1 or any(t != T for t in self._t) or len(self._timed) != T:
+            raise RuntimeError("no time statistics: no step was folded with time=True")
+        dev, S = self.rel.device, self.S
+        f32 = lambda v: v.to(torch.float32).to(dev)                            # noqa: E731
+        rel = self.rel.to(torch.int64)
+        o = {"rel_count": rel[0], "rel_hit": rel[1], "fss_raw": self.fss_raw}
+        hc, hh, hraw = rel[0].cpu(), rel[1].cpu(), self.fss_raw.cpu()
+        sc = event_table_scores(hc, hh, S)
+        for key in EVENT_STEP_KEYS:
+            o[key] = f32(sc[key])
+        o["fss"] = f32(event_fss(hraw, S))
+        tc, th, traw = hc[:, self._timed].sum(1), hh[:, self._timed].sum(1), hraw[:, self._timed].sum(1)
+        o["time_rel_count"], o["time_rel_hit"] = tc.to(dev), th.to(dev)
+        sc = event_table_scores(tc, th, S)
+        o["time_rel_obs_freq"] = f32(sc["obs_freq"])
+        o["time_roc_hit_rate"], o["time_roc_false_rate"] = f32(sc["roc_hit_rate"]), f32(sc["roc_false_rate"])
+        for key in EVENT_TIME_KEYS:
+            o["time_" + key] = f32(sc[key])
+        o["time_fss_uniform"] = f32(0.5 + sc["base_rate"] / 2)
+        o["time_fss"] = f32(event_fss(traw, S))
+        shp = (self.B, self.K, self.H, self.W)
+        ts = self.tsum.to(torch.int64)
+        o["time_event_count"], o["time_obs_count"] = ts[0].view(shp), ts[1].view(shp)
+        o["time_brier_map"] = ((ts[2] - 2 * S * ts[3] + S * S * ts[1]).double() / float(S * S * T)).to(torch.float32).view(shp)
+        o["event_scales"] = torch.tensor(self.scales, dtype=torch.int64)
         return o
 
 

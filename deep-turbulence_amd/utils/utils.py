@@ -100,7 +100,7 @@ _TARGET_STATS = (("target_time_mean", "time_mean_mean"), ("target_time_rms", "ti
 
 
 def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, turbulence, spectra=False,
-                   window="hann", scores=False, tspec=None, quant=None, energy=None, structure=None):
+                   window="hann", scores=False, tspec=None, quant=None, energy=None, structure=None, events=None):
     """The body of modelPredStats, modelPredTurbulence (turbulence: grid = (args.dx, args.dy)), modelPredSpectra (spectra: the same
     chunks also go through an EnsembleSpectrum with `window`), modelPredScores (scores: the same chunks also go through an
     EnsembleScores with the step's normalised target) and modelPredTimeSpectra (tspec = (nfreq, window, dt between kept steps): the
@@ -108,7 +108,8 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
     the same chunks also go through an EnsembleQuantiles with the step's normalised target) and modelPredEnergy (energy = the channel
     groups: the same chunks also go through an EnsembleEnergy with the step's normalised target) and modelPredStructure (structure =
     (lags, weights): the same chunks also go through an EnsembleStructure with the step's normalised target and grid = (args.dx,
-    args.dy)): same seed draws in the same order, same
+    args.dy)) and modelPredEvents (events = (events, scales): the same chunks also go through an EnsembleEvents with the step's
+    normalised target): same seed draws in the same order, same
     folding, same re-anchoring, so that the keys they share hold identical values under the same host RNG state."""
     import tmg_ops as ops
     core = getattr(model, "module", model)
@@ -142,7 +143,7 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
             B, C, Hh, Ww = inp.size(0), tgt.size(2), tgt.size(-2), tgt.size(-1)
             if C != 3:
                 raise ValueError("%s scales (ux, uy, p) by (u0, u0, u0^2) as modelPred does: 3 target channels, got %d" % (name, C))
-            if (scores or tspec is not None or quant is not None or energy is not None or structure is not None) and target0.size(1) <= (nkeep - 1) * stride:
+            if (scores or tspec is not None or quant is not None or energy is not None or structure is not None or events is not None) and target0.size(1) <= (nkeep - 1) * stride:
                 raise ValueError("%s: the target series holds %d steps, kept step %d needs step %d"
                                  % (name, target0.size(1), nkeep - 1, (nkeep - 1) * stride))
             keys = []
@@ -166,7 +167,9 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
             en = ops.EnsembleEnergy(samples, B, C, Hh, Ww, nkeep, dev, out_std, u=u.view(B, 3)[:, :C], groups=energy) if energy is not None else None
             sfn = ops.EnsembleStructure(samples, B, C, Hh, Ww, nkeep, dev, out_std, u=u.view(B, 3)[:, :C], lags=structure[0],
                                         weights=structure[1], grid=(args.dx, args.dy)) if structure is not None else None
-            tnorm = target0.to(dev) if scores or qt is not None or en is not None or sfn is not None else None                # the normalised series; one step at a time goes channels-last
+            evs = ops.EnsembleEvents(samples, B, C, Hh, Ww, nkeep, dev, out_mu, out_std, u=u.view(B, 3)[:, :C], events=events[0],
+                                     scales=events[1]) if events is not None else None
+            tnorm = target0.to(dev) if scores or qt is not None or en is not None or sfn is not None or evs is not None else None                # the normalised series; one step at a time goes channels-last
             for tstep in range(tmax):
                 keep = tstep % stride == 0 and tstep // stride < nkeep
                 tj = tnorm[:, tstep].contiguous(memory_format=torch.channels_last) if keep and tnorm is not None else None
@@ -186,6 +189,8 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
                             en.add(y0, m0, tj, time=tstep // stride >= t_start)
                         if sfn is not None:
                             sfn.add(y0, m0, tj, time=tstep // stride >= t_start)
+                        if evs is not None:
+                            evs.add(y0, m0, tj, time=tstep // stride >= t_start)
                     if tstep % 20 == 0:
                         states[ci] = [(0.5 * h + 0.5 * hk, 0.5 * c + 0.5 * ck) for (h, c), (hk, ck) in zip(states[ci], anchors[ci])]
             for key, t in st.finalize().items():
@@ -211,6 +216,12 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
             if sfn is not None:
                 for key, t in sfn.finalize().items():
                     if key in ("lags", "lag_dist"):
+                        sf_lags[key] = t
+                    else:
+                        outs.setdefault(key, []).append(t.cpu())
+            if evs is not None:
+                for key, t in evs.finalize().items():
+                    if key == "event_scales":
                         sf_lags[key] = t
                     else:
                         outs.setdefault(key, []).append(t.cpu())
@@ -259,6 +270,8 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
         res["levels"] = q_levels
     if energy is not None:
         res["energy_groups"] = tuple(energy)
+    if events is not None:
+        res["events"] = tuple(events[0])
     res.update(sf_lags)
     return res
 
@@ -467,3 +480,44 @@ def modelPredStructure(args, model, testing_loader, log, samples=1, stride=1, tm
         lags = ops.structure_lags(lags, 65, 65)                           # the rules that do not depend on the field; the field's come with it
     return _ensembleStats("modelPredStructure", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False,
                           structure=(lags, weights))
+
+
+def modelPredEvents(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, events=((0, 0.0, "<"),),
+                    scales=(1, 3, 5, 9, 17, 33)):
+    """modelPredStats plus the verification of the ensemble's event probabilities against the target, still without forming
+    modelPred's [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleEvents).  An event is (channel, value, ">" | "<"), strict, in
+    physical units, as modelPredQuantiles' `exceed` entries (1 to 4 of them; (0, 0.0, "<") is reverse flow): the forecast probability
+    of a pixel is the share n / S of the members in the event (modelPredQuantiles' exceed_prob), the observation o is whether the
+    target is in it.  The target of kept step j is series step j * stride; a series that is too short raises.  scales: 1 to 8
+    distinct odd neighbourhood widths in 1..33 pixels.  Same roll-outs as modelPredStats: under the same host RNG state the keys both
+    return are identical.
+
+    Returns modelPredStats' dict plus (CPU tensors; K events, NS widths, S = samples, kept steps t_start..Tk-1 are the Tn timed ones):
+      rel_count, rel_hit [N, Tk, K, S+1]  int64: the pixels with j of S members in the event, and those of them where the target is
+                                        in it: the reliability table.  rel_hit / rel_count against j / S is the reliability diagram: on
+                                        the diagonal a forecast probability of 0.7 comes true 70 % of the time
+      brier [N, Tk, K]                  the Brier score mean_p (n / S - o)^2; lower is better
+      brier_rel, brier_res, brier_unc   its Murphy decomposition, brier = brier_rel - brier_res + brier_unc: reliability (0 is
+                                        perfect), resolution (higher is better, at most brier_unc) and the target's own uncertainty
+      base_rate, fcst_rate [N, Tk, K]   the share of pixels at which the target is in the event, and the mean forecast probability
+      roc_area [N, Tk, K]               the area under the ROC curve of the rule "yes when n >= j": 0.5 = no discrimination between
+                                        event and non-event pixels, 1 = perfect; NaN when the target has no event or no non-event
+      fss_raw [N, Tk, K, NS, 3]         int64: (sum Nf^2, sum Nf No, sum No^2) of the w x w box sums of n and o (zeros outside the field)
+      fss [N, Tk, K, NS]                the fractions skill score (Roberts & Lean 2008) per width: 1 = the forecast puts the same area
+                                        fraction of the event into every neighbourhood, 0 = no overlap; NaN when neither has the event
+      time_rel_count, time_rel_hit [N, K, S+1], time_rel_obs_freq [N, K, S+1]   the tables summed over the timed steps and the
+                                        observed frequency per bin (NaN in empty bins): read it against the diagonal j / S
+      time_roc_hit_rate, time_roc_false_rate [N, K, S+2]   the ROC curve of the summed tables, thresholds j = 0..S+1
+      time_brier, time_brier_rel, time_brier_res, time_brier_unc, time_base_rate, time_roc_area [N, K]   the same formulas on the
+                                        summed tables: pooled over steps and pixels
+      time_fss [N, K, NS]               from the summed raw sums (the standard aggregation, not a mean of ratios).  Read it against
+      time_fss_uniform [N, K]           = 0.5 + time_base_rate / 2: the smallest width at which time_fss exceeds it is the scale from
+                                        which the forecast counts as skilful
+      time_event_count, time_obs_count [N, K, H, W]   int64: sum_t n and sum_t o per pixel (the first is modelPredQuantiles'
+                                        time_exceed_count); time_obs_count / Tn is the target's own event frequency
+      time_brier_map [N, K, H, W]       the Brier score per pixel over the timed steps
+      event_scales [NS] int64, events   the widths and the events as given."""
+    import tmg_ops as ops
+    events, scales = ops.event_args(events, scales, 3)
+    return _ensembleStats("modelPredEvents", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False,
+                          events=(tuple(events), tuple(scales)))
