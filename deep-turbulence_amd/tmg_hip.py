@@ -20,7 +20,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmglow_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip"]
+SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip"]
 # Sources compiled WITHOUT the packed-fp32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32): beside MFMAs a packed
 # f32 instruction costs ~13 cycles more than the two scalar ones it replaces (MI355X_MICROARCH.md, cycle constants, 'price of one
 # filler beside MFMAs'), and the compiler SLP-packs adjacent scalar adds / multiplies by itself under -O3.  The matrix-core kernels'
@@ -63,6 +63,9 @@ SFUN_EXPORTS = ["tmg_ens_sfun_plan", "tmg_ens_sfun_step"]
 # The event verification: Brier, reliability, ROC, fractions skill score (csrc/tmg_event.hip), declared in
 # include/tmglow_hip_event.h: ens_event_plan / ens_event_count / ens_event_step below.
 EVENT_EXPORTS = ["tmg_ens_event_plan", "tmg_ens_event_count", "tmg_ens_event_step"]
+# The pooled probability densities: marginal and joint histograms of the members and of the target (csrc/tmg_pdf.hip), declared in
+# include/tmglow_hip_pdf.h: ens_pdf_plan / ens_pdf_count below.
+PDF_EXPORTS = ["tmg_ens_pdf_plan", "tmg_ens_pdf_count"]
 # Every export returns int except the workspace sizes, which the header declares int64_t (read through a 32-bit return a request of
 # 2^31 floats or more would be truncated and the kernel handed a buffer smaller than it planned for).
 RET_I64 = ("tmg_conv_wgrad_ws_floats", "tmg_conv_wgrad_grouped_ws_floats", "tmg_conv_wino_wgrad_ws_floats",
@@ -77,7 +80,7 @@ def build(force=False, verbose=False):
     headers = [os.path.join(CSRC, "tmg_common.h"), os.path.join(inc, "tmglow_hip.h"), os.path.join(inc, "tmglow_hip_plan.h"),
                os.path.join(inc, "tmglow_hip_tspec.h"), os.path.join(inc, "tmglow_hip_quant.h"),
                os.path.join(inc, "tmglow_hip_gram.h"), os.path.join(inc, "tmglow_hip_sfun.h"),
-               os.path.join(inc, "tmglow_hip_event.h")]
+               os.path.join(inc, "tmglow_hip_event.h"), os.path.join(inc, "tmglow_hip_pdf.h")]
     hmt = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -131,7 +134,7 @@ def lib():
         for name in PLAN_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
             getattr(_lib, name).argtypes = PLAN_ARGTYPES[name]
-        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS + SFUN_EXPORTS + EVENT_EXPORTS:
+        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS + SFUN_EXPORTS + EVENT_EXPORTS + PDF_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
     return _lib
 
@@ -1300,6 +1303,37 @@ def ens_event_step(cnt, target, thr, ev, scales, rel_count, rel_hit, fss_raw, ts
                                   _i64(*scales) if scales else None, _ptr(rel_count), _ptr(rel_hit), _ptr(fss_raw), _ptr(tsum),
                                   _i64(*ostrides), _i64(S, B, Hh, Ww, Cc, len(ev), len(scales), t_before, flags), _stream()),
          "tmg_ens_event_step")
+
+
+PDF_PLAN_FIELDS = ("SL", "NSL", "lds", "copies", "instance", "threads", "blocks", "PPT")
+PDF_KINDS = {"speed": 4, "vort": 5, "div": 6}
+
+
+def ens_pdf_plan(k, B, H, W, F, nb, P, nbj, R, derived):
+    """The launch plan of ens_pdf_count for a chunk of k members of B cases of [H, W], F fields of nb inner bins, P pairs of nbj bins
+    per axis, R regions; derived: a field is speed, vort or div (tmg_ens_pdf_plan; nothing is launched) -> dict: one block per slice
+    of SL = 256 PPT pixels of one row (member, case), NSL slices per row, lds bytes per block, copies = the private marginal
+    histograms, instance (0: channel fields only, 1: with derived fields), threads, blocks = NSL k B."""
+    plan = (c_i64 * 8)()
+    _chk(lib().tmg_ens_pdf_plan(_i64(k, B, H, W, F, nb, P, nbj, R, 1 if derived else 0), plan), "tmg_ens_pdf_plan")
+    return {key: int(v) for key, v in zip(PDF_PLAN_FIELDS, plan)}
+
+
+def ens_pdf_count(y, u, out_mu, out_std, center, edges, jedges, kinds, pairs, boxes, step_count, step_joint, mtime, tjoint, ostrides, grid,
+                  S, k, m0, nb, nbj, flags):
+    """Bin one chunk of k members (y: NHWC [k*B, H, W, C] or a channel-slice view, rows member-major) of the fields `kinds` (0..C-1: a
+    channel, 4 / 5 / 6: speed / vort / div on grid = (dx, dy)) against the edge tables edges [B, F, nb + 1] / jedges [B, P, 2, nbj + 1]
+    (device fp32) over the pixel boxes (x0, x1, y0, y1), the pairs (fi, fj) jointly; center: c_raw [B, C, HW] or None.  Adds into the
+    int32 planes step_count ([R, F, nb + 2] per case) / step_joint ([R, P, (nbj + 2)^2] per case) with the per-case strides ostrides,
+    and with flags & 1 into mtime [B, S, R, F, nb + 2] (members m0 .. m0 + k - 1) / tjoint [B, R, P, (nbj + 2)^2]
+    (tmg_ens_pdf_count)."""
+    kB, Hh, Ww, Cc = y.shape
+    ptr, ps, co, _ = seg(y)
+    desc = [int(v) for v in kinds] + [int(v) for pr in pairs for v in pr] + [int(v) for bx in boxes for v in bx]
+    _chk(lib().tmg_ens_pdf_count(c_vp(ptr), _i64(ps, co), _ptr(u), _ptr(out_mu), _ptr(out_std), _ptr(center), _ptr(edges), _ptr(jedges),
+                                 _i64(*desc), _ptr(step_count), _ptr(step_joint), _ptr(mtime), _ptr(tjoint), _i64(*ostrides),
+                                 _i64(k, kB // k, Hh, Ww, Cc, S, m0, len(kinds), nb, len(pairs), nbj, len(boxes), flags),
+                                 _flts(grid) if grid is not None else None, _stream()), "tmg_ens_pdf_count")
 
 
 def spec_rows(y, u, out_mu, out_std, ft_w, yw, k):

@@ -2197,6 +2197,313 @@ class EnsembleEvents:
         return o
 
 
+PDF_MAX_FIELDS = 8
+PDF_MAX_BINS = 128
+PDF_MAX_JOINT_BINS = 32
+PDF_MAX_PAIRS = 2
+PDF_MAX_REGIONS = 4
+PDF_ALIASES = {"ux": 0, "uy": 1, "p": 2}
+PDF_DERIVED = H.PDF_KINDS                                                      # "speed", "vort", "div" -> the kernel's kind codes
+
+
+def _pdf_kind(f, C):
+    """A field entry -> the kernel's kind code, or None."""
+    if isinstance(f, str):
+        k = PDF_ALIASES.get(f, PDF_DERIVED.get(f))
+        return k if k is not None and (k >= 4 or k < C) else None
+    if isinstance(f, bool) or not isinstance(f, numbers.Integral) or not 0 <= f < C:
+        return None
+    return int(f)
+
+
+def pdf_args(fields, bins, ranges, joint, joint_bins, regions, grid, B, C, Hh, Ww):
+    """The checks of EnsemblePdfs' arguments for B cases of C channels of [Hh, Ww]; the first offending entry is named.
+    fields: 1 to 8 entries, each a channel 0..C-1 (aliases "ux", "uy", "p"), "speed", "vort" or "div"; the derived ones need
+    grid = (dx, dy), two positive finite cell sizes.  bins: 1..128 (no bools, no floats); joint_bins: 1..32.  ranges: one finite
+    (lo, hi), lo < hi, per field, or an array [B, F, 2].  joint: up to 2 pairs of distinct listed fields (an entry names the first field of its kind in the list).  regions: None (the whole
+    field) or 1 to 4 integer boxes (x0, x1, y0, y1), half open, non-empty, inside the field.
+    -> (kinds, nb, ranges as an fp64 CPU tensor [B, F, 2], pairs as field indices, nbj, regions as tuples of ints, grid or None)."""
+    fl = list(fields)
+    if not (1 <= len(fl) <= PDF_MAX_FIELDS):
+        raise ValueError("fields takes 1 to %d entries, got %d" % (PDF_MAX_FIELDS, len(fl)))
+    kinds = []
+    for f in fl:
+        k = _pdf_kind(f, C)
+        if k is None:
+            raise ValueError("fields are channels in 0..%d (\"ux\", \"uy\", \"p\" for 0, 1, 2), \"speed\", \"vort\" or \"div\", got %r" % (C - 1, f))
+        kinds.append(k)
+    F = len(kinds)
+    for name, v, top in (("bins", bins, PDF_MAX_BINS), ("joint_bins", joint_bins, PDF_MAX_JOINT_BINS)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 1 <= v <= top:
+            raise ValueError("%s is an integer in 1..%d, got %r" % (name, top, v))
+    if any(k >= 4 for k in kinds):
+        if grid is None:
+            raise ValueError("the derived field %r needs grid=(dx, dy)" % (fl[[k >= 4 for k in kinds].index(True)],))
+    if grid is not None:
+        grid = tuple(float(g) for g in grid)
+        if len(grid) != 2 or not all(math.isfinite(g) and g > 0 for g in grid):
+            raise ValueError("grid needs two positive finite cell sizes (dx, dy), got %s" % (grid,))
+    if ranges is None:
+        raise ValueError("ranges needs one (lo, hi) per field, or an array [B, F, 2]")
+    rg = torch.as_tensor(ranges, dtype=torch.float64).detach().cpu()
+    if tuple(rg.shape) == (F, 2):
+        rg = rg.unsqueeze(0).expand(B, F, 2)
+    if tuple(rg.shape) != (B, F, 2):
+        raise ValueError("ranges needs one (lo, hi) per field, or an array [%d, %d, 2], got shape %s" % (B, F, tuple(rg.shape)))
+    rg = rg.contiguous()
+    for b in range(B):
+        for f in range(F):
+            lo, hi = float(rg[b, f, 0]), float(rg[b, f, 1])
+            if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
+                raise ValueError("ranges are finite (lo, hi) with lo < hi, got (%r, %r) for field %r of case %d" % (lo, hi, fl[f], b))
+    jl = [tuple(pr) for pr in joint]
+    if len(jl) > PDF_MAX_PAIRS:
+        raise ValueError("joint takes at most %d pairs, got %d" % (PDF_MAX_PAIRS, len(jl)))
+    pairs = []
+    for pr in jl:
+        ks = [_pdf_kind(f, C) for f in pr] if len(pr) == 2 else [None]
+        if any(k is None or k not in kinds for k in ks) or ks[0] == ks[1]:
+            raise ValueError("joint entries are pairs of distinct listed fields, got %r" % (pr,))
+        pairs.append((kinds.index(ks[0]), kinds.index(ks[1])))
+    if regions is None:
+        regs = [(0, int(Ww), 0, int(Hh))]
+    else:
+        regs = [tuple(r) for r in regions]
+        if not (1 <= len(regs) <= PDF_MAX_REGIONS):
+            raise ValueError("regions takes 1 to %d boxes, got %d" % (PDF_MAX_REGIONS, len(regs)))
+        for r in regs:
+            if len(r) != 4 or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in r) \
+                    or not (0 <= r[0] < r[1] <= Ww and 0 <= r[2] < r[3] <= Hh):
+                raise ValueError("regions are integer boxes (x0, x1, y0, y1), half open, non-empty and inside the %d x %d field, got %r"
+                                 % (Hh, Ww, r))
+        regs = [tuple(int(v) for v in r) for r in regs]
+    return kinds, int(bins), rg, pairs, int(joint_bins), regs, grid
+
+
+def pdf_edge_tables(kinds, ranges, n, mu, sd, u=None, centered=False):
+    """The edges of n uniform bins per case and field: E_j = lo + j (hi - lo) / n in fp64 (physical), and the device table in fp64
+    rounded once to fp32: a channel field (E_j / u[b, c] - mu[c]) / sd[c], with a centre E_j / (u[b, c] sd[c]); a derived field E_j
+    itself (ranges: [B, F, 2] fp64, mu, sd: [C] fp32 CPU tensors, u: [B, C] fp32 CPU tensor or None for 1).  Edges that are not
+    strictly increasing after rounding are a ValueError.  -> (E [B, F, n + 1] fp64, e [B, F, n + 1] fp32), CPU tensors."""
+    B, F = ranges.shape[:2]
+    j = torch.arange(n + 1, dtype=torch.float64)
+    lo, hi = ranges[..., 0:1], ranges[..., 1:2]
+    E = lo + j * (hi - lo) / n
+    e = E.clone()
+    scd = torch.ones(B, mu.numel(), dtype=torch.float64) if u is None else u.double()
+    for f, k in enumerate(kinds):
+        if k < 4:
+            e[:, f] = E[:, f] / (scd[:, k:k + 1] * sd.double()[k]) if centered else (E[:, f] / scd[:, k:k + 1] - mu.double()[k]) / sd.double()[k]
+    e = e.to(torch.float32)
+    bad = (e[..., 1:] <= e[..., :-1]).any(-1).nonzero()
+    if bad.numel():
+        raise ValueError("the edges of field %d of case %d are not strictly increasing after rounding to fp32: [%r, %r] in %d bins"
+                         % (int(bad[0, 1]), int(bad[0, 0]), float(ranges[bad[0, 0], bad[0, 1], 0]), float(ranges[bad[0, 0], bad[0, 1], 1]), n))
+    return E, e
+
+
+def pdf_density(cnt, h):
+    """cnt [..., nb + 2] int64 (under- and overflow first and last), h the bin width broadcastable to [..., 1] -> the density of the
+    inner bins [..., nb] in fp64: inner count / (all counts h), so that what is out of range is missing from the integral; NaN
+    without a sample."""
+    return cnt[..., 1:-1].double() / (cnt.sum(-1, keepdim=True).double() * h)
+
+
+def pdf_w1(p, q, h):
+    """The Wasserstein-1 distance between the distributions of the counts p, q [..., nb + 2] int64 with each bin's mass at its
+    centre (the under- and overflow masses one width outside): h sum_{j=0}^{nb} |F_j - G_j| with F, G the cumulative shares, in fp64;
+    h broadcastable to [...].  NaN when either holds no sample."""
+    F = p.cumsum(-1)[..., :-1].double() / p.sum(-1, keepdim=True).double()
+    G = q.cumsum(-1)[..., :-1].double() / q.sum(-1, keepdim=True).double()
+    return (F - G).abs().sum(-1) * h
+
+
+def pdf_js(p, q):
+    """The Jensen-Shannon divergence in bits between the distributions of the counts p, q [..., n] int64, 0 log 0 = 0: in [0, 1];
+    NaN when either holds no sample.  fp64."""
+    P = p.double() / p.sum(-1, keepdim=True).double()
+    Q = q.double() / q.sum(-1, keepdim=True).double()
+    M = 0.5 * (P + Q)
+    one = torch.ones_like(M)
+    kl = lambda A: torch.where(A > 0, A * torch.log2(torch.where(A > 0, A, one) / torch.where(A > 0, M, one)), torch.zeros_like(A))   # noqa: E731
+    out = 0.5 * (kl(P).sum(-1) + kl(Q).sum(-1))
+    return torch.where(torch.isnan(P.sum(-1) + Q.sum(-1)), torch.full_like(out, float("nan")), out)
+
+
+class EnsemblePdfs:
+    """On-device probability densities of the flow quantities pooled over regions of the flow, for sampled roll-outs of B cases and
+    for the target (tmg_ens_pdf_count).  fields: up to 8 of a channel 0..C-1 ("ux", "uy", "p" for 0, 1, 2), "speed", "vort", "div"
+    (the derived ones on grid = (dx, dy): the 3x3 stencil of pc/ with zero padding at the field border, every fp32 operation rounded
+    on its own).  Each field has `bins` uniform bins over its physical range (lo, hi) of `ranges` (per field, or [B, F, 2] per case)
+    plus an underflow and an overflow bin; a value on an edge belongs to the bin above.  A channel field is binned on its raw
+    normalised value against the edges (E / u - out_mu) / out_std (u out_std > 0 keeps the order: no rounding); center [B, C, H, W]
+    (physical) subtracts c_raw = float32((center / u - out_mu) / out_std) first, one rounded fp32 subtraction, against the edges
+    E / (u out_std): fluctuations about a given mean flow.  joint: up to 2 pairs of listed fields with joint_bins bins per axis over
+    the same ranges; the first field indexes the rows.  regions: up to 4 pixel boxes (x0, x1, y0, y1), half open, x along W; they
+    may overlap; default the whole field.  Non-finite members are not supported.
+
+    The counts fold chunk by chunk by integer adds: no member buffer is kept, and every integer output is bitwise reproducible and
+    independent of the chunking.  The target goes through the same kernel as a one-member chunk into planes of its own.
+
+    Feeding protocol of EnsembleEvents: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
+    chunks before the next step's; every chunk comes with the step's target, and the last chunk's is the one that is used.
+    Outputs of finalize() (device tensors; Tn steps folded with time=True, nb = bins, nbj = joint_bins):
+      pdf_count, target_count [B, Tk, R, F, nb + 2] int64; joint_count, target_joint_count [B, Tk, R, P, nbj + 2, nbj + 2] int64
+      time_member_count [B, S, R, F, nb + 2], time_count (its sum over the members), time_target_count [B, R, F, nb + 2],
+      time_joint_count, time_target_joint_count [B, R, P, nbj + 2, nbj + 2] int64
+      pdf, target_pdf [B, Tk, R, F, nb]: inner count / (all counts * bin width); time_pdf, time_target_pdf [B, R, F, nb] (pooled);
+      time_pdf_mean, time_pdf_std: mean / population std over the members of each member's own time-pooled density
+      w1, js [B, Tk, R, F], time_w1, time_js [B, R, F]: Wasserstein-1 (physical units) and Jensen-Shannon divergence (bits, over
+      the nb + 2 bins) of the pooled ensemble against the target; time_member_w1 [B, S, R, F]; time_joint_js [B, R, P]
+      (formed on the host in fp64 from the integers, rounded once; NaN for a distribution without samples)
+      pdf_edges [B, F, nb + 1], joint_edges [B, P, 2, nbj + 1], pdf_ranges [B, F, 2] fp64 physical; pdf_fields, pdf_joint,
+      pdf_regions as given."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, fields=("ux", "uy"), bins=64, ranges=None, joint=(),
+                 joint_bins=32, regions=None, grid=None, center=None):
+        if not (2 <= C <= 4):
+            raise ValueError("ensemble pdfs need 2 <= C <= 4 channels, got %d" % C)
+        if int(steps) < 1:
+            raise ValueError("ensemble pdfs need steps >= 1, got %d" % int(steps))
+        if int(B) < 1 or int(Hh) < 1 or int(Ww) < 1:
+            raise ValueError("ensemble pdfs need B, H, W >= 1, got %d, %d, %d" % (B, Hh, Ww))
+        kinds, nb, rg, pairs, nbj, regs, grid = pdf_args(fields, bins, ranges, joint, joint_bins, regions, grid, int(B), C, int(Hh), int(Ww))
+        if not (1 <= int(members) <= SCORES_MAX_MEMBERS):
+            raise ValueError("ensemble pdfs need 1 <= members <= %d, got %d" % (SCORES_MAX_MEMBERS, int(members)))
+        sd = torch.as_tensor(out_std, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
+        mu = torch.as_tensor(out_mu, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
+        if sd.numel() != C or mu.numel() != C:
+            raise ValueError("out_mu / out_std need %d entries, got %d / %d" % (C, mu.numel(), sd.numel()))
+        if not bool((torch.isfinite(sd) & (sd > 0)).all()):
+            raise ValueError("out_std must be finite and strictly positive (u * out_std > 0 keeps the members' order), got %s" % sd.tolist())
+        if not bool(torch.isfinite(mu).all()):
+            raise ValueError("out_mu must be finite, got %s" % mu.tolist())
+        if u is not None:
+            u = torch.as_tensor(u, dtype=torch.float32).detach().reshape(B, C).cpu()
+            if not bool((torch.isfinite(u) & (u > 0)).all()):
+                raise ValueError("u must be finite and strictly positive (u * out_std > 0 keeps the members' order)")
+        S, Tk, HW = int(members), int(steps), int(Hh) * int(Ww)
+        for name, v in (("S H W", S * HW), ("Tk H W", Tk * HW), ("S Tk H W", S * Tk * HW)):
+            if v >= 2 ** 31:
+                raise ValueError("%s = %d does not stay under 2^31 (the int32 counts)" % (name, v))
+        cen = None
+        if center is not None:
+            cen = torch.as_tensor(center, dtype=torch.float32).detach().cpu()
+            if tuple(cen.shape) != (int(B), C, int(Hh), int(Ww)) or not bool(torch.isfinite(cen).all()):
+                raise ValueError("center is a finite array [%d, %d, %d, %d] in physical units, got shape %s" % (B, C, Hh, Ww, tuple(cen.shape)))
+            scd = torch.ones(int(B), C, dtype=torch.float64) if u is None else u.double()
+            cen = ((cen.double() / scd.view(int(B), C, 1, 1) - mu.double().view(1, C, 1, 1)) / sd.double().view(1, C, 1, 1)).to(torch.float32)
+        self.E, e = pdf_edge_tables(kinds, rg, nb, mu, sd, u, cen is not None)
+        jk = [kinds[i] for pr in pairs for i in pr]
+        jr = rg[:, [i for pr in pairs for i in pr]] if pairs else rg[:, :0]
+        self.JE, je = pdf_edge_tables(jk, jr, nbj, mu, sd, u, cen is not None)
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("ensemble pdfs run on the HIP path: device %s is not a GPU (there is no CPU path)" % dev)
+        self.S, self.B, self.C, self.H, self.W, self.Tk = S, int(B), int(C), int(Hh), int(Ww), Tk
+        self.fields, self.joint, self.regions = tuple(fields), tuple(tuple(pr) for pr in joint), tuple(regs)
+        self.kinds, self.pairs, self.nb, self.nbj, self.grid = kinds, pairs, nb, nbj, grid
+        self.F, self.P, self.R = len(kinds), len(pairs), len(regs)
+        self.ranges = rg
+        self.e, self.je = e.to(dev).contiguous(), je.to(dev).contiguous()
+        self.mu, self.sd = mu.to(dev).contiguous(), sd.to(dev).contiguous()
+        self.u = None if u is None else u.to(dev).contiguous()
+        self.cen = None if cen is None else cen.reshape(self.B, C, HW).to(dev).contiguous()
+        self.derived = any(k >= 4 for k in kinds)
+        self.plan = H.ens_pdf_plan(1, self.B, self.H, self.W, self.F, nb, self.P, nbj, self.R, self.derived)
+        i32 = dict(device=dev, dtype=torch.int32)
+        jb = (nbj + 2) ** 2
+        # [0]: the ensemble's planes, [1]: the target's (a one-member ensemble: S = 1)
+        self.cnt = torch.empty((2, self.B, Tk, self.R, self.F, nb + 2), **i32)
+        self.jnt = torch.empty((2, self.B, Tk, self.R, self.P, jb), **i32)
+        self.mt = (torch.empty((self.B, S, self.R, self.F, nb + 2), **i32), torch.empty((self.B, 1, self.R, self.F, nb + 2), **i32))
+        self.tj = torch.empty((2, self.B, self.R, self.P, jb), **i32)
+        self._n = 0           # members counted for the current step
+        self._step = 0        # the step being filled
+        self._t = [0] * S     # timed steps every member has been fed for
+        self._timed = []      # the steps that went into the time aggregates
+
+    def _count(self, which, yn, S, k, m0, t, timed):
+        marg, jb = self.R * self.F * (self.nb + 2), self.R * self.P * (self.nbj + 2) ** 2
+        H.ens_pdf_count(yn, self.u, self.mu, self.sd, self.cen, self.e, self.je if self.P else None, self.kinds, self.pairs, self.regions,
+                        self.cnt[which, :, t], self.jnt[which, :, t] if self.P else None, self.mt[which], self.tj[which] if self.P else None,
+                        (self.Tk * marg, self.Tk * jb), self.grid, S, k, m0, self.nb, self.nbj, 1 if timed else 0)
+
+    def add(self, y, m0, target, time=True):
+        """Bin the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
+        channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride rule.  The step's
+        first chunk zeroes the step's planes (the first timed one the time planes), the last chunk bins the target."""
+        yn = y.permute(0, 2, 3, 1)
+        kB = yn.shape[0]
+        if kB % self.B or tuple(yn.shape[1:]) != (self.H, self.W, self.C):
+            raise ValueError("chunk shape %s does not hold whole members of [%d, %d, %d, %d]" % (tuple(y.shape), self.B, self.C, self.H, self.W))
+        if target is None or tuple(target.shape) != (self.B, self.C, self.H, self.W):
+            raise ValueError("target shape %s is not [%d, %d, %d, %d]" % (None if target is None else tuple(target.shape), self.B, self.C,
+                                                                          self.H, self.W))
+        k = kB // self.B
+        if m0 != self._n or m0 + k > self.S or self._step >= self.Tk:
+            raise ValueError("members must be fed in order, every step's chunks before the next step's")
+        t_before = self._t[m0]
+        if time and any(self._t[m] != t_before for m in range(m0, m0 + k)):
+            raise ValueError("members of one chunk hold different numbers of time steps")
+        H.check_device(yn)
+        tn = target.permute(0, 2, 3, 1)
+        H.check_act(tn)
+        H.check_device(tn)
+        last = m0 + k == self.S
+        t = self._step
+        if m0 == 0:
+            self.cnt[:, :, t].zero_()
+            self.jnt[:, :, t].zero_()
+            if time and t_before == 0:
+                self.mt[0].zero_()
+                self.mt[1].zero_()
+                self.tj.zero_()
+        self._count(0, yn, self.S, k, m0, t, time)
+        if last:
+            self._count(1, tn, 1, 1, 0, t, time)
+            if time:
+                self._timed.append(t)
+        if time:
+            for m in range(m0, m0 + k):
+                self._t[m] += 1
+        self._n = 0 if last else self._n + k
+        self._step += 1 if last else 0
+
+    def finalize(self):
+        """-> dict of the outputs; the time aggregates cover the steps folded with time=True."""
+        if self._step != self.Tk:
+            raise RuntimeError("%d of %d steps folded" % (self._step, self.Tk))
+        T = self._t[0]
+        if T < 1 or any(t != T for t in self._t) or len(self._timed) != T:
+            raise RuntimeError("no time statistics: no step was folded with time=True")
+        dev = self.cnt.device
+        f32 = lambda v: v.to(torch.float32).to(dev)                            # noqa: E731
+        nj = self.nbj + 2
+        cnt, jnt = self.cnt.cpu().to(torch.int64), self.jnt.cpu().to(torch.int64)
+        mt, tmt, tj = self.mt[0].cpu().to(torch.int64), self.mt[1].cpu().to(torch.int64)[:, 0], self.tj.cpu().to(torch.int64)
+        ints = {"pdf_count": cnt[0], "target_count": cnt[1], "joint_count": jnt[0].view(self.B, self.Tk, self.R, self.P, nj, nj),
+                "target_joint_count": jnt[1].view(self.B, self.Tk, self.R, self.P, nj, nj), "time_member_count": mt,
+                "time_count": mt.sum(1), "time_target_count": tmt, "time_joint_count": tj[0].view(self.B, self.R, self.P, nj, nj),
+                "time_target_joint_count": tj[1].view(self.B, self.R, self.P, nj, nj)}
+        o = {key: v.to(dev) for key, v in ints.items()}
+        h = (self.ranges[..., 1] - self.ranges[..., 0]) / self.nb                # [B, F] fp64
+        h5, h4 = h.view(self.B, 1, 1, self.F, 1), h.view(self.B, 1, self.F, 1)
+        o["pdf"], o["target_pdf"] = f32(pdf_density(cnt[0], h5)), f32(pdf_density(cnt[1], h5))
+        tc = ints["time_count"]
+        o["time_pdf"], o["time_target_pdf"] = f32(pdf_density(tc, h4)), f32(pdf_density(tmt, h4))
+        dm = pdf_density(mt, h5)                                               # [B, S, R, F, nb]
+        o["time_pdf_mean"], o["time_pdf_std"] = f32(dm.mean(1)), f32(dm.std(1, unbiased=False))
+        o["w1"], o["js"] = f32(pdf_w1(cnt[0], cnt[1], h5[..., 0])), f32(pdf_js(cnt[0], cnt[1]))
+        o["time_w1"], o["time_js"] = f32(pdf_w1(tc, tmt, h4[..., 0])), f32(pdf_js(tc, tmt))
+        o["time_member_w1"] = f32(pdf_w1(mt, tmt.unsqueeze(1), h5[..., 0]))
+        o["time_joint_js"] = f32(pdf_js(tj[0], tj[1]))
+        o["pdf_edges"], o["joint_edges"] = self.E, self.JE.view(self.B, self.P, 2, self.nbj + 1)
+        o["pdf_ranges"] = self.ranges
+        o["pdf_fields"], o["pdf_joint"], o["pdf_regions"] = self.fields, self.joint, self.regions
+        return o
+
+
 def energy_groups(groups, C):
     """The checks of EnsembleEnergy's groups argument for C channels: non-empty tuples of distinct channels in 0..C-1, every channel in
     at most one group -> the groups as a tuple of tuples of ints."""

@@ -99,8 +99,28 @@ _TARGET_STATS = (("target_time_mean", "time_mean_mean"), ("target_time_rms", "ti
                  ("target_time_tke", "time_tke_mean"), ("target_time_vort", "time_vort_mean"))
 
 
+def _pdf_target_fields(tp, kinds, grid):
+    """tp [B, T, C, H, W] fp64 physical target -> per field of `kinds` (tmg_ops.EnsemblePdfs' codes) its values [B, T, H, W]: the
+    channel itself, or speed / vort / div by the 3x3 stencil of pc/ with zero padding (plain torch: this only chooses ranges)."""
+    U, V = tp[:, :, 0], tp[:, :, 1]
+    pad = lambda a: torch.nn.functional.pad(a, (1, 1, 1, 1))                  # noqa: E731
+    ddx = lambda q: 2 * q[..., 1:-1, 2:] + q[..., :-2, 2:] + q[..., 2:, 2:] - 2 * q[..., 1:-1, :-2] - q[..., :-2, :-2] - q[..., 2:, :-2]   # noqa: E731
+    ddy = lambda q: 2 * q[..., 2:, 1:-1] + q[..., 2:, :-2] + q[..., 2:, 2:] - 2 * q[..., :-2, 1:-1] - q[..., :-2, :-2] - q[..., :-2, 2:]   # noqa: E731
+    out = []
+    for k in kinds:
+        if k < 4:
+            out.append(tp[:, :, k])
+        elif k == 4:
+            out.append(torch.sqrt(U * U + V * V))
+        else:
+            rdx, rdy = 0.125 / float(grid[0]), 0.125 / float(grid[1])
+            pu, pv = pad(U), pad(V)
+            out.append(ddx(pv) * rdx - ddy(pu) * rdy if k == 5 else ddx(pu) * rdx + ddy(pv) * rdy)
+    return out
+
+
 def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, turbulence, spectra=False,
-                   window="hann", scores=False, tspec=None, quant=None, energy=None, structure=None, events=None):
+                   window="hann", scores=False, tspec=None, quant=None, energy=None, structure=None, events=None, pdfs=None):
     """The body of modelPredStats, modelPredTurbulence (turbulence: grid = (args.dx, args.dy)), modelPredSpectra (spectra: the same
     chunks also go through an EnsembleSpectrum with `window`), modelPredScores (scores: the same chunks also go through an
     EnsembleScores with the step's normalised target) and modelPredTimeSpectra (tspec = (nfreq, window, dt between kept steps): the
@@ -109,7 +129,9 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
     groups: the same chunks also go through an EnsembleEnergy with the step's normalised target) and modelPredStructure (structure =
     (lags, weights): the same chunks also go through an EnsembleStructure with the step's normalised target and grid = (args.dx,
     args.dy)) and modelPredEvents (events = (events, scales): the same chunks also go through an EnsembleEvents with the step's
-    normalised target): same seed draws in the same order, same
+    normalised target) and modelPredPdfs (pdfs = the keywords of EnsemblePdfs, with ranges None for the target's own and center
+    "target" for its time mean: the same chunks also go through an EnsemblePdfs with the step's normalised target and grid =
+    (args.dx, args.dy); neither option draws from the host RNG or iterates the loader again): same seed draws in the same order, same
     folding, same re-anchoring, so that the keys they share hold identical values under the same host RNG state."""
     import tmg_ops as ops
     core = getattr(model, "module", model)
@@ -131,6 +153,7 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
     in_std, in_mu = core.in_std.to(dev).view(shp), core.in_mu.to(dev).view(shp)
     out_std, out_mu = core.out_std.to(dev), core.out_mu.to(dev)
     outs, targets, inputs, sf_lags = {}, [], [], {}
+    case0 = 0                                                                 # cases before this mini-batch
     with torch.no_grad():
         for mbIdx, (input0, target0, u0) in enumerate(testing_loader):
             log.log('Running mini-batch {:d}/{:d}'.format(mbIdx + 1, len(testing_loader)))
@@ -143,7 +166,7 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
             B, C, Hh, Ww = inp.size(0), tgt.size(2), tgt.size(-2), tgt.size(-1)
             if C != 3:
                 raise ValueError("%s scales (ux, uy, p) by (u0, u0, u0^2) as modelPred does: 3 target channels, got %d" % (name, C))
-            if (scores or tspec is not None or quant is not None or energy is not None or structure is not None or events is not None) and target0.size(1) <= (nkeep - 1) * stride:
+            if (scores or tspec is not None or quant is not None or energy is not None or structure is not None or events is not None or pdfs is not None) and target0.size(1) <= (nkeep - 1) * stride:
                 raise ValueError("%s: the target series holds %d steps, kept step %d needs step %d"
                                  % (name, target0.size(1), nkeep - 1, (nkeep - 1) * stride))
             keys = []
@@ -169,7 +192,36 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
                                         weights=structure[1], grid=(args.dx, args.dy)) if structure is not None else None
             evs = ops.EnsembleEvents(samples, B, C, Hh, Ww, nkeep, dev, out_mu, out_std, u=u.view(B, 3)[:, :C], events=events[0],
                                      scales=events[1]) if events is not None else None
-            tnorm = target0.to(dev) if scores or qt is not None or en is not None or sfn is not None or evs is not None else None                # the normalised series; one step at a time goes channels-last
+            pdf = None
+            if pdfs is not None:
+                kw = dict(pdfs)
+                pgrid = (args.dx, args.dy)
+                kinds = ops.pdf_args(kw["fields"], kw["bins"], [(0.0, 1.0)] * len(kw["fields"]), kw["joint"], kw["joint_bins"], kw["regions"],
+                                     pgrid, B, C, Hh, Ww)[0]
+                # the target's physical series at the kept steps from t_start on, in fp64 (range and centre only: not the hot path)
+                tk = tgt[:, t_start * stride:(nkeep - 1) * stride + 1:stride].double()
+                if isinstance(kw["center"], str):
+                    kw["center"] = tk.mean(1).float()
+                elif kw["center"] is not None:
+                    kw["center"] = torch.as_tensor(kw["center"])[case0:case0 + B]
+                if kw["ranges"] is not None and torch.as_tensor(kw["ranges"]).dim() == 3:
+                    kw["ranges"] = torch.as_tensor(kw["ranges"])[case0:case0 + B]
+                if kw["ranges"] is None:
+                    cen = None if kw["center"] is None else kw["center"].to(dev).float().double().unsqueeze(1)
+                    vals = _pdf_target_fields(tk, kinds, pgrid)
+                    rg = torch.zeros(B, len(kinds), 2, dtype=torch.float64)
+                    for f, (k, v) in enumerate(zip(kinds, vals)):
+                        if k < 4 and cen is not None:
+                            v = v - cen[:, :, k]
+                        lo, hi = v.reshape(B, -1).min(1).values.cpu(), v.reshape(B, -1).max(1).values.cpu()
+                        if bool((hi <= lo).any()):
+                            raise ValueError("%s: field %r of the target of case %d is constant (%r): give ranges"
+                                             % (name, kw["fields"][f], case0 + int((hi <= lo).nonzero()[0]), float(lo[(hi <= lo).nonzero()[0]])))
+                        rg[:, f, 0], rg[:, f, 1] = lo - 0.25 * (hi - lo), hi + 0.25 * (hi - lo)
+                    kw["ranges"] = rg
+                pdf = ops.EnsemblePdfs(samples, B, C, Hh, Ww, nkeep, dev, out_mu, out_std, u=u.view(B, 3)[:, :C], grid=pgrid, **kw)
+            case0 += B
+            tnorm = target0.to(dev) if scores or qt is not None or en is not None or sfn is not None or evs is not None or pdf is not None else None                # the normalised series; one step at a time goes channels-last
             for tstep in range(tmax):
                 keep = tstep % stride == 0 and tstep // stride < nkeep
                 tj = tnorm[:, tstep].contiguous(memory_format=torch.channels_last) if keep and tnorm is not None else None
@@ -191,6 +243,8 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
                             sfn.add(y0, m0, tj, time=tstep // stride >= t_start)
                         if evs is not None:
                             evs.add(y0, m0, tj, time=tstep // stride >= t_start)
+                        if pdf is not None:
+                            pdf.add(y0, m0, tj, time=tstep // stride >= t_start)
                     if tstep % 20 == 0:
                         states[ci] = [(0.5 * h + 0.5 * hk, 0.5 * c + 0.5 * ck) for (h, c), (hk, ck) in zip(states[ci], anchors[ci])]
             for key, t in st.finalize().items():
@@ -222,6 +276,12 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
             if evs is not None:
                 for key, t in evs.finalize().items():
                     if key == "event_scales":
+                        sf_lags[key] = t
+                    else:
+                        outs.setdefault(key, []).append(t.cpu())
+            if pdf is not None:
+                for key, t in pdf.finalize().items():
+                    if key in ("pdf_fields", "pdf_joint", "pdf_regions"):
                         sf_lags[key] = t
                     else:
                         outs.setdefault(key, []).append(t.cpu())
@@ -521,3 +581,47 @@ def modelPredEvents(args, model, testing_loader, log, samples=1, stride=1, tmax=
     events, scales = ops.event_args(events, scales, 3)
     return _ensembleStats("modelPredEvents", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False,
                           events=(tuple(events), tuple(scales)))
+
+
+def modelPredPdfs(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, fields=("ux", "uy", "p", "vort"),
+                  bins=64, ranges=None, joint=(("ux", "uy"),), joint_bins=32, regions=None, center=None):
+    """modelPredStats plus the probability densities of the flow quantities themselves, pooled over regions of the flow, for the
+    ensemble and for the target, still without forming modelPred's [samples, N, T, C, H, W] tensor (tmg_ops.EnsemblePdfs, grid =
+    (args.dx, args.dy)): the PDF of the streamwise velocity in the wake, of the vorticity (whose tails are the vortex cores a smeared
+    surrogate loses first), of the divergence (nothing constrains a sampled field to be incompressible), and the joint PDF of
+    (ux, uy), whose quadrants are the sweep and ejection events of quadrant analysis.  The target of kept step j is series step
+    j * stride; a series that is too short raises.  Channel scales (u0, u0, u0^2).  Same roll-outs as modelPredStats: under the same
+    host RNG state the keys both return are identical; no option draws from the host RNG, and the loader is iterated once.
+
+    fields: up to 8 of a channel 0..2 ("ux", "uy", "p"), "speed", "vort", "div" (a field may be listed twice with two ranges).
+    bins: 1..128 uniform bins per field, plus an underflow and an overflow bin; a value on an edge belongs to the bin above.
+    ranges: one (lo, hi) per field in physical units, or [N, F, 2] per case; None: per case and field the min and max of that field of
+    the case's target series over the kept steps from t_start on, both ends widened by a quarter of the span (a constant field raises).
+    joint: up to 2 pairs of listed fields, joint_bins (1..32) bins per axis over the same ranges.  regions: up to 4 pixel boxes
+    (x0, x1, y0, y1), half open, x along W, possibly overlapping; None: the whole field.  center: None, [N, C, H, W] in physical
+    units, or "target" for the target's time mean over the same steps: channel fields are then binned as fluctuations about it, so
+    that ("ux", "uy") is the quadrant plane about the reference mean flow.
+
+    Returns modelPredStats' dict plus (CPU tensors; F fields, P pairs, R regions, nb = bins, nbj = joint_bins, S = samples, kept
+    steps t_start..Tk-1 are the timed ones; bins 0 and nb + 1 are the under- and overflow):
+      pdf_count, target_count [N, Tk, R, F, nb+2]   int64: the histograms per kept step, pooled over members and pixels / of the target
+      joint_count, target_joint_count [N, Tk, R, P, nbj+2, nbj+2]   int64: the joint histograms, the first field of a pair on the rows
+      time_member_count [N, S, R, F, nb+2]          int64: each member's histogram pooled over the timed steps
+      time_count, time_target_count [N, R, F, nb+2], time_joint_count, time_target_joint_count [N, R, P, nbj+2, nbj+2]   int64
+      pdf, target_pdf [N, Tk, R, F, nb]             inner count / (all counts * bin width): what is out of range is missing from
+                                                    the integral
+      time_pdf, time_target_pdf [N, R, F, nb]       the same of the pooled counts
+      time_pdf_mean, time_pdf_std [N, R, F, nb]     mean / population std over the members of each member's own time-pooled density
+      w1, js [N, Tk, R, F], time_w1, time_js [N, R, F]   the pooled ensemble against the target: the Wasserstein-1 distance (physical
+                                                    units; each bin's mass at its centre, the out-of-range masses one width outside)
+                                                    and the Jensen-Shannon divergence in bits over the nb + 2 bins, in [0, 1]
+      time_member_w1 [N, S, R, F]                   each member's time-pooled distribution against the target's: one member is a
+                                                    legitimate realisation, so it should match within sampling noise
+      time_joint_js [N, R, P]                       the Jensen-Shannon divergence of the time-pooled joint tables
+      pdf_edges [N, F, nb+1], joint_edges [N, P, 2, nbj+1], pdf_ranges [N, F, 2]   float64: the physical edges and the (lo, hi) used
+      pdf_fields, pdf_joint, pdf_regions            as given (regions None: the whole field as one box)."""
+    if isinstance(center, str) and center != "target":
+        raise ValueError("center is None, an array [N, C, H, W] in physical units or \"target\", got %r" % (center,))
+    return _ensembleStats("modelPredPdfs", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False,
+                          pdfs=dict(fields=tuple(fields), bins=bins, ranges=ranges, joint=tuple(tuple(pr) for pr in joint), joint_bins=joint_bins,
+                                    regions=regions, center=center))
