@@ -1618,7 +1618,136 @@ class LeadingChannelsFn(torch.autograd.Function):
         return dx, None
 
 
-class EnsembleStats:
+class EnsembleFeed:
+    """The feeding protocol of the Ensemble* accumulators: S members of B cases of [C, H, W] over Tk steps.  Members are fed in
+    order (m0 = 0 first), whole members per chunk, every step's chunks before the next step's; the step's last chunk is the one that
+    scores it.  Every accumulator folds in this one order, which is what makes its outputs bit-reproducible for every chunking.
+
+    Host bookkeeping only: no device, no kernel.  An accumulator's add() is open_chunk, its own launches, close_chunk; its
+    finalize() starts with finalize_guard.  C = None accepts any 2..4 channels (EnsembleSpectrum reads channels 0 and 1 only);
+    time = None is the variant whose add() has no time argument (EnsembleTimeSpectrum: every fed step counts)."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps):
+        self.S, self.B, self.H, self.W, self.Tk = int(members), int(B), int(Hh), int(Ww), int(steps)
+        self.C = None if C is None else int(C)
+        self._n = 0             # members fed for the current step
+        self._step = 0          # the step being filled
+        self._t = [0] * self.S  # timed steps every member has been fed for
+        self._timed = []        # the steps whose last chunk came with time=True
+
+    def open_chunk(self, y, m0, time=True, target=None, required=False):
+        """The checks of a chunk y (API-shaped [k*B, C, H, W], rows member-major) that holds the step's members m0 .. m0 + k - 1:
+        shape, target (required: None is an error; else optional, or absent when the add() has none to pass), order, time.
+        -> (yn, tn, k, t_before, last): the channels-last views of y and of the target (None without one), the timed steps these
+        members hold so far (None when time is None) and whether the chunk is the step's last."""
+        yn = y.permute(0, 2, 3, 1)
+        kB = yn.shape[0]
+        if self.C is None:
+            if kB % self.B or tuple(yn.shape[1:3]) != (self.H, self.W) or not 2 <= yn.shape[3] <= 4:
+                raise ValueError("chunk shape %s does not hold whole members of [%d, 2..4, %d, %d]" % (tuple(y.shape), self.B, self.H, self.W))
+        elif (time is None and kB < 1) or kB % self.B or tuple(yn.shape[1:]) != (self.H, self.W, self.C):
+            raise ValueError("chunk shape %s does not hold whole members of [%d, %d, %d, %d]" % (tuple(y.shape), self.B, self.C, self.H, self.W))
+        if (required and target is None) or (target is not None and tuple(target.shape) != (self.B, self.C, self.H, self.W)):
+            raise ValueError("target shape %s is not [%d, %d, %d, %d]" % (None if target is None else tuple(target.shape), self.B, self.C,
+                                                                          self.H, self.W))
+        k = kB // self.B
+        if m0 != self._n or m0 + k > self.S or self._step >= self.Tk:
+            raise ValueError("members must be fed in order, every step's chunks before the next step's")
+        t_before = None if time is None else self._t[m0]
+        if time and any(self._t[m] != t_before for m in range(m0, m0 + k)):
+            raise ValueError("members of one chunk hold different numbers of time steps")
+        return yn, None if target is None else target.permute(0, 2, 3, 1), k, t_before, m0 + k == self.S
+
+    def close_chunk(self, m0, k, time, last):
+        """Count the chunk open_chunk accepted, after its launches."""
+        if time:
+            for m in range(m0, m0 + k):
+                self._t[m] += 1
+            if last:
+                self._timed.append(self._step)
+        self._n = 0 if last else self._n + k
+        self._step += 1 if last else 0
+
+    def finalize_guard(self, timed=True):
+        """Every step is fed -> the number of steps fed with time=True (timed=False, the variant without a time argument: Tk)."""
+        if not timed:
+            if self._step != self.Tk or self._n != 0:
+                raise RuntimeError("%d of %d steps fed" % (self._step, self.Tk))
+            return self.Tk
+        if self._step != self.Tk:
+            raise RuntimeError("%d of %d steps folded" % (self._step, self.Tk))
+        T = self._t[0]
+        if T < 1 or any(t != T for t in self._t) or len(self._timed) != T:
+            raise RuntimeError("no time statistics: no step was folded with time=True")
+        return T
+
+
+def _on_device(yn, tn=None):
+    """The device checks of a chunk and its target, where an add() makes them itself: after open_chunk, before its launches."""
+    H.check_device(yn)
+    if tn is not None:
+        H.check_act(tn)
+        H.check_device(tn)
+
+
+def _ens_channels(noun, C, why=""):
+    if not (2 <= C <= 4):
+        raise ValueError("%s need 2 <= C <= 4 channels%s, got %d" % (noun, why, C))
+
+
+def _ens_members(noun, members):
+    if not (1 <= int(members) <= SCORES_MAX_MEMBERS):
+        raise ValueError("%s need 1 <= members <= %d, got %d" % (noun, SCORES_MAX_MEMBERS, int(members)))
+
+
+def _ens_tables(C, reason, out_std, out_mu=None):
+    """The first C entries of out_std (finite, strictly positive) and, when given, out_mu (finite) -> (sd, mu): fp32 CPU tensors, mu
+    None without out_mu."""
+    sd = torch.as_tensor(out_std, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
+    mu = None if out_mu is None else torch.as_tensor(out_mu, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
+    if mu is None and sd.numel() != C:
+        raise ValueError("out_std needs %d entries, got %d" % (C, sd.numel()))
+    if mu is not None and (sd.numel() != C or mu.numel() != C):
+        raise ValueError("out_mu / out_std need %d entries, got %d / %d" % (C, mu.numel(), sd.numel()))
+    if not bool((torch.isfinite(sd) & (sd > 0)).all()):
+        raise ValueError("out_std must be finite and strictly positive (%s), got %s" % (reason, sd.tolist()))
+    if mu is not None and not bool(torch.isfinite(mu).all()):
+        raise ValueError("out_mu must be finite, got %s" % mu.tolist())
+    return sd, mu
+
+
+def _ens_u(u, B, C, reason):
+    """u (finite, strictly positive) -> [B, C] fp32 CPU tensor, or None for 1."""
+    if u is None:
+        return None
+    u = torch.as_tensor(u, dtype=torch.float32).detach().reshape(B, C).cpu()
+    if not bool((torch.isfinite(u) & (u > 0)).all()):
+        raise ValueError("u must be finite and strictly positive (%s)" % reason)
+    return u
+
+
+def _ens_device(noun, device):
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("%s run on the HIP path: device %s is not a GPU (there is no CPU path)" % (noun, dev))
+    return dev
+
+
+def _ens_scale(sd, u, B, dtype):
+    """a[b, c] = u[b, c] out_std[c] (u None: 1), formed in dtype from the fp32 factors -> [B, C] CPU tensor."""
+    sd = sd.to(dtype).view(1, -1)
+    return (sd.expand(B, sd.shape[1]) if u is None else u.to(dtype) * sd).contiguous()
+
+
+def _ens_directions(entries):
+    """(channel, value, ">" | "<") entries -> the kernels' (channel, 1 for ">" else 0) list."""
+    return [(int(e[0]), 1 if e[2] == ">" else 0) for e in entries]
+
+
+_KEEPS_ORDER = "u * out_std > 0 keeps the members' order"
+
+
+class EnsembleStats(EnsembleFeed):
     """On-device statistics over the members of sampled roll-outs of B cases (tmg_ens_accum / tmg_ens_time_finalize): for every kept
     step the mean and population standard deviation (ddof 0, as np.std) over the members of each un-normalised channel
     yh = u[b, c] (out_std[c] y + out_mu[c]) and of the velocity magnitude sqrt(yh0^2 + yh1^2); per member the time mean and RMS
@@ -1635,17 +1764,14 @@ class EnsembleStats:
     time_vort_mean, time_vort_std (its time-mean vorticity), all [B, H, W].  The other outputs do not depend on grid."""
 
     def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, grid=None):
-        if not (2 <= C <= 4):
-            raise ValueError("ensemble statistics need 2 <= C <= 4 channels (the magnitude is formed from channels 0 and 1), got %d" % C)
+        _ens_channels("ensemble statistics", C, " (the magnitude is formed from channels 0 and 1)")
         if grid is not None:
             grid = tuple(float(g) for g in grid)
             if len(grid) != 2 or not all(math.isfinite(g) and g > 0 for g in grid):
                 raise ValueError("grid needs two positive finite cell sizes (dx, dy), got %s" % (grid,))
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("ensemble statistics run on the HIP path: device %s is not a GPU (there is no CPU path)" % dev)
+        dev = _ens_device("ensemble statistics", device)
         self.grid = grid
-        self.S, self.B, self.C, self.H, self.W, self.Tk = int(members), int(B), int(C), int(Hh), int(Ww), int(steps)
+        EnsembleFeed.__init__(self, members, B, C, Hh, Ww, steps)
         HW = self.H * self.W
         f32 = dict(device=dev, dtype=torch.float32)
         self.mu = torch.as_tensor(out_mu, **f32).reshape(-1)[:C].contiguous()
@@ -1661,24 +1787,11 @@ class EnsembleStats:
             self.vort_state = torch.empty((2, B, HW), **f32)                 # the step's (mean, M2) of the vorticity
             self.turb_state = torch.empty((2, self.S, B, HW), **f32)         # per member: time co-moment of (u, v), time-mean vorticity
             self.out.update(vort_mean=torch.empty((B, self.Tk, Hh, Ww), **f32), vort_std=torch.empty((B, self.Tk, Hh, Ww), **f32))
-        self._n = 0           # members folded into the current step
-        self._step = 0        # the step being filled
-        self._t = [0] * self.S  # steps folded into each member's time statistics
 
     def add(self, y, m0, time=True):
         """Fold the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
         channel-slice; rows member-major)."""
-        yn = y.permute(0, 2, 3, 1)
-        kB = yn.shape[0]
-        if kB % self.B or tuple(yn.shape[1:]) != (self.H, self.W, self.C):
-            raise ValueError("chunk shape %s does not hold whole members of [%d, %d, %d, %d]" % (tuple(y.shape), self.B, self.C, self.H, self.W))
-        k = kB // self.B
-        if m0 != self._n or m0 + k > self.S or self._step >= self.Tk:
-            raise ValueError("members must be fed in order, every step's chunks before the next step's")
-        t_before = self._t[m0]
-        if time and any(self._t[m] != t_before for m in range(m0, m0 + k)):
-            raise ValueError("members of one chunk hold different numbers of time steps")
-        last = m0 + k == self.S
+        yn, _, k, t_before, last = self.open_chunk(y, m0, time)    # the device checks are the wrappers'
         HW = self.H * self.W
         o = self.out
         t = self._step
@@ -1690,19 +1803,11 @@ class EnsembleStats:
         outs = (o["mean"][:, t], o["std"][:, t], o["mag_mean"][:, t], o["mag_std"][:, t]) if last else None
         H.ens_accum(yn, self.u, self.mu, self.sd, self.step_state[0], self.step_state[1], self.time_state[0], self.time_state[1], outs,
                     (self.Tk * self.C * HW, self.Tk * HW), k, self._n, m0, t_before, flags)
-        if time:
-            for m in range(m0, m0 + k):
-                self._t[m] += 1
-        self._n = 0 if last else self._n + k
-        self._step += 1 if last else 0
+        self.close_chunk(m0, k, time, last)
 
     def finalize(self):
         """-> dict of the outputs; the time statistics cover the steps folded with time=True."""
-        if self._step != self.Tk:
-            raise RuntimeError("%d of %d steps folded" % (self._step, self.Tk))
-        T = self._t[0]
-        if T < 1 or any(t != T for t in self._t):
-            raise RuntimeError("no time statistics: no step was folded with time=True")
+        T = self.finalize_guard()
         shp = (self.B, self.C, self.H, self.W)
         names = ("time_mean_mean", "time_mean_std", "time_rms_mean", "time_rms_std")
         for n in names:
@@ -1721,7 +1826,7 @@ class EnsembleStats:
 SCORES_MAX_MEMBERS = 1024
 
 
-class EnsembleScores:
+class EnsembleScores(EnsembleFeed):
     """On-device calibration scores of sampled roll-outs of B cases against the target (tmg_ens_score_store / tmg_ens_score_step).
     For case b, kept step t, channel c and pixel p, with the members x_1..x_S (raw normalised model outputs), the normalised target
     y, a = u[b, c] out_std[c] > 0 and the un-normalised xh = u (out_std x + out_mu), yh likewise:
@@ -1731,64 +1836,34 @@ class EnsembleScores:
     out_mu cancels in every term and a > 0 keeps the order, so the kernels work on the raw values and multiply by a once; out_mu is
     not an input.  rank_hist[b, t, c, r] counts the pixels of rank r = 0..S.
 
-    Feeding protocol of EnsembleStats: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
+    Feeding protocol of EnsembleFeed: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
     chunks before the next step's; every chunk comes with the step's target, and the last chunk's is the one that is scored.
     Outputs (device tensors): crps, crps_fair [B, Tk, C, H, W]; rank_hist [B, Tk, C, S + 1] int64; finalize() adds time_crps,
     time_crps_fair [B, C, H, W] (running means over the steps folded with time=True) and time_rank_hist [B, C, S + 1] int64 (the sum
     of rank_hist over those steps)."""
 
     def __init__(self, members, B, C, Hh, Ww, steps, device, out_std, u=None):
-        if not (2 <= C <= 4):
-            raise ValueError("ensemble scores need 2 <= C <= 4 channels, got %d" % C)
-        if not (1 <= int(members) <= SCORES_MAX_MEMBERS):
-            raise ValueError("ensemble scores need 1 <= members <= %d, got %d" % (SCORES_MAX_MEMBERS, int(members)))
-        sd = torch.as_tensor(out_std, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
-        if sd.numel() != C:
-            raise ValueError("out_std needs %d entries, got %d" % (C, sd.numel()))
-        if not bool((torch.isfinite(sd) & (sd > 0)).all()):
-            raise ValueError("out_std must be finite and strictly positive (the scores scale with u * out_std), got %s" % sd.tolist())
-        if u is not None:
-            u = torch.as_tensor(u, dtype=torch.float32).detach().reshape(B, C).cpu()
-            if not bool((torch.isfinite(u) & (u > 0)).all()):
-                raise ValueError("u must be finite and strictly positive (the scores scale with u * out_std)")
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("ensemble scores run on the HIP path: device %s is not a GPU (there is no CPU path)" % dev)
-        self.S, self.B, self.C, self.H, self.W, self.Tk = int(members), int(B), int(C), int(Hh), int(Ww), int(steps)
+        noun, why = "ensemble scores", "the scores scale with u * out_std"
+        _ens_channels(noun, C)
+        _ens_members(noun, members)
+        sd, _ = _ens_tables(C, why, out_std)
+        u = _ens_u(u, B, C, why)
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, C, Hh, Ww, steps)
         HW = self.H * self.W
         f32 = dict(device=dev, dtype=torch.float32)
-        self.scale = (sd.view(1, C).expand(self.B, C) if u is None else u * sd.view(1, C)).to(dev).contiguous()
+        self.scale = _ens_scale(sd, u, self.B, torch.float32).to(dev)
         self.xs = torch.empty((self.S, self.B, C, HW), **f32)
         self.time_state = torch.empty((2, self.B, C, HW), **f32)
         self.hist = torch.zeros((self.B, self.Tk, C, self.S + 1), device=dev, dtype=torch.int32)
         self.out = {"crps": torch.empty((self.B, self.Tk, C, Hh, Ww), **f32), "crps_fair": torch.empty((self.B, self.Tk, C, Hh, Ww), **f32)}
-        self._n = 0           # members stored for the current step
-        self._step = 0        # the step being filled
-        self._t = [0] * self.S  # timed steps every member has been fed for
-        self._timed = []      # the steps whose scores went into the time means
 
     def add(self, y, m0, target, time=True):
         """Store the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
         channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride rule.  The step's
         last chunk scores the step against its target."""
-        yn = y.permute(0, 2, 3, 1)
-        kB = yn.shape[0]
-        if kB % self.B or tuple(yn.shape[1:]) != (self.H, self.W, self.C):
-            raise ValueError("chunk shape %s does not hold whole members of [%d, %d, %d, %d]" % (tuple(y.shape), self.B, self.C, self.H, self.W))
-        if target is None or tuple(target.shape) != (self.B, self.C, self.H, self.W):
-            raise ValueError("target shape %s is not [%d, %d, %d, %d]" % (None if target is None else tuple(target.shape), self.B, self.C,
-                                                                          self.H, self.W))
-        k = kB // self.B
-        if m0 != self._n or m0 + k > self.S or self._step >= self.Tk:
-            raise ValueError("members must be fed in order, every step's chunks before the next step's")
-        t_before = self._t[m0]
-        if time and any(self._t[m] != t_before for m in range(m0, m0 + k)):
-            raise ValueError("members of one chunk hold different numbers of time steps")
-        H.check_device(yn)
-        tn = target.permute(0, 2, 3, 1)
-        H.check_act(tn)
-        H.check_device(tn)
-        last = m0 + k == self.S
+        yn, tn, k, t_before, last = self.open_chunk(y, m0, time, target, required=True)
+        _on_device(yn, tn)
         H.ens_score_store(yn, self.xs, k, m0)
         if last:
             HW = self.H * self.W
@@ -1797,21 +1872,11 @@ class EnsembleScores:
             H.ens_score_step(self.xs, tn, self.scale, o["crps"][:, t], o["crps_fair"][:, t], self.hist[:, t],
                              (self.time_state[0], self.time_state[1]), (self.Tk * self.C * HW, self.Tk * self.C * (self.S + 1)),
                              t_before, 1 if time else 0)
-            if time:
-                self._timed.append(t)
-        if time:
-            for m in range(m0, m0 + k):
-                self._t[m] += 1
-        self._n = 0 if last else self._n + k
-        self._step += 1 if last else 0
+        self.close_chunk(m0, k, time, last)
 
     def finalize(self):
         """-> dict of the outputs; the time statistics cover the steps folded with time=True."""
-        if self._step != self.Tk:
-            raise RuntimeError("%d of %d steps folded" % (self._step, self.Tk))
-        T = self._t[0]
-        if T < 1 or any(t != T for t in self._t) or len(self._timed) != T:
-            raise RuntimeError("no time statistics: no step was folded with time=True")
+        self.finalize_guard()
         shp = (self.B, self.C, self.H, self.W)
         self.out["rank_hist"] = self.hist.to(torch.int64)
         self.out["time_crps"] = self.time_state[0].view(shp)
@@ -1863,7 +1928,7 @@ def raw_thresholds(entries, B, C, mu, sd, u=None):
     return thr.to(torch.float32)
 
 
-class EnsembleQuantiles:
+class EnsembleQuantiles(EnsembleFeed):
     """On-device prediction intervals of sampled roll-outs of B cases (tmg_ens_score_store / tmg_ens_quant_step): per case b, kept
     step t, channel c and pixel p the quantiles of the S members at the probability `levels` (numpy's method="linear": exact order
     statistics, ties broken by member index, then one fp32 interpolation, see quantile_levels), un-normalised as
@@ -1873,7 +1938,7 @@ class EnsembleQuantiles:
     thresholds (value / u - out_mu) / out_std, formed in fp64 and rounded once.  Non-finite members are not supported: the outputs
     of a pixel that holds one are unspecified.
 
-    Feeding protocol of EnsembleScores: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
+    Feeding protocol of EnsembleFeed: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
     chunks before the next step's.  The target is optional, but given for every step or for none; the last chunk's is the one used.
     Outputs (device tensors): quant [B, Tk, Q, C, H, W]; exceed_prob [B, Tk, K, H, W] (K > 0); finalize() adds, over the steps folded
     with time=True (Tn of them), time_quant [B, Q, C, H, W] (the running mean of quant), with a target time_below_count int64 (the
@@ -1882,29 +1947,16 @@ class EnsembleQuantiles:
     float64 as given."""
 
     def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, levels=(0.05, 0.5, 0.95), exceed=()):
-        if not (2 <= C <= 4):
-            raise ValueError("ensemble quantiles need 2 <= C <= 4 channels, got %d" % C)
+        noun = "ensemble quantiles"
+        _ens_channels(noun, C)
         if int(steps) < 1:
-            raise ValueError("ensemble quantiles need steps >= 1, got %d" % int(steps))
+            raise ValueError("%s need steps >= 1, got %d" % (noun, int(steps)))
         lv, ex = quantile_args(levels, exceed, C)
-        if not (1 <= int(members) <= SCORES_MAX_MEMBERS):
-            raise ValueError("ensemble quantiles need 1 <= members <= %d, got %d" % (SCORES_MAX_MEMBERS, int(members)))
-        sd = torch.as_tensor(out_std, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
-        mu = torch.as_tensor(out_mu, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
-        if sd.numel() != C or mu.numel() != C:
-            raise ValueError("out_mu / out_std need %d entries, got %d / %d" % (C, mu.numel(), sd.numel()))
-        if not bool((torch.isfinite(sd) & (sd > 0)).all()):
-            raise ValueError("out_std must be finite and strictly positive (u * out_std > 0 keeps the members' order), got %s" % sd.tolist())
-        if not bool(torch.isfinite(mu).all()):
-            raise ValueError("out_mu must be finite, got %s" % mu.tolist())
-        if u is not None:
-            u = torch.as_tensor(u, dtype=torch.float32).detach().reshape(B, C).cpu()
-            if not bool((torch.isfinite(u) & (u > 0)).all()):
-                raise ValueError("u must be finite and strictly positive (u * out_std > 0 keeps the members' order)")
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("ensemble quantiles run on the HIP path: device %s is not a GPU (there is no CPU path)" % dev)
-        self.S, self.B, self.C, self.H, self.W, self.Tk = int(members), int(B), int(C), int(Hh), int(Ww), int(steps)
+        _ens_members(noun, members)
+        sd, mu = _ens_tables(C, _KEEPS_ORDER, out_std, out_mu)
+        u = _ens_u(u, B, C, _KEEPS_ORDER)
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, C, Hh, Ww, steps)
         self.levels = lv
         self.lo, self.hi, self.w = quantile_levels(self.S, lv)
         self.Q, self.K = len(lv), len(ex)
@@ -1916,40 +1968,20 @@ class EnsembleQuantiles:
         self.tquant = torch.empty((self.B, self.Q, C, HW), **f32)
         self.tbelow = torch.empty((self.B, self.Q, C, HW), device=dev, dtype=torch.int32)
         self.out = {"quant": torch.empty((self.B, self.Tk, self.Q, C, Hh, Ww), **f32)}
-        self.ex = [(int(e[0]), 1 if e[2] == ">" else 0) for e in ex]
+        self.ex = _ens_directions(ex)
         self.thr = self.texceed = None
         if self.K:
             self.thr = raw_thresholds(ex, self.B, C, mu, sd, u).to(dev).contiguous()
             self.texceed = torch.empty((self.B, self.K, HW), device=dev, dtype=torch.int32)
             self.out["exceed_prob"] = torch.empty((self.B, self.Tk, self.K, Hh, Ww), **f32)
-        self._n = 0           # members stored for the current step
-        self._step = 0        # the step being filled
-        self._t = [0] * self.S  # timed steps every member has been fed for
         self._scored = None   # whether the steps come with a target: the first step decides
 
     def add(self, y, m0, target=None, time=True):
         """Store the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
         channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride rule, or None.  The
         step's last chunk selects the step's quantiles."""
-        yn = y.permute(0, 2, 3, 1)
-        kB = yn.shape[0]
-        if kB % self.B or tuple(yn.shape[1:]) != (self.H, self.W, self.C):
-            raise ValueError("chunk shape %s does not hold whole members of [%d, %d, %d, %d]" % (tuple(y.shape), self.B, self.C, self.H, self.W))
-        if target is not None and tuple(target.shape) != (self.B, self.C, self.H, self.W):
-            raise ValueError("target shape %s is not [%d, %d, %d, %d]" % (tuple(target.shape), self.B, self.C, self.H, self.W))
-        k = kB // self.B
-        if m0 != self._n or m0 + k > self.S or self._step >= self.Tk:
-            raise ValueError("members must be fed in order, every step's chunks before the next step's")
-        t_before = self._t[m0]
-        if time and any(self._t[m] != t_before for m in range(m0, m0 + k)):
-            raise ValueError("members of one chunk hold different numbers of time steps")
-        H.check_device(yn)
-        tn = None
-        if target is not None:
-            tn = target.permute(0, 2, 3, 1)
-            H.check_act(tn)
-            H.check_device(tn)
-        last = m0 + k == self.S
+        yn, tn, k, t_before, last = self.open_chunk(y, m0, time, target)
+        _on_device(yn, tn)
         if last:
             if self._scored is None:
                 self._scored = tn is not None
@@ -1963,19 +1995,11 @@ class EnsembleQuantiles:
             H.ens_quant_step(self.xs, tn, self.u, self.mu, self.sd, self.lo, self.hi, self.w, self.thr, self.ex, o["quant"][:, t],
                              o["exceed_prob"][:, t] if self.K else None, (self.tquant, self.tbelow, self.texceed),
                              (self.Tk * self.Q * self.C * HW, self.Tk * self.K * HW), t_before, (1 if time else 0) | (2 if tn is not None else 0))
-        if time:
-            for m in range(m0, m0 + k):
-                self._t[m] += 1
-        self._n = 0 if last else self._n + k
-        self._step += 1 if last else 0
+        self.close_chunk(m0, k, time, last)
 
     def finalize(self):
         """-> dict of the outputs; the time aggregates cover the steps folded with time=True."""
-        if self._step != self.Tk:
-            raise RuntimeError("%d of %d steps folded" % (self._step, self.Tk))
-        T = self._t[0]
-        if T < 1 or any(t != T for t in self._t):
-            raise RuntimeError("no time statistics: no step was folded with time=True")
+        T = self.finalize_guard()
         shp = (self.B, self.Q, self.C, self.H, self.W)
         o = self.out
         o["time_quant"] = self.tquant.view(shp)
@@ -2056,7 +2080,7 @@ EVENT_STEP_KEYS = ("brier", "brier_rel", "brier_res", "brier_unc", "base_rate", 
 EVENT_TIME_KEYS = ("brier", "brier_rel", "brier_res", "brier_unc", "base_rate", "roc_area")
 
 
-class EnsembleEvents:
+class EnsembleEvents(EnsembleFeed):
     """On-device probabilistic event verification of sampled roll-outs of B cases against the target (tmg_ens_event_count /
     tmg_ens_event_step).  An event k is (channel, value, ">" | "<"), strict, in physical units ((0, 0.0, "<") is reverse flow); it
     is decided on the raw normalised values against the raw threshold of raw_thresholds (u out_std > 0 keeps the order).  Per case b,
@@ -2071,7 +2095,7 @@ class EnsembleEvents:
     The counts fold chunk by chunk: no member buffer [S][..] is kept.  The device memory of this class is O(B K HW) (the counts and
     four running sums per pixel, int32) plus the tables, not O(S B C HW).
 
-    Feeding protocol of EnsembleQuantiles: every step's members in chunks of whole members, in member order (m0 = 0 first), each
+    Feeding protocol of EnsembleFeed: every step's members in chunks of whole members, in member order (m0 = 0 first), each
     step's chunks before the next step's; every chunk comes with the step's target, and the last chunk's is the one that is used.
     Outputs (device tensors): rel_count, rel_hit [B, Tk, K, S + 1] int64; brier, brier_rel, brier_res, brier_unc, base_rate,
     fcst_rate, roc_area [B, Tk, K]; fss_raw [B, Tk, K, NS, 3] int64; fss [B, Tk, K, NS]; finalize() adds, over the steps folded with
@@ -2083,39 +2107,26 @@ class EnsembleEvents:
     S^2 sum o) / (S^2 Tn), and event_scales [NS] int64 as given."""
 
     def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, events=((0, 0.0, "<"),), scales=EVENT_DEFAULT_SCALES):
-        if not (2 <= C <= 4):
-            raise ValueError("ensemble events need 2 <= C <= 4 channels, got %d" % C)
+        noun = "ensemble events"
+        _ens_channels(noun, C)
         if int(steps) < 1:
-            raise ValueError("ensemble events need steps >= 1, got %d" % int(steps))
+            raise ValueError("%s need steps >= 1, got %d" % (noun, int(steps)))
         ev, sc = event_args(events, scales, C)
-        if not (1 <= int(members) <= SCORES_MAX_MEMBERS):
-            raise ValueError("ensemble events need 1 <= members <= %d, got %d" % (SCORES_MAX_MEMBERS, int(members)))
-        sd = torch.as_tensor(out_std, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
-        mu = torch.as_tensor(out_mu, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
-        if sd.numel() != C or mu.numel() != C:
-            raise ValueError("out_mu / out_std need %d entries, got %d / %d" % (C, mu.numel(), sd.numel()))
-        if not bool((torch.isfinite(sd) & (sd > 0)).all()):
-            raise ValueError("out_std must be finite and strictly positive (u * out_std > 0 keeps the members' order), got %s" % sd.tolist())
-        if not bool(torch.isfinite(mu).all()):
-            raise ValueError("out_mu must be finite, got %s" % mu.tolist())
-        if u is not None:
-            u = torch.as_tensor(u, dtype=torch.float32).detach().reshape(B, C).cpu()
-            if not bool((torch.isfinite(u) & (u > 0)).all()):
-                raise ValueError("u must be finite and strictly positive (u * out_std > 0 keeps the members' order)")
+        _ens_members(noun, members)
+        sd, mu = _ens_tables(C, _KEEPS_ORDER, out_std, out_mu)
+        u = _ens_u(u, B, C, _KEEPS_ORDER)
         S, Tk, HW, wmax = int(members), int(steps), int(Hh) * int(Ww), max(sc)
         if int(B) < 1 or HW < 1:
-            raise ValueError("ensemble events need B, H, W >= 1, got %d, %d, %d" % (B, Hh, Ww))
+            raise ValueError("%s need B, H, W >= 1, got %d, %d, %d" % (noun, B, Hh, Ww))
         if S * S * Tk >= 2 ** 31:
             raise ValueError("S^2 Tk = %d^2 * %d does not stay under 2^31 (the int32 per-pixel sums)" % (S, Tk))
         if S * S * wmax ** 4 * HW * Tk >= 2 ** 63:
             raise ValueError("S^2 w_max^4 HW Tk = %d^2 * %d^4 * %d * %d does not stay under 2^63 (the int64 raw sums)" % (S, wmax, HW, Tk))
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("ensemble events run on the HIP path: device %s is not a GPU (there is no CPU path)" % dev)
-        self.S, self.B, self.C, self.H, self.W, self.Tk = S, int(B), int(C), int(Hh), int(Ww), Tk
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, C, Hh, Ww, steps)
         self.events, self.scales = ev, sc
         self.K, self.NS = len(ev), len(sc)
-        self.ev = [(int(e[0]), 1 if e[2] == ">" else 0) for e in ev]
+        self.ev = _ens_directions(ev)
         self.thr = raw_thresholds(ev, self.B, C, mu, sd, u).to(dev).contiguous()
         self.plan = H.ens_event_plan(S, self.B, self.H, self.W, self.K, sc)
         i32 = dict(device=dev, dtype=torch.int32)
@@ -2123,54 +2134,24 @@ class EnsembleEvents:
         self.tsum = torch.empty((4, self.B, self.K, HW), **i32)
         self.rel = torch.empty((2, self.B, Tk, self.K, S + 1), **i32)
         self.fss_raw = torch.empty((self.B, Tk, self.K, self.NS, 3), device=dev, dtype=torch.int64)
-        self._n = 0           # members counted for the current step
-        self._step = 0        # the step being filled
-        self._t = [0] * S     # timed steps every member has been fed for
-        self._timed = []      # the steps that went into the time aggregates
 
     def add(self, y, m0, target, time=True):
         """Count the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
         channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride rule.  The step's
         last chunk verifies the step against its target."""
-        yn = y.permute(0, 2, 3, 1)
-        kB = yn.shape[0]
-        if kB % self.B or tuple(yn.shape[1:]) != (self.H, self.W, self.C):
-            raise ValueError("chunk shape %s does not hold whole members of [%d, %d, %d, %d]" % (tuple(y.shape), self.B, self.C, self.H, self.W))
-        if target is None or tuple(target.shape) != (self.B, self.C, self.H, self.W):
-            raise ValueError("target shape %s is not [%d, %d, %d, %d]" % (None if target is None else tuple(target.shape), self.B, self.C,
-                                                                          self.H, self.W))
-        k = kB // self.B
-        if m0 != self._n or m0 + k > self.S or self._step >= self.Tk:
-            raise ValueError("members must be fed in order, every step's chunks before the next step's")
-        t_before = self._t[m0]
-        if time and any(self._t[m] != t_before for m in range(m0, m0 + k)):
-            raise ValueError("members of one chunk hold different numbers of time steps")
-        H.check_device(yn)
-        tn = target.permute(0, 2, 3, 1)
-        H.check_act(tn)
-        H.check_device(tn)
-        last = m0 + k == self.S
+        yn, tn, k, t_before, last = self.open_chunk(y, m0, time, target, required=True)
+        _on_device(yn, tn)
         H.ens_event_count(yn, self.thr, self.ev, self.cnt, self.S, k, m0)
         if last:
             t = self._step
             H.ens_event_step(self.cnt, tn, self.thr, self.ev, self.scales, self.rel[0, :, t], self.rel[1, :, t], self.fss_raw[:, t],
                              self.tsum, (self.Tk * self.K * (self.S + 1), self.Tk * self.K * self.NS * 3), self.S, t_before,
                              1 if time else 0)
-            if time:
-                self._timed.append(t)
-        if time:
-            for m in range(m0, m0 + k):
-                self._t[m] += 1
-        self._n = 0 if last else self._n + k
-        self._step += 1 if last else 0
+        self.close_chunk(m0, k, time, last)
 
     def finalize(self):
         """-> dict of the outputs; the time aggregates cover the steps folded with time=True."""
-        if self._step != self.Tk:
-            raise RuntimeError("%d of %d steps folded" % (self._step, self.Tk))
-        T = self._t[0]
-        if T < 1 or any(t != T for t in self._t) or len(self._timed) != T:
-            raise RuntimeError("no time statistics: no step was folded with time=True")
+        T = self.finalize_guard()
         dev, S = self.rel.device, self.S
         f32 = lambda v: v.to(torch.float32).to(dev)                            # noqa: E731
         rel = self.rel.to(torch.int64)
@@ -2330,7 +2311,7 @@ def pdf_js(p, q):
     return torch.where(torch.isnan(P.sum(-1) + Q.sum(-1)), torch.full_like(out, float("nan")), out)
 
 
-class EnsemblePdfs:
+class EnsemblePdfs(EnsembleFeed):
     """On-device probability densities of the flow quantities pooled over regions of the flow, for sampled roll-outs of B cases and
     for the target (tmg_ens_pdf_count).  fields: up to 8 of a channel 0..C-1 ("ux", "uy", "p" for 0, 1, 2), "speed", "vort", "div"
     (the derived ones on grid = (dx, dy): the 3x3 stencil of pc/ with zero padding at the field border, every fp32 operation rounded
@@ -2345,7 +2326,7 @@ class EnsemblePdfs:
     The counts fold chunk by chunk by integer adds: no member buffer is kept, and every integer output is bitwise reproducible and
     independent of the chunking.  The target goes through the same kernel as a one-member chunk into planes of its own.
 
-    Feeding protocol of EnsembleEvents: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
+    Feeding protocol of EnsembleFeed: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
     chunks before the next step's; every chunk comes with the step's target, and the last chunk's is the one that is used.
     Outputs of finalize() (device tensors; Tn steps folded with time=True, nb = bins, nbj = joint_bins):
       pdf_count, target_count [B, Tk, R, F, nb + 2] int64; joint_count, target_joint_count [B, Tk, R, P, nbj + 2, nbj + 2] int64
@@ -2361,27 +2342,16 @@ class EnsemblePdfs:
 
     def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, fields=("ux", "uy"), bins=64, ranges=None, joint=(),
                  joint_bins=32, regions=None, grid=None, center=None):
-        if not (2 <= C <= 4):
-            raise ValueError("ensemble pdfs need 2 <= C <= 4 channels, got %d" % C)
+        noun = "ensemble pdfs"
+        _ens_channels(noun, C)
         if int(steps) < 1:
-            raise ValueError("ensemble pdfs need steps >= 1, got %d" % int(steps))
+            raise ValueError("%s need steps >= 1, got %d" % (noun, int(steps)))
         if int(B) < 1 or int(Hh) < 1 or int(Ww) < 1:
-            raise ValueError("ensemble pdfs need B, H, W >= 1, got %d, %d, %d" % (B, Hh, Ww))
+            raise ValueError("%s need B, H, W >= 1, got %d, %d, %d" % (noun, B, Hh, Ww))
         kinds, nb, rg, pairs, nbj, regs, grid = pdf_args(fields, bins, ranges, joint, joint_bins, regions, grid, int(B), C, int(Hh), int(Ww))
-        if not (1 <= int(members) <= SCORES_MAX_MEMBERS):
-            raise ValueError("ensemble pdfs need 1 <= members <= %d, got %d" % (SCORES_MAX_MEMBERS, int(members)))
-        sd = torch.as_tensor(out_std, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
-        mu = torch.as_tensor(out_mu, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
-        if sd.numel() != C or mu.numel() != C:
-            raise ValueError("out_mu / out_std need %d entries, got %d / %d" % (C, mu.numel(), sd.numel()))
-        if not bool((torch.isfinite(sd) & (sd > 0)).all()):
-            raise ValueError("out_std must be finite and strictly positive (u * out_std > 0 keeps the members' order), got %s" % sd.tolist())
-        if not bool(torch.isfinite(mu).all()):
-            raise ValueError("out_mu must be finite, got %s" % mu.tolist())
-        if u is not None:
-            u = torch.as_tensor(u, dtype=torch.float32).detach().reshape(B, C).cpu()
-            if not bool((torch.isfinite(u) & (u > 0)).all()):
-                raise ValueError("u must be finite and strictly positive (u * out_std > 0 keeps the members' order)")
+        _ens_members(noun, members)
+        sd, mu = _ens_tables(C, _KEEPS_ORDER, out_std, out_mu)
+        u = _ens_u(u, B, C, _KEEPS_ORDER)
         S, Tk, HW = int(members), int(steps), int(Hh) * int(Ww)
         for name, v in (("S H W", S * HW), ("Tk H W", Tk * HW), ("S Tk H W", S * Tk * HW)):
             if v >= 2 ** 31:
@@ -2397,10 +2367,8 @@ class EnsemblePdfs:
         jk = [kinds[i] for pr in pairs for i in pr]
         jr = rg[:, [i for pr in pairs for i in pr]] if pairs else rg[:, :0]
         self.JE, je = pdf_edge_tables(jk, jr, nbj, mu, sd, u, cen is not None)
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("ensemble pdfs run on the HIP path: device %s is not a GPU (there is no CPU path)" % dev)
-        self.S, self.B, self.C, self.H, self.W, self.Tk = S, int(B), int(C), int(Hh), int(Ww), Tk
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, C, Hh, Ww, steps)
         self.fields, self.joint, self.regions = tuple(fields), tuple(tuple(pr) for pr in joint), tuple(regs)
         self.kinds, self.pairs, self.nb, self.nbj, self.grid = kinds, pairs, nb, nbj, grid
         self.F, self.P, self.R = len(kinds), len(pairs), len(regs)
@@ -2418,10 +2386,6 @@ class EnsemblePdfs:
         self.jnt = torch.empty((2, self.B, Tk, self.R, self.P, jb), **i32)
         self.mt = (torch.empty((self.B, S, self.R, self.F, nb + 2), **i32), torch.empty((self.B, 1, self.R, self.F, nb + 2), **i32))
         self.tj = torch.empty((2, self.B, self.R, self.P, jb), **i32)
-        self._n = 0           # members counted for the current step
-        self._step = 0        # the step being filled
-        self._t = [0] * S     # timed steps every member has been fed for
-        self._timed = []      # the steps that went into the time aggregates
 
     def _count(self, which, yn, S, k, m0, t, timed):
         marg, jb = self.R * self.F * (self.nb + 2), self.R * self.P * (self.nbj + 2) ** 2
@@ -2433,24 +2397,8 @@ class EnsemblePdfs:
         """Bin the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
         channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride rule.  The step's
         first chunk zeroes the step's planes (the first timed one the time planes), the last chunk bins the target."""
-        yn = y.permute(0, 2, 3, 1)
-        kB = yn.shape[0]
-        if kB % self.B or tuple(yn.shape[1:]) != (self.H, self.W, self.C):
-            raise ValueError("chunk shape %s does not hold whole members of [%d, %d, %d, %d]" % (tuple(y.shape), self.B, self.C, self.H, self.W))
-        if target is None or tuple(target.shape) != (self.B, self.C, self.H, self.W):
-            raise ValueError("target shape %s is not [%d, %d, %d, %d]" % (None if target is None else tuple(target.shape), self.B, self.C,
-                                                                          self.H, self.W))
-        k = kB // self.B
-        if m0 != self._n or m0 + k > self.S or self._step >= self.Tk:
-            raise ValueError("members must be fed in order, every step's chunks before the next step's")
-        t_before = self._t[m0]
-        if time and any(self._t[m] != t_before for m in range(m0, m0 + k)):
-            raise ValueError("members of one chunk hold different numbers of time steps")
-        H.check_device(yn)
-        tn = target.permute(0, 2, 3, 1)
-        H.check_act(tn)
-        H.check_device(tn)
-        last = m0 + k == self.S
+        yn, tn, k, t_before, last = self.open_chunk(y, m0, time, target, required=True)
+        _on_device(yn, tn)
         t = self._step
         if m0 == 0:
             self.cnt[:, :, t].zero_()
@@ -2462,21 +2410,11 @@ class EnsemblePdfs:
         self._count(0, yn, self.S, k, m0, t, time)
         if last:
             self._count(1, tn, 1, 1, 0, t, time)
-            if time:
-                self._timed.append(t)
-        if time:
-            for m in range(m0, m0 + k):
-                self._t[m] += 1
-        self._n = 0 if last else self._n + k
-        self._step += 1 if last else 0
+        self.close_chunk(m0, k, time, last)
 
     def finalize(self):
         """-> dict of the outputs; the time aggregates cover the steps folded with time=True."""
-        if self._step != self.Tk:
-            raise RuntimeError("%d of %d steps folded" % (self._step, self.Tk))
-        T = self._t[0]
-        if T < 1 or any(t != T for t in self._t) or len(self._timed) != T:
-            raise RuntimeError("no time statistics: no step was folded with time=True")
+        self.finalize_guard()
         dev = self.cnt.device
         f32 = lambda v: v.to(torch.float32).to(dev)                            # noqa: E731
         nj = self.nbj + 2
@@ -2527,7 +2465,7 @@ def energy_groups(groups, C):
 ENERGY_STEP_KEYS = ("energy_score", "energy_score_fair", "target_dist_mean", "pair_dist_mean", "nearest_dist")
 
 
-class EnsembleEnergy:
+class EnsembleEnergy(EnsembleFeed):
     """On-device energy score and member distances of sampled roll-outs of B cases against the target (tmg_ens_score_store /
     tmg_ens_gram_step): the score of every member as ONE vector over the pixels, which no per-pixel score can see.  For case b and
     kept step t, with the rows x_0..x_{S-1} (raw normalised members) and x_S = y (the normalised target), a_c = u[b, c] out_std[c] > 0
@@ -2539,7 +2477,7 @@ class EnsembleEnergy:
     out_mu cancels in every term and is not an input.  The kernels form d2 from the Gram matrix of the rows centred about the members'
     mean (csrc/tmg_gram.hip), on the fp32 matrix pipe.
 
-    Feeding protocol of EnsembleScores: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
+    Feeding protocol of EnsembleFeed: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
     chunks before the next step's; every chunk comes with the step's target, and the last chunk's is the one that is scored.
     Outputs (device tensors, Gn groups): energy_score, energy_score_fair, target_dist_mean, pair_dist_mean, nearest_dist [B, Tk, Gn]
     float32; medoid, nearest [B, Tk, Gn] int64; finalize() adds, over the steps folded with time=True, time_energy_score,
@@ -2548,31 +2486,21 @@ class EnsembleEnergy:
     traj_energy_score_fair [B, Gn] and traj_medoid, traj_nearest [B, Gn] int64 (the same formulas on sqrt(traj_dist2))."""
 
     def __init__(self, members, B, C, Hh, Ww, steps, device, out_std, u=None, groups=None):
-        if not (2 <= C <= 4):
-            raise ValueError("ensemble energy scores need 2 <= C <= 4 channels, got %d" % C)
-        if not (1 <= int(members) <= SCORES_MAX_MEMBERS):
-            raise ValueError("ensemble energy scores need 1 <= members <= %d, got %d" % (SCORES_MAX_MEMBERS, int(members)))
-        sd = torch.as_tensor(out_std, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
-        if sd.numel() != C:
-            raise ValueError("out_std needs %d entries, got %d" % (C, sd.numel()))
-        if not bool((torch.isfinite(sd) & (sd > 0)).all()):
-            raise ValueError("out_std must be finite and strictly positive (the distances scale with u * out_std), got %s" % sd.tolist())
-        if u is not None:
-            u = torch.as_tensor(u, dtype=torch.float32).detach().reshape(B, C).cpu()
-            if not bool((torch.isfinite(u) & (u > 0)).all()):
-                raise ValueError("u must be finite and strictly positive (the distances scale with u * out_std)")
+        noun, why = "ensemble energy scores", "the distances scale with u * out_std"
+        _ens_channels(noun, C)
+        _ens_members(noun, members)
+        sd, _ = _ens_tables(C, why, out_std)
+        u = _ens_u(u, B, C, why)
         if groups is None:
             groups = ((0, 1), (2,)) if C == 3 else (tuple(range(C)),)
         self.groups = energy_groups(groups, C)
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("ensemble energy scores run on the HIP path: device %s is not a GPU (there is no CPU path)" % dev)
-        self.S, self.B, self.C, self.H, self.W, self.Tk = int(members), int(B), int(C), int(Hh), int(Ww), int(steps)
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, C, Hh, Ww, steps)
         HW = self.H * self.W
         Gn = len(self.groups)
         f32 = dict(device=dev, dtype=torch.float32)
         # a_c^2 = (u out_std)^2 in fp64 from the fp32 factors, rounded once
-        a = sd.double().view(1, C).expand(self.B, C) if u is None else u.double() * sd.double().view(1, C)
+        a = _ens_scale(sd, u, self.B, torch.float64)
         self.a2 = (a * a).to(torch.float32).to(dev).contiguous()
         self.plan = H.ens_gram_plan(self.S, self.B, C, HW)
         self.xs = torch.empty((self.S, self.B, C, HW), **f32)
@@ -2583,52 +2511,22 @@ class EnsembleEnergy:
         self.outi = torch.empty((2, self.B, self.Tk, Gn), device=dev, dtype=torch.int64)
         self.out = dict(zip(ENERGY_STEP_KEYS, self.outf))
         self.out["medoid"], self.out["nearest"] = self.outi[0], self.outi[1]
-        self._n = 0           # members stored for the current step
-        self._step = 0        # the step being filled
-        self._t = [0] * self.S  # timed steps every member has been fed for
-        self._timed = []      # the steps whose distances went into traj_dist2
 
     def add(self, y, m0, target, time=True):
         """Store the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
         channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride rule.  The step's
         last chunk scores the step against its target."""
-        yn = y.permute(0, 2, 3, 1)
-        kB = yn.shape[0]
-        if kB % self.B or tuple(yn.shape[1:]) != (self.H, self.W, self.C):
-            raise ValueError("chunk shape %s does not hold whole members of [%d, %d, %d, %d]" % (tuple(y.shape), self.B, self.C, self.H, self.W))
-        if target is None or tuple(target.shape) != (self.B, self.C, self.H, self.W):
-            raise ValueError("target shape %s is not [%d, %d, %d, %d]" % (None if target is None else tuple(target.shape), self.B, self.C,
-                                                                          self.H, self.W))
-        k = kB // self.B
-        if m0 != self._n or m0 + k > self.S or self._step >= self.Tk:
-            raise ValueError("members must be fed in order, every step's chunks before the next step's")
-        t_before = self._t[m0]
-        if time and any(self._t[m] != t_before for m in range(m0, m0 + k)):
-            raise ValueError("members of one chunk hold different numbers of time steps")
-        H.check_device(yn)
-        tn = target.permute(0, 2, 3, 1)
-        H.check_act(tn)
-        H.check_device(tn)
-        last = m0 + k == self.S
+        yn, tn, k, t_before, last = self.open_chunk(y, m0, time, target, required=True)
+        _on_device(yn, tn)
         H.ens_score_store(yn, self.xs, k, m0)
         if last:
             H.ens_gram_step(self.xs, tn, self.a2, self.groups, self.r, self.ws, self.traj, self.outf, self.outi, self._step, t_before,
                             1 if time else 0)
-            if time:
-                self._timed.append(self._step)
-        if time:
-            for m in range(m0, m0 + k):
-                self._t[m] += 1
-        self._n = 0 if last else self._n + k
-        self._step += 1 if last else 0
+        self.close_chunk(m0, k, time, last)
 
     def finalize(self):
         """-> dict of the outputs; the time statistics cover the steps folded with time=True."""
-        if self._step != self.Tk:
-            raise RuntimeError("%d of %d steps folded" % (self._step, self.Tk))
-        T = self._t[0]
-        if T < 1 or any(t != T for t in self._t) or len(self._timed) != T:
-            raise RuntimeError("no time statistics: no step was folded with time=True")
+        self.finalize_guard()
         o = self.out
         Gn = len(self.groups)
         tf = torch.empty((5, self.B, Gn), device=self.traj.device, dtype=torch.float32)
@@ -2679,7 +2577,7 @@ def structure_lags(lags, H, W):
     return tuple((int(l[0]), int(l[1])) for l in ls)
 
 
-class EnsembleStructure:
+class EnsembleStructure(EnsembleFeed):
     """On-device structure functions and variogram score of sampled roll-outs of B cases against the target (tmg_ens_score_store /
     tmg_ens_sfun_step): the dependence between neighbouring pixels of one member.  Permute the members independently at every pixel
     and every per-pixel score stays bit-identical; the increments do not.
@@ -2703,25 +2601,17 @@ class EnsembleStructure:
     Lag outputs.  lags is int64 [L, 2].  lag_dist is float64 [L] = hypot(dx * grid_dx, dy * grid_dy).
     Not supported.  Non-finite members, as in EnsembleQuantiles.
 
-    Feeding protocol of EnsembleEnergy: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
+    Feeding protocol of EnsembleFeed: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
     chunks before the next step's; every chunk comes with the step's target, and the last chunk's is the one that is scored.  The raw
     device buffers: xs [S, B, C, HW], ws (the workspace), mom [Tk, 3, B, C, L, S+1] and vsum [Tk, B, C, L] (step t writes its own
     plane), tmom [3, B, C, L, S+1], tvar [B, C, L]."""
 
     def __init__(self, members, B, C, Hh, Ww, steps, device, out_std, u=None, lags=None, weights=None, grid=(1.0, 1.0)):
-        if not (2 <= C <= 4):
-            raise ValueError("ensemble structure functions need 2 <= C <= 4 channels, got %d" % C)
-        if not (1 <= int(members) <= SCORES_MAX_MEMBERS):
-            raise ValueError("ensemble structure functions need 1 <= members <= %d, got %d" % (SCORES_MAX_MEMBERS, int(members)))
-        sd = torch.as_tensor(out_std, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
-        if sd.numel() != C:
-            raise ValueError("out_std needs %d entries, got %d" % (C, sd.numel()))
-        if not bool((torch.isfinite(sd) & (sd > 0)).all()):
-            raise ValueError("out_std must be finite and strictly positive (the increments scale with u * out_std), got %s" % sd.tolist())
-        if u is not None:
-            u = torch.as_tensor(u, dtype=torch.float32).detach().reshape(B, C).cpu()
-            if not bool((torch.isfinite(u) & (u > 0)).all()):
-                raise ValueError("u must be finite and strictly positive (the increments scale with u * out_std)")
+        noun, why = "ensemble structure functions", "the increments scale with u * out_std"
+        _ens_channels(noun, C)
+        _ens_members(noun, members)
+        sd, _ = _ens_tables(C, why, out_std)
+        u = _ens_u(u, B, C, why)
         self.lags = structure_lags(lags, Hh, Ww)
         L = len(self.lags)
         if weights is None:
@@ -2736,14 +2626,12 @@ class EnsembleStructure:
             raise ValueError("grid must be the cell sizes (dx, dy), got %r" % (grid,))
         if not (0 < gx < float("inf") and 0 < gy < float("inf")):
             raise ValueError("grid must be positive finite cell sizes (dx, dy), got %r" % (grid,))
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("ensemble structure functions run on the HIP path: device %s is not a GPU (there is no CPU path)" % dev)
-        self.S, self.B, self.C, self.H, self.W, self.Tk = int(members), int(B), int(C), int(Hh), int(Ww), int(steps)
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, C, Hh, Ww, steps)
         self.L = L
         HW = self.H * self.W
         f32 = dict(device=dev, dtype=torch.float32)
-        self.a = (sd.double().view(1, C).expand(self.B, C) if u is None else u.double() * sd.double().view(1, C)).contiguous()   # fp64, host
+        self.a = _ens_scale(sd, u, self.B, torch.float64)                    # fp64, host
         self.w = w
         self.lag_dist = torch.tensor([math.hypot(dx * gx, dy * gy) for dx, dy in self.lags], dtype=torch.float64)
         self.plan = H.ens_sfun_plan(self.S, self.B, C, self.H, self.W, self.lags)
@@ -2754,52 +2642,22 @@ class EnsembleStructure:
         self.vsum = torch.empty((self.Tk, self.B, C, L), **f32)
         self.tmom = torch.empty((3, self.B, C, L, R), **f32)
         self.tvar = torch.empty((self.B, C, L), **f32)
-        self._n = 0           # members stored for the current step
-        self._step = 0        # the step being filled
-        self._t = [0] * self.S  # timed steps every member has been fed for
-        self._timed = []      # the steps whose sums went into tmom / tvar
 
     def add(self, y, m0, target, time=True):
         """Store the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
         channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride rule.  The step's
         last chunk forms the step's sums against its target."""
-        yn = y.permute(0, 2, 3, 1)
-        kB = yn.shape[0]
-        if kB % self.B or tuple(yn.shape[1:]) != (self.H, self.W, self.C):
-            raise ValueError("chunk shape %s does not hold whole members of [%d, %d, %d, %d]" % (tuple(y.shape), self.B, self.C, self.H, self.W))
-        if target is None or tuple(target.shape) != (self.B, self.C, self.H, self.W):
-            raise ValueError("target shape %s is not [%d, %d, %d, %d]" % (None if target is None else tuple(target.shape), self.B, self.C,
-                                                                          self.H, self.W))
-        k = kB // self.B
-        if m0 != self._n or m0 + k > self.S or self._step >= self.Tk:
-            raise ValueError("members must be fed in order, every step's chunks before the next step's")
-        t_before = self._t[m0]
-        if time and any(self._t[m] != t_before for m in range(m0, m0 + k)):
-            raise ValueError("members of one chunk hold different numbers of time steps")
-        H.check_device(yn)
-        tn = target.permute(0, 2, 3, 1)
-        H.check_act(tn)
-        H.check_device(tn)
-        last = m0 + k == self.S
+        yn, tn, k, t_before, last = self.open_chunk(y, m0, time, target, required=True)
+        _on_device(yn, tn)
         H.ens_score_store(yn, self.xs, k, m0)
         if last:
             H.ens_sfun_step(self.xs, tn, self.lags, self.ws, self.mom[self._step], self.vsum[self._step], self.tmom, self.tvar,
                             self.H, self.W, t_before, 1 if time else 0)
-            if time:
-                self._timed.append(self._step)
-        if time:
-            for m in range(m0, m0 + k):
-                self._t[m] += 1
-        self._n = 0 if last else self._n + k
-        self._step += 1 if last else 0
+        self.close_chunk(m0, k, time, last)
 
     def finalize(self):
         """-> dict of the outputs; the time statistics cover the steps folded with time=True."""
-        if self._step != self.Tk:
-            raise RuntimeError("%d of %d steps folded" % (self._step, self.Tk))
-        T = self._t[0]
-        if T < 1 or any(t != T for t in self._t) or len(self._timed) != T:
-            raise RuntimeError("no time statistics: no step was folded with time=True")
+        T = self.finalize_guard()
         dev = self.mom.device
         f32 = torch.float32
         a = self.a.to(dev)                                                   # [B, C] fp64
@@ -2881,7 +2739,7 @@ def _spectrum_lists(bins, NK):
 SPECTRUM_MAX_SHELLS = 8192
 
 
-class EnsembleSpectrum:
+class EnsembleSpectrum(EnsembleFeed):
     """On-device shell-binned kinetic-energy spectra E(k) of sampled roll-outs of B cases (tmg_spec_rows / tmg_spec_cols /
     tmg_spec_accum / tmg_spec_finalize).  Per case, member and kept step: z = g (u + i v) from channels 0 and 1 of the un-normalised
     field yh = u[b, c] (out_std[c] y + out_mu[c]) (the pressure is ignored), g[y, x] = w_H[y] w_W[x] the periodic Hann window
@@ -2889,7 +2747,7 @@ class EnsembleSpectrum:
     E[s] the sum of E2 over shell s of spectrum_bins(H, W, dx, dy).  The transform is a dense DFT on the fp32 matrix pipe with the
     window folded into its operand matrices; H and W are multiples of 16 up to 512.
 
-    Feeding protocol of EnsembleStats: every step's members in chunks of whole members, in member order, each step's chunks before
+    Feeding protocol of EnsembleFeed: every step's members in chunks of whole members, in member order, each step's chunks before
     the next step's.  y: API-shaped [k*B, C, H, W], 2 <= C <= 4.  Outputs (device tensors): spec_mean, spec_std [B, Tk, NK] (mean and
     population std over the members); finalize() adds time_spec_mean, time_spec_std [B, NK] (mean / std over the members of each
     member's time mean of E over the steps folded with time=True) and spec_k [NK] (float64, host: the shell centres s 2 pi / Lmax)."""
@@ -2906,15 +2764,14 @@ class EnsembleSpectrum:
         Hh, Ww = int(Hh), int(Ww)
         if not all(16 <= n <= 512 and n % 16 == 0 for n in (Hh, Ww)):
             raise ValueError("spectra need H and W that are a multiple of 16 in [16, 512], got %d x %d" % (Hh, Ww))
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("ensemble spectra run on the HIP path: device %s is not a GPU (there is no CPU path)" % dev)
+        dev = _ens_device("ensemble spectra", device)
         bins, k = spectrum_bins(Hh, Ww, grid[0], grid[1])
         NK = k.numel()
         if NK > SPECTRUM_MAX_SHELLS:
             raise ValueError("grid %s gives %d shells on %d x %d modes, at most %d are supported" % (grid, NK, Hh, Ww, SPECTRUM_MAX_SHELLS))
         self.grid, self.window = grid, window
-        self.S, self.B, self.H, self.W, self.Tk, self.NK = int(members), int(B), Hh, Ww, int(steps), NK
+        EnsembleFeed.__init__(self, members, B, None, Hh, Ww, steps)
+        self.NK = NK
         f32 = dict(device=dev, dtype=torch.float32)
         self.mu = torch.as_tensor(out_mu, **f32).reshape(-1)[:2].contiguous()
         self.sd = torch.as_tensor(out_std, **f32).reshape(-1)[:2].contiguous()
@@ -2933,25 +2790,13 @@ class EnsembleSpectrum:
         self.time_state = torch.empty((self.S, self.B, NK), **f32)
         self.out = {"spec_mean": torch.empty((self.B, self.Tk, NK), **f32), "spec_std": torch.empty((self.B, self.Tk, NK), **f32)}
         self._yw = self._part = None      # workspace of the largest chunk: the planar row transform, the tiles' partial spectra
-        self._n = 0
-        self._step = 0
-        self._t = [0] * self.S
 
     def add(self, y, m0, time=True):
         """Fold the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
         channel-slice; rows member-major)."""
-        yn = y.permute(0, 2, 3, 1)
-        kB = yn.shape[0]
-        if kB % self.B or tuple(yn.shape[1:3]) != (self.H, self.W) or not 2 <= yn.shape[3] <= 4:
-            raise ValueError("chunk shape %s does not hold whole members of [%d, 2..4, %d, %d]" % (tuple(y.shape), self.B, self.H, self.W))
-        k = kB // self.B
-        if m0 != self._n or m0 + k > self.S or self._step >= self.Tk:
-            raise ValueError("members must be fed in order, every step's chunks before the next step's")
-        t_before = self._t[m0]
-        if time and any(self._t[m] != t_before for m in range(m0, m0 + k)):
-            raise ValueError("members of one chunk hold different numbers of time steps")
-        H.check_device(yn)
-        last = m0 + k == self.S
+        yn, _, k, t_before, last = self.open_chunk(y, m0, time)
+        _on_device(yn)
+        kB = k * self.B
         QT = self.W // 16
         if self._yw is None or self._yw.numel() < 2 * kB * self.H * self.W:
             self._yw = torch.empty(2 * kB * self.H * self.W, device=self.step_state.device, dtype=torch.float32)
@@ -2964,19 +2809,11 @@ class EnsembleSpectrum:
         H.spec_accum(self._part, self.step_state[0], self.step_state[1], self.time_state,
                      (o["spec_mean"][:, t], o["spec_std"][:, t]) if last else None, self.Tk * self.NK, k, self.B, self.NK, QT, self._n,
                      m0, t_before, flags)
-        if time:
-            for m in range(m0, m0 + k):
-                self._t[m] += 1
-        self._n = 0 if last else self._n + k
-        self._step += 1 if last else 0
+        self.close_chunk(m0, k, time, last)
 
     def finalize(self):
         """-> dict of the outputs; the time statistics cover the steps folded with time=True."""
-        if self._step != self.Tk:
-            raise RuntimeError("%d of %d steps folded" % (self._step, self.Tk))
-        T = self._t[0]
-        if T < 1 or any(t != T for t in self._t):
-            raise RuntimeError("no time statistics: no step was folded with time=True")
+        self.finalize_guard()
         for n in ("time_spec_mean", "time_spec_std"):
             self.out[n] = empty((self.B, self.NK), self.step_state.device)
         H.spec_finalize(self.time_state, self.out["time_spec_mean"], self.out["time_spec_std"], self.S, self.B, self.NK)
@@ -3021,7 +2858,7 @@ def _tspec_operand(Tn, NF, window):
 TSPEC_BLOCK = 16      # steps per ring pass (csrc/tmg_tspec.hip)
 
 
-class EnsembleTimeSpectrum:
+class EnsembleTimeSpectrum(EnsembleFeed):
     """On-device temporal power spectra of sampled roll-outs of B cases (tmg_tspec_store / tmg_tspec_block / tmg_tspec_finalize).
     For case b, member m, channel c and pixel p, with xh_n = u[b, c] (out_std[c] y + out_mu[c]) at the fed steps n = 0 .. Tn - 1:
       xbar = mean_n xh_n
@@ -3033,7 +2870,7 @@ class EnsembleTimeSpectrum:
     The steps are gathered 16 at a time in a planar ring and folded by a dense DFT on the fp32 matrix pipe; the state is
     (2 NF + 1 + 16) * 4 bytes per element of [members, B, C, H, W].  H and W are any positive sizes.
 
-    `steps` is Tn: there are no per-step outputs, so only the steps of the time window are fed.  Feeding protocol of EnsembleStats:
+    `steps` is Tn: there are no per-step outputs, so only the steps of the time window are fed.  Feeding protocol of EnsembleFeed:
     every step's members in chunks of whole members, in member order (m0 = 0 first), each step's chunks before the next step's.
     finalize() returns psd_mean, psd_std [B, NF, C, H, W] (device; mean and population std of P_k over the members) and psd_freq [NF]
     (float64, host: k / (Tn dt), dt the time between two fed steps).
@@ -3042,8 +2879,7 @@ class EnsembleTimeSpectrum:
     u; a device that is not a GPU comes last (RuntimeError)."""
 
     def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, nfreq=32, window="hann", dt=1.0):
-        if not (2 <= C <= 4):
-            raise ValueError("temporal spectra need 2 <= C <= 4 channels, got %d" % C)
+        _ens_channels("temporal spectra", C)
         if int(steps) < 2:
             raise ValueError("temporal spectra need steps >= 2 (the window of the transform), got %d" % int(steps))
         if int(nfreq) < 1:
@@ -3066,10 +2902,9 @@ class EnsembleTimeSpectrum:
             u = torch.as_tensor(u, dtype=torch.float32).detach()
             if u.numel() != int(B) * C:
                 raise ValueError("u needs %d x %d entries, got %d" % (int(B), C, u.numel()))
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("temporal spectra run on the HIP path: device %s is not a GPU (there is no CPU path)" % dev)
-        self.S, self.B, self.C, self.H, self.W, self.Tn = int(members), int(B), int(C), int(Hh), int(Ww), int(steps)
+        dev = _ens_device("temporal spectra", device)
+        EnsembleFeed.__init__(self, members, B, C, Hh, Ww, steps)
+        self.Tn = self.Tk
         self.NF = min(int(nfreq), self.Tn // 2 + 1)
         self.window, self.dt = window, dt
         f32 = dict(device=dev, dtype=torch.float32)
@@ -3082,8 +2917,6 @@ class EnsembleTimeSpectrum:
         self.acc = torch.empty((2 * self.NF + 1, self.S, self.B, C, HW), **f32)
         self.freq = torch.arange(self.NF, dtype=torch.float64) / (self.Tn * dt)
         self.out = None
-        self._n = 0           # members stored for the current step
-        self._step = 0        # the step being filled
 
     def _fold(self, n0, nb):
         H.tspec_block(self.tm, self.ring, self.acc, self.Tn, self.NF, n0, nb, n0 == 0)
@@ -3091,27 +2924,16 @@ class EnsembleTimeSpectrum:
     def add(self, y, m0):
         """Store the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
         channel-slice; rows member-major); the last chunk of every 16th step folds the ring into the accumulator."""
-        yn = y.permute(0, 2, 3, 1)
-        kB = yn.shape[0]
-        if kB < 1 or kB % self.B or tuple(yn.shape[1:]) != (self.H, self.W, self.C):
-            raise ValueError("chunk shape %s does not hold whole members of [%d, %d, %d, %d]" % (tuple(y.shape), self.B, self.C, self.H, self.W))
-        k = kB // self.B
-        if m0 != self._n or m0 + k > self.S or self._step >= self.Tn:
-            raise ValueError("members must be fed in order, every step's chunks before the next step's")
-        H.check_device(yn)
+        yn, _, k, _, last = self.open_chunk(y, m0, None)
+        _on_device(yn)
         H.tspec_store(yn, self.u, self.mu, self.sd, self.ring, k, m0, self._step % TSPEC_BLOCK)
-        if m0 + k < self.S:
-            self._n += k
-            return
-        self._n = 0
-        self._step += 1
-        if self._step % TSPEC_BLOCK == 0:
+        self.close_chunk(m0, k, None, last)
+        if last and self._step % TSPEC_BLOCK == 0:
             self._fold(self._step - TSPEC_BLOCK, TSPEC_BLOCK)
 
     def finalize(self):
         """-> dict of psd_mean, psd_std (device) and psd_freq (host)."""
-        if self._step != self.Tn or self._n != 0:
-            raise RuntimeError("%d of %d steps fed" % (self._step, self.Tn))
+        self.finalize_guard(timed=False)
         if self.out is None:
             nb = self.Tn % TSPEC_BLOCK
             if nb:

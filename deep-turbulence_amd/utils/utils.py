@@ -2,11 +2,13 @@
 utils/utils.py:55-148): `<name><id>.zip` holding `torchModel<id>.pth` = {'epoch', 'state_dict', 'optimizer'} and
 `args.json`.  A workspace written by either code base loads in the other (the state_dict schema is the reference's, see
 tests/test_boundary_cpu.py)."""
+import collections
 import io
 import json
 import math
 import os
 import zipfile
+from types import SimpleNamespace
 
 import torch
 
@@ -119,20 +121,57 @@ def _pdf_target_fields(tp, kinds, grid):
     return out
 
 
-def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, turbulence, spectra=False,
-                   window="hann", scores=False, tspec=None, quant=None, energy=None, structure=None, events=None, pdfs=None):
-    """The body of modelPredStats, modelPredTurbulence (turbulence: grid = (args.dx, args.dy)), modelPredSpectra (spectra: the same
-    chunks also go through an EnsembleSpectrum with `window`), modelPredScores (scores: the same chunks also go through an
-    EnsembleScores with the step's normalised target) and modelPredTimeSpectra (tspec = (nfreq, window, dt between kept steps): the
-    chunks of the kept steps from t_start on also go through an EnsembleTimeSpectrum) and modelPredQuantiles (quant = (levels, exceed):
-    the same chunks also go through an EnsembleQuantiles with the step's normalised target) and modelPredEnergy (energy = the channel
-    groups: the same chunks also go through an EnsembleEnergy with the step's normalised target) and modelPredStructure (structure =
-    (lags, weights): the same chunks also go through an EnsembleStructure with the step's normalised target and grid = (args.dx,
-    args.dy)) and modelPredEvents (events = (events, scales): the same chunks also go through an EnsembleEvents with the step's
-    normalised target) and modelPredPdfs (pdfs = the keywords of EnsemblePdfs, with ranges None for the target's own and center
-    "target" for its time mean: the same chunks also go through an EnsemblePdfs with the step's normalised target and grid =
-    (args.dx, args.dy); neither option draws from the host RNG or iterates the loader again): same seed draws in the same order, same
-    folding, same re-anchoring, so that the keys they share hold identical values under the same host RNG state."""
+# One optional accumulator of _ensembleStats, built by a modelPred* wrapper.
+#   make(mb, members, steps) -> the tmg_ops accumulator of one mini-batch.  mb holds what the constructors take: B, C, H, W, dev,
+#       out_mu, out_std, u [B, C], grid (the statistics': None without turbulence), and for the PDFs' ranges and centre tgt (the
+#       physical target series on the device) and case0 (the cases before this mini-batch)
+#   target: add() takes the step's normalised target
+#   window: fed only the kept steps from t_start on, by add(y, m0) without time= (the temporal spectrum); finalized last
+#   meta:   result keys that are returned once, not concatenated over the mini-batches
+#   extra:  fixed results
+#   tail:   (result key, source key) pairs read from a one-member accumulator of the same make that is fed the target series
+_Acc = collections.namedtuple("_Acc", "make target window meta extra tail", defaults=(False, False, (), {}, ()))
+
+
+def _pdf_factory(name, args, stride, t_start, pdfs):
+    """The make of modelPredPdfs' record.  pdfs: the keywords of tmg_ops.EnsemblePdfs, with ranges None for the target's own and
+    center "target" for its time mean, both over the kept steps from t_start on; arrays per case are cut to the mini-batch."""
+    def make(mb, members, steps):
+        import tmg_ops as ops
+        kw = dict(pdfs)
+        B, pgrid = mb.B, (args.dx, args.dy)
+        kinds = ops.pdf_args(kw["fields"], kw["bins"], [(0.0, 1.0)] * len(kw["fields"]), kw["joint"], kw["joint_bins"], kw["regions"],
+                             pgrid, B, mb.C, mb.H, mb.W)[0]
+        # the target's physical series at the kept steps from t_start on, in fp64 (range and centre only: not the hot path)
+        tk = mb.tgt[:, t_start * stride:(steps - 1) * stride + 1:stride].double()
+        if isinstance(kw["center"], str):
+            kw["center"] = tk.mean(1).float()
+        elif kw["center"] is not None:
+            kw["center"] = torch.as_tensor(kw["center"])[mb.case0:mb.case0 + B]
+        if kw["ranges"] is not None and torch.as_tensor(kw["ranges"]).dim() == 3:
+            kw["ranges"] = torch.as_tensor(kw["ranges"])[mb.case0:mb.case0 + B]
+        if kw["ranges"] is None:
+            cen = None if kw["center"] is None else kw["center"].to(mb.dev).float().double().unsqueeze(1)
+            vals = _pdf_target_fields(tk, kinds, pgrid)
+            rg = torch.zeros(B, len(kinds), 2, dtype=torch.float64)
+            for f, (k, v) in enumerate(zip(kinds, vals)):
+                if k < 4 and cen is not None:
+                    v = v - cen[:, :, k]
+                lo, hi = v.reshape(B, -1).min(1).values.cpu(), v.reshape(B, -1).max(1).values.cpu()
+                if bool((hi <= lo).any()):
+                    raise ValueError("%s: field %r of the target of case %d is constant (%r): give ranges"
+                                     % (name, kw["fields"][f], mb.case0 + int((hi <= lo).nonzero()[0]), float(lo[(hi <= lo).nonzero()[0]])))
+                rg[:, f, 0], rg[:, f, 1] = lo - 0.25 * (hi - lo), hi + 0.25 * (hi - lo)
+            kw["ranges"] = rg
+        return ops.EnsemblePdfs(members, B, mb.C, mb.H, mb.W, steps, mb.dev, mb.out_mu, mb.out_std, u=mb.u, grid=pgrid, **kw)
+    return make
+
+
+def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, turbulence, accs=()):
+    """The body of every modelPred* wrapper below: modelPred's roll-outs, folded chunk by chunk into an EnsembleStats (turbulence:
+    with grid = (args.dx, args.dy)) and then, in list order, into the accumulators of `accs`, the wrapper's _Acc records.  No record
+    draws from the host RNG or iterates the loader again: same seed draws in the same order, same folding, same re-anchoring, so that
+    the keys two wrappers share hold identical values under the same host RNG state."""
     import tmg_ops as ops
     core = getattr(model, "module", model)
     core.eval()
@@ -146,13 +185,18 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
         raise ValueError("%s needs samples >= 1 and tmax >= stride (samples=%d, tmax=%d, stride=%d)" % (name, samples, tmax, stride))
     if not 0 <= t_start < nkeep:
         raise ValueError("t_start=%d outside the %d kept steps" % (t_start, nkeep))
-    if tspec is not None and nkeep - t_start < 2:
+    if any(a.window for a in accs) and nkeep - t_start < 2:
         raise ValueError("%s needs at least 2 kept steps from t_start on, got %d (tmax=%d, stride=%d, t_start=%d)"
                          % (name, nkeep - t_start, tmax, stride, t_start))
+    needs_series = any(a.target or a.window for a in accs)
+    stats = _Acc(lambda mb, S, T: ops.EnsembleStats(S, mb.B, mb.C, mb.H, mb.W, T, mb.dev, mb.out_mu, mb.out_std, u=mb.u, grid=mb.grid),
+                 tail=_TARGET_STATS if turbulence else ())
+    accs = [stats] + list(accs)
+    tails = [a for a in accs if a.tail]
     shp = (1, -1, 1, 1)
     in_std, in_mu = core.in_std.to(dev).view(shp), core.in_mu.to(dev).view(shp)
     out_std, out_mu = core.out_std.to(dev), core.out_mu.to(dev)
-    outs, targets, inputs, sf_lags = {}, [], [], {}
+    outs, targets, inputs, meta = {}, [], [], {}
     case0 = 0                                                                 # cases before this mini-batch
     with torch.no_grad():
         for mbIdx, (input0, target0, u0) in enumerate(testing_loader):
@@ -166,9 +210,9 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
             B, C, Hh, Ww = inp.size(0), tgt.size(2), tgt.size(-2), tgt.size(-1)
             if C != 3:
                 raise ValueError("%s scales (ux, uy, p) by (u0, u0, u0^2) as modelPred does: 3 target channels, got %d" % (name, C))
-            if (scores or tspec is not None or quant is not None or energy is not None or structure is not None or events is not None or pdfs is not None) and target0.size(1) <= (nkeep - 1) * stride:
-                raise ValueError("%s: the target series holds %d steps, kept step %d needs step %d"
-                                 % (name, target0.size(1), nkeep - 1, (nkeep - 1) * stride))
+            short = "%s: the target series holds %d steps, kept step %d needs step %d" % (name, target0.size(1), nkeep - 1, (nkeep - 1) * stride)
+            if needs_series and target0.size(1) <= (nkeep - 1) * stride:
+                raise ValueError(short)
             keys = []
             for i in range(samples):                                   # modelPred's seed draws, member by member
                 seeds = torch.LongTensor(B).random_(0, int(1e8))
@@ -179,160 +223,54 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
             anchors = [[tuple(torch.cat([keys[m0 + j][lv][s] for j in range(k)]) for s in (0, 1)) for lv in range(len(keys[0]))]
                        for m0, k in chunks]
             states = [[(h.clone(), c.clone()) for h, c in a] for a in anchors]
-            st = ops.EnsembleStats(samples, B, C, Hh, Ww, nkeep, dev, out_mu, out_std, u=u.view(B, 3)[:, :C], grid=grid)
-            sp = ops.EnsembleSpectrum(samples, B, Hh, Ww, nkeep, dev, out_mu, out_std, u=u.view(B, 3), grid=grid,
-                                      window=window) if spectra else None
-            sc = ops.EnsembleScores(samples, B, C, Hh, Ww, nkeep, dev, out_std, u=u.view(B, 3)[:, :C]) if scores else None
-            tsp_t = ops.EnsembleTimeSpectrum(samples, B, C, Hh, Ww, nkeep - t_start, dev, out_mu, out_std, u=u.view(B, 3)[:, :C],
-                                             nfreq=tspec[0], window=tspec[1], dt=tspec[2]) if tspec is not None else None
-            qt = ops.EnsembleQuantiles(samples, B, C, Hh, Ww, nkeep, dev, out_mu, out_std, u=u.view(B, 3)[:, :C], levels=quant[0],
-                                       exceed=quant[1]) if quant is not None else None
-            en = ops.EnsembleEnergy(samples, B, C, Hh, Ww, nkeep, dev, out_std, u=u.view(B, 3)[:, :C], groups=energy) if energy is not None else None
-            sfn = ops.EnsembleStructure(samples, B, C, Hh, Ww, nkeep, dev, out_std, u=u.view(B, 3)[:, :C], lags=structure[0],
-                                        weights=structure[1], grid=(args.dx, args.dy)) if structure is not None else None
-            evs = ops.EnsembleEvents(samples, B, C, Hh, Ww, nkeep, dev, out_mu, out_std, u=u.view(B, 3)[:, :C], events=events[0],
-                                     scales=events[1]) if events is not None else None
-            pdf = None
-            if pdfs is not None:
-                kw = dict(pdfs)
-                pgrid = (args.dx, args.dy)
-                kinds = ops.pdf_args(kw["fields"], kw["bins"], [(0.0, 1.0)] * len(kw["fields"]), kw["joint"], kw["joint_bins"], kw["regions"],
-                                     pgrid, B, C, Hh, Ww)[0]
-                # the target's physical series at the kept steps from t_start on, in fp64 (range and centre only: not the hot path)
-                tk = tgt[:, t_start * stride:(nkeep - 1) * stride + 1:stride].double()
-                if isinstance(kw["center"], str):
-                    kw["center"] = tk.mean(1).float()
-                elif kw["center"] is not None:
-                    kw["center"] = torch.as_tensor(kw["center"])[case0:case0 + B]
-                if kw["ranges"] is not None and torch.as_tensor(kw["ranges"]).dim() == 3:
-                    kw["ranges"] = torch.as_tensor(kw["ranges"])[case0:case0 + B]
-                if kw["ranges"] is None:
-                    cen = None if kw["center"] is None else kw["center"].to(dev).float().double().unsqueeze(1)
-                    vals = _pdf_target_fields(tk, kinds, pgrid)
-                    rg = torch.zeros(B, len(kinds), 2, dtype=torch.float64)
-                    for f, (k, v) in enumerate(zip(kinds, vals)):
-                        if k < 4 and cen is not None:
-                            v = v - cen[:, :, k]
-                        lo, hi = v.reshape(B, -1).min(1).values.cpu(), v.reshape(B, -1).max(1).values.cpu()
-                        if bool((hi <= lo).any()):
-                            raise ValueError("%s: field %r of the target of case %d is constant (%r): give ranges"
-                                             % (name, kw["fields"][f], case0 + int((hi <= lo).nonzero()[0]), float(lo[(hi <= lo).nonzero()[0]])))
-                        rg[:, f, 0], rg[:, f, 1] = lo - 0.25 * (hi - lo), hi + 0.25 * (hi - lo)
-                    kw["ranges"] = rg
-                pdf = ops.EnsemblePdfs(samples, B, C, Hh, Ww, nkeep, dev, out_mu, out_std, u=u.view(B, 3)[:, :C], grid=pgrid, **kw)
+            mb = SimpleNamespace(B=B, C=C, H=Hh, W=Ww, dev=dev, out_mu=out_mu, out_std=out_std, u=u.view(B, 3)[:, :C], grid=grid, tgt=tgt,
+                                 case0=case0)
+            live = [(a, a.make(mb, samples, nkeep - t_start if a.window else nkeep)) for a in accs]
             case0 += B
-            tnorm = target0.to(dev) if scores or qt is not None or en is not None or sfn is not None or evs is not None or pdf is not None else None                # the normalised series; one step at a time goes channels-last
+            tnorm = target0.to(dev) if any(a.target for a in accs) else None   # the normalised series; one step at a time goes channels-last
             for tstep in range(tmax):
                 keep = tstep % stride == 0 and tstep // stride < nkeep
+                timed = tstep // stride >= t_start
                 tj = tnorm[:, tstep].contiguous(memory_format=torch.channels_last) if keep and tnorm is not None else None
                 for ci, (m0, k) in enumerate(chunks):
                     y0, _logp, states[ci] = core.sampleEnsemble(inp[:, tstep], states[ci], k)
                     if keep:
-                        st.add(y0, m0, time=tstep // stride >= t_start)
-                        if sp is not None:
-                            sp.add(y0, m0, time=tstep // stride >= t_start)
-                        if sc is not None:
-                            sc.add(y0, m0, tj, time=tstep // stride >= t_start)
-                        if tsp_t is not None and tstep // stride >= t_start:
-                            tsp_t.add(y0, m0)
-                        if qt is not None:
-                            qt.add(y0, m0, tj, time=tstep // stride >= t_start)
-                        if en is not None:
-                            en.add(y0, m0, tj, time=tstep // stride >= t_start)
-                        if sfn is not None:
-                            sfn.add(y0, m0, tj, time=tstep // stride >= t_start)
-                        if evs is not None:
-                            evs.add(y0, m0, tj, time=tstep // stride >= t_start)
-                        if pdf is not None:
-                            pdf.add(y0, m0, tj, time=tstep // stride >= t_start)
+                        for a, acc in live:
+                            if a.window:
+                                if timed:
+                                    acc.add(y0, m0)
+                            elif a.target:
+                                acc.add(y0, m0, tj, time=timed)
+                            else:
+                                acc.add(y0, m0, time=timed)
                     if tstep % 20 == 0:
                         states[ci] = [(0.5 * h + 0.5 * hk, 0.5 * c + 0.5 * ck) for (h, c), (hk, ck) in zip(states[ci], anchors[ci])]
-            for key, t in st.finalize().items():
-                outs.setdefault(key, []).append(t.cpu())
-            if sp is not None:
-                for key, t in sp.finalize().items():
-                    if key == "spec_k":
-                        spec_k = t
+            for a, acc in sorted(live, key=lambda p: p[0].window):    # list order, the windowed ones last
+                for key, t in acc.finalize().items():
+                    if key in a.meta:
+                        meta[key] = t
                     else:
                         outs.setdefault(key, []).append(t.cpu())
-            if sc is not None:
-                for key, t in sc.finalize().items():
-                    outs.setdefault(key, []).append(t.cpu())
-            if qt is not None:
-                for key, t in qt.finalize().items():
-                    if key == "levels":
-                        q_levels = t
-                    else:
-                        outs.setdefault(key, []).append(t.cpu())
-            if en is not None:
-                for key, t in en.finalize().items():
-                    outs.setdefault(key, []).append(t.cpu())
-            if sfn is not None:
-                for key, t in sfn.finalize().items():
-                    if key in ("lags", "lag_dist"):
-                        sf_lags[key] = t
-                    else:
-                        outs.setdefault(key, []).append(t.cpu())
-            if evs is not None:
-                for key, t in evs.finalize().items():
-                    if key == "event_scales":
-                        sf_lags[key] = t
-                    else:
-                        outs.setdefault(key, []).append(t.cpu())
-            if pdf is not None:
-                for key, t in pdf.finalize().items():
-                    if key in ("pdf_fields", "pdf_joint", "pdf_regions"):
-                        sf_lags[key] = t
-                    else:
-                        outs.setdefault(key, []).append(t.cpu())
-            if tsp_t is not None:
-                for key, t in tsp_t.finalize().items():
-                    if key == "psd_freq":
-                        psd_freq = t
-                    else:
-                        outs.setdefault(key, []).append(t.cpu())
-                # the target series over the same kept steps through the same kernels: a one-member ensemble
-                tn = target0.to(dev)
-                tts = ops.EnsembleTimeSpectrum(1, B, C, Hh, Ww, nkeep - t_start, dev, out_mu, out_std, u=u.view(B, 3)[:, :C],
-                                               nfreq=tspec[0], window=tspec[1], dt=tspec[2])
-                for j in range(t_start, nkeep):
-                    tts.add(tn[:, j * stride].contiguous(memory_format=torch.channels_last), 0)
-                outs.setdefault("target_psd", []).append(tts.finalize()["psd_mean"].cpu())
-            if grid is not None:
-                # the target's own time statistics over the same kept steps: the normalised series as a one-member ensemble
+            if tails:
+                # the target series over the kept steps from t_start on through the same kernels: a one-member ensemble
                 if target0.size(1) <= (nkeep - 1) * stride:
-                    raise ValueError("%s: the target series holds %d steps, kept step %d needs step %d"
-                                     % (name, target0.size(1), nkeep - 1, (nkeep - 1) * stride))
+                    raise ValueError(short)
                 tn = target0.to(dev)
-                ts = ops.EnsembleStats(1, B, C, Hh, Ww, nkeep - t_start, dev, out_mu, out_std, u=u.view(B, 3)[:, :C], grid=grid)
-                tsp = ops.EnsembleSpectrum(1, B, Hh, Ww, nkeep - t_start, dev, out_mu, out_std, u=u.view(B, 3), grid=grid,
-                                           window=window) if spectra else None
+                ones = [a.make(mb, 1, nkeep - t_start) for a in tails]
                 for j in range(t_start, nkeep):
                     tj = tn[:, j * stride].contiguous(memory_format=torch.channels_last)
-                    ts.add(tj, 0)
-                    if tsp is not None:
-                        tsp.add(tj, 0)
-                tout = ts.finalize()
-                for key, src in _TARGET_STATS:
-                    outs.setdefault(key, []).append(tout[src].cpu())
-                if tsp is not None:
-                    tout = tsp.finalize()
-                    outs.setdefault("target_spec", []).append(tout["spec_mean"].cpu())
-                    outs.setdefault("target_time_spec", []).append(tout["time_spec_mean"].cpu())
+                    for acc in ones:
+                        acc.add(tj, 0)
+                for a, acc in zip(tails, ones):
+                    tout = acc.finalize()
+                    for key, src in a.tail:
+                        outs.setdefault(key, []).append(tout[src].cpu())
     res = {key: torch.cat(v, dim=0) for key, v in outs.items()}
     res["target"] = torch.cat(targets, dim=0)
     res["input"] = torch.cat(inputs, dim=0)
-    if spectra:
-        res["spec_k"] = spec_k
-    if tspec is not None:
-        res["psd_freq"] = psd_freq
-    if quant is not None:
-        res["levels"] = q_levels
-    if energy is not None:
-        res["energy_groups"] = tuple(energy)
-    if events is not None:
-        res["events"] = tuple(events[0])
-    res.update(sf_lags)
+    for a in accs:
+        res.update(a.extra)
+    res.update(meta)
     return res
 
 
@@ -390,8 +328,10 @@ def modelPredSpectra(args, model, testing_loader, log, samples=1, stride=1, tmax
                                              time mean, through the same kernels as a one-member ensemble."""
     if window not in ("hann", None):
         raise ValueError("window must be 'hann' or None, got %r" % (window,))
-    return _ensembleStats("modelPredSpectra", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, True,
-                          spectra=True, window=window)
+    import tmg_ops as ops
+    acc = _Acc(lambda mb, S, T: ops.EnsembleSpectrum(S, mb.B, mb.H, mb.W, T, mb.dev, mb.out_mu, mb.out_std, u=mb.u, grid=mb.grid, window=window),
+               meta=("spec_k",), tail=(("target_spec", "spec_mean"), ("target_time_spec", "time_spec_mean")))
+    return _ensembleStats("modelPredSpectra", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, True, [acc])
 
 
 def modelPredScores(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64):
@@ -407,8 +347,9 @@ def modelPredScores(args, model, testing_loader, log, samples=1, stride=1, tmax=
                                         (the Talagrand histogram; flat for a calibrated ensemble)
       time_crps, time_crps_fair [N, C, H, W]   the means of crps / crps_fair over the kept steps t_start..Tk-1
       time_rank_hist [N, C, S + 1]      int64: the sum of rank_hist over those steps."""
-    return _ensembleStats("modelPredScores", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False,
-                          scores=True)
+    import tmg_ops as ops
+    acc = _Acc(lambda mb, S, T: ops.EnsembleScores(S, mb.B, mb.C, mb.H, mb.W, T, mb.dev, mb.out_std, u=mb.u), target=True)
+    return _ensembleStats("modelPredScores", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
 
 
 def modelPredTimeSpectra(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, nfreq=32, window="hann",
@@ -437,8 +378,10 @@ def modelPredTimeSpectra(args, model, testing_loader, log, samples=1, stride=1, 
     step_dt = 1.0 if dt is None else float(stride) * float(dt)
     if not (math.isfinite(step_dt) and step_dt > 0):
         raise ValueError("dt must be a positive finite time between two model steps, got %r" % (dt,))
-    return _ensembleStats("modelPredTimeSpectra", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False,
-                          tspec=(int(nfreq), window, step_dt))
+    import tmg_ops as ops
+    acc = _Acc(lambda mb, S, T: ops.EnsembleTimeSpectrum(S, mb.B, mb.C, mb.H, mb.W, T, mb.dev, mb.out_mu, mb.out_std, u=mb.u, nfreq=int(nfreq), window=window, dt=step_dt),
+               window=True, meta=("psd_freq",), tail=(("target_psd", "psd_mean"),))
+    return _ensembleStats("modelPredTimeSpectra", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
 
 
 def modelPredQuantiles(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, levels=(0.05, 0.5, 0.95),
@@ -469,9 +412,10 @@ def modelPredQuantiles(args, model, testing_loader, log, samples=1, stride=1, tm
     members gives 0.5, but level 0 gives 1 / 6 and level 1 gives 5 / 6.  A level between two members is approximately the linear
     interpolation ((lo + 1) + w) / (S + 1) of its two neighbours."""
     import tmg_ops as ops
-    levels, exceed = ops.quantile_args(levels, exceed, 3)
-    return _ensembleStats("modelPredQuantiles", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False,
-                          quant=(tuple(levels), tuple(exceed)))
+    levels, exceed = (tuple(v) for v in ops.quantile_args(levels, exceed, 3))
+    acc = _Acc(lambda mb, S, T: ops.EnsembleQuantiles(S, mb.B, mb.C, mb.H, mb.W, T, mb.dev, mb.out_mu, mb.out_std, u=mb.u, levels=levels, exceed=exceed), target=True,
+               meta=("levels",))
+    return _ensembleStats("modelPredQuantiles", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
 
 
 def modelPredEnergy(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, groups=((0, 1), (2,))):
@@ -507,8 +451,9 @@ def modelPredEnergy(args, model, testing_loader, log, samples=1, stride=1, tmax=
     from them mean an over-dispersive one."""
     import tmg_ops as ops
     groups = ops.energy_groups(groups, 3)
-    return _ensembleStats("modelPredEnergy", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False,
-                          energy=groups)
+    acc = _Acc(lambda mb, S, T: ops.EnsembleEnergy(S, mb.B, mb.C, mb.H, mb.W, T, mb.dev, mb.out_std, u=mb.u, groups=groups), target=True,
+               extra={"energy_groups": tuple(groups)})
+    return _ensembleStats("modelPredEnergy", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
 
 
 def modelPredStructure(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, lags=None, weights=None):
@@ -535,11 +480,12 @@ def modelPredStructure(args, model, testing_loader, log, samples=1, stride=1, tm
                                         increment skewness and flatness, the standard measures of intermittency (3 for Gaussian increments)
       time_vario_lag [N, C, L], time_vario_score [N, C]   the means of vario_lag / vario_score over the timed steps
       lags [L, 2] int64, lag_dist [L] float64       the lags and their lengths hypot(dx args.dx, dy args.dy)."""
+    import tmg_ops as ops
     if lags is not None:
-        import tmg_ops as ops
         lags = ops.structure_lags(lags, 65, 65)                           # the rules that do not depend on the field; the field's come with it
-    return _ensembleStats("modelPredStructure", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False,
-                          structure=(lags, weights))
+    acc = _Acc(lambda mb, S, T: ops.EnsembleStructure(S, mb.B, mb.C, mb.H, mb.W, T, mb.dev, mb.out_std, u=mb.u, lags=lags, weights=weights, grid=(args.dx, args.dy)),
+               target=True, meta=("lags", "lag_dist"))
+    return _ensembleStats("modelPredStructure", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
 
 
 def modelPredEvents(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, events=((0, 0.0, "<"),),
@@ -578,9 +524,10 @@ def modelPredEvents(args, model, testing_loader, log, samples=1, stride=1, tmax=
       time_brier_map [N, K, H, W]       the Brier score per pixel over the timed steps
       event_scales [NS] int64, events   the widths and the events as given."""
     import tmg_ops as ops
-    events, scales = ops.event_args(events, scales, 3)
-    return _ensembleStats("modelPredEvents", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False,
-                          events=(tuple(events), tuple(scales)))
+    events, scales = (tuple(v) for v in ops.event_args(events, scales, 3))
+    acc = _Acc(lambda mb, S, T: ops.EnsembleEvents(S, mb.B, mb.C, mb.H, mb.W, T, mb.dev, mb.out_mu, mb.out_std, u=mb.u, events=events, scales=scales), target=True,
+               meta=("event_scales",), extra={"events": events})
+    return _ensembleStats("modelPredEvents", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
 
 
 def modelPredPdfs(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, fields=("ux", "uy", "p", "vort"),
@@ -622,6 +569,7 @@ def modelPredPdfs(args, model, testing_loader, log, samples=1, stride=1, tmax=1,
       pdf_fields, pdf_joint, pdf_regions            as given (regions None: the whole field as one box)."""
     if isinstance(center, str) and center != "target":
         raise ValueError("center is None, an array [N, C, H, W] in physical units or \"target\", got %r" % (center,))
-    return _ensembleStats("modelPredPdfs", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False,
-                          pdfs=dict(fields=tuple(fields), bins=bins, ranges=ranges, joint=tuple(tuple(pr) for pr in joint), joint_bins=joint_bins,
-                                    regions=regions, center=center))
+    pdfs = dict(fields=tuple(fields), bins=bins, ranges=ranges, joint=tuple(tuple(pr) for pr in joint), joint_bins=joint_bins,
+                regions=regions, center=center)
+    acc = _Acc(_pdf_factory("modelPredPdfs", args, stride, t_start, pdfs), target=True, meta=("pdf_fields", "pdf_joint", "pdf_regions"))
+    return _ensembleStats("modelPredPdfs", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
