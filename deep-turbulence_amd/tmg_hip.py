@@ -20,14 +20,18 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmglow_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip"]
+SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip"]
 # Sources compiled WITHOUT the packed-fp32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32): beside MFMAs a packed
 # f32 instruction costs ~13 cycles more than the two scalar ones it replaces (MI355X_MICROARCH.md, cycle constants, 'price of one
 # filler beside MFMAs'), and the compiler SLP-packs adjacent scalar adds / multiplies by itself under -O3.  The matrix-core kernels'
 # files are listed; the vector-ALU kernels (tmg_pointwise.hip, tmg_physics.hip) keep the packed forms, which double their arithmetic
 # rate.  Round 3 measured the switch inside the noise and left the list empty; round 5 on one box, alternating three times: packed
 # everywhere 43.62 / 43.98 / 43.76 ms per step, this list 43.51 / 43.60 / 43.37 (wino + conv + coupling alone 43.64 / 43.52 / 43.58).
-NO_PACKED_F32 = ["tmg_wino.hip", "tmg_conv.hip", "tmg_coupling.hip", "tmg_thin.hip", "tmg_mix16.hip", "tmg_spectrum.hip", "tmg_tspec.hip"]
+# tmg_pod.hip is listed: its vector work (the fluctuation's subtraction and product, the energy's fmaf chain) is issued between the
+# MFMAs of the projection, exactly the filler position the list is about; its results do not depend on the choice (a packed
+# instruction rounds each half as the scalar one does).
+NO_PACKED_F32 = ["tmg_wino.hip", "tmg_conv.hip", "tmg_coupling.hip", "tmg_thin.hip", "tmg_mix16.hip", "tmg_spectrum.hip", "tmg_tspec.hip",
+                 "tmg_pod.hip"]
 _lib = None
 
 c_i64 = ctypes.c_int64
@@ -66,6 +70,9 @@ EVENT_EXPORTS = ["tmg_ens_event_plan", "tmg_ens_event_count", "tmg_ens_event_ste
 # The pooled probability densities: marginal and joint histograms of the members and of the target (csrc/tmg_pdf.hip), declared in
 # include/tmglow_hip_pdf.h: ens_pdf_plan / ens_pdf_count below.
 PDF_EXPORTS = ["tmg_ens_pdf_plan", "tmg_ens_pdf_count"]
+# The projection on the target's POD modes (csrc/tmg_pod.hip), declared in include/tmglow_hip_pod.h: ens_pod_plan / ens_pod_project
+# below.
+POD_EXPORTS = ["tmg_ens_pod_plan", "tmg_ens_pod_project"]
 # Every export returns int except the workspace sizes, which the header declares int64_t (read through a 32-bit return a request of
 # 2^31 floats or more would be truncated and the kernel handed a buffer smaller than it planned for).
 RET_I64 = ("tmg_conv_wgrad_ws_floats", "tmg_conv_wgrad_grouped_ws_floats", "tmg_conv_wino_wgrad_ws_floats",
@@ -80,7 +87,7 @@ def build(force=False, verbose=False):
     headers = [os.path.join(CSRC, "tmg_common.h"), os.path.join(inc, "tmglow_hip.h"), os.path.join(inc, "tmglow_hip_plan.h"),
                os.path.join(inc, "tmglow_hip_tspec.h"), os.path.join(inc, "tmglow_hip_quant.h"),
                os.path.join(inc, "tmglow_hip_gram.h"), os.path.join(inc, "tmglow_hip_sfun.h"),
-               os.path.join(inc, "tmglow_hip_event.h"), os.path.join(inc, "tmglow_hip_pdf.h")]
+               os.path.join(inc, "tmglow_hip_event.h"), os.path.join(inc, "tmglow_hip_pdf.h"), os.path.join(inc, "tmglow_hip_pod.h")]
     hmt = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -134,7 +141,7 @@ def lib():
         for name in PLAN_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
             getattr(_lib, name).argtypes = PLAN_ARGTYPES[name]
-        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS + SFUN_EXPORTS + EVENT_EXPORTS + PDF_EXPORTS:
+        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS + SFUN_EXPORTS + EVENT_EXPORTS + PDF_EXPORTS + POD_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
     return _lib
 
@@ -1334,6 +1341,30 @@ def ens_pdf_count(y, u, out_mu, out_std, center, edges, jedges, kinds, pairs, bo
                                  _i64(*desc), _ptr(step_count), _ptr(step_joint), _ptr(mtime), _ptr(tjoint), _i64(*ostrides),
                                  _i64(k, kB // k, Hh, Ww, Cc, S, m0, len(kinds), nb, len(pairs), nbj, len(boxes), flags),
                                  _flts(grid) if grid is not None else None, _stream()), "tmg_ens_pdf_count")
+
+
+def ens_pod_plan(S, B, Cg, HW, K):
+    """The slice plan of ens_pod_project for calls of S members of B cases of [Cg, HW] against K modes (tmg_ens_pod_plan; nothing is
+    launched) -> dict: P pixel slices of SL pixels (a function of HW alone: the same for every S), L = SL Cg the fmaf terms of one
+    partial (L P >= HW Cg), ws the workspace floats of a call of S members (0 for P = 1)."""
+    plan = (c_i64 * 4)()
+    _chk(lib().tmg_ens_pod_plan(_i64(S, B, Cg, HW, K), plan), "tmg_ens_pod_plan")
+    P, SL, L, ws = [int(v) for v in plan]
+    return {"P": P, "SL": SL, "L": L, "ws": ws}
+
+
+def ens_pod_project(y, channels, a, m, psi, ws, coef, en, ostrides, k):
+    """Project one chunk of k members (y: NHWC [k*B, H, W, C] or a channel-slice view, rows member-major; k = 1: the B target rows) on
+    the modes psi [B, K, Cg, HW] about the mean planes m [B, Cg, HW] with the scales a [B, Cg] (device fp32) over the channels
+    `channels`: the raw sums coef_raw [K] and en_raw of row (s, b) at coef + b ostrides[0] + s ostrides[1] and en + b ostrides[2] +
+    s ostrides[3] (coef / en: views that start at the chunk's first member and step); ws: the workspace (>= ens_pod_plan's floats
+    for S = k) or None when the plan needs none (tmg_ens_pod_project)."""
+    kB, Hh, Ww, Cc = y.shape
+    ptr, ps, co, _ = seg(y)
+    B, K, Cg, HW = psi.shape
+    _chk(lib().tmg_ens_pod_project(c_vp(ptr), _i64(ps, co), _i64(*[int(c) for c in channels]), _ptr(a), _ptr(m), _ptr(psi), _ptr(ws),
+                                   c_i64(ws.numel() if ws is not None else 0), _ptr(coef), _ptr(en), _i64(*ostrides),
+                                   _i64(k, kB // k, Hh * Ww, Cg, K), _stream()), "tmg_ens_pod_project")
 
 
 def spec_rows(y, u, out_mu, out_std, ft_w, yw, k):

@@ -2540,6 +2540,187 @@ class EnsembleEnergy(EnsembleFeed):
         return o
 
 
+POD_MAX_MODES = 16
+
+
+def pod_channels(channels, C):
+    """The checks of the POD's channels argument for C channels: 1 to 4 distinct channels in 0..C-1 -> a tuple of ints."""
+    try:
+        chs = tuple(channels)
+    except TypeError:
+        raise ValueError("channels must be a tuple of channels, got %r" % (channels,))
+    if not 1 <= len(chs) <= 4:
+        raise ValueError("channels must hold 1 to 4 channels, got %r" % (channels,))
+    for ch in chs:
+        if isinstance(ch, bool) or not isinstance(ch, numbers.Integral) or not 0 <= ch < C:
+            raise ValueError("channels hold distinct channels in 0..%d, got %r" % (C - 1, channels))
+    if len(set(int(ch) for ch in chs)) != len(chs):
+        raise ValueError("channels hold distinct channels in 0..%d, got %r" % (C - 1, channels))
+    return tuple(int(ch) for ch in chs)
+
+
+def pod_basis(series, a, channels, K, name="pod_basis", case0=0):
+    """The POD basis of a target series by the method of snapshots, in fp64 plain torch on the series' device (once per mini-batch:
+    not the hot path).  series [B, Tn, C, H, W]: the normalised target at the Tn kept steps; a [B, C]: the scales u out_std > 0;
+    channels: the Cg distinct channels of the inner product <f, g> = (1 / HW) sum_{c in channels} sum_p f_c g_c; 1 <= K <= 16 modes,
+    K <= Tn - 1 (the centred snapshots have rank at most Tn - 1), Tn >= 2.  With m the time mean and d_j = a_c (x_j - m):
+      R[j, j'] = <d_j, d_j'> / Tn = sum_k lam_k v_k[j] v_k[j'], lam_0 >= lam_1 >= ..; every v_k with its entry of largest magnitude
+      positive (the first such entry on a tie); psi_k = sum_j v_k[j] d_j / sqrt(Tn lam_k): <psi_k, psi_l> = delta_kl, RMS 1
+    -> (m [B, Cg, H, W], psi [B, K, Cg, H, W], lam [B, K], lam_total [B] = trace R, target_coef [B, Tn, K] = <d_j, psi_k> =
+    sqrt(Tn lam_k) v_k[j]), all fp64.  A mode with lam_k <= 1e-12 lam_0, or lam_0 == 0 (at most 2^-80 of the un-centred energy <a x, a x>,
+    what the rounding of the mean leaves of a constant series), raises (a constant target has no modes);
+    name and case0 (the cases before this batch) only word that message."""
+    series = torch.as_tensor(series)
+    if series.dim() != 5:
+        raise ValueError("the series is [B, Tn, C, H, W], got shape %s" % (tuple(series.shape),))
+    B, Tn, C, Hh, Ww = series.shape
+    chs = pod_channels(channels, C)
+    if isinstance(K, bool) or not isinstance(K, numbers.Integral) or not 1 <= K <= POD_MAX_MODES:
+        raise ValueError("the POD keeps 1 <= modes <= %d, got %r" % (POD_MAX_MODES, K))
+    if Tn < 2:
+        raise ValueError("the POD needs at least 2 snapshots, got %d" % Tn)
+    if K > Tn - 1:
+        raise ValueError("%d centred snapshots have rank at most %d: modes = %d is too many" % (Tn, Tn - 1, K))
+    a = torch.as_tensor(a, dtype=torch.float64).to(series.device).reshape(B, C)[:, list(chs)]
+    if not bool((torch.isfinite(a) & (a > 0)).all()):
+        raise ValueError("the scales a = u out_std must be finite and strictly positive")
+    x = series[:, :, list(chs)].double()
+    if not bool(torch.isfinite(x).all()):
+        raise ValueError("the series must be finite")
+    m = x.mean(1)
+    d = (a.view(B, 1, -1, 1, 1) * (x - m.unsqueeze(1))).reshape(B, Tn, -1)   # [B, Tn, Cg HW]
+    HW = Hh * Ww
+    R = d @ d.transpose(1, 2) / (HW * Tn)
+    lam_total = torch.diagonal(R, dim1=1, dim2=2).sum(1)
+    w, v = torch.linalg.eigh(R)                                              # ascending
+    lam = w.flip(1)[:, :K]
+    v = v.flip(2)[:, :, :K]                                                  # [B, Tn, K]: column k is v_k
+    # lam_0 == 0 as fp64 sees it: below the rounding of the mean, (2^-40)^2 of the un-centred energy <a x, a x>
+    floor = 2.0 ** -80 * ((a.view(B, 1, -1, 1, 1) * x) ** 2).reshape(B, -1).sum(1, keepdim=True) / (HW * Tn)
+    bad = (lam <= 1e-12 * lam[:, :1]) | (lam[:, :1] <= floor)
+    if bool(bad.any()):
+        b, k = [int(i) for i in bad.nonzero()[0]]
+        raise ValueError("%s: mode %d of the target of case %d carries no energy (lam = %r, lam_0 = %r): a constant target has no "
+                         "modes; keep fewer" % (name, k, case0 + b, float(lam[b, k]), float(lam[b, 0])))
+    top = v.abs().argmax(1, keepdim=True)                                    # the first entry of largest magnitude
+    sgn = torch.where(torch.gather(v, 1, top) < 0, -1.0, 1.0).to(v.dtype)
+    v = v * sgn
+    amp = torch.sqrt(Tn * lam)                                               # [B, K]
+    psi = (v.transpose(1, 2) @ d) / amp.unsqueeze(2)                         # [B, K, Cg HW]
+    return m, psi.reshape(B, K, len(chs), Hh, Ww), lam, lam_total, v * amp.unsqueeze(1)
+
+
+def _pod_time(coef, en):
+    """coef [.., T, K], en [.., T] fp64 over the timed steps -> the time aggregates of EnsembleModes (fp64)."""
+    mean = coef.mean(-2)
+    dev = coef - mean.unsqueeze(-2)
+    energy = (coef * coef).mean(-2)
+    cov = dev.transpose(-1, -2) @ dev / coef.shape[-2]
+    fl = en.mean(-1)
+    cap = energy.sum(-1)
+    return {"time_mode_energy": energy, "time_mode_mean": mean, "time_coef_cov": cov, "time_captured_frac": cap / fl,
+            "time_resid_energy": fl - cap}
+
+
+class EnsembleModes(EnsembleFeed):
+    """On-device projection of sampled roll-outs of B cases, and of the target, on given POD modes of the target (tmg_ens_pod_project):
+    do the members hold the reference's coherent structures, with the right energy and the right dynamics?  Given per case the mean
+    planes `mean` [B, Cg, H, W] (normalised) and the modes `basis` [B, K, Cg, H, W] (K <= 16; pod_basis builds both from the target
+    series; any finite tables are accepted and rounded to fp32 once), a_c = u[b, c] out_std[c] > 0 and the inner product
+    <f, g> = (1 / HW) sum_{c in channels} sum_p f_c g_c, for every row x (a member, or the step's target):
+      d = fl(a_c fl(x - mean))                              the fluctuation in physical units, two fp32 roundings
+      coef[k] = <d, basis_k>,  fluct_energy = <d, d>        fp32 sums on the device (the modes on the matrix pipe), / HW in fp64
+    A member's coefficients need no other member: the kernel reads the chunk's rows in place and no member buffer is kept; the pixel
+    slicing of the sums depends on the field alone, so every output is bitwise the same for every chunking and ensemble size.
+
+    Feeding protocol of EnsembleFeed: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
+    chunks before the next step's; every chunk comes with the step's target, and the last chunk's is the one that is projected.
+    Outputs (device tensors): coef [B, S, Tk, K], fluct_energy [B, S, Tk], target_coef [B, Tk, K], target_fluct_energy [B, Tk]
+    float32; finalize() adds, over the steps folded with time=True (formed in fp64 from the outputs above, rounded once):
+      time_mode_energy [B, S, K]      mean_t coef^2: each member's energy in the target's mode k; compare with the target's
+      time_mode_mean [B, S, K]        mean_t coef: the member's mean-flow error as mode k sees it
+      time_coef_cov [B, S, K, K]      mean_t (coef - mean)(coef - mean)^T: off-diagonals show structures rotated inside the subspace
+      time_captured_frac [B, S]       sum_k time_mode_energy / mean_t fluct_energy
+      time_resid_energy [B, S]        mean_t fluct_energy - sum_k time_mode_energy: what the K modes do not hold
+      target_time_* [B, ..]           the same of the target's row; for pod_basis' tables over the same steps
+                                      target_time_mode_energy is lam_k and target_time_captured_frac is sum_k lam_k / lam_total
+      mode_energy_ratio_mean, mode_energy_ratio_std [B, K]   mean / population std over the members of time_mode_energy / lam_k,
+                                      lam the attribute `lam` [B, K] (pod_basis' energies, set by whoever built the tables); None,
+                                      the default: target_time_mode_energy, which is lam_k as this kernel measures it
+    and the entries of the attribute `extra` (a dict, empty by default) as they are."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_std, u=None, channels=(0, 1), mean=None, basis=None):
+        noun, why = "ensemble modes", "the fluctuations scale with u * out_std"
+        _ens_channels(noun, C)
+        _ens_members(noun, members)
+        sd, _ = _ens_tables(C, why, out_std)
+        u = _ens_u(u, B, C, why)
+        self.channels = pod_channels(channels, C)
+        Cg = len(self.channels)
+        if int(steps) < 1 or int(B) < 1 or int(Hh) < 1 or int(Ww) < 1:
+            raise ValueError("%s need steps, B, H, W >= 1, got %d, %d, %d, %d" % (noun, steps, B, Hh, Ww))
+        if mean is None or basis is None:
+            raise ValueError("%s need the tables mean [B, Cg, H, W] and basis [B, K, Cg, H, W] (pod_basis builds them)" % noun)
+        mean, basis = torch.as_tensor(mean).detach(), torch.as_tensor(basis).detach()
+        if tuple(mean.shape) != (int(B), Cg, int(Hh), int(Ww)) or not bool(torch.isfinite(mean).all()):
+            raise ValueError("mean is a finite array [%d, %d, %d, %d], got shape %s" % (B, Cg, Hh, Ww, tuple(mean.shape)))
+        if (basis.dim() != 5 or not 1 <= basis.shape[1] <= POD_MAX_MODES or tuple(basis.shape[:1] + basis.shape[2:]) != tuple(mean.shape)
+                or not bool(torch.isfinite(basis).all())):
+            raise ValueError("basis is a finite array [%d, 1..%d, %d, %d, %d], got shape %s" % (B, POD_MAX_MODES, Cg, Hh, Ww, tuple(basis.shape)))
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, C, Hh, Ww, steps)
+        HW, K = self.H * self.W, int(basis.shape[1])
+        self.K = K
+        f32 = dict(device=dev, dtype=torch.float32)
+        # a_c = u out_std in fp64 from the fp32 factors, rounded once; the tables rounded once
+        self.a = _ens_scale(sd, u, self.B, torch.float64)[:, list(self.channels)].to(torch.float32).to(dev).contiguous()
+        self.m = mean.to(torch.float32).reshape(self.B, Cg, HW).to(dev).contiguous()
+        self.psi = basis.to(torch.float32).reshape(self.B, K, Cg, HW).to(dev).contiguous()
+        self.plan = H.ens_pod_plan(self.S, self.B, Cg, HW, K)
+        self.ws = torch.empty((self.plan["ws"],), **f32) if self.plan["ws"] else None
+        self.coef_raw = torch.empty((self.B, self.S, self.Tk, K), **f32)
+        self.en_raw = torch.empty((self.B, self.S, self.Tk), **f32)
+        self.tcoef_raw = torch.empty((self.B, self.Tk, K), **f32)
+        self.ten_raw = torch.empty((self.B, self.Tk), **f32)
+        self.extra = {}
+        self.lam = None
+
+    def add(self, y, m0, target, time=True):
+        """Project the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
+        channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride rule.  The step's
+        last chunk projects the target as one more row."""
+        yn, tn, k, t_before, last = self.open_chunk(y, m0, time, target, required=True)
+        _on_device(yn, tn)
+        t, S, Tk, K = self._step, self.S, self.Tk, self.K
+        H.ens_pod_project(yn, self.channels, self.a, self.m, self.psi, self.ws, self.coef_raw[:, m0:, t], self.en_raw[:, m0:, t],
+                          (S * Tk * K, Tk * K, S * Tk, Tk), k)
+        if last:
+            H.ens_pod_project(tn, self.channels, self.a, self.m, self.psi, self.ws, self.tcoef_raw[:, t], self.ten_raw[:, t],
+                              (Tk * K, 0, Tk, 0), 1)
+        self.close_chunk(m0, k, time, last)
+
+    def finalize(self):
+        """-> dict of the outputs; the time aggregates cover the steps folded with time=True."""
+        self.finalize_guard()
+        dev = self.coef_raw.device
+        hw = float(self.H * self.W)
+        f32 = lambda v: v.to(torch.float32)                                   # noqa: E731
+        # the host divides the raw sums by HW in fp64 and rounds once
+        o = {"coef": f32(self.coef_raw.double() / hw), "fluct_energy": f32(self.en_raw.double() / hw),
+             "target_coef": f32(self.tcoef_raw.double() / hw), "target_fluct_energy": f32(self.ten_raw.double() / hw)}
+        tm = _pod_time(o["coef"][:, :, self._timed].double().cpu(), o["fluct_energy"][:, :, self._timed].double().cpu())
+        tt = _pod_time(o["target_coef"][:, self._timed].double().cpu(), o["target_fluct_energy"][:, self._timed].double().cpu())
+        lam = tt["time_mode_energy"] if self.lam is None else torch.as_tensor(self.lam, dtype=torch.float64).cpu().reshape(self.B, self.K)
+        ratio = tm["time_mode_energy"] / lam.unsqueeze(1)
+        for key, v in tm.items():
+            o[key] = f32(v).to(dev)
+        for key, v in tt.items():
+            o["target_" + key] = f32(v).to(dev)
+        o["mode_energy_ratio_mean"], o["mode_energy_ratio_std"] = f32(ratio.mean(1)).to(dev), f32(ratio.std(1, unbiased=False)).to(dev)
+        o.update(self.extra)
+        return o
+
+
 STRUCTURE_MAX_LAGS = 16
 STRUCTURE_MAX_LAG = 64
 

@@ -573,3 +573,58 @@ def modelPredPdfs(args, model, testing_loader, log, samples=1, stride=1, tmax=1,
                 regions=regions, center=center)
     acc = _Acc(_pdf_factory("modelPredPdfs", args, stride, t_start, pdfs), target=True, meta=("pdf_fields", "pdf_joint", "pdf_regions"))
     return _ensembleStats("modelPredPdfs", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
+
+
+def _modes_factory(name, stride, t_start, modes, channels):
+    """The make of modelPredModes' record: the POD basis of the case's target over the kept steps from t_start on (tmg_ops.pod_basis,
+    fp64: not the hot path), handed to tmg_ops.EnsembleModes as fp32 tables, and the basis itself as results."""
+    def make(mb, members, steps):
+        import tmg_ops as ops
+        B, C = mb.B, mb.C
+        # the target's series at the kept steps from t_start on, back in normalised units, in fp64
+        tk = mb.tgt[:, t_start * stride:(steps - 1) * stride + 1:stride].double()
+        u, sd, mu = mb.u.double(), mb.out_std.double()[:C], mb.out_mu.double()[:C]
+        xn = (tk / u.view(B, 1, C, 1, 1) - mu.view(1, 1, C, 1, 1)) / sd.view(1, 1, C, 1, 1)
+        m, psi, lam, lam_total, _ = ops.pod_basis(xn, u * sd.view(1, C), channels, modes, name=name, case0=mb.case0)
+        acc = ops.EnsembleModes(members, B, C, mb.H, mb.W, steps, mb.dev, mb.out_std, u=mb.u, channels=channels, mean=m, basis=psi)
+        acc.lam = lam
+        acc.extra = {"pod_energy": lam, "pod_energy_frac": lam / lam_total.unsqueeze(1), "pod_modes": psi.float(),
+                     "pod_mean": tk.mean(1)[:, list(channels)].float()}
+        return acc
+    return make
+
+
+def modelPredModes(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, modes=8, channels=(0, 1)):
+    """modelPredStats plus the proper orthogonal decomposition (POD) of the target and every member's projection on it, still without
+    forming modelPred's [samples, N, T, C, H, W] tensor (tmg_ops.pod_basis / tmg_ops.EnsembleModes): do the members hold the
+    reference's coherent structures (the cylinder's shedding pair and its limit cycle in the (a1, a2) plane, the step's shear-layer
+    flapping mode) with the right energy and the right dynamics?  Spectra see energy per scale or frequency, never which spatial
+    pattern carries it; a member can match them all and still place its shedding mode half a diameter off.  The target of kept step
+    j is series step j * stride; a series that is too short raises.  Channel scales a = (u0, u0, u0^2) * out_std.  Same roll-outs as
+    modelPredStats: under the same host RNG state the keys both return are identical; the basis draws nothing from the host RNG.
+
+    Per case the basis comes from the target's fluctuations d_j = a (x_j - mean_j x_j) at the Tn kept steps from t_start on, with
+    <f, g> = (1 / HW) sum_{c in channels} sum_p f_c g_c, by the method of snapshots: modes psi_k with <psi_k, psi_l> = delta_kl (RMS
+    1 over the pixels) and energies lam_0 >= lam_1 >= .., each mode's sign fixed so that its temporal coefficient of largest
+    magnitude is positive.  modes: 1..16 and at most Tn - 1; channels: distinct channels of one unit, default the velocity.  A
+    target with fewer energetic modes than asked for (a constant one has none) raises.
+
+    Returns modelPredStats' dict plus (CPU tensors; K = modes, Cg channels, S = samples, kept steps t_start..Tk-1 are the timed ones):
+      coef [N, S, Tk, K], target_coef [N, Tk, K]     <d, psi_k> of every member and of the target, d about the TARGET's mean: plot
+                                                     (coef[.., 0], coef[.., 1]) for the limit cycle
+      fluct_energy [N, S, Tk], target_fluct_energy [N, Tk]   <d, d>
+      time_mode_energy [N, S, K]                     mean_t coef^2: each member's energy in target mode k; compare with pod_energy
+      time_mode_mean [N, S, K]                       mean_t coef: the member's mean-flow error as mode k sees it (the target's is 0)
+      time_coef_cov [N, S, K, K]                     the covariance of the coefficients over time: the target's is diag(pod_energy);
+                                                     off-diagonals show a member whose structures are rotated inside the subspace
+      time_captured_frac, time_resid_energy [N, S]   sum_k time_mode_energy / mean_t fluct_energy, and the energy outside the K modes
+      target_time_mode_energy, target_time_mode_mean [N, K], target_time_coef_cov [N, K, K], target_time_captured_frac,
+      target_time_resid_energy [N]                   the same of the target through the same kernel (pod_energy, 0, diag(pod_energy),
+                                                     sum_k pod_energy_frac up to rounding)
+      mode_energy_ratio_mean, mode_energy_ratio_std [N, K]   mean / std over the members of time_mode_energy / pod_energy
+      pod_energy, pod_energy_frac [N, K] float64     lam_k and lam_k / trace: the share of the target's fluctuation energy in mode k
+      pod_modes [N, K, Cg, H, W], pod_mean [N, Cg, H, W]   the modes and the target's time mean, physical units."""
+    import tmg_ops as ops
+    channels = ops.pod_channels(channels, 3)
+    acc = _Acc(_modes_factory("modelPredModes", stride, t_start, int(modes), channels), target=True)
+    return _ensembleStats("modelPredModes", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
