@@ -2721,6 +2721,213 @@ class EnsembleModes(EnsembleFeed):
         return o
 
 
+PHASE_BINS = (4, 8, 16, 32)
+
+
+def phase_args(pair, bins, min_amp, K=None):
+    """The checks of the phase arguments: pair two distinct mode indices >= 0 (below K when given), bins one of 4, 8, 16, 32,
+    min_amp finite and >= 0 -> (pair, bins, min_amp) as ints and a float."""
+    try:
+        pr = tuple(pair)
+    except TypeError:
+        raise ValueError("pair must hold two modes, got %r" % (pair,))
+    if len(pr) != 2 or any(isinstance(p, bool) or not isinstance(p, numbers.Integral) or p < 0 for p in pr):
+        raise ValueError("pair must hold two mode indices >= 0, got %r" % (pair,))
+    if pr[0] == pr[1]:
+        raise ValueError("pair must hold two different modes, got %r" % (pair,))
+    if K is not None and max(pr) + 1 > K:
+        raise ValueError("pair %r needs modes >= %d, got %d" % (tuple(pr), max(pr) + 1, K))
+    if isinstance(bins, bool) or not isinstance(bins, numbers.Integral) or bins not in PHASE_BINS:
+        raise ValueError("bins must be one of %s, got %r" % (PHASE_BINS, bins))
+    if isinstance(min_amp, bool) or not isinstance(min_amp, numbers.Real) or not 0 <= float(min_amp) < float("inf"):
+        raise ValueError("min_amp must be finite and >= 0, got %r" % (min_amp,))
+    return (int(pr[0]), int(pr[1])), int(bins), float(min_amp)
+
+
+def phase_table(bins, min_amp):
+    """The 8 host floats of tmg_ens_phase_label: the gate thr = 2 min_amp^2 and the tangents tan(2 pi q / bins), q = 1 .. bins / 4 - 1,
+    each formed in fp64 and rounded to fp32 once (unused entries 0) -> a list of Python floats that are exact fp32 values."""
+    r32 = lambda v: float(torch.tensor(v, dtype=torch.float64).to(torch.float32))   # noqa: E731
+    tab = [r32(2.0 * float(min_amp) * float(min_amp))]
+    tab += [r32(math.tan(2.0 * math.pi * q / bins)) for q in range(1, bins // 4)]
+    return tab + [0.0] * (8 - len(tab))
+
+
+def _phase_fields(cnt, raw, C):
+    """cnt [B, NB] (fp64 counts), raw [B, NB, Q, P] (fp64 raw sums, Q = 2 C + 1) -> the phase fields and the triple decomposition
+    about the target's mean (fp64): dev [B, NB, C, P] = sum d / n, var [B, NB, C, P], uv [B, NB, P] (NaN where n = 0), coh_var,
+    incoh_var [B, C, P], coh_uv, incoh_uv [B, P], coh_tke_frac [B], coh [B, NB, C, P] = dev - sum_k w_k dev_k (NaN where n = 0)."""
+    nan = float("nan")
+    n = cnt.view(cnt.shape + (1, 1))
+    has = n > 0
+    safe = torch.where(has, n, torch.ones_like(n))
+    ex = raw / safe
+    dev, sq, xy = ex[:, :, :C], ex[:, :, C:2 * C], ex[:, :, 2 * C]
+    var = sq - dev * dev
+    uv = xy - dev[:, :, 0] * dev[:, :, 1]
+    tot = cnt.sum(1)
+    w = (cnt / torch.where(tot > 0, tot, torch.ones_like(tot)).unsqueeze(1)).view(n.shape)   # 0 for an empty sector
+    mbar = (w * dev).sum(1, keepdim=True)
+    coh = dev - mbar
+    o = {"coh_var": (w * coh * coh).sum(1), "incoh_var": (w * var).sum(1), "coh_uv": (w[:, :, 0] * coh[:, :, 0] * coh[:, :, 1]).sum(1),
+         "incoh_uv": (w[:, :, 0] * uv).sum(1)}
+    num = o["coh_var"][:, :2].sum((1, 2))
+    o["coh_tke_frac"] = num / (num + o["incoh_var"][:, :2].sum((1, 2)))
+    none = (tot <= 0)
+    for key in ("coh_var", "incoh_var", "coh_uv", "incoh_uv", "coh_tke_frac"):
+        o[key] = torch.where(none.view((-1,) + (1,) * (o[key].dim() - 1)), torch.full_like(o[key], nan), o[key])
+    fill = lambda v, h: torch.where(h, v, torch.full_like(v, nan))           # noqa: E731
+    o["dev"], o["var"], o["uv"], o["coh"] = fill(dev, has), fill(var, has), fill(uv, has[:, :, 0]), fill(coh, has)
+    return o
+
+
+class EnsemblePhase(EnsembleFeed):
+    """On-device phase averages of sampled roll-outs of B cases, and of the target, on the shedding phase (tmg_ens_phase_label /
+    tmg_ens_phase_accum): the triple decomposition u = U + u~ + u' of Reynolds & Hussain.  At a given phase of the cycle, do the
+    members put the vortices where the reference puts them, and how much of the Reynolds stress is organised motion?
+
+    `modes` is a ready EnsembleModes of the same feed that this accumulator drives: add() calls modes.add() first, so the projection
+    runs once, through tmg_ens_pod_project.  The phase of a row is the angle of (x, y) = (coef_i / sqrt(lam_i), coef_j / sqrt(lam_j)),
+    (i, j) = pair, lam [B, 2] the pair's energies: on the device x = fl(g_i raw_i) with g = 1 / (HW sqrt(lam)) formed in fp64 and
+    rounded once.  A row with fl(fl(x x) + fl(y y)) < fl(2 min_amp^2) is skipped (label -1; a clean limit cycle has x^2 + y^2 = 2);
+    else its label is the sector 0 .. bins - 1 of the angle counted from the positive x axis towards positive y.  A point exactly on
+    an edge belongs to the higher sector; (0, 0) with min_amp = 0 is sector 0.  No transcendental runs on the device and every
+    operation is rounded on its own, so the labels equal a float32 numpy mirror bit for bit.
+
+    `mean` [B, C, H, W] is the target's time mean in normalised units for all C channels; with a_c = u[b, c] out_std[c] every labelled
+    row adds d_c = fl(a_c fl(x_c - mean_c)), d_c^2 and d_0 d_1 to the fp32 sums of its sector (centred on the target's mean, so that
+    E[d^2] - E[d]^2 does not cancel).  The additions into one element run steps in order, members in order for every chunking: the
+    outputs are bitwise reproducible.  The attribute `mean_phys` [B, C, H, W] (fp64; None, the default: a mean from the fp32 tables, an
+    output mean of zero) is the physical mean that phase_mean is counted from; whoever built the tables sets it.
+
+    Feeding protocol of EnsembleFeed, with the step's target on every chunk.  Every kept step is labelled; only steps with time=True
+    are accumulated.  finalize() returns modes.finalize()'s dict plus (n_k the rows of sector k, all formed in fp64 on the host from
+    the raw sums and the labels, rounded once; NaN where a sector is empty, empty sectors left out of every aggregate):
+      phase_bin [B, S, Tk], target_phase_bin [B, Tk] int32     the labels, -1 for a skipped row
+      phase_count [B, NB], member_phase_count [B, S, NB], target_phase_count [B, NB] int64, over the timed steps; phase_skipped,
+      target_phase_skipped [B]
+      phase_mean [B, NB, C, H, W]     mean_phys + sum d / n_k: the phase average <u>_k
+      phase_var [B, NB, C, H, W]      sum d^2 / n_k - (sum d / n_k)^2: the incoherent <u'_c u'_c>_k
+      phase_uv [B, NB, H, W]          the incoherent <u'_0 u'_1>_k
+      coh_var [B, C, H, W], coh_uv [B, H, W]        sum_k w_k (M_k - M)^2 and the same cross product, w_k = n_k / sum n, M = sum w_k M_k
+      incoh_var [B, C, H, W], incoh_uv [B, H, W]    sum_k w_k phase_var_k, sum_k w_k phase_uv_k
+      coh_tke_frac [B]                channels 0 and 1: sum_p coh_var / sum_p (coh_var + incoh_var)
+      target_*                        each of the fields above for the target's rows
+      phase_mean_rmse [B, NB, C]      RMS over the pixels of phase_mean - target_phase_mean
+      coh_corr [B, NB]                sum (M_k - M)(T_k - T) / sqrt(sum (M_k - M)^2 sum (T_k - T)^2) over channels 0, 1 and the pixels
+      phase_speed [B, S], target_phase_speed [B]    the mean increment of atan2(y, x), from the returned coef and lam in fp64, between
+                                      consecutive timed steps, wrapped to (-pi, pi], radians per kept step (NaN with one timed step)
+      phase_edges [NB + 1]            the sector angles 2 pi k / NB, float64 on the host."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_std, u=None, modes=None, pair=(0, 1), bins=8, min_amp=0.25, mean=None,
+                 lam=None):
+        noun, why = "ensemble phase averages", "the fluctuations scale with u * out_std"
+        _ens_channels(noun, C)
+        _ens_members(noun, members)
+        sd, _ = _ens_tables(C, why, out_std)
+        u = _ens_u(u, B, C, why)
+        if int(steps) < 1 or int(B) < 1 or int(Hh) < 1 or int(Ww) < 1:
+            raise ValueError("%s need steps, B, H, W >= 1, got %d, %d, %d, %d" % (noun, steps, B, Hh, Ww))
+        if not isinstance(modes, EnsembleModes):
+            raise ValueError("%s need modes, a ready EnsembleModes of the same feed" % noun)
+        if (modes.S, modes.B, modes.C, modes.H, modes.W, modes.Tk) != (int(members), int(B), int(C), int(Hh), int(Ww), int(steps)):
+            raise ValueError("modes is an EnsembleModes of another feed: %s" % ((modes.S, modes.B, modes.C, modes.H, modes.W, modes.Tk),))
+        self.pair, self.NB, self.min_amp = phase_args(pair, bins, min_amp, modes.K)
+        if mean is None or lam is None:
+            raise ValueError("%s need the tables mean [B, C, H, W] and lam [B, 2]" % noun)
+        mean, lam = torch.as_tensor(mean).detach(), torch.as_tensor(lam).detach().double().cpu()
+        if tuple(mean.shape) != (int(B), int(C), int(Hh), int(Ww)) or not bool(torch.isfinite(mean).all()):
+            raise ValueError("mean is a finite array [%d, %d, %d, %d], got shape %s" % (B, C, Hh, Ww, tuple(mean.shape)))
+        if tuple(lam.shape) != (int(B), 2) or not bool((torch.isfinite(lam) & (lam > 0)).all()):
+            raise ValueError("lam is a finite, strictly positive array [%d, 2], got shape %s" % (B, tuple(lam.shape)))
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, C, Hh, Ww, steps)
+        HW, NB = self.H * self.W, self.NB
+        self.modes, self.lam = modes, lam
+        f32 = dict(device=dev, dtype=torch.float32)
+        # a_c = u out_std in fp64 from the fp32 factors, rounded once; the tables rounded once
+        self.a = _ens_scale(sd, u, self.B, torch.float64).to(torch.float32).to(dev).contiguous()
+        self.m = mean.to(torch.float32).reshape(self.B, self.C, HW).to(dev).contiguous()
+        self.g = (1.0 / (HW * torch.sqrt(lam))).to(torch.float32).to(dev).contiguous()
+        self.tab = phase_table(NB, self.min_amp)
+        self.plan = H.ens_phase_plan(self.S, self.B, self.C, HW, NB)
+        Q = 2 * self.C + 1
+        self.acc = torch.zeros((self.B, NB, Q, HW), **f32)
+        self.tacc = torch.zeros((self.B, NB, Q, HW), **f32)
+        self.label = torch.full((self.B, self.S, self.Tk), -1, device=dev, dtype=torch.int32)
+        self.tlabel = torch.full((self.B, self.Tk), -1, device=dev, dtype=torch.int32)
+        self.mean_phys = None
+
+    def add(self, y, m0, target, time=True):
+        """Project (modes.add) and label the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose
+        channels-last view is an NHWC channel-slice; rows member-major) and, with time=True, add them to their sectors; target: the
+        step's normalised target [B, C, H, W] under the same stride rule.  The step's last chunk labels and adds the target's row."""
+        self.modes.add(y, m0, target, time=time)
+        yn, tn, k, t_before, last = self.open_chunk(y, m0, time, target, required=True)
+        _on_device(yn, tn)
+        t, S, Tk, K, B, NB = self._step, self.S, self.Tk, self.modes.K, self.B, self.NB
+        lab, ls = self.label[:, m0:, t], (S * Tk, Tk)
+        H.ens_phase_label(self.modes.coef_raw[:, m0:, t], (S * Tk * K, Tk * K), self.pair, self.g, self.tab, lab, ls, k, B, NB)
+        if time:
+            H.ens_phase_accum(yn, lab, ls, self.a, self.m, self.acc, k)
+        if last:
+            tlab, tls = self.tlabel[:, t], (Tk, 0)
+            H.ens_phase_label(self.modes.tcoef_raw[:, t], (Tk * K, 0), self.pair, self.g, self.tab, tlab, tls, 1, B, NB)
+            if time:
+                H.ens_phase_accum(tn, tlab, tls, self.a, self.m, self.tacc, 1)
+        self.close_chunk(m0, k, time, last)
+
+    def finalize(self):
+        """-> dict of the outputs; the counts, fields and speeds cover the steps folded with time=True."""
+        self.finalize_guard()
+        o = self.modes.finalize()
+        dev = self.acc.device
+        B, S, C, NB, Hh, Ww = self.B, self.S, self.C, self.NB, self.H, self.W
+        f32 = lambda v: v.to(torch.float32).to(dev)                           # noqa: E731
+        lab, tlab = self.label.cpu().long(), self.tlabel.cpu().long()
+        o["phase_bin"], o["target_phase_bin"] = self.label.clone(), self.tlabel.clone()
+        lt, tlt = lab[:, :, self._timed], tlab[:, self._timed]
+        sectors = torch.arange(NB).view(1, 1, 1, NB)
+        mcount = (lt.unsqueeze(-1) == sectors).sum(2)                            # [B, S, NB]
+        tcount = (tlt.unsqueeze(-1) == sectors[0]).sum(1)                        # [B, NB]
+        count = mcount.sum(1)
+        o["member_phase_count"], o["phase_count"], o["target_phase_count"] = mcount.to(dev), count.to(dev), tcount.to(dev)
+        o["phase_skipped"], o["target_phase_skipped"] = (lt < 0).sum((1, 2)).to(dev), (tlt < 0).sum(1).to(dev)
+        mp = (self.a.double().cpu().view(B, C, 1, 1) * self.m.double().cpu().view(B, C, Hh, Ww) if self.mean_phys is None
+              else torch.as_tensor(self.mean_phys).detach().double().cpu().reshape(B, C, Hh, Ww))
+        fe = _phase_fields(count.double(), self.acc.double().cpu(), C)
+        ft = _phase_fields(tcount.double(), self.tacc.double().cpu(), C)
+        for pre, f in (("", fe), ("target_", ft)):
+            o[pre + "phase_mean"] = f32((mp.view(B, 1, C, -1) + f["dev"]).view(B, NB, C, Hh, Ww))
+            o[pre + "phase_var"] = f32(f["var"].view(B, NB, C, Hh, Ww))
+            o[pre + "phase_uv"] = f32(f["uv"].view(B, NB, Hh, Ww))
+            for key in ("coh_var", "incoh_var"):
+                o[pre + key] = f32(f[key].view(B, C, Hh, Ww))
+            for key in ("coh_uv", "incoh_uv"):
+                o[pre + key] = f32(f[key].view(B, Hh, Ww))
+            o[pre + "coh_tke_frac"] = f32(f["coh_tke_frac"])
+        diff = fe["dev"] - ft["dev"]                                             # mean_phys cancels
+        o["phase_mean_rmse"] = f32(torch.sqrt((diff * diff).mean(-1)))
+        ce, ct = fe["coh"][:, :, :2].reshape(B, NB, -1), ft["coh"][:, :, :2].reshape(B, NB, -1)
+        o["coh_corr"] = f32((ce * ct).sum(-1) / torch.sqrt((ce * ce).sum(-1) * (ct * ct).sum(-1)))
+        sl = torch.sqrt(self.lam)                                                # [B, 2]
+        i, j = self.pair
+
+        def speed(coef, s):
+            """coef [.., T, K] fp64 over the timed steps, s [.., 1, 2] -> the mean wrapped increment of the angle."""
+            if coef.shape[-2] < 2:
+                return torch.full(coef.shape[:-2], float("nan"), dtype=torch.float64)
+            th = torch.atan2(coef[..., j] / s[..., 1], coef[..., i] / s[..., 0])
+            dth = th[..., 1:] - th[..., :-1]
+            dth = dth - 2 * math.pi * torch.ceil((dth - math.pi) / (2 * math.pi))
+            return dth.mean(-1)
+
+        o["phase_speed"] = f32(speed(o["coef"][:, :, self._timed].double().cpu(), sl.view(B, 1, 1, 2)))
+        o["target_phase_speed"] = f32(speed(o["target_coef"][:, self._timed].double().cpu(), sl.view(B, 1, 2)))
+        o["phase_edges"] = 2 * math.pi * torch.arange(NB + 1, dtype=torch.float64) / NB   # (a host table)
+        return o
+
+
 STRUCTURE_MAX_LAGS = 16
 STRUCTURE_MAX_LAG = 64
 

@@ -6,6 +6,7 @@ import collections
 import io
 import json
 import math
+import numbers
 import os
 import zipfile
 from types import SimpleNamespace
@@ -628,3 +629,61 @@ def modelPredModes(args, model, testing_loader, log, samples=1, stride=1, tmax=1
     channels = ops.pod_channels(channels, 3)
     acc = _Acc(_modes_factory("modelPredModes", stride, t_start, int(modes), channels), target=True)
     return _ensembleStats("modelPredModes", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
+
+
+def _phase_factory(name, stride, t_start, modes, channels, pair, bins, min_amp):
+    """The make of modelPredPhase's record: the POD basis of the case's target as _modes_factory builds it, the target's all-channel
+    time mean over the same steps in normalised units, a tmg_ops.EnsembleModes and the tmg_ops.EnsemblePhase that drives it."""
+    make_modes = _modes_factory(name, stride, t_start, modes, channels)
+
+    def make(mb, members, steps):
+        import tmg_ops as ops
+        B, C = mb.B, mb.C
+        em = make_modes(mb, members, steps)
+        tk = mb.tgt[:, t_start * stride:(steps - 1) * stride + 1:stride].double()
+        u, sd, mu = mb.u.double(), mb.out_std.double()[:C], mb.out_mu.double()[:C]
+        xn = (tk / u.view(B, 1, C, 1, 1) - mu.view(1, 1, C, 1, 1)) / sd.view(1, 1, C, 1, 1)
+        acc = ops.EnsemblePhase(members, B, C, mb.H, mb.W, steps, mb.dev, mb.out_std, u=mb.u, modes=em, pair=pair, bins=bins,
+                                min_amp=min_amp, mean=xn.mean(1), lam=em.lam[:, list(pair)])
+        acc.mean_phys = tk.mean(1)
+        return acc
+    return make
+
+
+def modelPredPhase(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, modes=8, channels=(0, 1),
+                   pair=(0, 1), bins=8, min_amp=0.25):
+    """modelPredModes plus the phase averages of the members and of the target on the shedding phase, and the triple decomposition
+    u = U + u~ + u' of Reynolds & Hussain (applied to cylinder wakes by Cantwell & Coles), still without forming modelPred's
+    [samples, N, T, C, H, W] tensor (tmg_ops.EnsemblePhase around tmg_ops.EnsembleModes; the projection runs once): at a given phase
+    of the shedding cycle, do the members put the vortices where the reference simulation puts them, and how much of the Reynolds
+    stress that modelPredTurbulence reports is organised motion, how much turbulence?  Same roll-outs as modelPredModes: under the
+    same host RNG state the keys both return are identical.
+
+    The phase of a row (a member or the target at a kept step) is the angle of (coef_i / sqrt(pod_energy_i), coef_j /
+    sqrt(pod_energy_j)), (i, j) = pair, cut into `bins` (4, 8, 16 or 32) equal sectors from the positive first axis; a row whose
+    squared radius is under 2 min_amp^2 (the limit cycle's is 2) is skipped.  Fluctuations are taken about the TARGET's time mean
+    over the kept steps from t_start on, in physical units, for all three channels.  modes >= max(pair) + 1.  Every raw sum is bitwise
+    reproducible and independent of max_rows.
+
+    Returns modelPredModes' dict plus (CPU tensors; NB = bins, n_k the rows of sector k over the kept steps t_start..Tk-1; fields are
+    NaN where a sector is empty and empty sectors are left out of every aggregate):
+      phase_bin [N, S, Tk], target_phase_bin [N, Tk] int32           the sector of every row at every kept step, -1 for a skipped row
+      phase_count [N, NB], member_phase_count [N, S, NB], target_phase_count [N, NB], phase_skipped, target_phase_skipped [N]
+      phase_mean [N, NB, C, H, W], phase_var [N, NB, C, H, W], phase_uv [N, NB, H, W]
+                                      the phase average <u>_k over all members, the incoherent <u'_c u'_c>_k and <u'_0 u'_1>_k
+      coh_var, incoh_var [N, C, H, W], coh_uv, incoh_uv [N, H, W]    sum_k w_k (M_k - M)^2 with w_k = n_k / sum n, M = sum_k w_k M_k, and
+                                      sum_k w_k phase_var_k; their sum is the variance of the labelled rows (law of total variance)
+      coh_tke_frac [N]                the coherent share of the velocity variance summed over the pixels
+      target_phase_mean, .. target_coh_tke_frac                      the same of the target's rows through the same kernels
+      phase_mean_rmse [N, NB, C]      RMS over the pixels of phase_mean - target_phase_mean
+      coh_corr [N, NB]                pattern correlation of the ensemble's and the target's coherent velocity fields of sector k
+      phase_speed [N, S], target_phase_speed [N]                     mean phase increment per kept step in radians, wrapped to
+                                      (-pi, pi]; over 2 pi stride dt it is the shedding frequency
+      phase_edges [NB + 1] float64    the sector angles."""
+    import tmg_ops as ops
+    channels = ops.pod_channels(channels, 3)
+    if isinstance(modes, bool) or not isinstance(modes, numbers.Integral):
+        raise ValueError("modelPredPhase: modes must be an integer, got %r" % (modes,))
+    pair, bins, min_amp = ops.phase_args(pair, bins, min_amp, int(modes))
+    acc = _Acc(_phase_factory("modelPredPhase", stride, t_start, int(modes), channels, pair, bins, min_amp), target=True, meta=("phase_edges",))
+    return _ensembleStats("modelPredPhase", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])

@@ -507,6 +507,7 @@ int tmg_spec_finalize(const void* tmean, void* tm_mean, void* tm_std, const int6
 #include "tmglow_hip_event.h"
 #include "tmglow_hip_pdf.h"
 #include "tmglow_hip_pod.h"
+#include "tmglow_hip_phase.h"
 
 /* The benchmark loss of SURVEY 8-D, generative direction: *loss += fl[0] sum(y^2) + fl[1] sum(logdet) (the caller zeroes *loss;
  * fl = {1 / numel(y), 1 / (B noc H W)}), and its gradient dy = 2 fl[0] *g y, dld[b] = fl[1] *g with the upstream gradient read from
