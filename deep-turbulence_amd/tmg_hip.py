@@ -20,7 +20,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmglow_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip", "tmg_phase.hip"]
+SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip", "tmg_phase.hip", "tmg_spod.hip"]
 # Sources compiled WITHOUT the packed-fp32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32): beside MFMAs a packed
 # f32 instruction costs ~13 cycles more than the two scalar ones it replaces (MI355X_MICROARCH.md, cycle constants, 'price of one
 # filler beside MFMAs'), and the compiler SLP-packs adjacent scalar adds / multiplies by itself under -O3.  The matrix-core kernels'
@@ -29,9 +29,10 @@ SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hi
 # everywhere 43.62 / 43.98 / 43.76 ms per step, this list 43.51 / 43.60 / 43.37 (wino + conv + coupling alone 43.64 / 43.52 / 43.58).
 # tmg_pod.hip is listed: its vector work (the fluctuation's subtraction and product, the energy's fmaf chain) is issued between the
 # MFMAs of the projection, exactly the filler position the list is about; its results do not depend on the choice (a packed
-# instruction rounds each half as the scalar one does).
+# instruction rounds each half as the scalar one does).  tmg_spod.hip is listed for the same reason: the correction
+# x - xbar G of every fragment element is vector work between the MFMAs of the Gram product and of the synthesis.
 NO_PACKED_F32 = ["tmg_wino.hip", "tmg_conv.hip", "tmg_coupling.hip", "tmg_thin.hip", "tmg_mix16.hip", "tmg_spectrum.hip", "tmg_tspec.hip",
-                 "tmg_pod.hip"]
+                 "tmg_pod.hip", "tmg_spod.hip"]
 _lib = None
 
 c_i64 = ctypes.c_int64
@@ -76,6 +77,9 @@ POD_EXPORTS = ["tmg_ens_pod_plan", "tmg_ens_pod_project"]
 # The phase averages on the shedding phase (csrc/tmg_phase.hip), declared in include/tmglow_hip_phase.h: ens_phase_plan /
 # ens_phase_label / ens_phase_accum below.
 PHASE_EXPORTS = ["tmg_ens_phase_plan", "tmg_ens_phase_label", "tmg_ens_phase_accum"]
+# The spectral POD: the members' cross-spectral density matrices and the synthesis of the modes (csrc/tmg_spod.hip), declared in
+# include/tmglow_hip_spod.h, a header of its own: ens_spod_plan / ens_spod_csd / ens_spod_modes below.
+SPOD_EXPORTS = ["tmg_ens_spod_plan", "tmg_ens_spod_csd", "tmg_ens_spod_modes"]
 # Every export returns int except the workspace sizes, which the header declares int64_t (read through a 32-bit return a request of
 # 2^31 floats or more would be truncated and the kernel handed a buffer smaller than it planned for).
 RET_I64 = ("tmg_conv_wgrad_ws_floats", "tmg_conv_wgrad_grouped_ws_floats", "tmg_conv_wino_wgrad_ws_floats",
@@ -91,7 +95,7 @@ def build(force=False, verbose=False):
                os.path.join(inc, "tmglow_hip_tspec.h"), os.path.join(inc, "tmglow_hip_quant.h"),
                os.path.join(inc, "tmglow_hip_gram.h"), os.path.join(inc, "tmglow_hip_sfun.h"),
                os.path.join(inc, "tmglow_hip_event.h"), os.path.join(inc, "tmglow_hip_pdf.h"), os.path.join(inc, "tmglow_hip_pod.h"),
-               os.path.join(inc, "tmglow_hip_phase.h")]
+               os.path.join(inc, "tmglow_hip_phase.h"), os.path.join(inc, "tmglow_hip_spod.h")]
     hmt = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -145,7 +149,7 @@ def lib():
         for name in PLAN_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
             getattr(_lib, name).argtypes = PLAN_ARGTYPES[name]
-        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS + SFUN_EXPORTS + EVENT_EXPORTS + PDF_EXPORTS + POD_EXPORTS + PHASE_EXPORTS:
+        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS + SFUN_EXPORTS + EVENT_EXPORTS + PDF_EXPORTS + POD_EXPORTS + PHASE_EXPORTS + SPOD_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
     return _lib
 
@@ -1421,6 +1425,59 @@ def ens_phase_accum(y, lab, lstrides, a, m, acc, k):
     _phase_span(lab, lstrides, k, B, 0, "ens_phase_accum: lab")
     _chk(lib().tmg_ens_phase_accum(c_vp(ptr), _i64(ps, co), _ptr(lab), _i64(*lstrides), _ptr(a), _ptr(m), _ptr(acc),
                                    _i64(k, B, HW, Cc, NB), _stream()), "tmg_ens_phase_accum")
+
+
+def ens_spod_plan(S, B, Cg, HW, NB, acc=None):
+    """The launch plan of ens_spod_csd / ens_spod_modes for S members (R = S + 1 rows with the target) of B cases, Cg selected channels
+    of HW pixels and NB bins (tmg_ens_spod_plan; nothing is launched) -> dict: P pixel slices of SL pixels, L the fmaf terms of one
+    partial (L P >= Cg HW), NT row macro-tiles of 64 rows over the 2 R rows of Z, pairs = the NT (NT + 1) / 2 macro-tile pairs (I, J),
+    I <= J, in workspace order, part the floats of one partial, ws the workspace floats, vec whether the rows are read with 16-byte
+    loads (HW a multiple of 4 and, when the accumulator acc or its address is given, a 16-byte aligned base), MB the pixel blocks of the
+    modes kernel."""
+    addr = 0 if acc is None else (int(acc) if isinstance(acc, int) else acc.data_ptr())
+    plan = (c_i64 * 9)()
+    _chk(lib().tmg_ens_spod_plan(_i64(S, B, Cg, HW, NB, addr & 15), plan), "tmg_ens_spod_plan")
+    P, L, NP, ws, SL, NT, part, vec, MB = [int(v) for v in plan]
+    pairs = [(i, j) for i in range(NT) for j in range(i, NT)]
+    assert len(pairs) == NP
+    return {"P": P, "L": L, "pairs": pairs, "ws": ws, "SL": SL, "NT": NT, "part": part, "vec": bool(vec), "MB": MB}
+
+
+def ens_spod_csd(acc, cst, bins, channels, ws, csd_raw, Tn):
+    """The cross-spectral density sums of the R rows of the temporal-spectrum accumulator acc [2 NF + 1, R, B, C, HW] (cst [3, NF]: its
+    constants; Tn its window) at the selected bins and over the selected channels into csd_raw [B, NB, 2, R, R]:
+    raw0 + i raw1 = sum conj(X_m) X_n; ws: the workspace (>= ens_spod_plan's floats) (tmg_ens_spod_csd)."""
+    check_act(acc)
+    check_device(acc)
+    _, R, B, Cc, HW = acc.shape
+    NF = cst.shape[1]
+    if acc.shape[0] != 2 * NF + 1 or tuple(cst.shape) != (3, NF) or not acc.is_contiguous() or not cst.is_contiguous() or \
+            tuple(csd_raw.shape) != (B, len(bins), 2, R, R) or not csd_raw.is_contiguous() or csd_raw.dtype != torch.float32:
+        raise ValueError("ens_spod_csd: acc is [2 NF + 1, R, B, C, HW], cst [3, NF] and csd_raw [B, NB, 2, R, R] float32, got %s, %s and %s"
+                         % (tuple(acc.shape), tuple(cst.shape), tuple(csd_raw.shape)))
+    _chk(lib().tmg_ens_spod_csd(_ptr(acc), _ptr(cst), _i64(*bins), _i64(*channels), _ptr(ws), _ptr(csd_raw),
+                                _i64(R - 1, B, Cc, HW, NF, Tn, len(bins), len(channels), ws.numel()), _stream()), "tmg_ens_spod_csd")
+
+
+def ens_spod_modes(acc, cst, bins, channels, w, modes, Tn):
+    """modes [B, NB, 2 J, Cg, HW] = w [B, NB, 16, 2 SP] (SP = S rounded up to 4) times the rows [Re X_0 .. Re X_{S-1}, 0 ..; Im X_0 ..
+    Im X_{S-1}, 0 ..] of the accumulator acc [2 NF + 1, S + 1, B, C, HW] at the selected bins and channels (tmg_ens_spod_modes)."""
+    check_act(acc)
+    check_device(acc)
+    _, R, B, Cc, HW = acc.shape
+    NF = cst.shape[1]
+    SP = (R - 1 + 3) // 4 * 4
+    if acc.shape[0] != 2 * NF + 1 or tuple(cst.shape) != (3, NF) or not acc.is_contiguous() or not cst.is_contiguous():
+        raise ValueError("ens_spod_modes: acc is [2 NF + 1, R, B, C, HW] and cst [3, NF], got %s and %s" % (tuple(acc.shape), tuple(cst.shape)))
+    if w.dtype != torch.float32 or modes.dtype != torch.float32:
+        raise ValueError("ens_spod_modes: w and modes are float32")
+    if tuple(w.shape) != (B, len(bins), 16, 2 * SP) or not w.is_contiguous() or tuple(modes.shape[:2]) != (B, len(bins)) or \
+            tuple(modes.shape[3:]) != (len(channels), HW) or modes.shape[2] % 2 or not modes.is_contiguous():
+        raise ValueError("ens_spod_modes: w is [B, NB, 16, %d] and modes [B, NB, 2 J, Cg, HW], got %s and %s"
+                         % (2 * SP, tuple(w.shape), tuple(modes.shape)))
+    _chk(lib().tmg_ens_spod_modes(_ptr(acc), _ptr(cst), _i64(*bins), _i64(*channels), _ptr(w), _ptr(modes),
+                                  _i64(R - 1, B, Cc, HW, NF, Tn, len(bins), len(channels), modes.shape[2] // 2), _stream()),
+         "tmg_ens_spod_modes")
 
 
 def spec_rows(y, u, out_mu, out_std, ft_w, yw, k):

@@ -3332,3 +3332,258 @@ class EnsembleTimeSpectrum(EnsembleFeed):
             H.tspec_finalize(self.acc, self.cst, self.out["psd_mean"], self.out["psd_std"], self.S, self.B, self.C, self.H * self.W,
                              self.NF, self.Tn)
         return self.out
+
+
+SPOD_MAX_MEMBERS = 255
+SPOD_MAX_BINS = 16
+SPOD_MAX_MODES = 8
+# Roundings of one csd_raw entry beside the plan's L + P (csrc/tmg_spod.hip): 3 per operand for the correction (xbar, xbar G, the
+# subtraction), 1 for the final combine, 1 for the second-order terms.
+SPOD_ROUNDINGS = 8
+
+
+def spod_args(bins, modes, channels, Tn, C):
+    """The checks of the SPOD arguments for a window of Tn steps and C channels, in this order: Tn >= 2; bins None (the bins
+    1..min(16, Tn // 2)) or 1 to 16 strictly increasing integers in 1..Tn // 2; modes an integer in 1..8; channels 1 to C distinct
+    channels in 0..C-1 in any order (pod_channels' rules) -> (bins, modes, channels) as tuples of ints and an int."""
+    if isinstance(Tn, bool) or not isinstance(Tn, numbers.Integral) or Tn < 2:
+        raise ValueError("the SPOD needs a window of Tn >= 2 steps, got %r" % (Tn,))
+    Tn = int(Tn)
+    if bins is None:
+        bins = tuple(range(1, min(SPOD_MAX_BINS, Tn // 2) + 1))
+    else:
+        try:
+            bins = tuple(bins)
+        except TypeError:
+            raise ValueError("bins must be None or a tuple of frequency bins, got %r" % (bins,)) from None
+        if not 1 <= len(bins) <= SPOD_MAX_BINS:
+            raise ValueError("bins must hold 1 to %d bins, got %d" % (SPOD_MAX_BINS, len(bins)))
+        for k in bins:
+            if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 1 <= k <= Tn // 2:
+                raise ValueError("bins hold integers in 1..%d (k = 0 is not offered), got %r" % (Tn // 2, bins))
+        if any(b <= a for a, b in zip(bins, bins[1:])):
+            raise ValueError("bins must be strictly increasing, got %r" % (bins,))
+        bins = tuple(int(k) for k in bins)
+    if isinstance(modes, bool) or not isinstance(modes, numbers.Integral) or not 1 <= modes <= SPOD_MAX_MODES:
+        raise ValueError("the SPOD keeps 1 <= modes <= %d, got %r" % (SPOD_MAX_MODES, modes))
+    return bins, int(modes), pod_channels(channels, C)
+
+
+def _spod_phase(theta):
+    """Every eigenvector (the columns of theta [.., S, J], complex) rotated so that its entry of largest modulus (ties: the lowest
+    member) is real and positive."""
+    top = theta.abs().argmax(-2, keepdim=True)
+    v = torch.gather(theta, -2, top)
+    mod = v.abs()
+    rot = torch.where(mod > 0, v.conj() / torch.where(mod > 0, mod, torch.ones_like(mod)), torch.ones_like(v))
+    out = theta * rot
+    # the rotated entry is real by construction: drop the rounding residue of its imaginary part
+    fix = torch.gather(out, -2, top)
+    return out.scatter(-2, top, torch.complex(fix.real, torch.zeros_like(fix.real)))
+
+
+def _spod_eig(A, J):
+    """Hermitian A [.., n, n] complex128 -> (lam [.., min(J, n)] descending, theta [.., n, min(J, n)] with _spod_phase's convention)."""
+    w, v = torch.linalg.eigh(A)
+    j = min(J, A.shape[-1])
+    return w.flip(-1)[..., :j], _spod_phase(v.flip(-1)[..., :j])
+
+
+def spod_decompose(csd_raw, S, HW, kappa, J, cnt, loo=True):
+    """The host step of the spectral POD, plain torch fp64 on the CPU (once per mini-batch: not the hot path).  csd_raw
+    [B, NB, 2, R, R], R = S + 1 (the members, then the target): raw0 + i raw1 = M[m, n] = sum conj(X_m) X_n over the Cg HW elements;
+    HW: the pixels of the inner product <f, g> = (1 / HW) sum conj(f) g; kappa [NB] (or a number): c_k / Tn^2; J: the modes kept;
+    cnt: the counted roundings of one csd_raw entry.  Per case and bin:
+      A = kappa M[:S, :S] / (S HW) = Theta Lambda Theta^H (torch.linalg.eigh, eigenvalues descending; every eigenvector rotated so that
+      its entry of largest modulus, the lowest member on a tie, is real and positive)
+      spod_energy [B, NB, J] = lambda_j (0 for j >= S), spod_total [B, NB] = trace A, spod_energy_frac = spod_energy / spod_total,
+      captured = sum_j spod_energy_frac, member_mode_energy [B, NB, S, J] = S lambda_j |Theta_mj|^2
+      spod_noise_floor [B, NB] = cnt 2^-24 spod_total: bounds ||dA||_F, so eigenvalues below it cannot be told from rounding (Weyl)
+      weights w_mj = Theta_mj sqrt(kappa / (S lambda_j)): Phi_j = sum_m X_m w_mj has <Phi_i, Phi_j> = delta_ij
+      target_coef [B, NB, J] complex128 = b_j = <Phi_j, X_S> = sqrt(kappa / (S lambda_j)) sum_n conj(Theta_nj) M[n, S] / HW
+      target_mode_energy = kappa |b_j|^2, target_energy [B, NB] = kappa M[S, S] / HW, target_captured = sum_j target_mode_energy /
+      target_energy
+      csd [B, NB, R, R] complex128 = M / HW
+    A mode with lambda_j <= spod_noise_floor, or j >= S, has NaN weights, target_coef and target_mode_energy and is left out of
+    target_captured.  loo: loo_captured [B, NB, S], the share of member m's energy kappa M[m, m] / HW in the leading J modes (above
+    their own floor) of the other S - 1 members, which costs S eigendecompositions per case and bin, and target_captured_rank
+    [B, NB], the number of members whose loo_captured is strictly under target_captured; both NaN for S = 1, absent for loo=False.
+    -> dict of CPU tensors (float64 / complex128) with the keys above and `weights` [B, NB, S, J] complex128, `valid` [B, NB, J] bool."""
+    raw = torch.as_tensor(csd_raw).detach().to("cpu", torch.float64)
+    S, HW, J = int(S), int(HW), int(J)
+    if raw.dim() != 5 or raw.shape[2] != 2 or tuple(raw.shape[3:]) != (S + 1, S + 1):
+        raise ValueError("csd_raw is [B, NB, 2, %d, %d], got shape %s" % (S + 1, S + 1, tuple(raw.shape)))
+    B, NB = raw.shape[:2]
+    kap = torch.as_tensor(kappa, dtype=torch.float64).reshape(-1)
+    if kap.numel() not in (1, NB):
+        raise ValueError("kappa holds one value per bin (%d), got %d" % (NB, kap.numel()))
+    kap = kap.expand(NB).reshape(1, NB)
+    M = torch.complex(raw[:, :, 0], raw[:, :, 1])
+    nan = float("nan")
+    A = kap.view(1, NB, 1, 1) * M[:, :, :S, :S] / (S * HW)
+    lam_s, theta_s = _spod_eig(A, J)                                         # [B, NB, Js], [B, NB, S, Js]
+    Js = lam_s.shape[-1]
+    total = torch.diagonal(A, dim1=-2, dim2=-1).real.sum(-1)
+    floor = float(cnt) * 2.0 ** -24 * total
+    lam = torch.zeros((B, NB, J), dtype=torch.float64)
+    lam[..., :Js] = lam_s
+    valid = torch.zeros((B, NB, J), dtype=torch.bool)
+    valid[..., :Js] = lam_s > floor.unsqueeze(-1)
+    theta = torch.zeros((B, NB, S, J), dtype=torch.complex128)
+    theta[..., :Js] = theta_s
+    safe = torch.where(valid, lam, torch.ones_like(lam))
+    scale = torch.sqrt(kap.view(1, NB, 1) / (S * safe))                      # [B, NB, J]
+    cnan = torch.complex(torch.full_like(lam, nan), torch.full_like(lam, nan))
+    w = torch.where(valid.unsqueeze(2), theta * scale.unsqueeze(2), cnan.unsqueeze(2).expand(B, NB, S, J))
+    col = M[:, :, :S, S]                                                     # [B, NB, S]
+    bj = scale * (theta.conj() * col.unsqueeze(-1)).sum(2) / HW
+    tme = torch.where(valid, kap.view(1, NB, 1) * bj.abs() ** 2, torch.full_like(lam, nan))
+    ten = kap * M[:, :, S, S].real / HW
+    frac = lam / total.unsqueeze(-1)
+    o = {"spod_energy": lam, "spod_total": total, "spod_energy_frac": frac, "captured": frac.sum(-1),
+         "member_mode_energy": S * lam.unsqueeze(2) * theta.abs() ** 2, "spod_noise_floor": floor,
+         "target_coef": torch.where(valid, bj, cnan), "target_mode_energy": tme, "target_energy": ten,
+         "target_captured": torch.where(valid, tme, torch.zeros_like(tme)).sum(-1) / ten, "csd": M / HW, "weights": w, "valid": valid}
+    if loo:
+        if S == 1:
+            o["loo_captured"] = torch.full((B, NB, 1), nan, dtype=torch.float64)
+            o["target_captured_rank"] = torch.full((B, NB), nan, dtype=torch.float64)
+        else:
+            cap = torch.empty((B, NB, S), dtype=torch.float64)
+            for m in range(S):
+                rest = [n for n in range(S) if n != m]
+                Ao = kap.view(1, NB, 1, 1) * M[:, :, rest][:, :, :, rest] / ((S - 1) * HW)
+                lo, to = _spod_eig(Ao, J)
+                fo = float(cnt) * 2.0 ** -24 * torch.diagonal(Ao, dim1=-2, dim2=-1).real.sum(-1)
+                ok = lo > fo.unsqueeze(-1)
+                so = torch.sqrt(kap.view(1, NB, 1) / ((S - 1) * torch.where(ok, lo, torch.ones_like(lo))))
+                bo = so * (to.conj() * M[:, :, rest, m].unsqueeze(-1)).sum(2) / HW
+                en = torch.where(ok, kap.view(1, NB, 1) * bo.abs() ** 2, torch.zeros_like(lo)).sum(-1)
+                cap[:, :, m] = en / (kap * M[:, :, m, m].real / HW)
+            o["loo_captured"] = cap
+            o["target_captured_rank"] = (cap < o["target_captured"].unsqueeze(-1)).sum(-1).to(torch.float64)
+    return o
+
+
+class EnsembleSpod(EnsembleFeed):
+    """On-device spectral POD (SPOD; Towne, Schmidt & Colonius 2018) of sampled roll-outs of B cases, the members standing where
+    Welch's blocks stand: per frequency bin the modes that are coherent in space and time among the members, their energies, and whether
+    the target's Fourier coefficient at that bin lies in the same subspace with the same energy (tmg_tspec_store / tmg_tspec_block,
+    unchanged, then tmg_ens_spod_csd / tmg_ens_spod_modes).  The rows are the S members and, as row S, the target at the same steps.
+    X_m(c, p) at bin k is EnsembleTimeSpectrum's coefficient of row m (un-normalised to physical units, mean removed, periodic Hann over
+    its RMS or no window), <f, g> = (1 / HW) sum_{c in channels} sum_p conj(f) g and kappa_k = c_k / Tn^2.  The device forms
+      csd_raw [B, NB, 2, R, R]: raw0 + i raw1 = M[m, n] = sum conj(X_m) X_n            (fp32 on the matrix pipe, R = S + 1)
+    spod_decompose turns it into the energies and weights on the host in fp64, and the device synthesises
+      spod_modes [B, NB, J, 2, Cg, H, W]: the real and imaginary parts of Phi_j = sum_m X_m w_mj, <Phi_i, Phi_j> = delta_ij
+    from the members' rows alone.  A mode at or below spod_noise_floor, or with j >= S, is NaN.
+
+    bins: None for 1..min(16, Tn // 2), else 1 to 16 strictly increasing bins in 1..Tn // 2 (k = 0 is not offered); modes: J in 1..8;
+    channels: 1 to C distinct channels in any order; 1 <= members <= 255; 2 <= C <= 4; any H, W >= 1.  `steps` is Tn: only the steps
+    of the time window are fed.  The state is EnsembleTimeSpectrum's, (2 NF + 1 + 16) * 4 bytes per element of [R, B, C, H W] with
+    NF = max(bins) + 1: all C channels are kept although only those of `channels` are used.  loo=True adds loo_captured and
+    target_captured_rank, host fp64 from M alone at the cost of S eigendecompositions per case and bin.
+
+    Feeding protocol of EnsembleFeed: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
+    chunks before the next step's; every chunk comes with the step's target, and the last chunk's is the one that is stored.
+    finalize() returns csd_raw and spod_modes (device, float32) and, on the host in float64 / complex128, spod_decompose's keys
+    (spod_energy, spod_total, spod_energy_frac, captured, member_mode_energy, spod_noise_floor, target_coef, target_mode_energy,
+    target_energy, target_captured, csd, and with loo loo_captured, target_captured_rank), spod_bins [NB] int64 and spod_freq [NB]
+    = k / (Tn dt).  The attribute `cnt` is the counted roundings of one csd_raw entry, plan L + P + 8.
+
+    Argument errors are ValueError in this order: C, steps, bins, modes, channels, window, dt, members (and B, H, W), the entries of
+    out_mu / out_std, the shape of u; a device that is not a GPU comes last (RuntimeError)."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, bins=None, modes=4, channels=(0, 1), window="hann",
+                 dt=1.0, loo=True):
+        noun = "the SPOD"
+        _ens_channels(noun, C)
+        if isinstance(steps, bool) or not isinstance(steps, numbers.Integral) or int(steps) < 2:
+            raise ValueError("%s needs steps >= 2 (the window of the transform), got %r" % (noun, steps))
+        self.bins, self.J, self.channels = spod_args(bins, modes, channels, int(steps), int(C))
+        if window not in ("hann", None):
+            raise ValueError("window must be 'hann' or None, got %r" % (window,))
+        try:
+            dt = float(dt)
+        except (TypeError, ValueError):
+            raise ValueError("dt needs a positive finite time between two fed steps, got %r" % (dt,)) from None
+        if not (math.isfinite(dt) and dt > 0):
+            raise ValueError("dt needs a positive finite time between two fed steps, got %r" % (dt,))
+        if not 1 <= int(members) <= SPOD_MAX_MEMBERS or int(B) < 1 or int(Hh) < 1 or int(Ww) < 1:
+            raise ValueError("%s needs 1 <= members <= %d and B, H, W >= 1, got %d, %d, %d x %d"
+                             % (noun, SPOD_MAX_MEMBERS, int(members), int(B), int(Hh), int(Ww)))
+        mu = torch.as_tensor(out_mu, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
+        sd = torch.as_tensor(out_std, dtype=torch.float32).detach().reshape(-1)[:C].cpu()
+        if mu.numel() != C or sd.numel() != C:
+            raise ValueError("out_mu / out_std need %d entries, got %d / %d" % (C, mu.numel(), sd.numel()))
+        if u is not None:
+            u = torch.as_tensor(u, dtype=torch.float32).detach()
+            if u.numel() != int(B) * C:
+                raise ValueError("u needs %d x %d entries, got %d" % (int(B), C, u.numel()))
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, C, Hh, Ww, steps)
+        self.Tn = self.Tk
+        self.R = self.S + 1
+        self.NF = max(self.bins) + 1
+        self.window, self.dt, self.loo = window, dt, bool(loo)
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.mu, self.sd = mu.to(dev).contiguous(), sd.to(dev).contiguous()
+        self.u = None if u is None else u.to(dev).reshape(self.B, C).contiguous()
+        tm, cst = _tspec_operand(self.Tn, self.NF, window)
+        self.tm, self.cst = tm.to(dev), cst.to(dev)
+        ck = torch.full((len(self.bins),), 2.0, dtype=torch.float64)
+        if self.Tn % 2 == 0:
+            ck[torch.tensor(self.bins) == self.Tn // 2] = 1.0
+        self.kappa = ck / float(self.Tn) ** 2
+        HW = self.H * self.W
+        self.ring = torch.empty((TSPEC_BLOCK, self.R, self.B, C, HW), **f32)
+        self.acc = torch.empty((2 * self.NF + 1, self.R, self.B, C, HW), **f32)
+        self.plan = H.ens_spod_plan(self.S, self.B, len(self.channels), HW, len(self.bins), self.acc)
+        self.cnt = self.plan["L"] + self.plan["P"] + SPOD_ROUNDINGS
+        self.ws = torch.empty((self.plan["ws"],), **f32)
+        self.freq = torch.tensor(self.bins, dtype=torch.float64) / (self.Tn * dt)
+        self.out = None
+
+    def _fold(self, n0, nb):
+        H.tspec_block(self.tm, self.ring, self.acc, self.Tn, self.NF, n0, nb, n0 == 0)
+
+    def add(self, y, m0, target):
+        """Store the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
+        channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride rule.  The step's
+        last chunk stores the target as row S; the last chunk of every 16th step folds the ring into the accumulator."""
+        yn, tn, k, _, last = self.open_chunk(y, m0, None, target, required=True)
+        _on_device(yn, tn)
+        slot = self._step % TSPEC_BLOCK
+        H.tspec_store(yn, self.u, self.mu, self.sd, self.ring, k, m0, slot)
+        if last:
+            H.tspec_store(tn, self.u, self.mu, self.sd, self.ring, 1, self.S, slot)
+        self.close_chunk(m0, k, None, last)
+        if last and self._step % TSPEC_BLOCK == 0:
+            self._fold(self._step - TSPEC_BLOCK, TSPEC_BLOCK)
+
+    def finalize(self):
+        """-> dict of the outputs: csd_raw and spod_modes on the device, the derived ones on the host."""
+        self.finalize_guard(timed=False)
+        if self.out is None:
+            nb = self.Tn % TSPEC_BLOCK
+            if nb:
+                self._fold(self.Tn - nb, nb)
+            dev = self.acc.device
+            B, NB, J, S, Cg, HW = self.B, len(self.bins), self.J, self.S, len(self.channels), self.H * self.W
+            raw = empty((B, NB, 2, self.R, self.R), dev)
+            H.ens_spod_csd(self.acc, self.cst, self.bins, self.channels, self.ws, raw, self.Tn)
+            o = spod_decompose(raw, S, HW, self.kappa, J, self.cnt, self.loo)
+            w, valid = o.pop("weights"), o.pop("valid")
+            # the operand of the synthesis, fp64 rounded once: row 2 j = [Re w_j | -Im w_j], row 2 j + 1 = [Im w_j | Re w_j]; a mode under
+            # the floor gets zero weights and its NaN afterwards, not through the pipe
+            w = torch.where(valid.unsqueeze(2), w, torch.zeros_like(w)).transpose(2, 3)   # [B, NB, J, S]
+            SP = (S + 3) // 4 * 4
+            wr = torch.zeros((B, NB, 16, 2 * SP), dtype=torch.float64)
+            wr[:, :, 0:2 * J:2, :S], wr[:, :, 0:2 * J:2, SP:SP + S] = w.real, -w.imag
+            wr[:, :, 1:2 * J:2, :S], wr[:, :, 1:2 * J:2, SP:SP + S] = w.imag, w.real
+            modes = empty((B, NB, 2 * J, Cg, HW), dev)
+            H.ens_spod_modes(self.acc, self.cst, self.bins, self.channels, wr.to(torch.float32).to(dev).contiguous(), modes, self.Tn)
+            modes = modes.view(B, NB, J, 2, Cg, self.H, self.W)
+            modes[(~valid).to(dev)] = float("nan")
+            o.update({"csd_raw": raw, "spod_modes": modes, "spod_bins": torch.tensor(self.bins, dtype=torch.int64), "spod_freq": self.freq})
+            self.out = o
+        return self.out

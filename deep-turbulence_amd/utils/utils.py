@@ -127,7 +127,8 @@ def _pdf_target_fields(tp, kinds, grid):
 #       out_mu, out_std, u [B, C], grid (the statistics': None without turbulence), and for the PDFs' ranges and centre tgt (the
 #       physical target series on the device) and case0 (the cases before this mini-batch)
 #   target: add() takes the step's normalised target
-#   window: fed only the kept steps from t_start on, by add(y, m0) without time= (the temporal spectrum); finalized last
+#   window: fed only the kept steps from t_start on, by add(y, m0) without time= (the temporal spectrum), or by add(y, m0, target) when
+#       the record also has target (the SPOD); finalized last
 #   meta:   result keys that are returned once, not concatenated over the mini-batches
 #   extra:  fixed results
 #   tail:   (result key, source key) pairs read from a one-member accumulator of the same make that is fed the target series
@@ -239,7 +240,10 @@ def _ensembleStats(name, args, model, testing_loader, log, samples, stride, tmax
                         for a, acc in live:
                             if a.window:
                                 if timed:
-                                    acc.add(y0, m0)
+                                    if a.target:
+                                        acc.add(y0, m0, tj)
+                                    else:
+                                        acc.add(y0, m0)
                             elif a.target:
                                 acc.add(y0, m0, tj, time=timed)
                             else:
@@ -687,3 +691,52 @@ def modelPredPhase(args, model, testing_loader, log, samples=1, stride=1, tmax=1
     pair, bins, min_amp = ops.phase_args(pair, bins, min_amp, int(modes))
     acc = _Acc(_phase_factory("modelPredPhase", stride, t_start, int(modes), channels, pair, bins, min_amp), target=True, meta=("phase_edges",))
     return _ensembleStats("modelPredPhase", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
+
+
+def modelPredSpod(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, bins=None, modes=4, channels=(0, 1),
+                  window="hann", loo=True, dt=None):
+    """modelPredStats plus the spectral POD (SPOD; Towne, Schmidt & Colonius 2018) of the members over the kept steps t_start..Tk-1
+    (Tn = Tk - t_start >= 2 of them), still without forming modelPred's [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleSpod): per
+    frequency bin the structures that are coherent in space AND time among the members, how much of the fluctuation energy at that
+    frequency the leading ones hold, and whether the target's Fourier coefficient at that bin lies in the same subspace with the same
+    energy.  A POD mode (modelPredModes) mixes every frequency that shares a spatial pattern and modelPredPhase conditions on one
+    frequency; the cylinder array sheds at several, and the step's shear layer flaps and rolls up at different ones.  SPOD needs many
+    independent realisations of one stationary process: the members stand where Welch's blocks stand.  The target of kept step j is
+    series step j * stride; a series that is too short raises.  Channel scales (u0, u0, u0^2).  Same roll-outs as modelPredStats: under
+    the same host RNG state the keys both return are identical; no option draws from the host RNG, and the loader is iterated once.
+
+    X_m(c, p) at bin k is modelPredTimeSpectra's Fourier coefficient of member m (row S: the target), <f, g> = (1 / HW) sum_{c in
+    channels} sum_p conj(f) g, kappa_k = c_k / Tn^2.  bins: None for 1..min(16, Tn // 2), else 1 to 16 strictly increasing bins in
+    1..Tn // 2; modes: J in 1..8; channels: distinct channels of one unit, default the velocity; samples <= 255; loo: the leave-one-out
+    yardstick, S eigendecompositions per case and bin on the host.
+
+    Returns modelPredStats' dict plus (CPU tensors; NB bins, J modes, Cg channels, S = samples, R = S + 1):
+      csd_raw [N, NB, 2, R, R]              the device's sums: raw0 + i raw1 = M[m, n] = sum conj(X_m) X_n, the target last
+      csd [N, NB, R, R] complex128          M / HW: form coherences or other estimators from it
+      spod_energy [N, NB, J], spod_total [N, NB], spod_energy_frac [N, NB, J], captured [N, NB]
+                                            the eigenvalues lambda_j of A = kappa M[:S, :S] / (S HW), descending; trace A, which is the
+                                            field mean over `channels` of psd_mean at the bin; their ratio and its sum over the J modes
+      member_mode_energy [N, NB, S, J]      S lambda_j |Theta_mj|^2: each member's share of mode j
+      spod_modes [N, NB, J, 2, Cg, H, W]    real and imaginary part of Phi_j, <Phi_i, Phi_j> = delta_ij, from the members alone
+      target_coef [N, NB, J] complex128, target_mode_energy [N, NB, J], target_energy, target_captured [N, NB]
+                                            b_j = <Phi_j, X_S>, kappa |b_j|^2 (for a realisation of the members' own process its
+                                            expectation is lambda_j), kappa <X_S, X_S> and the share of it in the J modes
+      loo_captured [N, NB, S], target_captured_rank [N, NB]   (loo) the share of member m's energy in the leading modes of the OTHER
+                                            members - the fair yardstick for target_captured, captured being in-sample and
+                                            optimistic - and the number of members strictly under the target; NaN for samples = 1
+      spod_noise_floor [N, NB]              eigenvalues at or below it cannot be told from fp32 rounding: their modes, target_coef
+                                            and target_mode_energy are NaN and they are left out of target_captured
+      spod_bins [NB] int64, spod_freq [NB] float64   the bins and k / Tn, cycles per kept step, when dt is None; else k / (Tn stride dt)."""
+    if window not in ("hann", None):
+        raise ValueError("window must be 'hann' or None, got %r" % (window,))
+    step_dt = 1.0 if dt is None else float(stride) * float(dt)
+    if not (math.isfinite(step_dt) and step_dt > 0):
+        raise ValueError("dt must be a positive finite time between two model steps, got %r" % (dt,))
+    import tmg_ops as ops
+    nkeep = tmax // stride
+    if nkeep - t_start >= 2:                                                  # (else _ensembleStats words the error)
+        bins, modes, channels = ops.spod_args(bins, modes, channels, nkeep - t_start, 3)
+    acc = _Acc(lambda mb, S, T: ops.EnsembleSpod(S, mb.B, mb.C, mb.H, mb.W, T, mb.dev, mb.out_mu, mb.out_std, u=mb.u, bins=bins, modes=modes,
+                                                 channels=channels, window=window, dt=step_dt, loo=loo),
+               target=True, window=True, meta=("spod_bins", "spod_freq"))
+    return _ensembleStats("modelPredSpod", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
