@@ -401,8 +401,9 @@ struct CplBP {
     float* DH; int dhs;              // [npix] x C slice: e^kappa * dhh
     float* dtin; int dts;            // gradient w.r.t. the layer input, half 1 = dto1 (pass-through gradient, completed by dense2_bwd)
     float* dtin2; int dt2s;          //                                  half 2 = dtin2
-    float* G0;                       // [npix][ch]
+    float* G0;                       // [npix][ch]; null selects the SUMMED form (see cpl_bwd_kernel's SUM)
     float* GD;                       // [npix][4]
+    const float* x1; int x1s;        // summed form only: the FIRST half of the layer input (the coupling network's input, for its ReLU mask)
     int B, H, W, C;
     int tiles_x, tiles_y, ntiles;
     // fwd = 1: the DENSITY direction's layer (mix -> coupling, flowAffine.py:76-83): no mix in front of the coupling's backward (dout
@@ -417,13 +418,22 @@ struct CplBP {
 // hold only pass-through channels and the lanes q >= 2 only coupling channels, so the wave executed BOTH epilogues under masks - the
 // coupling arithmetic of four elements per lane for half of the lanes; dealt out, every lane does two elements and the wave issues half
 // of those instructions (the kernel is bound by vector-instruction issue: ablation table in DESIGN.md).
-template <int CT, int MT, int KS, bool PERM = false>
+// SUM (G0 == null): the two ch-wide tensors this kernel hands to tmg_dense2_bwd - dto1 (phase A, dtin half 1) and G0 (phase B) -
+// leave as ONE: dtin half 1 = dto1 + [x1 > 0] G0.  The next launch computes dt1 = dto1 + [x1 > 0] (G0 + growth share); the ReLU of the
+// coupling network's input masks G0 but not the pass-through gradient, so the sum can only be formed with the mask applied here.
+// Phase A parks dto1 of the tile's own 256 pixels in LDS ([256][ch]) instead of storing it, phase B reads x1 of its pixel (one float4
+// per tile row, issued ahead of the MFMA chain), adds the masked accumulator onto the parked quad and stores it.  The mask itself
+// goes out as a bit pattern in channel 2 of GD (bit c = [x1_c > 0], ch <= 16 bits; never the operand of an arithmetic instruction),
+// so that tmg_dense2_bwd masks its own share without reading x1: per pixel one ch-wide write and two ch-wide reads less over the
+// pair of launches, one ch-wide read more here.
+template <int CT, int MT, int KS, bool PERM = false, bool SUM = false>
 __global__ __launch_bounds__(256, CT == 1 ? 2 : 2) void cpl_bwd_kernel(CplBP p) {
     static_assert(!PERM || CT == 1, "the dealt row order is built for one 16-row tile");
     constexpr int PW = 18, PP = PW * PW;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int C = p.C, ch = C >> 1;
     float* DHL = lds;                                 // [ch][PP][2]: dhh pairs (da_j, dr_j) e^kappa on the tile + 1 halo pixel, zero outside the image
+    float* T1 = lds + ch * PP * 2;                    // SUM: [256][ch] dto1 of the tile's own pixels
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, q = lane >> 4;
     const float osc = out_scale_of(p.kappa);
@@ -530,7 +540,10 @@ __global__ __launch_bounds__(256, CT == 1 ? 2 : 2) void cpl_bwd_kernel(CplBP p) 
                 // this lane: acc[0][0..1] = dto1 channels 2 q, 2 q + 1; acc[0][2..3] = dto2 of the coupling channels j0 = 2 q, 2 q + 1
                 const int j0 = 2 * q;
                 if (j0 < ch) {
-                    if (center) *reinterpret_cast<float2*>(p.dtin + TMG_PXO(gp, p.dts) + j0) = make_float2(acc[0][0], acc[0][1]);
+                    if (center) {
+                        if constexpr (SUM) *reinterpret_cast<float2*>(T1 + ((ry - 1) * 16 + rx - 1) * ch + j0) = make_float2(acc[0][0], acc[0][1]);
+                        else *reinterpret_cast<float2*>(p.dtin + TMG_PXO(gp, p.dts) + j0) = make_float2(acc[0][0], acc[0][1]);
+                    }
                     const float rr[2] = {rcu[0].x, rcu[0].y}, tt[2] = {tcu[0].x, tcu[0].y};
                     float di[2], da[2], dr[2];
 #pragma unroll
@@ -557,7 +570,11 @@ __global__ __launch_bounds__(256, CT == 1 ? 2 : 2) void cpl_bwd_kernel(CplBP p) 
                 const int c = 16 * mo + 4 * q;
                 if (c < ch) {
                     // pass-through half: dto1 -> first half of dtin (dense2_bwd adds the coupling network's share)
-                    if (center) *reinterpret_cast<float4*>(p.dtin + TMG_PXO(gp, p.dts) + c) = make_float4(acc[mo][0], acc[mo][1], acc[mo][2], acc[mo][3]);
+                    if (center) {
+                        const float4 d1v = make_float4(acc[mo][0], acc[mo][1], acc[mo][2], acc[mo][3]);
+                        if constexpr (SUM) *reinterpret_cast<float4*>(T1 + ((ry - 1) * 16 + rx - 1) * ch + c) = d1v;
+                        else *reinterpret_cast<float4*>(p.dtin + TMG_PXO(gp, p.dts) + c) = d1v;
+                    }
                 } else if (c < C) {
                     const int j0 = c - ch;
                     const float rr[4] = {rcu[mo].x, rcu[mo].y, rcu[mo].z, rcu[mo].w};
@@ -604,6 +621,13 @@ __global__ __launch_bounds__(256, CT == 1 ? 2 : 2) void cpl_bwd_kernel(CplBP p) 
         for (int nt = 0; nt < 4; ++nt) {
             const int gy = oy0 + row0 + nt;
             const float* hbn = hb + nt * (PW * 2);
+            const bool pin = gy < p.H && gx < p.W;
+            // SUM: x1 of this lane's channel quad (ch <= 16: only m-tile 0 holds pass-through channels); the zero page reads as "masked"
+            float4 xm = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (SUM) {
+                const unsigned gpc = img + (unsigned)min(gy, p.H - 1) * (unsigned)p.W + (unsigned)min(gx, p.W - 1);
+                xm = *reinterpret_cast<const float4*>((pin && 4 * q < ch) ? p.x1 + TMG_PXO(gpc, p.x1s) + 4 * q : tmg_zero_page);
+            }
             f32x4 acc[MT];
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) acc[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -639,7 +663,26 @@ __global__ __launch_bounds__(256, CT == 1 ? 2 : 2) void cpl_bwd_kernel(CplBP p) 
                 for (int uy = 0; uy < 3; ++uy) { TMG_CPLB_TAP(3 * uy, uy - 1, 0, right) }
             }
 #undef TMG_CPLB_TAP
-            if (gy < p.H && gx < p.W) {
+            if constexpr (SUM) {
+                // the pixel's mask word: this lane's four bits at its channels, gathered over the pixel's four lanes (li + 16 q')
+                unsigned mb = ((xm.x > 0.f ? 1u : 0u) | (xm.y > 0.f ? 2u : 0u) | (xm.z > 0.f ? 4u : 0u) | (xm.w > 0.f ? 8u : 0u)) << (4 * q);
+                mb |= (unsigned)__shfl_xor((int)mb, 16);
+                mb |= (unsigned)__shfl_xor((int)mb, 32);
+                if (pin) {
+                    const unsigned gp = img + (unsigned)gy * (unsigned)p.W + (unsigned)gx;
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt) {
+                        const int c = 16 * mt + 4 * q;
+                        if (c < ch) {
+                            const float4 t = *reinterpret_cast<const float4*>(T1 + ((row0 + nt) * 16 + li) * ch + c);
+                            *reinterpret_cast<float4*>(p.dtin + TMG_PXO(gp, p.dts) + c) =
+                                make_float4(t.x + (xm.x > 0.f ? acc[mt][0] : 0.f), t.y + (xm.y > 0.f ? acc[mt][1] : 0.f),
+                                            t.z + (xm.z > 0.f ? acc[mt][2] : 0.f), t.w + (xm.w > 0.f ? acc[mt][3] : 0.f));
+                        } else if (c == ch)
+                            *reinterpret_cast<float4*>(p.GD + TMG_PXO(gp, 4)) = make_float4(acc[mt][0], acc[mt][1], __uint_as_float(mb), 0.f);
+                    }
+                }
+            } else if (pin) {
                 const unsigned gp = img + (unsigned)gy * (unsigned)p.W + (unsigned)gx;
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) {
@@ -654,25 +697,27 @@ __global__ __launch_bounds__(256, CT == 1 ? 2 : 2) void cpl_bwd_kernel(CplBP p) 
     }
 }
 
-template <int CT, int MT, int KS>
+template <int CT, int MT, int KS, bool SUM>
 static int launch_cpl_bwd(const CplBP& p, hipStream_t st) {
-    const size_t lds = (size_t)(p.C / 2) * 324 * 2 * sizeof(float);
-    if (lds > 64 * 1024) TMG_LDS_OPTIN((&cpl_bwd_kernel<CT, MT, KS>));
+    // the dhh patch; summed form: + dto1 of the 256 tile pixels (58 KB at C = 32: below the opt-in limit)
+    const size_t lds = (size_t)(p.C / 2) * (324 * 2 + (SUM ? 256 : 0)) * sizeof(float);
+    if (lds > 64 * 1024) TMG_LDS_OPTIN((&cpl_bwd_kernel<CT, MT, KS, false, SUM>));
     // blocks: measured at 64 x 128 x 128 (C = 16: 4 096 tiles) 256: 193 us, 512: 140, 768: 139, 1 024: 119, 2 048: 124, 4 096: 136 - two
     // resident blocks per CU, twice as many blocks as that with an even tile count each; at C = 32 (1 024 tiles) 512: 87, 768: 90, 1 024: 100
     static const int gcap = getenv("TMG_CPL_GRID") ? atoi(getenv("TMG_CPL_GRID")) : (CT == 1 ? 4 : 2) * tmg_num_cus();   // 1 024 / 512 on an MI355X
     const int per_blk = (p.ntiles + gcap - 1) / gcap;
     const int grid = (p.ntiles + per_blk - 1) / per_blk;
-    // algorithmic HBM bytes: dout (C), r (C/2), tin2 (C/2) read; DH (C), dtin (C), G0 (C/2), GD (4) written
+    // algorithmic HBM bytes: dout (C), r (C/2), tin2 (C/2) read; DH (C), dtin (C), G0 (C/2), GD (4) written (summed form: x1 (C/2) read
+    // in place of the G0 write)
     TmgProf prof(TMG_PROF_CPLB, 4.0 * p.B * (double)p.H * p.W * (4.5 * p.C + 4), st);
     if constexpr (CT == 1) {
         if (!p.fwd) {
-            hipLaunchKernelGGL((cpl_bwd_kernel<CT, MT, KS, true>), dim3(grid), dim3(256), lds, st, p);
+            hipLaunchKernelGGL((cpl_bwd_kernel<CT, MT, KS, true, SUM>), dim3(grid), dim3(256), lds, st, p);
             TMG_CHECK_LAUNCH();
             return 0;
         }
     }
-    hipLaunchKernelGGL((cpl_bwd_kernel<CT, MT, KS>), dim3(grid), dim3(256), lds, st, p);
+    hipLaunchKernelGGL((cpl_bwd_kernel<CT, MT, KS, false, SUM>), dim3(grid), dim3(256), lds, st, p);
     TMG_CHECK_LAUNCH();
     return 0;
 }
@@ -687,7 +732,9 @@ extern "C" int tmg_coupling_bwd_halves(const void* dout1, const void* dout2, con
 extern "C" int tmg_coupling_bwd(const void* dout, const void* x, const void* r, const void* g, const void* Wm, const void* wz,
                                 const void* kappa, void* DH, void* dtin, void* G0, void* GD, const int64_t* dims, hipStream_t st) {
     const int64_t ch = dims[3] / 2;
-    const int64_t d2[13] = {dims[0], dims[1], dims[2], dims[3], dims[4], dims[5], dims[6], dims[7], dims[8], dims[9], dims[4], dims[7], 0};
+    // (summed form: x1 = the first half of x, handed on as the halves entry takes it)
+    const int64_t d2[15] = {dims[0], dims[1], dims[2], dims[3], dims[4], dims[5], dims[6], dims[7], dims[8], dims[9], dims[4], dims[7], 0,
+                            (int64_t)(uintptr_t)x, dims[5]};
     return tmg_coupling_bwd_halves(dout, (const float*)dout + ch, (const float*)x + ch, r, g, Wm, wz, kappa, DH, dtin, (float*)dtin + ch, G0, GD,
                                    d2, st);
 }
@@ -695,6 +742,8 @@ extern "C" int tmg_coupling_bwd(const void* dout, const void* x, const void* r, 
 // As tmg_coupling_bwd with the channel halves of dout / dtin addressed separately and x2 = the second half of the layer input.
 // dims = {B, H, W, C, dout1 pixel stride, x2 pixel stride, DH pixel stride, dtin1 pixel stride, row length of wz, column of d1 in wz,
 // dout2 pixel stride, dtin2 pixel stride, density direction (0 / 1: see CplBP::fwd - then x2 is the second half of the coupling OUTPUT)}.
+// G0 == null selects the summed form (see cpl_bwd_kernel): dtin1 = dto1 + [x1 > 0] G0, GD = (d d1, d d2, mask bits, 0); dims then
+// carries two more entries, {.., x1 device pointer (as an integer), x1 pixel stride}: the first half of the layer input.
 extern "C" int tmg_coupling_bwd_halves(const void* dout1, const void* dout2, const void* x2, const void* r, const void* g, const void* Wm,
                                        const void* wz, const void* kappa, void* DH, void* dtin1, void* dtin2, void* G0, void* GD,
                                        const int64_t* dims, hipStream_t st) {
@@ -711,17 +760,27 @@ extern "C" int tmg_coupling_bwd_halves(const void* dout1, const void* dout2, con
     p.dtin2 = (float*)dtin2; p.dt2s = (int)dims[11];
     p.fwd = (int)dims[12];
     p.G0 = (float*)G0; p.GD = (float*)GD;
+    p.x1 = G0 ? nullptr : (const float*)(uintptr_t)dims[13]; p.x1s = G0 ? 0 : (int)dims[14];
+    if (!G0 && (!p.x1 || (p.x1s & 3) || (((uintptr_t)p.x1) & 15))) return -100;
     const int ch = p.C / 2;
     if (p.C < 8 || p.C > 32 || (ch & 3) || (p.dos & 3) || (p.xs & 3) || (p.dhs & 3) || (p.dts & 3) || (p.do2s & 3) || (p.dt2s & 3)) return -100;
     if ((((uintptr_t)dout1) | ((uintptr_t)dout2) | ((uintptr_t)x2) | ((uintptr_t)dtin1) | ((uintptr_t)dtin2)) & 15) return -100;
     p.tiles_x = (p.W + 15) / 16; p.tiles_y = (p.H + 15) / 16; p.ntiles = p.B * p.tiles_x * p.tiles_y;
     if (p.ntiles <= 0) return 0;
     if ((long long)p.B * p.H * p.W >= (1LL << 31)) return -100;     // 32-bit pixel indices
-    switch (ch / 4) {
-        case 1: return launch_cpl_bwd<1, 1, 2>(p, st);   // C = 8:  outputs ch + 2 = 6
-        case 2: return launch_cpl_bwd<1, 1, 4>(p, st);   // C = 16: 10
-        case 3: return launch_cpl_bwd<2, 1, 6>(p, st);   // C = 24: 14
-        case 4: return launch_cpl_bwd<2, 2, 8>(p, st);   // C = 32: 18
-    }
+    if (G0)
+        switch (ch / 4) {
+            case 1: return launch_cpl_bwd<1, 1, 2, false>(p, st);   // C = 8:  outputs ch + 2 = 6
+            case 2: return launch_cpl_bwd<1, 1, 4, false>(p, st);   // C = 16: 10
+            case 3: return launch_cpl_bwd<2, 1, 6, false>(p, st);   // C = 24: 14
+            case 4: return launch_cpl_bwd<2, 2, 8, false>(p, st);   // C = 32: 18
+        }
+    else
+        switch (ch / 4) {
+            case 1: return launch_cpl_bwd<1, 1, 2, true>(p, st);
+            case 2: return launch_cpl_bwd<1, 1, 4, true>(p, st);
+            case 3: return launch_cpl_bwd<2, 1, 6, true>(p, st);
+            case 4: return launch_cpl_bwd<2, 2, 8, true>(p, st);
+        }
     return -100;
 }

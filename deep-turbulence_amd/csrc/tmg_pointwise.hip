@@ -1130,6 +1130,7 @@ struct D2BP {
     const float* add0; int add0_stride;
     float* dd1_out; float* dd2_out; int dd_stride;  // optional: masked gradients w.r.t. d1 / d2 per pixel (null: not written)
     int dd_quad;                                    // the two are channels 0, 1 of a float4 slot whose channels 2, 3 are to be zero: one 16-byte store
+    int g0_masked;                                  // g0 = add0 + [t0 > 0] G0 already (tmg_coupling_bwd's summed form), mask bits in GD channel 2
     int TW_log2, tiles_x, tiles_y, ntiles, KCH;
 };
 
@@ -1350,7 +1351,11 @@ __global__ __launch_bounds__(256) void dense2_bwd_kernel(D2BP p) {
 // (TWL = log2 of the tile width as a template parameter: with the patch widths known at compile time every tap of the two stencils is
 // an immediate offset from one LDS address per thread; with a run-time width the compiler hoists ~50 tap addresses out of the tile
 // loop and spills.)
-template <int NQ, int TWL>
+// PM (D2BP::g0_masked): the upstream tensor is tmg_coupling_bwd's summed one, s = dto1 + [t0 > 0] G0, and the ReLU mask of the pixel
+// arrives as the bit pattern in channel 2 of GD (bit c = [t0_c > 0]): out = s + [t0 > 0] (growth share); neither t0 nor an add operand is
+// read.  g0 may then alias out (the level node's call): a thread reads s only at its own pixel and channels, before it writes them, and
+// no other thread writes those; a lane outside the image reads a clamped pixel that its owner may be writing - it drops that value.
+template <int NQ, int TWL, bool PM = false>
 __global__ __launch_bounds__(256, NQ <= 2 ? 4 : 3) void dense2_bwd_lean_kernel(D2BP p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
@@ -1423,12 +1428,16 @@ __global__ __launch_bounds__(256, NQ <= 2 ? 4 : 3) void dense2_bwd_lean_kernel(D
             }
         }
         float4 mq[NQ], gq[NQ], aq[NQ];
+        unsigned mw = 0u;
+        if constexpr (PM) mw = *reinterpret_cast<const unsigned*>(gdb + (opix * gds4 + 8u)) >> c0;
 #pragma unroll
         for (int j = 0; j < NQ; ++j) {
             const unsigned cj = 16u * (unsigned)min(j, nq_here - 1);     // a quad past the end re-reads the last live one (never stored)
-            mq[j] = *reinterpret_cast<const float4*>(xb + (opix * xs4 + cj));
             gq[j] = *reinterpret_cast<const float4*>(gb + (opix * gs4 + cj));
-            aq[j] = *reinterpret_cast<const float4*>(ab + (opix * as4 + (p.add0 ? cj : 0u)));
+            if constexpr (!PM) {
+                mq[j] = *reinterpret_cast<const float4*>(xb + (opix * xs4 + cj));
+                aq[j] = *reinterpret_cast<const float4*>(ab + (opix * as4 + (p.add0 ? cj : 0u)));
+            }
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -1482,10 +1491,18 @@ __global__ __launch_bounds__(256, NQ <= 2 ? 4 : 3) void dense2_bwd_lean_kernel(D
                         v.w += a.w * n1[tap] + bq.w * n2[tap];
                     }
                     float4 o;
+                    if constexpr (PM) {
+                        const unsigned m4 = mw >> (4 * j);
+                        o.x = gq[j].x + ((m4 & 1u) ? v.x : 0.f);
+                        o.y = gq[j].y + ((m4 & 2u) ? v.y : 0.f);
+                        o.z = gq[j].z + ((m4 & 4u) ? v.z : 0.f);
+                        o.w = gq[j].w + ((m4 & 8u) ? v.w : 0.f);
+                    } else {
                     o.x = (mq[j].x > 0.f ? gq[j].x + v.x : 0.f) + aq[j].x;
                     o.y = (mq[j].y > 0.f ? gq[j].y + v.y : 0.f) + aq[j].y;
                     o.z = (mq[j].z > 0.f ? gq[j].z + v.z : 0.f) + aq[j].z;
                     o.w = (mq[j].w > 0.f ? gq[j].w + v.w : 0.f) + aq[j].w;
+                    }
                     *reinterpret_cast<float4*>(ob + (opix * os4 + 16u * j)) = o;
                 }
             }
@@ -2006,7 +2023,9 @@ extern "C" int tmg_c1_bwd(const void* const* in_ptrs, const int64_t* in_desc, in
 }
 
 // Fused backward of both growth-1 layers (see dense2_bwd_kernel).
-// in segments: nn inputs followed by D (4 channels); dims = {B,H,W,Cin_total (incl. D's 4),cin_nn,rows1,rows2,dd1_out ptr,dd2_out ptr,dd stride,split2,gap2,dd_quad}
+// in segments: nn inputs followed by D (4 channels); dims = {B,H,W,Cin_total (incl. D's 4),cin_nn,rows1,rows2,dd1_out ptr,dd2_out ptr,dd stride,split2,gap2,dd_quad,g0_masked}
+// (g0_masked: g0 is the summed tensor of tmg_coupling_bwd with G0 == null and GD carries the mask bits - see dense2_bwd_lean_kernel's
+// PM; only the level node's call shape takes it, with cin_nn <= 16 and add0 null: -4 otherwise)
 // (dd_quad: dd1 / dd2 are channels 0, 1 of a 16-byte aligned float4 slot per pixel; the kernel writes (dd1, dd2, 0, 0) in one store)
 // g0/out: up to two segments each (same channel split as the nn inputs); add0 optional (null) added to out segment 0.
 extern "C" int tmg_dense2_bwd(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* w1, const void* w2,
@@ -2031,6 +2050,8 @@ extern "C" int tmg_dense2_bwd(const void* const* in_ptrs, const int64_t* in_desc
     p.dd1_out = (float*)dims[7]; p.dd2_out = (float*)dims[8]; p.dd_stride = (int)dims[9];
     p.dd_quad = dims[12] && p.dd1_out && p.dd2_out == p.dd1_out + 1 && !(p.dd_stride & 3) && !(((uintptr_t)p.dd1_out) & 15);
     if (dims[12] && !p.dd_quad) return -4;   // the caller relies on the zero channels
+    p.g0_masked = dims[13] != 0;
+    if (p.g0_masked && (add0 || p.cin_nn > 16 || p.dW1 || p.dW2 || (p.gd_stride & 3) || (((uintptr_t)p.GD) & 15))) return -4;
     p.split2 = dims[10] > 0 ? (int)dims[10] : 0x7fffffff; p.gap2 = (int)dims[11];
     if (add0 && ((add0_stride & 3) || (((uintptr_t)add0) & 15))) p.vec4 = 0;
     c1_tile(p.Win, p.Hin, &p.TW_log2);
@@ -2069,13 +2090,18 @@ extern "C" int tmg_dense2_bwd(const void* const* in_ptrs, const int64_t* in_desc
         const int per_blk = (p.ntiles + gl - 1) / gl;
         gl = (p.ntiles + per_blk - 1) / per_blk;
         const size_t lb = ((size_t)((QQ + 3) & ~3) + ((PP + 3) & ~3) + 18 * 4 * NQ) * 4;
-#define TMG_D2L(NQ_, TWL_) hipLaunchKernelGGL((dense2_bwd_lean_kernel<NQ_, TWL_>), dim3(gl, nch), dim3(256), lb, st, p)
+#define TMG_D2L(NQ_, TWL_)                                                                                                      \
+        do {                                                                                                                    \
+            if (p.g0_masked) hipLaunchKernelGGL((dense2_bwd_lean_kernel<NQ_, TWL_, true>), dim3(gl, nch), dim3(256), lb, st, p);  \
+            else hipLaunchKernelGGL((dense2_bwd_lean_kernel<NQ_, TWL_>), dim3(gl, nch), dim3(256), lb, st, p);                   \
+        } while (0)
         if (NQ == 2) { if (p.TW_log2 == 5) TMG_D2L(2, 5); else if (p.TW_log2 == 4) TMG_D2L(2, 4); else TMG_D2L(2, 3); }
         else { if (p.TW_log2 == 5) TMG_D2L(4, 5); else if (p.TW_log2 == 4) TMG_D2L(4, 4); else TMG_D2L(4, 3); }
 #undef TMG_D2L
         TMG_CHECK_LAUNCH();
         return 0;
     }
+    if (p.g0_masked) return -4;   // the general kernel reads its mask from the inputs
     if (p.dW1) hipLaunchKernelGGL(dense2_bwd_kernel<true>, dim3(gx, nchunks), dim3(256), lds_bytes, st, p);
     else hipLaunchKernelGGL(dense2_bwd_kernel<false>, dim3(gx, nchunks), dim3(256), lds_bytes, st, p);
     TMG_CHECK_LAUNCH();

@@ -22,6 +22,7 @@ struct ThinP {
     const long long* gtab;   // [G][16]: 3 input segments {pointer, pixel stride, 0, channels} + {dy pointer or 0, ...}   (tmg_conv_wgrad_grouped)
     const float* dy;         // shared upstream gradient: group g at channels [dyc g, dyc g + dyc)
     int dys, dyc;            // pixel stride; channels per group: 4, or 2 (compact: rows 2, 3 of a group's dW stay zero)
+    long long dyg;           // floats from one group's dy to the next: dyc (channels of one tensor), or the size of a per-group plane
     float* dW;               // [G][4][Cin][3][3], accumulated into
     int B, H, W, relu_in;
     int tiles_x, tiles_y, ntiles;   // per group
@@ -59,7 +60,7 @@ __global__ __launch_bounds__(256) void wgrad_thin_kernel(ThinP p) {
     const float* sp2 = reinterpret_cast<const float*>(gt[8]);
     const int ss0 = (int)gt[1], ss1 = (int)gt[5], ss2 = (int)gt[9];
     const int n0 = (int)gt[3], n1 = (int)gt[7];
-    const float* dyb = p.dy + p.dyc * g;
+    const float* dyb = p.dy + p.dyg * g;
 
     // lane offsets of the A operand inside the patch, per slot: block beta = 16 t + lane / 4 = tap * Q + quad (blocks past NB repeat
     // the last one; their results are dropped)
@@ -174,7 +175,11 @@ static int thin_impl(const void* gtab, int64_t G, const int64_t* seg_channels, i
     ThinP p;
     p.gtab = (const long long*)gtab; p.dy = (const float*)dy; p.dys = (int)dy_stride; p.dW = (float*)dW;
     p.B = (int)dims[0]; p.H = (int)dims[1]; p.W = (int)dims[2]; p.relu_in = (int)dims[4];
-    p.dyc = dims[5] == 2 ? 2 : 4;      // dims[5]: dy channels per group (0 / 4: a float4 per pixel, 2: a float2)
+    // dims[5]: dy channels per group (0 / 4: a float4 per pixel, 2: a float2), or - above 4 - the groups' dy are float2 PLANES
+    // [G][npix][dy_stride] and dims[5] is the distance between two of them in floats (an even number)
+    p.dyc = (dims[5] == 2 || dims[5] > 4) ? 2 : 4;
+    p.dyg = dims[5] > 4 ? (long long)dims[5] : p.dyc;
+    if (dims[5] > 4 && ((dims[5] & 1) || dims[5] < dims[0] * dims[1] * dims[2] * dy_stride)) return -100;
     const int Cin = (int)dims[3];
     if (G < 1 || !gtab || nseg < 1 || nseg > 3 || (dy_stride & (p.dyc - 1)) || ((uintptr_t)dy & (4 * p.dyc - 1))) return -100;
     for (int i = 0; i < nseg; ++i)
@@ -379,6 +384,43 @@ __global__ __launch_bounds__(256) void layer_planes_kernel(const float* __restri
             *reinterpret_cast<float2*>(dst + ((size_t)k * npix + p0 + px) * 2) = v;
         }
     }
+}
+
+// The inverse: K float2 planes [K][npix][2] -> [npix][CP] with channels 2 K .. CP - 1 zero (the padding layers of a level's stash).  The
+// per-layer backward kernels write (dd1, dd2) of their layer as a plane (8 useful bytes out of every 8 written, instead of 8 out of a
+// 128-byte pixel of the interleaved stash); the level-wide conditioning contractions read all layers of a pixel at once.
+__global__ __launch_bounds__(256) void layer_unplanes_kernel(const float* __restrict__ src, float* __restrict__ dst, long long npix, int CP, int K) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int RS = CP + 2;
+    const long long p0 = (long long)blockIdx.x * 64;
+    const int KP = CP >> 1;
+    for (int it = threadIdx.x; it < 64 * KP; it += 256) {
+        const int k = it >> 6, px = it & 63;
+        float2 v = make_float2(0.f, 0.f);
+        if (k < K && p0 + px < npix) v = *reinterpret_cast<const float2*>(src + ((size_t)k * npix + p0 + px) * 2);
+        *reinterpret_cast<float2*>(lds + px * RS + 2 * k) = v;
+    }
+    __syncthreads();
+    const int q4 = CP >> 2;
+    for (int it = threadIdx.x; it < 64 * q4; it += 256) {
+        const int px = it / q4, c4 = it - px * q4;
+        if (p0 + px < npix) {
+            const float* s = lds + px * RS + 4 * c4;
+            *reinterpret_cast<float4*>(dst + (p0 + px) * CP + 4 * c4) = make_float4(s[0], s[1], s[2], s[3]);
+        }
+    }
+}
+
+// src [K][npix][2] contiguous, dst [npix][CP] contiguous, 1 <= K <= CP / 2, CP as for tmg_layer_planes; -1 otherwise (nothing launched).
+extern "C" int tmg_layer_unplanes(const void* src, void* dst, int64_t npix, int64_t CP, int64_t K, hipStream_t st) {
+    if (npix < 1 || CP < 4 || (CP & 3) || CP > 512 || K < 1 || 2 * K > CP) return -1;
+    const long long blocks = (npix + 63) / 64;
+    const size_t lds_bytes = (size_t)64 * (CP + 2) * 4;
+    if (lds_bytes > 64 * 1024) TMG_LDS_OPTIN((&layer_unplanes_kernel));
+    hipLaunchKernelGGL(layer_unplanes_kernel, dim3((unsigned)blocks), dim3(256), lds_bytes, st, (const float*)src, (float*)dst,
+                       (long long)npix, (int)CP, (int)K);
+    TMG_CHECK_LAUNCH();
+    return 0;
 }
 
 // src [npix][CP] contiguous (CP a multiple of 4, 4 <= CP <= 512; from CP = 256 on the staging rows need the LDS opt-in), dst [CP / 2][npix][2];

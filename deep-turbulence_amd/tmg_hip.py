@@ -80,6 +80,8 @@ PHASE_EXPORTS = ["tmg_ens_phase_plan", "tmg_ens_phase_label", "tmg_ens_phase_acc
 # The spectral POD: the members' cross-spectral density matrices and the synthesis of the modes (csrc/tmg_spod.hip), declared in
 # include/tmglow_hip_spod.h, a header of its own: ens_spod_plan / ens_spod_csd / ens_spod_modes below.
 SPOD_EXPORTS = ["tmg_ens_spod_plan", "tmg_ens_spod_csd", "tmg_ens_spod_modes"]
+# The layout conversions of the level node's backward pass (csrc/tmg_thin.hip), declared in include/tmglow_hip_layout.h: layer_unplanes below.
+LAYOUT_EXPORTS = ["tmg_layer_unplanes"]
 # Every export returns int except the workspace sizes, which the header declares int64_t (read through a 32-bit return a request of
 # 2^31 floats or more would be truncated and the kernel handed a buffer smaller than it planned for).
 RET_I64 = ("tmg_conv_wgrad_ws_floats", "tmg_conv_wgrad_grouped_ws_floats", "tmg_conv_wino_wgrad_ws_floats",
@@ -95,7 +97,7 @@ def build(force=False, verbose=False):
                os.path.join(inc, "tmglow_hip_tspec.h"), os.path.join(inc, "tmglow_hip_quant.h"),
                os.path.join(inc, "tmglow_hip_gram.h"), os.path.join(inc, "tmglow_hip_sfun.h"),
                os.path.join(inc, "tmglow_hip_event.h"), os.path.join(inc, "tmglow_hip_pdf.h"), os.path.join(inc, "tmglow_hip_pod.h"),
-               os.path.join(inc, "tmglow_hip_phase.h"), os.path.join(inc, "tmglow_hip_spod.h")]
+               os.path.join(inc, "tmglow_hip_phase.h"), os.path.join(inc, "tmglow_hip_spod.h"), os.path.join(inc, "tmglow_hip_layout.h")]
     hmt = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -149,7 +151,7 @@ def lib():
         for name in PLAN_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
             getattr(_lib, name).argtypes = PLAN_ARGTYPES[name]
-        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS + SFUN_EXPORTS + EVENT_EXPORTS + PDF_EXPORTS + POD_EXPORTS + PHASE_EXPORTS + SPOD_EXPORTS:
+        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS + SFUN_EXPORTS + EVENT_EXPORTS + PDF_EXPORTS + POD_EXPORTS + PHASE_EXPORTS + SPOD_EXPORTS + LAYOUT_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
     return _lib
 
@@ -613,6 +615,15 @@ def layer_planes(src):
     return dst
 
 
+def layer_unplanes(planes, CP):
+    """[K,B,H,W,2] contiguous -> [B,H,W,CP] with channel 2k / 2k+1 = plane k and the channels from 2K on zero (tmg_layer_unplanes)."""
+    K, B, Hh, Ww, two = planes.shape
+    assert planes.is_contiguous() and two == 2 and CP % 4 == 0 and 2 * K <= CP
+    dst = torch.empty((B, Hh, Ww, CP), device=planes.device, dtype=torch.float32)
+    _chk(lib().tmg_layer_unplanes(_ptr(planes), _ptr(dst), c_i64(B * Hh * Ww), c_i64(CP), c_i64(K), _stream()), "tmg_layer_unplanes")
+    return dst
+
+
 def _pixel_linear(t):
     """[B,H,W,c] view whose pixels are equally spaced in memory (address = base + pixel index * stride(2) + channel)."""
     B, Hh, Ww, _ = t.shape
@@ -646,20 +657,27 @@ def _group_rows(group_inputs, group_dy=None):
     return rows
 
 
-def conv_wgrad_thin_grouped(group_inputs, dy, dy_group_channels, dW, relu_in=False, gtab=None):
+def conv_wgrad_thin_grouped(group_inputs, dy, dy_group_channels, dW, relu_in=False, gtab=None, dy_planes=False):
     """The thin grouped 3x3 weight gradient (tmg_conv_wgrad_thin_grouped) called directly: group_inputs[g] a list of <= 3 NHWC
     segments, dy the shared upstream gradient with dy_group_channels (4 or 2) channels per group, dW [G, 4, Cin, 3, 3] accumulated
-    into.  Returns the library's code: 0 launched, -100 outside the kernel's envelope (nothing launched)."""
+    into.  dy_planes: dy is [G,B,H,W,2] contiguous, one float2 plane per group.
+    Returns the library's code: 0 launched, -100 outside the kernel's envelope (nothing launched)."""
     first = group_inputs[0]
     B, Hin, Win, _ = first[0].shape
+    dyc, dys = int(dy_group_channels), dy.stride(-2)
+    if dy_planes:
+        assert dy.is_contiguous() and dy.shape == (len(group_inputs), B, Hin, Win, 2) and dyc == 2
+        dyc = dy.stride(0)      # the distance between two planes takes the place of the channel count (see thin_impl)
+        if dyc <= 4:
+            return -100
     # the part of the envelope the library cannot see (the segments' addresses live in the device table): float4-addressable pixels
     if not all(t.stride(2) % 4 == 0 and t.data_ptr() % 16 == 0 for segs in group_inputs for t in segs):
         return -100
     if gtab is None:
         gtab = _segment_table(_group_rows(group_inputs), dy.device)
     return lib().tmg_conv_wgrad_thin_grouped(_ptr(gtab), c_i64(len(group_inputs)), _i64(*[t.shape[3] for t in first]), c_i64(len(first)),
-                                             _ptr(dy), c_i64(dy.stride(2)), _ptr(dW),
-                                             _i64(B, Hin, Win, sum(t.shape[3] for t in first), relu_in, int(dy_group_channels)), _stream())
+                                             _ptr(dy), c_i64(dys), _ptr(dW),
+                                             _i64(B, Hin, Win, sum(t.shape[3] for t in first), relu_in, dyc), _stream())
 
 
 def mix_wgrad_grouped(group_inputs, group_dy, dW, dbias, gtab=None):
@@ -769,19 +787,28 @@ def coupling_fwd(x, out, rsave, y2save, D, hc, wz, bz, kappa, Wm, bm, logdet, re
     return _launched(rc, "tmg_coupling_fwd_halves")
 
 
-def coupling_bwd(dout, x2, r, g, Wm, wz, kappa, DH, dtin, G0, GD, wz_d1col, fwd=False):
+def coupling_bwd(dout, x2, r, g, Wm, wz, kappa, DH, dtin, G0, GD, wz_d1col, fwd=False, x1=None):
     """Mix input gradient + affine-coupling backward + zero-conv input gradient (exact replicate adjoint) of one generative-
     direction coupling layer in one launch (tmg_coupling_bwd_halves).  dout / dtin: [B,H,W,C] tensors or pairs of [B,H,W,C/2] halves;
     x2: the SECOND half of the layer input [B,H,W,C/2] (a channel-slice view or a tensor of its own); DH: [B,H,W,C] channel-slice
     view of the level's stash.  fwd=True: the density direction's layer (mix -> coupling): dout = gradient w.r.t. the coupling
-    output, x2 = second half of the coupling OUTPUT, no mix in front (Wm is not read)."""
+    output, x2 = second half of the coupling OUTPUT, no mix in front (Wm is not read).
+    G0=None: the summed form - the first half of dtin receives dto1 + [x1 > 0] G0 and GD = (d d1, d d2, mask bits, 0) for
+    dense2_bwd(.., g0_masked=True); x1 [B,H,W,C/2]: the first half of the layer input (a view or a tensor of its own)."""
     d1, d2 = _halves(dout)
     t1, t2 = _halves(dtin)
     B, Hh, Ww, ch = d1.shape
     assert x2.shape[3] == ch
     sd1, sd2, sx, sh, st1, st2 = seg(d1), seg(d2), seg(x2), seg(DH), seg(t1), seg(t2)
-    assert r.is_contiguous() and G0.is_contiguous() and GD.is_contiguous() and Wm.is_contiguous() and wz.is_contiguous()
-    dims = _i64(B, Hh, Ww, 2 * ch, sd1[1], sx[1], sh[1], st1[1], wz.shape[1], wz_d1col, sd2[1], st2[1], 1 if fwd else 0)
+    assert r.is_contiguous() and GD.is_contiguous() and Wm.is_contiguous() and wz.is_contiguous()
+    assert (G0 is None) != (x1 is None), "the summed form (G0=None) reads x1, the separate form does not"
+    dims = [B, Hh, Ww, 2 * ch, sd1[1], sx[1], sh[1], st1[1], wz.shape[1], wz_d1col, sd2[1], st2[1], 1 if fwd else 0]
+    if G0 is None:
+        assert x1.shape[3] == ch
+        dims += list(seg(x1)[:2])
+    else:
+        assert G0.is_contiguous()
+    dims = _i64(*dims)
     rc = lib().tmg_coupling_bwd_halves(c_vp(sd1[0]), c_vp(sd2[0]), c_vp(sx[0]), _ptr(r), _ptr(g), _ptr(Wm), _ptr(wz), _ptr(kappa), c_vp(sh[0]),
                                        c_vp(st1[0]), c_vp(st2[0]), _ptr(G0), _ptr(GD), dims, _stream())
     return _launched(rc, "tmg_coupling_bwd_halves")
@@ -1676,8 +1703,9 @@ def dkappa(w, dw, b, db, kappa, dk):
 
 
 def dense2_bwd(inputs, w1p, w2p, dW1p, dW2p, GD, D, g0, outs, cin_nn, add0=None, rows1=0, rows2=0, dd1=None, dd2=None, split2=0, gap2=0,
-               dd_quad=False):
-    """Fused backward of the two growth-1 layers; `inputs` = nn inputs + [D]; g0 / outs: lists (<= 2) of NHWC tensors."""
+               dd_quad=False, g0_masked=False):
+    """Fused backward of the two growth-1 layers; `inputs` = nn inputs + [D]; g0 / outs: lists (<= 2) of NHWC tensors.
+    g0_masked: g0 / GD come from coupling_bwd's summed form (g0 may be the output tensor itself; add0 must be None)."""
     B, H, W, _ = inputs[0].shape
     ip, idesc, n_in = _segs(inputs)
     gp, gdesc, ng = _segs(g0)
@@ -1687,7 +1715,8 @@ def dense2_bwd(inputs, w1p, w2p, dW1p, dW2p, GD, D, g0, outs, cin_nn, add0=None,
     _chk(lib().tmg_dense2_bwd(ip, idesc, c_i64(n_in), _ptr(w1p), _ptr(w2p), _ptr(dW1p), _ptr(dW2p), _ptr(GD), c_i64(seg(GD)[1]), _ptr(D),
                               c_i64(seg(D)[1]), gp, gdesc, op, odesc, c_i64(ng), _ptr(add0), c_i64(a_stride),
                               _i64(B, H, W, Cin, cin_nn, rows1 or Cin, rows2 or Cin, dd1.data_ptr() if dd1 is not None else 0,
-                                   dd2.data_ptr() if dd2 is not None else 0, seg(dd1)[1] if dd1 is not None else 0, split2, gap2, 1 if dd_quad else 0),
+                                   dd2.data_ptr() if dd2 is not None else 0, seg(dd1)[1] if dd1 is not None else 0, split2, gap2, 1 if dd_quad else 0,
+                                   1 if g0_masked else 0),
                               _stream()),
          "tmg_dense2_bwd")
 

@@ -1113,7 +1113,7 @@ def _mix_bwd(x, dy, Wk, dWk, dbk):
 # One flow level as LevelCouplingFn sees it (built once per forward pass and carried on ctx); w1s .. kps: (w1, w2, wz, bz, kappa) per layer
 _Level = collections.namedtuple("_Level", "NL NLp C ch Cc cin reverse fuse split rec w1s w2s wzs bzs kps")
 # What the per-layer steps of LevelCouplingFn.backward share (see there)
-_LevelBwd = collections.namedtuple("_LevelBwd", "g Wm PZt PMt DH DD quad_last grouped zc_kw wg_in mix_wg dWz dBz dW1 dW2 dWm dbm")
+_LevelBwd = collections.namedtuple("_LevelBwd", "g Wm PZt PMt DH DD quad_last grouped zc_kw wg_in mix_wg dWz dBz dW1 dW2 dWm dbm DDp")
 
 
 def _level(wts, C, Cc, reverse):
@@ -1344,11 +1344,18 @@ class LevelCouplingFn(torch.autograd.Function):
     def _growth_bwd(L, S, k, x1, D, G0, GD, dt1, add0):
         """Both growth-1 layers' backward, ReLU masks and the concat adjoint of layer k in one launch: dt1 (the first half of the
         layer-input gradient) = add0 (the pass-through half of the coupling's gradient) + G0 + the growth layers' share; (dd1, dd2)
-        go to the layer's channels of DD; the x1 | d1 weight-gradient rows here unless the level's grouped launch writes them."""
+        go to the layer's channels of DD; the x1 | d1 weight-gradient rows here unless the level's grouped launch writes them.
+        G0 None: dt1 already holds add0 + [x1 > 0] G0 and GD the mask bits (the coupling backward's summed form): read and completed
+        in place."""
         ch = L.ch
         dW1, dW2 = (None, None) if S.grouped else (S.dW1[k], S.dW2[k])
-        H.dense2_bwd([x1, D], L.w1s[k], L.w2s[k], dW1, dW2, GD, D, [G0], [dt1], ch, add0=add0, rows1=ch, rows2=ch + 1, split2=ch, gap2=L.Cc,
-                     dd1=S.DD[..., 2 * k:2 * k + 1], dd2=S.DD[..., 2 * k + 1:2 * k + 2], dd_quad=(S.quad_last and k == L.NL - 1))
+        summed = G0 is None
+        if S.DDp is not None:     # large levels: the layer's own float2 plane (pixel stride 2)
+            dd1, dd2, quad = S.DDp[k][..., 0:1], S.DDp[k][..., 1:2], False
+        else:
+            dd1, dd2, quad = S.DD[..., 2 * k:2 * k + 1], S.DD[..., 2 * k + 1:2 * k + 2], S.quad_last and k == L.NL - 1
+        H.dense2_bwd([x1, D], L.w1s[k], L.w2s[k], dW1, dW2, GD, D, [dt1 if summed else G0], [dt1], ch, add0=None if summed else add0,
+                     rows1=ch, rows2=ch + 1, split2=ch, gap2=L.Cc, dd1=dd1, dd2=dd2, dd_quad=quad, g0_masked=summed)
 
     @staticmethod
     def _bwd_fused_generative(L, S, k, dcur, tin, D, r, y):
@@ -1360,11 +1367,13 @@ class LevelCouplingFn(torch.autograd.Function):
             dtin = (empty(bhw + (ch,), dev), empty(bhw + (ch,), dev))
         else:                            # (k = NL - 1: the node's own input gradient)
             dtin = empty(bhw + (C,), dev)
-        G0, GD = empty(bhw + (ch,), dev), empty(bhw + (4,), dev)
+        # (the summed form - no G0 tensor - needs the growth backward without weight gradients: the grouped level)
+        G0, GD = None if S.grouped else empty(bhw + (ch,), dev), empty(bhw + (4,), dev)
         dhh = S.DH[..., k * C:(k + 1) * C]
         x1, x2 = H._halves(tin)
         dt1 = H._halves(dtin)[0]
-        ok = H.coupling_bwd(dcur, x2, r, S.g, S.Wm[k].contiguous(), L.wzs[k], L.kps[k], dhh, dtin, G0, GD, L.cin)
+        ok = H.coupling_bwd(dcur, x2, r, S.g, S.Wm[k].contiguous(), L.wzs[k], L.kps[k], dhh, dtin, G0, GD, L.cin,
+                            x1=x1 if G0 is None else None)
         assert ok
         LevelCouplingFn._zero_conv_wgrad(L, S, k, [x1, D])
         LevelCouplingFn._mix_wgrad(L, S, k, y, dcur)
@@ -1380,10 +1389,11 @@ class LevelCouplingFn(torch.autograd.Function):
         C, ch = L.C, L.ch
         bhw, dev = D.shape[:3], D.device
         dtin = empty(bhw + (C,), dev)
-        G0, GD = empty(bhw + (ch,), dev), empty(bhw + (4,), dev)
+        G0, GD = None if S.grouped else empty(bhw + (ch,), dev), empty(bhw + (4,), dev)
         dhh = S.DH[..., k * C:(k + 1) * C]
         x1, dt1 = tin[..., :ch], dtin[..., :ch]
-        ok = H.coupling_bwd(dcur, y[..., ch:], r, S.g, S.Wm[k].contiguous(), L.wzs[k], L.kps[k], dhh, dtin, G0, GD, L.cin, fwd=True)
+        ok = H.coupling_bwd(dcur, y[..., ch:], r, S.g, S.Wm[k].contiguous(), L.wzs[k], L.kps[k], dhh, dtin, G0, GD, L.cin, fwd=True,
+                            x1=x1 if G0 is None else None)
         assert ok
         LevelCouplingFn._zero_conv_wgrad(L, S, k, [x1, D])
         LevelCouplingFn._growth_bwd(L, S, k, x1, D, G0, GD, dt1, dt1)
@@ -1435,7 +1445,12 @@ class LevelCouplingFn(torch.autograd.Function):
         # x1 | d1 rows of the growth-layer weight gradients: same inputs, dy = this layer's (dd1, dd2, 0, 0) quad; row 0 of the
         # result belongs to w1, row 1 to w2 (its column ch is the d1 input)
         tmpX = zeros((NL, 4, ch + 4, 3, 3), S.DH.device)
-        if not H.conv_wgrad_grouped(S.wg_in, S.DD, 2, tmpX, None, 3, 1, relu_in=True):
+        if S.DDp is not None:     # every group reads its own plane
+            if os.environ.get("TMG_NO_THIN_WGRAD") is not None or not H._launched(
+                    H.conv_wgrad_thin_grouped(S.wg_in, S.DDp, 2, tmpX, relu_in=True, dy_planes=True), "tmg_conv_wgrad_thin_grouped"):
+                for k in range(NL):
+                    H.conv_wgrad(S.wg_in[k], S.DDp[k], tmpX[k][:2], None, 3, 1, relu_in=True)
+        elif not H.conv_wgrad_grouped(S.wg_in, S.DD, 2, tmpX, None, 3, 1, relu_in=True):
             for k in range(NL):
                 H.conv_wgrad(S.wg_in[k], S.DD[..., 2 * k:2 * k + 2], tmpX[k][:2], None, 3, 1, relu_in=True)
         S.wg_in.clear()
@@ -1499,9 +1514,16 @@ class LevelCouplingFn(torch.autograd.Function):
         # weight gradient w.r.t. the conditioning columns 60 output channels for 30, the conditioning input gradient K = NL (C + 4)).
         # Written whole by the per-layer backward kernels (8 bytes per pixel and layer; the LAST layer writes a (dd1, dd2, 0, 0) quad
         # when there is ONE padding layer, which zeroes its two channels; more padding layers are filled): no zero fill at NL = 15
-        DD = empty(bhw + (2 * NLp,), dev)
+        # Large levels (the forward direction's threshold, _cond_parts): one float2 plane per layer instead - a layer's 8 bytes per pixel
+        # are then whole lines of its plane, not a fragment of every 128-byte pixel of the interleaved stash, for its writer and for the
+        # grouped growth-row weight gradients; one re-interleaving launch (padding channels zeroed) in front of the conditioning side
+        DDp = None
+        if math.prod(bhw) >= int(os.environ.get("TMG_LAYER_PLANES_MIN", 1 << 17)):
+            DDp, DD = empty((NL,) + bhw + (2,), dev), None
+        else:
+            DD = empty(bhw + (2 * NLp,), dev)
         quad_last = NLp - NL == 1        # (NL = 15 in the reference's models: one padding layer, zeroed by the last layer's quad store)
-        if NLp - NL > 1:
+        if DD is not None and NLp - NL > 1:
             DD[..., 2 * NL:].zero_()
         # The NL zero-conv weight gradients (x1 | D part) are independent of each other once DH holds every layer's
         # exp(kappa)*dhh: they run as ONE grouped launch after the loop (a few microseconds of MFMA work each otherwise,
@@ -1512,7 +1534,7 @@ class LevelCouplingFn(torch.autograd.Function):
         zc_kw = dict(relu_in=True, pad_rep=True, cin_dst=cin + 2, cin_valid=ch + 2, ci_split=ch, ci_off0=0, ci_off1=Cc)
         # wg_in[k] = [x1, D] of layer k's zero conv; mix_wg[k] = (input, upstream gradient) of its 1x1 mix
         S = _LevelBwd(g, Wm, PZt, PMt, DH, DD, quad_last, grouped, zc_kw, [None] * NL, [None] * NL if grouped else None, dWz, dBz, dW1, dW2,
-                      dWm, dbm)
+                      dWm, dbm, DDp)
         R = None
         if ctx.rec_out is not None:     # recompute mode: see _rebuild
             Hc_r, Dc_r, dc_of_r = LevelCouplingFn._cond_parts(L, cond, Wcat)
@@ -1527,6 +1549,8 @@ class LevelCouplingFn(torch.autograd.Function):
         for k in (range(NL) if L.reverse else range(NL - 1, -1, -1)):
             dcur = step(L, S, k, dcur, *LevelCouplingFn._activations(L, R, saved, k))
         tmpX = LevelCouplingFn._grouped_wgrads(L, S) if grouped else None
+        if DDp is not None:
+            S = S._replace(DD=H.layer_unplanes(DDp, 2 * NLp), DDp=None)
         Gc, tmpC = LevelCouplingFn._cond_bwd(L, S, cond, Wcat)
         dK = LevelCouplingFn._finish(L, S, Wz, Bz, Kp, tmpX, tmpC)
         grads = []

@@ -242,7 +242,11 @@ int tmg_c1_bwd(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg,
  * and the concat adjoint: one pass over the network input.  in segments = nn inputs followed by the 4-channel D
  * buffer; dims = {B,H,W,Cin_total(incl. D),cin_nn,rows1,rows2,dd1_out,dd2_out,dd_stride,split2,gap2,dd_quad} (dd*_out: optional device
  * pointers, passed as integers, receiving the masked gradients w.r.t. d1 / d2; dd_quad = 1: they are channels 0, 1 of a 16-byte aligned
- * float4 slot per pixel and the kernel stores (dd1, dd2, 0, 0) whole - the level-wide stash then needs no zero fill). */
+ * float4 slot per pixel and the kernel stores (dd1, dd2, 0, 0) whole - the level-wide stash then needs no zero fill).
+ * dims[13] = g0_masked (0 / 1): g0 and GD come from tmg_coupling_bwd's summed form - g0 = add0 + [t0 > 0] G0 already, channel 2 of GD
+ * holds the mask bits of the pixel - so out = g0 + [bit] (growth share); neither t0 nor add0 (which must be NULL) is read for it, and
+ * g0 may be the output tensor itself (each thread reads its own pixel's channels before it writes them).  Taken by the lean kernel
+ * alone (no dW1 / dW2, inputs (t0, D), one float4-addressable segment, cin_nn <= 16): -4 for any other call. */
 int tmg_dense2_bwd(const void* const* in_ptrs, const int64_t* in_desc, int64_t nseg, const void* w1, const void* w2, void* dW1,
                    void* dW2, const void* GD, int64_t gd_stride, const void* Dp, int64_t d_stride, const void* const* g0_ptrs,
                    const int64_t* g0_desc, void* const* out_ptrs, const int64_t* out_desc, int64_t ng, const void* add0,
@@ -308,7 +312,12 @@ int tmg_coupling_bwd(const void* dout, const void* x, const void* r, const void*
  * bwd dims = {B,H,W,C, dout1 stride, x2 stride, DH stride, dtin1 stride, wz row length, d1 column, dout2 stride, dtin2 stride, fwd};
  * x2 = the second half of the layer input (the only part of it the backward pass reads).  fwd = 1: backward of the DENSITY
  * direction's layer (flowAffine.py:76-83: mix first, coupling second): dout is the gradient w.r.t. the coupling output (no mix
- * in front; Wm is not read), x2 = the second half of the coupling OUTPUT, dtin = the gradient w.r.t. the coupling input. */
+ * in front; Wm is not read), x2 = the second half of the coupling OUTPUT, dtin = the gradient w.r.t. the coupling input.
+ * Summed form, both bwd entries: G0 == NULL.  dtin half 1 then receives dto1 + [x1 > 0] G0 (the ReLU in front of the coupling network
+ * masks G0, not the pass-through gradient, so the mask is applied where the sum is formed) and GD = (d d1, d d2, m, 0) with m the
+ * integer bit pattern sum_c [x1_c > 0] 2^c stored in the float slot, for tmg_dense2_bwd's g0_masked form.  x1 = the first half of the
+ * layer input: tmg_coupling_bwd takes it from x; tmg_coupling_bwd_halves from two more dims entries, {.., fwd, x1 device pointer (as
+ * an integer), x1 pixel stride} (16-byte aligned, stride a multiple of 4).  With a non-NULL G0 nothing changes. */
 int tmg_coupling_fwd_halves(const void* x1, const void* x2, void* out1, void* out2, void* rsave, void* y2save, const void* D,
                             const void* hc, const void* wz, const void* bz, const void* kappa, const void* Wm, const void* bm,
                             void* logdet, const int64_t* dims, tmg_stream_t st);
@@ -357,8 +366,10 @@ int tmg_lu_fold_bwd_split(const void* tab, const void* sign_s, const void* perm,
  * instead of 16x16 tiles that would be 2/16 used.  gtab: device int64 [G][16] as for tmg_conv_wgrad_grouped; seg_channels[nseg]: channels of
  * the input segments; dy: shared upstream gradient, group g at channels [c g, c g + c), c = dims[5] = 4 or 2 (2: the compact stash of
  * (dd1, dd2) per layer - rows 2, 3 of a group's dW stay untouched), pixel stride dy_stride; dW [G][4][Cin][3][3] is accumulated into
- * (atomics).  dims = {B, H, W, Cin, relu_in, dy channels per group}; zero padding, stride 1.  -100: shape outside the envelope (Cin not
- * in {12, 20, 36, 68} or unaligned segments), nothing launched. */
+ * (atomics).  dims = {B, H, W, Cin, relu_in, dy channels per group}; zero padding, stride 1.  dims[5] > 4: the groups' dy are float2
+ * PLANES, group g at dy + dims[5] g floats (an even number, at least B H W dy_stride), pixel stride dy_stride - the per-layer planes of
+ * the level node's stash on large levels.  -100: shape outside the envelope (Cin not in {12, 20, 36, 68} or unaligned segments), nothing
+ * launched. */
 int tmg_conv_wgrad_thin_grouped(const void* gtab, int64_t G, const int64_t* seg_channels, int64_t nseg, const void* dy, int64_t dy_stride,
                                 void* dW, const int64_t* dims, tmg_stream_t st);
 
@@ -374,6 +385,7 @@ int tmg_mix_wgrad_grouped(const void* gtab, int64_t G, void* dW, void* db, const
  * that each layer's launch reads 8 bytes per pixel instead of a whole line of the interleaved tensor.  CP a multiple of 4, 4 <= CP <= 512
  * (64 (CP + 2) floats of LDS: above 64 KB, i.e. from CP = 256 on, the launcher opts the kernel in); -1 otherwise, nothing launched. */
 int tmg_layer_planes(const void* src, void* dst, int64_t npix, int64_t CP, tmg_stream_t st);
+/* (its inverse for the backward pass, tmg_layer_unplanes: tmglow_hip_layout.h) */
 
 /* Parameter-gradient epilogue of a level's NL plain coupling layers, one launch: d(kappa_k) = (<Wz_k, dWz_k> + <bz_k, dBz_k>) inside the
  * clamp range of the zero conv's log-scale (flowUtils.py:104-106; fp64 accumulation), and the scatter-add of the grouped 4-row
@@ -508,6 +520,7 @@ int tmg_spec_finalize(const void* tmean, void* tm_mean, void* tm_std, const int6
 #include "tmglow_hip_pdf.h"
 #include "tmglow_hip_pod.h"
 #include "tmglow_hip_phase.h"
+#include "tmglow_hip_layout.h"
 
 /* The benchmark loss of SURVEY 8-D, generative direction: *loss += fl[0] sum(y^2) + fl[1] sum(logdet) (the caller zeroes *loss;
  * fl = {1 / numel(y), 1 / (B noc H W)}), and its gradient dy = 2 fl[0] *g y, dld[b] = fl[1] *g with the upstream gradient read from

@@ -79,6 +79,14 @@ def main():
         t = timeit(lambda: H.coupling_bwd(dout, x2, r, g, Wm, wz, kap, DH[..., k * C:(k + 1) * C], dtin, G0, GD, ch + Cc))
         byts = npx * 4.0 * (C + ch + ch + C + C + ch + 4)
         print("[%s] L%d cpl_bwd          %7.1f us  alg %.2f TB/s" % (tag, lvl, t, byts / t / 1e6), flush=True)
+        # the summed form of the pair (the level node's): x1 read in place of the G0 write; G0, x1 and add0 not read by dense2_bwd
+        t = timeit(lambda: H.coupling_bwd(dout, x2, r, g, Wm, wz, kap, DH[..., k * C:(k + 1) * C], dtin, None, GD, ch + Cc, x1=x1))
+        print("[%s] L%d cpl_bwd summed   %7.1f us  alg %.2f TB/s" % (tag, lvl, t, byts / t / 1e6), flush=True)
+        t = timeit(lambda: H.dense2_bwd([x1, D], w1, w2, None, None, GD, D, [dt1], [dt1], ch, add0=None, rows1=ch, rows2=ch + 1,
+                                        dd1=DD[..., 4 * k:4 * k + 1], dd2=DD[..., 4 * k + 1:4 * k + 2], split2=ch, gap2=Cc, dd_quad=True,
+                                        g0_masked=True))
+        byts = npx * 4.0 * (4 + 4 + ch + ch + 4)
+        print("[%s] L%d dense2_bwd masked %6.1f us  alg %.2f TB/s" % (tag, lvl, t, byts / t / 1e6), flush=True)
 
 if __name__ == "__main__":
     main()
