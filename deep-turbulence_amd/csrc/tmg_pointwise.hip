@@ -389,6 +389,17 @@ __global__ void pad_halves_kernel(const float* __restrict__ src, int ss, float* 
 // ---------------------------------------------------------------------------------------------
 // bilinear up-sampling, align_corners = True
 // ---------------------------------------------------------------------------------------------
+// The source coordinate of output index o is the fp32 product r * o, ROUNDED: the integer part and the fraction are both taken from
+// that one value, in all four kernels.  Contraction is switched off for it: left to the compiler, "s - i0" became fma(r, o, -i0) on
+// the unrounded product while (int)s used the rounded one (a fraction just below 0 beside an integer part already stepped up), each
+// kernel with its own choice, so the backward weights were not the forward's and the result was up to u * s (s the coordinate:
+// thousands of u on a wide map) away from the operation as stated (tests/test_upsample_kernels.py, tests/test_upsample_window_cpu.py).
+__device__ __forceinline__ float upsample_coord(float r, int o) {
+#pragma clang fp contract(off)
+    const float s = r * (float)o;
+    return s;
+}
+
 __global__ void upsample_fwd_kernel(const float* __restrict__ src, float* __restrict__ dst, int B, int hi, int wi, int ho, int wo,
                                     int C) {
     const float ry = ho > 1 ? (float)(hi - 1) / (float)(ho - 1) : 0.f;
@@ -401,7 +412,7 @@ __global__ void upsample_fwd_kernel(const float* __restrict__ src, float* __rest
         r /= wo;
         const int oy = r % ho;
         const int b = r / ho;
-        const float sy = ry * oy, sx = rx * ox;
+        const float sy = upsample_coord(ry, oy), sx = upsample_coord(rx, ox);
         int y0 = (int)sy, x0 = (int)sx;
         y0 = min(y0, hi - 1);
         x0 = min(x0, wi - 1);
@@ -439,7 +450,7 @@ __global__ void upsample_bwd_kernel(const float* __restrict__ dout, float* __res
         }
         float acc = 0.f;
         for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-            const float sy = ry * oy;
+            const float sy = upsample_coord(ry, oy);
             int y0 = min((int)sy, hi - 1);
             const int y1 = min(y0 + 1, hi - 1);
             const float fy = sy - y0;
@@ -448,7 +459,7 @@ __global__ void upsample_bwd_kernel(const float* __restrict__ dout, float* __res
             if (y1 == iy) wy += fy;
             if (wy == 0.f) continue;
             for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-                const float sx = rx * ox;
+                const float sx = upsample_coord(rx, ox);
                 int x0 = min((int)sx, wi - 1);
                 const int x1 = min(x0 + 1, wi - 1);
                 const float fx = sx - x0;
@@ -479,14 +490,15 @@ __global__ __launch_bounds__(256) void upsample_fwd4_kernel(const float* __restr
         r /= (unsigned)wo;
         const int oy = r % (unsigned)ho;
         const int b = r / (unsigned)ho;
-        const float sy = ry * oy, sx = rx * ox;
+        const float sy = upsample_coord(ry, oy), sx = upsample_coord(rx, ox);
         const int y0 = min((int)sy, hi - 1), x0 = min((int)sx, wi - 1);
         const int y1 = min(y0 + 1, hi - 1), x1 = min(x0 + 1, wi - 1);
         const float fy = sy - y0, fx = sx - x0;
         const float4* sb = reinterpret_cast<const float4*>(src) + (size_t)b * hi * wi * C4 + c4;
         const float4 v00 = sb[(size_t)(y0 * wi + x0) * C4], v01 = sb[(size_t)(y0 * wi + x1) * C4];
         const float4 v10 = sb[(size_t)(y1 * wi + x0) * C4], v11 = sb[(size_t)(y1 * wi + x1) * C4];
-        // (same expression, evaluated per component in the same order as the scalar kernel: bit-identical results)
+        // (the scalar kernel's expression per component.  NOT bit-identical to it: the compiler contracts the two kernels' products and
+        // sums into different fma chains, one or two ulp apart on a device; both are held to the same fp64 bound)
         float4 o;
         o.x = (1.f - fy) * ((1.f - fx) * v00.x + fx * v01.x) + fy * ((1.f - fx) * v10.x + fx * v11.x);
         o.y = (1.f - fy) * ((1.f - fx) * v00.y + fx * v01.y) + fy * ((1.f - fx) * v10.y + fx * v11.y);
@@ -498,7 +510,7 @@ __global__ __launch_bounds__(256) void upsample_fwd4_kernel(const float* __restr
 
 // hat weight of output coordinate o (source coordinate r * o) on input index idx, as the forward kernel rounds it
 __device__ __forceinline__ float upsample_hat(float r, int o, int idx, int n_in) {
-    const float sv = r * o;
+    const float sv = upsample_coord(r, o);
     const int i0 = min((int)sv, n_in - 1), i1 = min(i0 + 1, n_in - 1);
     const float f = sv - i0;
     return (i0 == idx ? 1.f - f : 0.f) + (i1 == idx ? f : 0.f);

@@ -2,7 +2,9 @@
 
   tmg_layer_unplanes: [K][npix][2] -> [npix][CP], the exact inverse of tmg_layer_planes on its first K planes, channels from 2K on
   zero - on pixel counts that are not a multiple of the kernel's 64-pixel block: (npix, CP) = (1, 4), (65, 32), (130, 8), with K = CP / 2
-  and with padding planes (K < CP / 2).  Pure data movement: bit for bit.
+  and with padding planes (K < CP / 2).  From CP = 256 on the 64 staging rows of CP + 2 words exceed 64 KB (66 048 bytes) and the
+  launcher takes the LDS opt-in: (65, 256, 128), (130, 256, 100), (65, 512, 256) (131 584 bytes) and (1, 512, 3); the forward
+  tmg_layer_planes runs at these CP in thin_cases.PLANES_CASES.  Pure data movement: bit for bit.
   The level node (LevelCouplingFn through LSTMFLowBlock, C = 16, 2 x 20 x 24, both directions in one backward) with
   TMG_LAYER_PLANES_MIN=1 (planes: dense2_bwd writes plane k, the thin grouped weight gradient reads one plane per group, one
   re-interleaving launch in front of the conditioning side) against the default (960 pixels: the interleaved stash).  The stash
@@ -20,9 +22,11 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
-@pytest.mark.parametrize("shape,CP,K", [((1, 1, 1), 4, 2), ((1, 5, 13), 32, 16), ((2, 5, 13), 8, 4), ((1, 5, 13), 32, 15), ((2, 5, 13), 8, 1)])
+@pytest.mark.parametrize("shape,CP,K", [((1, 1, 1), 4, 2), ((1, 5, 13), 32, 16), ((2, 5, 13), 8, 4), ((1, 5, 13), 32, 15), ((2, 5, 13), 8, 1),
+                                        ((1, 5, 13), 256, 128), ((2, 5, 13), 256, 100), ((1, 5, 13), 512, 256), ((1, 1, 1), 512, 3)])
 def test_layer_unplanes_inverts_layer_planes(shape, CP, K):
     import tmg_hip as H
+    assert (64 * (CP + 2) * 4 > 64 * 1024) == (CP >= 256)      # the launcher's staging rows: 66 048 bytes at CP = 256, 131 584 at 512
     g = torch.Generator().manual_seed(CP + K)
     src = torch.randn(*shape, CP, generator=g).to(DEV)
     planes = H.layer_planes(src)

@@ -853,28 +853,41 @@ def test_hip_adam_matches_torch_adam(amsgrad, wd):
     ob.load_state_dict(oa.state_dict())     # same schema
 
 
-@pytest.mark.parametrize("NL,C_,Cc,with_x", [(3, 16, 8, True), (15, 32, 32, True), (2, 128, 32, False), (1, 12, 4, True)])
+@pytest.mark.parametrize("NL,C_,Cc,with_x", [(3, 16, 8, True), (15, 32, 32, True), (2, 128, 32, False), (1, 12, 4, True),
+                                             (3, 16, 8, "compact"), (2, 128, 162, "compact"), (2, 6, 4, "compact"), (3, 16, 8, "x_only")])
 def test_level_finish_kernel(NL, C_, Cc, with_x):
     """tmg_level_finish (parameter-gradient epilogue of a level's fused coupling node, one launch) against the torch formulation
     it replaces: d(kappa) = (<Wz, dWz> + <bz, dBz>) inside the clamp range in fp64, and the scatter-add of the grouped
-    weight-gradient rows into dW1 / dW2."""
+    weight-gradient rows into dW1 / dW2.
+    with_x: True / False = tmpX given / None with the grouped launches' 4-row tmpC; "compact" = tmpX given and tmpC
+    [NLp, 2, Cc, 3, 3] with NLp > NL, the layout LevelCouplingFn._cond_bwd produces (the wrapper passes tmpC.shape[1] as the row
+    count); "x_only" = tmpX given, tmpC None.  C = 128, ch = 64, Cc = 162: nz / 4 = 65 664 float4, S computes to 33 and is capped at
+    32, every block loops.  C = 6, ch = 3, Cc = 4: nz = 486 is no multiple of 4, the scalar inner product from the shape itself."""
     import tmg_hip as H
     g = torch.Generator().manual_seed(5 + NL)
     ch = C_ // 2
     cin = ch + Cc
+    nz = C_ * (cin + 2) * 9
+    s_raw = (nz // 4 + 256 * 8 - 1) // (256 * 8)          # the launcher's block count per layer, capped at 32
+    S = min(32, max(1, s_raw))
+    if (C_, Cc) == (128, 162):
+        assert nz // 4 == 65664 and s_raw == 33 and S == 32 and nz // 4 > S * 256
+    if (C_, Cc) == (6, 4):
+        assert nz == 486 and nz % 4 != 0 and S == 1
     rnd = lambda *s_: torch.randn(s_, generator=g).to(DEV)  # noqa: E731
     Wz, dWz, Bz, dBz = rnd(NL, C_, cin + 2, 3, 3), rnd(NL, C_, cin + 2, 3, 3), rnd(NL, C_), rnd(NL, C_)
     Kp = torch.tensor([(-4.5, -4.0, 0.3, 1.38, 1.3862944, 1.5)[k % 6] for k in range(NL)], device=DEV)
     tmpX = rnd(NL, 4, ch + 4, 3, 3) if with_x else None
-    tmpC = rnd(NL, 4, Cc, 3, 3)
+    tmpC = None if with_x == "x_only" else (rnd(NL + 2, 2, Cc, 3, 3) if with_x == "compact" else rnd(NL, 4, Cc, 3, 3))
     dW1, dW2 = rnd(NL, 1, cin, 3, 3), rnd(NL, 1, cin + 1, 3, 3)
     r1, r2 = dW1.clone(), dW2.clone()
     if with_x:
         r1[:, 0, :ch] += tmpX[:, 0, :ch]
         r2[:, 0, :ch] += tmpX[:, 1, :ch]
         r2[:, 0, cin] += tmpX[:, 1, ch]
-    r1[:, 0, ch:cin] += tmpC[:, 0]
-    r2[:, 0, ch:cin] += tmpC[:, 1]
+    if tmpC is not None:
+        r1[:, 0, ch:cin] += tmpC[:NL, 0]
+        r2[:, 0, ch:cin] += tmpC[:NL, 1]
     rK = ((Wz.double() * dWz.double()).flatten(1).sum(1) + (Bz.double() * dBz.double()).sum(1)).float() \
         * ((Kp >= -4.0) & (Kp <= math.log(4.0))).to(torch.float32)
     dK = torch.full((NL,), 7.0, device=DEV)
