@@ -20,7 +20,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmglow_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip", "tmg_phase.hip", "tmg_spod.hip"]
+SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip", "tmg_phase.hip", "tmg_spod.hip", "tmg_budget.hip"]
 # Sources compiled WITHOUT the packed-fp32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32): beside MFMAs a packed
 # f32 instruction costs ~13 cycles more than the two scalar ones it replaces (MI355X_MICROARCH.md, cycle constants, 'price of one
 # filler beside MFMAs'), and the compiler SLP-packs adjacent scalar adds / multiplies by itself under -O3.  The matrix-core kernels'
@@ -82,6 +82,9 @@ PHASE_EXPORTS = ["tmg_ens_phase_plan", "tmg_ens_phase_label", "tmg_ens_phase_acc
 SPOD_EXPORTS = ["tmg_ens_spod_plan", "tmg_ens_spod_csd", "tmg_ens_spod_modes"]
 # The layout conversions of the level node's backward pass (csrc/tmg_thin.hip), declared in include/tmglow_hip_layout.h: layer_unplanes below.
 LAYOUT_EXPORTS = ["tmg_layer_unplanes"]
+# The budget of the turbulent kinetic energy (csrc/tmg_budget.hip), declared in include/tmglow_hip_budget.h, a header of its own:
+# ens_budget_plan / ens_budget_accum / ens_budget_terms below.
+BUDGET_EXPORTS = ["tmg_ens_budget_plan", "tmg_ens_budget_accum", "tmg_ens_budget_terms"]
 # Every export returns int except the workspace sizes, which the header declares int64_t (read through a 32-bit return a request of
 # 2^31 floats or more would be truncated and the kernel handed a buffer smaller than it planned for).
 RET_I64 = ("tmg_conv_wgrad_ws_floats", "tmg_conv_wgrad_grouped_ws_floats", "tmg_conv_wino_wgrad_ws_floats",
@@ -97,7 +100,8 @@ def build(force=False, verbose=False):
                os.path.join(inc, "tmglow_hip_tspec.h"), os.path.join(inc, "tmglow_hip_quant.h"),
                os.path.join(inc, "tmglow_hip_gram.h"), os.path.join(inc, "tmglow_hip_sfun.h"),
                os.path.join(inc, "tmglow_hip_event.h"), os.path.join(inc, "tmglow_hip_pdf.h"), os.path.join(inc, "tmglow_hip_pod.h"),
-               os.path.join(inc, "tmglow_hip_phase.h"), os.path.join(inc, "tmglow_hip_spod.h"), os.path.join(inc, "tmglow_hip_layout.h")]
+               os.path.join(inc, "tmglow_hip_phase.h"), os.path.join(inc, "tmglow_hip_spod.h"), os.path.join(inc, "tmglow_hip_layout.h"),
+               os.path.join(inc, "tmglow_hip_budget.h")]
     hmt = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -151,7 +155,7 @@ def lib():
         for name in PLAN_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
             getattr(_lib, name).argtypes = PLAN_ARGTYPES[name]
-        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS + SFUN_EXPORTS + EVENT_EXPORTS + PDF_EXPORTS + POD_EXPORTS + PHASE_EXPORTS + SPOD_EXPORTS + LAYOUT_EXPORTS:
+        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS + SFUN_EXPORTS + EVENT_EXPORTS + PDF_EXPORTS + POD_EXPORTS + PHASE_EXPORTS + SPOD_EXPORTS + LAYOUT_EXPORTS + BUDGET_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
     return _lib
 
@@ -1452,6 +1456,59 @@ def ens_phase_accum(y, lab, lstrides, a, m, acc, k):
     _phase_span(lab, lstrides, k, B, 0, "ens_phase_accum: lab")
     _chk(lib().tmg_ens_phase_accum(c_vp(ptr), _i64(ps, co), _ptr(lab), _i64(*lstrides), _ptr(a), _ptr(m), _ptr(acc),
                                    _i64(k, B, HW, Cc, NB), _stream()), "tmg_ens_phase_accum")
+
+
+def ens_budget_plan(S, B, Hh, Ww):
+    """The launch plan of ens_budget_accum for S members of B cases of [3, H, W] (tmg_ens_budget_plan; nothing is launched) -> dict:
+    tile pixels per block, tiles blocks per field (the grid is tiles x B), vec: True when the planes of the state are read and written
+    with 16-byte accesses (W % 4 == 0 and an aligned state), ws = 0 workspace floats."""
+    plan = (c_i64 * 4)()
+    _chk(lib().tmg_ens_budget_plan(_i64(S, B, Hh, Ww), plan), "tmg_ens_budget_plan")
+    tile, tiles, vec, ws = [int(v) for v in plan]
+    return {"tile": tile, "tiles": tiles, "grid": (tiles, int(B)), "vec": bool(vec), "ws": ws}
+
+
+def ens_budget_accum(y, a, m, raw, k, row0, t_before):
+    """Add one chunk of k rows (y: NHWC [k*B, H, W, 3] or a channel-slice view, rows member-major) to the planes of the rows row0 ..
+    row0 + k - 1 of the state raw [S + 1, B, 14, HW] (the target: k = 1, row0 = S), about the mean planes m [B, 3, HW] (None: 0) with
+    the scales a [B, 3] (device fp32); t_before == 0 stores instead of adding (tmg_ens_budget_accum)."""
+    kB, Hh, Ww, Cc = y.shape
+    ptr, ps, co, _ = seg(y)
+    check_device(y)
+    check_act(raw)
+    check_device(raw)
+    check_act(a)
+    R, B, Q, HW = raw.shape
+    if Cc != 3 or Q != 14 or HW != Hh * Ww or kB != k * B or tuple(a.shape) != (B, 3) or (m is not None and tuple(m.shape) != (B, 3, HW)):
+        raise RuntimeError("ens_budget_accum: raw %s, m %s, a %s do not fit %d rows of %s" % (
+            tuple(raw.shape), None if m is None else tuple(m.shape), tuple(a.shape), k, tuple(y.shape)))
+    if not (raw.is_contiguous() and a.is_contiguous() and (m is None or (m.is_contiguous() and m.is_cuda and m.dtype == torch.float32))):
+        raise RuntimeError("ens_budget_accum: contiguous fp32 device tables")
+    _chk(lib().tmg_ens_budget_accum(c_vp(ptr), _i64(ps, co), _ptr(a), _ptr(m), _ptr(raw), _i64(k, R - 1, B, Hh, Ww, row0, t_before),
+                                    _stream()), "tmg_ens_budget_accum")
+
+
+def ens_budget_terms(raw, M, fl, outs, member_budget, Hh, Ww, T):
+    """The seven budget terms and the stresses of every row of the state raw [S + 1, B, 14, HW] after T timed steps: outs =
+    (budget_mean, budget_std, target_budget [B, 7, HW], stress_mean, stress_std, target_stress [B, 3, HW]) fp32, member_budget
+    [B, S, 7, HW] or None; M [B, 2, HW] fp64 the physical mean velocity, fl = (dx, dy, nu, rho) (tmg_ens_budget_terms)."""
+    check_act(raw)
+    check_device(raw)
+    R, B, Q, HW = raw.shape
+    if Q != 14 or HW != Hh * Ww or not raw.is_contiguous() or tuple(M.shape) != (B, 2, HW) or M.dtype != torch.float64 or \
+            not (M.is_cuda and M.is_contiguous()) or len(fl) != 4 or len(outs) != 6:
+        raise RuntimeError("ens_budget_terms: raw is [S + 1, B, 14, HW] fp32 and M [B, 2, HW] fp64 on the device, got %s and %s"
+                           % (tuple(raw.shape), tuple(M.shape)))
+    for t, n in zip(outs, (7, 7, 7, 3, 3, 3)):
+        check_act(t)
+        if tuple(t.shape) != (B, n, HW) or not t.is_contiguous():
+            raise RuntimeError("ens_budget_terms: an output is %s, not a contiguous %s" % (tuple(t.shape), (B, n, HW)))
+    if member_budget is not None:
+        check_act(member_budget)
+        if tuple(member_budget.shape) != (B, R - 1, 7, HW) or not member_budget.is_contiguous():
+            raise RuntimeError("ens_budget_terms: member_budget is %s, not a contiguous %s" % (tuple(member_budget.shape), (B, R - 1, 7, HW)))
+    _chk(lib().tmg_ens_budget_terms(_ptr(raw), _ptr(M), (ctypes.c_double * 4)(*[float(v) for v in fl]), *[_ptr(t) for t in outs],
+                                    _ptr(member_budget), _i64(R - 1, B, Hh, Ww, T), _stream()), "tmg_ens_budget_terms")
 
 
 def ens_spod_plan(S, B, Cg, HW, NB, acc=None):

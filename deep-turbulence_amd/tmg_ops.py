@@ -2952,6 +2952,122 @@ class EnsemblePhase(EnsembleFeed):
         return o
 
 
+BUDGET_TERMS = ("conv", "prod", "turb", "pres", "visc", "diss", "resid")
+BUDGET_PLANES = 14
+
+
+def budget_args(C, Hh, Ww, grid, nu, rho):
+    """The checks of the budget arguments: C == 3 (the pressure is needed), H, W >= 3 (the stencils need neighbours), grid two
+    positive finite sizes, nu >= 0 and rho > 0, both finite -> (dx, dy, nu, rho) as floats."""
+    real = lambda v: not isinstance(v, bool) and isinstance(v, numbers.Real) and math.isfinite(float(v))   # noqa: E731
+    if int(C) != 3:
+        raise ValueError("the TKE budget needs C == 3 channels (ux, uy, p: the pressure diffusion reads p), got %d" % int(C))
+    if int(Hh) < 3 or int(Ww) < 3:
+        raise ValueError("the TKE budget needs H, W >= 3 (the stencils have no neighbours otherwise), got %d x %d" % (int(Hh), int(Ww)))
+    try:
+        g = tuple(grid)
+    except TypeError:
+        raise ValueError("grid must hold (dx, dy), got %r" % (grid,))
+    if len(g) != 2 or not all(real(v) and float(v) > 0 for v in g):
+        raise ValueError("grid must hold two positive finite sizes (dx, dy), got %r" % (grid,))
+    if not real(nu) or float(nu) < 0:
+        raise ValueError("nu must be finite and >= 0, got %r" % (nu,))
+    if not real(rho) or float(rho) <= 0:
+        raise ValueError("rho must be finite and > 0, got %r" % (rho,))
+    return float(g[0]), float(g[1]), float(nu), float(rho)
+
+
+class EnsembleBudget(EnsembleFeed):
+    """On-device budget of the turbulent kinetic energy k = 1/2 <u'_i u'_i> of sampled roll-outs of B cases, and of the target
+    (tmg_ens_budget_accum / tmg_ens_budget_terms): is the kinetic energy of the fluctuations produced, transported and dissipated
+    where the reference simulation produces, transports and dissipates it?
+
+    Rows are the S members plus the target as row S.  A row's fluctuation about the TARGET's time mean is d_c = fl(a_c fl(y_c - m_c)),
+    c = (ux, uy, p), a = u * out_std (formed in fp64, rounded once), m = `mean` [B, 3, H, W] in normalised units (None: 0).  Every
+    timed step adds 14 fp32 quantities per row and pixel to the state `raw` [S + 1, B, 14, HW]: d_u, d_v, d_p; d_u^2, d_u d_v, d_v^2;
+    d_u^3, d_u^2 d_v, d_u d_v^2, d_v^3; d_p d_u, d_p d_v; (Sx d_u)^2 + (Sx d_v)^2; (Sy d_u)^2 + (Sy d_v)^2, with the un-scaled 3x3
+    first-derivative stencils of pc/ (zero outside the field): Sx f = (f[h-1,w+1] - f[h-1,w-1]) + 2 (f[h,w+1] - f[h,w-1]) +
+    (f[h+1,w+1] - f[h+1,w-1]), Sy with h and w exchanged, d/dx = Sx / (8 dx), d/dy = Sy / (8 dy).  An element of raw is touched by one
+    thread once per step: the state is bitwise reproducible, independent of the chunking, and needs no memset (the first timed step
+    stores).  It takes 14 * 4 bytes per element of [S + 1, B, HW].
+
+    finalize() forms, in fp64 on the device, each row's central moments about its OWN mean from raw by the shift formulas (T timed
+    steps, D_c = raw_c / T: uu = raw_3 / T - D_u^2, .., gx = raw_12 / T - (Sx D_u)^2 - (Sx D_v)^2), k = (uu + vv) / 2, the absolute
+    mean velocity U = M_u + D_u, V = M_v + D_v (M = a m + u out_mu, the target's physical mean, in fp64 from the fp32 tables) and
+    the seven terms of budget_terms, signed as they enter dk/dt:
+      conv  = -(U dk/dx + V dk/dy)                       prod = -(uu dU/dx + uv (dU/dy + dV/dx) + vv dV/dy)
+      turb  = -1/2 (d(uuu + uvv)/dx + d(uuv + vvv)/dy)   pres = -(1 / rho) (d pu/dx + d pv/dy)
+      visc  = nu ((k[h,w+1] - 2 k + k[h,w-1]) / dx^2 + (k[h+1,w] - 2 k + k[h-1,w]) / dy^2)
+      diss  = -nu (gx / (64 dx^2) + gy / (64 dy^2))     a sink
+      resid = the sum of the six: what a resolved two-dimensional budget over a finite window does not close (-dk/dt of the window,
+              sub-grid dissipation, out-of-plane terms); it is a term of the budget, not an error.
+    Every term is NaN on the one-pixel frame of the field, where the stencils have no neighbours.
+
+    Feeding protocol of EnsembleFeed, with the step's target on every chunk; a step fed with time=False launches nothing.
+    finalize() -> dict:
+      budget_mean, budget_std [B, 7, H, W]     Welford mean / population std (ddof 0) over the members, in member order
+      target_budget [B, 7, H, W]               the target's terms
+      stress_mean, stress_std, target_stress [B, 3, H, W]    the same of (uu, uv, vv), on the whole field
+      member_budget [B, S, 7, H, W]            every member's terms (per_member=True only)
+      budget_terms                             the names of the seven terms."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, grid=(1.0, 1.0), nu=0.0, rho=1.0, mean=None,
+                 per_member=False):
+        noun, why = "ensemble TKE budgets", "the fluctuations scale with u * out_std"
+        _ens_members(noun, members)
+        self.fl = budget_args(C, Hh, Ww, grid, nu, rho)
+        sd, mu = _ens_tables(3, why, out_std, out_mu)
+        u = _ens_u(u, B, 3, why)
+        if int(steps) < 1 or int(B) < 1:
+            raise ValueError("%s need steps, B >= 1, got %d, %d" % (noun, steps, B))
+        if mean is not None:
+            mean = torch.as_tensor(mean).detach()
+            if tuple(mean.shape) != (int(B), 3, int(Hh), int(Ww)) or not bool(torch.isfinite(mean).all()):
+                raise ValueError("mean is a finite array [%d, 3, %d, %d], got shape %s" % (B, Hh, Ww, tuple(mean.shape)))
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, 3, Hh, Ww, steps)
+        HW = self.H * self.W
+        self.per_member = bool(per_member)
+        self.a = _ens_scale(sd, u, self.B, torch.float64).to(torch.float32).to(dev).contiguous()
+        self.m = None if mean is None else mean.to(torch.float32).reshape(self.B, 3, HW).to(dev).contiguous()
+        # M = a m + u out_mu in fp64 from the fp32 tables (channels 0, 1)
+        a64 = self.a.double().cpu()
+        M = (_ens_scale(torch.ones(3), u, self.B, torch.float64) * mu.double().view(1, 3)).view(self.B, 3, 1).expand(self.B, 3, HW)
+        if self.m is not None:
+            M = M + a64.view(self.B, 3, 1) * self.m.double().cpu()
+        self.M = M[:, :2].contiguous().to(dev)
+        self.plan = H.ens_budget_plan(self.S, self.B, self.H, self.W)
+        self.raw = torch.empty((self.S + 1, self.B, BUDGET_PLANES, HW), device=dev, dtype=torch.float32)
+
+    def add(self, y, m0, target, time=True):
+        """Add the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, 3, H, W], any strides whose channels-last view is an NHWC
+        channel-slice; rows member-major); target: the step's normalised target [B, 3, H, W] under the same stride rule, added as
+        row S with the step's last chunk.  A step fed with time=False launches nothing."""
+        yn, tn, k, t_before, last = self.open_chunk(y, m0, time, target, required=True)
+        _on_device(yn, tn)
+        if time:
+            H.ens_budget_accum(yn, self.a, self.m, self.raw, k, m0, t_before)
+            if last:
+                H.ens_budget_accum(tn, self.a, self.m, self.raw, 1, self.S, t_before)
+        self.close_chunk(m0, k, time, last)
+
+    def finalize(self):
+        """-> dict of the outputs over the steps folded with time=True."""
+        T = self.finalize_guard()
+        B, S, Hh, Ww = self.B, self.S, self.H, self.W
+        HW, dev = Hh * Ww, self.raw.device
+        outs = [torch.empty((B, n, HW), device=dev, dtype=torch.float32) for n in (7, 7, 7, 3, 3, 3)]
+        mb = torch.empty((B, S, 7, HW), device=dev, dtype=torch.float32) if self.per_member else None
+        H.ens_budget_terms(self.raw, self.M, self.fl, outs, mb, Hh, Ww, T)
+        o = {}
+        for key, t in zip(("budget_mean", "budget_std", "target_budget", "stress_mean", "stress_std", "target_stress"), outs):
+            o[key] = t.view(B, t.shape[1], Hh, Ww)
+        if mb is not None:
+            o["member_budget"] = mb.view(B, S, 7, Hh, Ww)
+        o["budget_terms"] = BUDGET_TERMS
+        return o
+
+
 STRUCTURE_MAX_LAGS = 16
 STRUCTURE_MAX_LAG = 64
 

@@ -693,6 +693,60 @@ def modelPredPhase(args, model, testing_loader, log, samples=1, stride=1, tmax=1
     return _ensembleStats("modelPredPhase", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
 
 
+def _budget_factory(stride, t_start, grid, nu, rho, per_member):
+    """The make of modelPredBudget's record: the target's time mean over the kept steps from t_start on, back in normalised units
+    (fp64, as _phase_factory forms it), and the tmg_ops.EnsembleBudget about it."""
+    def make(mb, members, steps):
+        import tmg_ops as ops
+        B, C = mb.B, mb.C
+        tk = mb.tgt[:, t_start * stride:(steps - 1) * stride + 1:stride].double()
+        u, sd, mu = mb.u.double(), mb.out_std.double()[:C], mb.out_mu.double()[:C]
+        xn = (tk / u.view(B, 1, C, 1, 1) - mu.view(1, 1, C, 1, 1)) / sd.view(1, 1, C, 1, 1)
+        return ops.EnsembleBudget(members, B, C, mb.H, mb.W, steps, mb.dev, mb.out_mu, mb.out_std, u=mb.u, grid=grid, nu=nu, rho=rho,
+                                  mean=xn.mean(1), per_member=per_member)
+    return make
+
+
+def modelPredBudget(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, nu=None, rho=1.0,
+                    per_member=False):
+    """modelPredStats plus the budget of the turbulent kinetic energy k = 1/2 <u'_i u'_i> of every member and of the target, still
+    without forming modelPred's [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleBudget): are the members' Reynolds stresses right for
+    the right reason, is the energy of the fluctuations produced, transported and dissipated where the reference simulation does
+    it?  Same roll-outs as modelPredStats: under the same host RNG state the keys both return are identical.  nu=None reads args.nu;
+    the grid is (args.dx along W, args.dy along H).  The target of kept step j is series step j * stride.
+
+    Rows are the S members and the target.  Every timed step (kept steps t_start..Tk-1) adds, per row and pixel, 14 fp32 sums of the
+    row's fluctuation d = (u0, u0, u0^2) out_std (y - m) about the TARGET's time mean m: d, the second and third velocity moments,
+    the pressure-velocity products and the squared outputs of the un-scaled 3x3 first-derivative stencils of pc/ (zero padding):
+    Sx f = (f[h-1,w+1] - f[h-1,w-1]) + 2 (f[h,w+1] - f[h,w-1]) + (f[h+1,w+1] - f[h+1,w-1]), Sy with h and w exchanged, d/dx =
+    Sx / (8 dx), d/dy = Sy / (8 dy).  The state takes 14 * 4 bytes per element of [S + 1, N, HW]; it is bitwise reproducible and
+    independent of max_rows.  From it, in fp64 on the device, the central moments of each row about its OWN time mean (uu, uv, vv,
+    uuu, uuv, uvv, vvv, pu, pv, the gradient variances gx, gy), k = (uu + vv) / 2, the row's mean velocity (U, V) and the terms, signed
+    as they enter dk/dt:
+      conv  = -(U dk/dx + V dk/dy)                       convection by the mean flow
+      prod  = -(uu dU/dx + uv (dU/dy + dV/dx) + vv dV/dy)  production
+      turb  = -1/2 (d(uuu + uvv)/dx + d(uuv + vvv)/dy)   turbulent transport
+      pres  = -(1 / rho) (d pu/dx + d pv/dy)             pressure diffusion
+      visc  = nu (second differences of k / dx^2, dy^2)  viscous diffusion
+      diss  = -nu (gx / (64 dx^2) + gy / (64 dy^2))      dissipation, a sink
+      resid = the sum of the six: what a resolved two-dimensional budget over a finite window cannot close (-dk/dt of the window,
+              sub-grid dissipation, out-of-plane terms).  It is a term of the budget, not an error.
+    Every term is NaN on the one-pixel frame of the field, where the stencils have no neighbours.
+
+    Returns modelPredStats' dict plus (CPU tensors):
+      budget_mean, budget_std [N, 7, H, W]               mean / population std (ddof 0) over the members of each member's terms
+      target_budget [N, 7, H, W]                         the target's terms through the same kernels
+      stress_mean, stress_std, target_stress [N, 3, H, W]   the same of (uu, uv, vv), defined on the whole field
+      member_budget [N, S, 7, H, W]                      every member's terms (per_member=True only)
+      budget_terms                                       ("conv", "prod", "turb", "pres", "visc", "diss", "resid").
+    Not supported: pixel boxes and region integrals, the 5x5 stencils, a budget of the individual Reynolds stresses, the
+    phase-conditioned budget, non-finite members."""
+    import tmg_ops as ops
+    fl = ops.budget_args(3, 3, 3, (args.dx, args.dy), args.nu if nu is None else nu, rho)
+    acc = _Acc(_budget_factory(stride, t_start, fl[:2], fl[2], fl[3], bool(per_member)), target=True, meta=("budget_terms",))
+    return _ensembleStats("modelPredBudget", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
+
+
 def modelPredSpod(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, bins=None, modes=4, channels=(0, 1),
                   window="hann", loo=True, dt=None):
     """modelPredStats plus the spectral POD (SPOD; Towne, Schmidt & Colonius 2018) of the members over the kept steps t_start..Tk-1
