@@ -20,7 +20,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmglow_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip", "tmg_phase.hip", "tmg_spod.hip", "tmg_budget.hip"]
+SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip", "tmg_phase.hip", "tmg_spod.hip", "tmg_budget.hip", "tmg_corr.hip"]
 # Sources compiled WITHOUT the packed-fp32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32): beside MFMAs a packed
 # f32 instruction costs ~13 cycles more than the two scalar ones it replaces (MI355X_MICROARCH.md, cycle constants, 'price of one
 # filler beside MFMAs'), and the compiler SLP-packs adjacent scalar adds / multiplies by itself under -O3.  The matrix-core kernels'
@@ -85,6 +85,9 @@ LAYOUT_EXPORTS = ["tmg_layer_unplanes"]
 # The budget of the turbulent kinetic energy (csrc/tmg_budget.hip), declared in include/tmglow_hip_budget.h, a header of its own:
 # ens_budget_plan / ens_budget_accum / ens_budget_terms below.
 BUDGET_EXPORTS = ["tmg_ens_budget_plan", "tmg_ens_budget_accum", "tmg_ens_budget_terms"]
+# The two-point space-time correlations about probe points (csrc/tmg_corr.hip), declared in include/tmglow_hip_corr.h, a header of its
+# own: ens_corr_plan / ens_corr_probe / ens_corr_accum / ens_corr_finalize below.
+CORR_EXPORTS = ["tmg_ens_corr_plan", "tmg_ens_corr_probe", "tmg_ens_corr_accum", "tmg_ens_corr_finalize"]
 # Every export returns int except the workspace sizes, which the header declares int64_t (read through a 32-bit return a request of
 # 2^31 floats or more would be truncated and the kernel handed a buffer smaller than it planned for).
 RET_I64 = ("tmg_conv_wgrad_ws_floats", "tmg_conv_wgrad_grouped_ws_floats", "tmg_conv_wino_wgrad_ws_floats",
@@ -101,7 +104,7 @@ def build(force=False, verbose=False):
                os.path.join(inc, "tmglow_hip_gram.h"), os.path.join(inc, "tmglow_hip_sfun.h"),
                os.path.join(inc, "tmglow_hip_event.h"), os.path.join(inc, "tmglow_hip_pdf.h"), os.path.join(inc, "tmglow_hip_pod.h"),
                os.path.join(inc, "tmglow_hip_phase.h"), os.path.join(inc, "tmglow_hip_spod.h"), os.path.join(inc, "tmglow_hip_layout.h"),
-               os.path.join(inc, "tmglow_hip_budget.h")]
+               os.path.join(inc, "tmglow_hip_budget.h"), os.path.join(inc, "tmglow_hip_corr.h")]
     hmt = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -155,7 +158,7 @@ def lib():
         for name in PLAN_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
             getattr(_lib, name).argtypes = PLAN_ARGTYPES[name]
-        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS + SFUN_EXPORTS + EVENT_EXPORTS + PDF_EXPORTS + POD_EXPORTS + PHASE_EXPORTS + SPOD_EXPORTS + LAYOUT_EXPORTS + BUDGET_EXPORTS:
+        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS + SFUN_EXPORTS + EVENT_EXPORTS + PDF_EXPORTS + POD_EXPORTS + PHASE_EXPORTS + SPOD_EXPORTS + LAYOUT_EXPORTS + BUDGET_EXPORTS + CORR_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
     return _lib
 
@@ -1509,6 +1512,98 @@ def ens_budget_terms(raw, M, fl, outs, member_budget, Hh, Ww, T):
             raise RuntimeError("ens_budget_terms: member_budget is %s, not a contiguous %s" % (tuple(member_budget.shape), (B, R - 1, 7, HW)))
     _chk(lib().tmg_ens_budget_terms(_ptr(raw), _ptr(M), (ctypes.c_double * 4)(*[float(v) for v in fl]), *[_ptr(t) for t in outs],
                                     _ptr(member_budget), _i64(R - 1, B, Hh, Ww, T), _stream()), "tmg_ens_budget_terms")
+
+
+def ens_corr_cfg(probes, pairs, lags):
+    """The host integers the three correlation launches share: {P, Q, L, (h, w) of every probe, (ci, cj) of every pair, the lags}."""
+    flat = [len(probes), len(pairs), len(lags)]
+    for hw in probes:
+        flat += [hw[0], hw[1]]
+    for cc in pairs:
+        flat += [cc[0], cc[1]]
+    return _i64(*(flat + list(lags)))
+
+
+def ens_corr_plan(S, B, Hh, Ww, P, Q, L, J):
+    """The launch plan of ens_corr_accum for S members of B cases of [3, H, W], P probes, Q channel pairs, L lags and J distinct field
+    channels (tmg_ens_corr_plan; nothing is launched) -> dict: tile pixels per block, tiles blocks per field (the grid is tiles x B),
+    vec: True when the planes of the state are read and written with 16-byte accesses (W % 4 == 0 and an aligned state), planes =
+    P Q L + 2 J L the planes of one row and case, offX, offF, offG the first plane of each kind, ws = 0 workspace floats."""
+    plan = (c_i64 * 8)()
+    _chk(lib().tmg_ens_corr_plan(_i64(S, B, Hh, Ww, P, Q, L, J), plan), "tmg_ens_corr_plan")
+    tile, tiles, vec, npl, offx, offf, offg, ws = [int(v) for v in plan]
+    return {"tile": tile, "tiles": tiles, "grid": (tiles, int(B)), "vec": bool(vec), "planes": npl, "offX": offx, "offF": offf,
+            "offG": offg, "ws": ws}
+
+
+def _corr_feed(name, y, a, m, series, k, P):
+    kB, Hh, Ww, Cc = y.shape
+    ptr, ps, co, _ = seg(y)
+    check_device(y)
+    check_act(series)
+    check_device(series)
+    check_act(a)
+    if series.dim() != 5:
+        raise RuntimeError("%s: series is [S + 1, B, steps, P, 3], got %s" % (name, tuple(series.shape)))
+    R, B, steps, Ps, three = series.shape
+    HW = Hh * Ww
+    if Cc != 3 or Ps != P or three != 3 or kB != k * B or tuple(a.shape) != (B, 3) or (m is not None and tuple(m.shape) != (B, 3, HW)):
+        raise RuntimeError("%s: series %s, m %s, a %s do not fit %d rows of %s and %d probes" % (
+            name, tuple(series.shape), None if m is None else tuple(m.shape), tuple(a.shape), k, tuple(y.shape), P))
+    if not (series.is_contiguous() and a.is_contiguous() and (m is None or (m.is_contiguous() and m.is_cuda and m.dtype == torch.float32))):
+        raise RuntimeError("%s: contiguous fp32 device tables" % name)
+    return ptr, ps, co, R, B, Hh, Ww, steps
+
+
+def ens_corr_probe(y, a, m, series, probes, pairs, lags, k, row0, t):
+    """Write the fluctuations of one chunk of k rows (y: NHWC [k*B, H, W, 3] or a channel-slice view, rows member-major) at the probe
+    pixels into series [S + 1, B, steps, P, 3] at the timed step t, rows row0 .. row0 + k - 1 (the target: k = 1, row0 = S), about the
+    mean planes m [B, 3, HW] (None: 0) with the scales a [B, 3] (device fp32) (tmg_ens_corr_probe).  Before ens_corr_accum, on the
+    same stream."""
+    ptr, ps, co, R, B, Hh, Ww, steps = _corr_feed("ens_corr_probe", y, a, m, series, k, len(probes))
+    _chk(lib().tmg_ens_corr_probe(c_vp(ptr), _i64(ps, co), _ptr(a), _ptr(m), _ptr(series), ens_corr_cfg(probes, pairs, lags),
+                                  _i64(k, R - 1, B, Hh, Ww, row0, t, steps), _stream()), "tmg_ens_corr_probe")
+
+
+def ens_corr_accum(y, a, m, series, raw, probes, pairs, lags, k, row0, t):
+    """Add one chunk of k rows (y as in ens_corr_probe, which has written these rows' series at step t) to the live planes of the rows
+    row0 .. row0 + k - 1 of the state raw [S + 1, B, P Q L + 2 |J| L, HW]: the planes of the lags tau_l <= t, stored instead of added
+    at t == tau_l (tmg_ens_corr_accum)."""
+    ptr, ps, co, R, B, Hh, Ww, steps = _corr_feed("ens_corr_accum", y, a, m, series, k, len(probes))
+    check_act(raw)
+    check_device(raw)
+    npl = len(probes) * len(pairs) * len(lags) + 2 * len(set(cc[1] for cc in pairs)) * len(lags)
+    if tuple(raw.shape) != (R, B, npl, Hh * Ww) or not raw.is_contiguous():
+        raise RuntimeError("ens_corr_accum: raw is %s, not a contiguous %s" % (tuple(raw.shape), (R, B, npl, Hh * Ww)))
+    _chk(lib().tmg_ens_corr_accum(c_vp(ptr), _i64(ps, co), _ptr(a), _ptr(m), _ptr(series), _ptr(raw), ens_corr_cfg(probes, pairs, lags),
+                                  _i64(k, R - 1, B, Hh, Ww, row0, t, steps), _stream()), "tmg_ens_corr_accum")
+
+
+def ens_corr_finalize(raw, pm, pv, outs, member_rho, lines, probes, pairs, lags, Hh, Ww, T):
+    """The covariance and the Pearson coefficient of every row of the state raw [S + 1, B, NPL, HW] after T timed steps: outs =
+    (cov_mean, cov_std, rho_mean, rho_std, target_cov, target_rho) [B, P, Q, L, HW] fp32, member_rho [B, S, P, Q, L, HW] or None,
+    lines = (line_x [B, S + 1, P, Q, L, W], line_y [B, S + 1, P, Q, L, H]); pm, pv [S + 1, B, P, Q, L] fp64 on the device, the mean
+    and the population variance of the probe's first n_l values (tmg_ens_corr_finalize)."""
+    check_act(raw)
+    check_device(raw)
+    P, Q, L = len(probes), len(pairs), len(lags)
+    npl = P * Q * L + 2 * len(set(cc[1] for cc in pairs)) * L
+    if raw.dim() != 4 or raw.shape[2] != npl or raw.shape[3] != Hh * Ww or not raw.is_contiguous() or len(outs) != 6 or len(lines) != 2:
+        raise RuntimeError("ens_corr_finalize: raw is [S + 1, B, %d, %d] fp32 on the device, got %s" % (npl, Hh * Ww, tuple(raw.shape)))
+    R, B, _, HW = raw.shape
+    for t in (pm, pv):
+        if tuple(t.shape) != (R, B, P, Q, L) or t.dtype != torch.float64 or not (t.is_cuda and t.is_contiguous()):
+            raise RuntimeError("ens_corr_finalize: pm and pv are [S + 1, B, P, Q, L] fp64 on the device, got %s" % (tuple(t.shape),))
+    want = [(B, P, Q, L, HW)] * 6 + [(B, R, P, Q, L, Ww), (B, R, P, Q, L, Hh)]
+    if member_rho is not None:
+        want.append((B, R - 1, P, Q, L, HW))
+    for t, shp in zip(list(outs) + list(lines) + ([member_rho] if member_rho is not None else []), want):
+        check_act(t)
+        if tuple(t.shape) != shp or not t.is_contiguous():
+            raise RuntimeError("ens_corr_finalize: an output is %s, not a contiguous %s" % (tuple(t.shape), shp))
+    _chk(lib().tmg_ens_corr_finalize(_ptr(raw), _ptr(pm), _ptr(pv), *[_ptr(t) for t in outs], _ptr(member_rho), _ptr(lines[0]),
+                                     _ptr(lines[1]), ens_corr_cfg(probes, pairs, lags), _i64(R - 1, B, Hh, Ww, T), _stream()),
+         "tmg_ens_corr_finalize")
 
 
 def ens_spod_plan(S, B, Cg, HW, NB, acc=None):

@@ -3068,6 +3068,239 @@ class EnsembleBudget(EnsembleFeed):
         return o
 
 
+CORR_MAX_PROBES = 8
+CORR_MAX_PAIRS = 4
+CORR_MAX_LAGS = 8
+CORR_MAX_LAG = 64
+
+
+def corr_args(probes, pairs, lags, C, Hh, Ww):
+    """The checks and the defaults of the two-point correlation arguments: C == 3; probes (None: the three pixels (H // 2, W // 4),
+    (H // 2, W // 2), (H // 2, 3 W // 4)) at most 8 pixels (h, w) inside the field, duplicates allowed; pairs (None: ((0, 0), (1, 1)))
+    at most 4 pairs (ci, cj) of channels in 0..2; lags (None: (0, 1, 2, 4)) at most 8 strictly increasing integers that start at 0
+    and stay <= 64 -> (probes, pairs, lags) as tuples of ints."""
+    whole = lambda v: not isinstance(v, bool) and isinstance(v, numbers.Integral)   # noqa: E731
+    if int(C) != 3:
+        raise ValueError("two-point correlations need C == 3 channels (ux, uy, p), got %d" % int(C))
+    Hh, Ww = int(Hh), int(Ww)
+    if Hh < 1 or Ww < 1:
+        raise ValueError("two-point correlations need H, W >= 1, got %d x %d" % (Hh, Ww))
+    if probes is None:
+        probes = ((Hh // 2, Ww // 4), (Hh // 2, Ww // 2), (Hh // 2, 3 * Ww // 4))
+    if pairs is None:
+        pairs = ((0, 0), (1, 1))
+    if lags is None:
+        lags = (0, 1, 2, 4)
+
+    def table(v, name, width):
+        try:
+            rows = [tuple(r) if width else r for r in v]
+        except TypeError:
+            raise ValueError("%s must be a sequence%s, got %r" % (name, " of pairs of integers" if width else " of integers", v))
+        if width and not all(len(r) == 2 and whole(r[0]) and whole(r[1]) for r in rows):
+            raise ValueError("%s must hold pairs of integers, got %r" % (name, v))
+        if not width and not all(whole(r) for r in rows):
+            raise ValueError("%s must hold integers, got %r" % (name, v))
+        return rows
+
+    probes, pairs, lags = table(probes, "probes", 2), table(pairs, "pairs", 2), table(lags, "lags", 0)
+    if not 1 <= len(probes) <= CORR_MAX_PROBES:
+        raise ValueError("1 to %d probes, got %d" % (CORR_MAX_PROBES, len(probes)))
+    if not 1 <= len(pairs) <= CORR_MAX_PAIRS:
+        raise ValueError("1 to %d channel pairs, got %d" % (CORR_MAX_PAIRS, len(pairs)))
+    if not 1 <= len(lags) <= CORR_MAX_LAGS:
+        raise ValueError("1 to %d lags, got %d" % (CORR_MAX_LAGS, len(lags)))
+    for h, w in probes:
+        if not (0 <= h < Hh and 0 <= w < Ww):
+            raise ValueError("probe (%d, %d) lies outside the %d x %d field" % (h, w, Hh, Ww))
+    for ci, cj in pairs:
+        if not (0 <= ci <= 2 and 0 <= cj <= 2):
+            raise ValueError("pair (%d, %d): channels are 0..2" % (ci, cj))
+    if lags[0] != 0 or any(b <= a for a, b in zip(lags, lags[1:])):
+        raise ValueError("lags start at 0 and increase strictly (a negative lag: exchange ci and cj), got %r" % (lags,))
+    if lags[-1] > CORR_MAX_LAG:
+        raise ValueError("the largest lag is %d kept steps, got %d" % (CORR_MAX_LAG, lags[-1]))
+    return (tuple((int(h), int(w)) for h, w in probes), tuple((int(a), int(b)) for a, b in pairs), tuple(int(v) for v in lags))
+
+
+def corr_probe_stats(series, pairs, lags, T):
+    """The probe's side of the Pearson coefficient, fp64 on the host (not the hot path): series [S + 1, B, steps, P, 3], the rows'
+    fluctuations at the probes at the timed steps 0 .. T - 1 -> (pm, pv) [S + 1, B, P, Q, L] fp64 CPU tensors: the mean and the
+    population variance (about that mean) of the first n_l = T - tau_l values of series[.., p, ci_q]; NaN where n_l < 1."""
+    s = torch.as_tensor(series).detach().cpu().double()
+    R, B, _, P, _ = s.shape
+    pm = torch.full((R, B, P, len(pairs), len(lags)), float("nan"), dtype=torch.float64)
+    pv = pm.clone()
+    for q, (ci, _cj) in enumerate(pairs):
+        for l, tau in enumerate(lags):
+            n = int(T) - int(tau)
+            if n >= 1:
+                v = s[:, :, :n, :, ci]
+                mean = v.sum(2) / n
+                pm[:, :, :, q, l] = mean
+                pv[:, :, :, q, l] = ((v - mean.unsqueeze(2)) ** 2).sum(2) / n
+    return pm, pv
+
+
+def corr_lengths(line, pos, step):
+    """Integral length scales from a lag-0 correlation line through the probe, fp64 on the host: line [.., n] with the probe at index
+    pos -> [.., 2] fp64 CPU tensor, towards growing and towards falling index.  With rho_i the value i pixels from the probe and k the
+    first i >= 1 that is outside the line or has rho_i <= 0 or NaN: len = step (rho_0 / 2 + sum_{i = 1}^{k - 1} rho_i), the trapezoid
+    to a zero at k."""
+    a = torch.as_tensor(line).detach().cpu().double()
+    pos = int(pos)
+    out = torch.empty(tuple(a.shape[:-1]) + (2,), dtype=torch.float64)
+    for d, seq in enumerate((a[..., pos + 1:], a[..., :pos].flip(-1))):
+        alive = torch.cumprod((seq > 0).to(torch.int64), dim=-1) > 0          # (NaN > 0 is False)
+        out[..., d] = float(step) * (a[..., pos] / 2.0 + torch.where(alive, seq, torch.zeros_like(seq)).sum(-1))
+    return out
+
+
+def corr_shift(line, pos):
+    """The displacement in pixels of the maximum of a correlation line from the probe at index pos, fp64 on the host: line [.., n] ->
+    [..] fp64 CPU tensor; refined by the parabola through the peak and its two neighbours when the peak is interior, all three are
+    finite and the second difference is negative; NaN for an all-NaN line."""
+    a = torch.as_tensor(line).detach().cpu().double()
+    n = a.shape[-1]
+    flat = a.reshape(-1, n)
+    nan = torch.isnan(flat)
+    k = torch.where(nan, torch.full_like(flat, -math.inf), flat).argmax(-1)
+    at = lambda i: flat.gather(1, i.clamp(0, n - 1).unsqueeze(1)).squeeze(1)   # noqa: E731
+    y0, ym, yp = at(k), at(k - 1), at(k + 1)
+    den = (ym - 2.0 * y0) + yp
+    ok = (k > 0) & (k < n - 1) & torch.isfinite(ym) & torch.isfinite(yp) & torch.isfinite(y0) & (den < 0)
+    delta = torch.where(ok, 0.5 * (ym - yp) / torch.where(ok, den, torch.ones_like(den)), torch.zeros_like(den))
+    out = (k - int(pos)).double() + delta
+    out[nan.all(-1)] = float("nan")
+    return out.reshape(tuple(a.shape[:-1]))
+
+
+class EnsembleCorrelation(EnsembleFeed):
+    """On-device two-point space-time correlations of sampled roll-outs of B cases, and of the target, about probe points
+    (tmg_ens_corr_probe / tmg_ens_corr_accum / tmg_ens_corr_finalize):
+
+      R(x0; x, tau) = < u'_i(x0, t) u'_j(x, t + tau) >
+
+    the size and shape of the structure that passes a chosen point (the integral length scales), where that structure is tau later,
+    and from that displacement the convection velocity.
+
+    Rows are the S members plus the target as row S.  A row's fluctuation about the TARGET's time mean is d_c = fl(a_c fl(y_c - m_c)),
+    a = u * out_std (formed in fp64, rounded once), m = `mean` [B, 3, H, W] in normalised units (None: 0).  probes: P <= 8 pixels
+    (h, w), pairs: Q <= 4 channel pairs (ci at the probe, cj in the field), lags: L <= 8 strictly increasing lags tau_l in timed
+    steps, the first 0, the largest <= 64 (corr_args); J the sorted set of distinct cj.  t = 0, 1, .. numbers the timed steps; after T
+    of them lag l has n_l = T - tau_l pairs (probe at t - tau_l, field at t).  State, fp32 on the device:
+      series [S + 1, B, steps, P, 3]   every row's d at the probe pixels at every timed step
+      raw [S + 1, B, NPL, HW], NPL = P Q L + 2 |J| L:  X[p,q,l] += fl(series[t - tau_l, p, ci_q] * d_{cj_q}(x, t)),  F[j,l] += d_j(x, t),
+      G[j,l] += fl(d_j d_j), each plane at t >= tau_l only and stored instead of added at t == tau_l, so raw needs no memset; a lag
+      with tau_l >= T leaves its planes unwritten and they are never read.
+    The state takes NPL * 4 bytes per element of [S + 1, B, HW]: 40 planes, 160 bytes, at the defaults.  An element of raw is touched
+    by one thread once per call: the state is bitwise reproducible and independent of the chunking.
+
+    finalize() reads series back, forms on the host in fp64 the mean pm and the population variance pv of the probe's first n_l values
+    (corr_probe_stats) and then, on the device in fp64, per (p, q, l) and row with n = n_l:
+      mf = F / n,  vf = G / n - mf^2,  cov = X / n - pm mf,  rho = cov / sqrt(pv vf) when pv > 0 and vf > 0, else NaN
+    the Pearson coefficient of the n paired samples, so |rho| <= 1 up to rounding.  Lags with n_l < 2 give NaN.
+
+    Feeding protocol of EnsembleFeed, with the step's target on every chunk; a step fed with time=False launches nothing.
+    finalize() -> dict:
+      tp_cov_mean, tp_cov_std, tp_rho_mean, tp_rho_std [B, P, Q, L, H, W]   Welford mean / population std over the members
+      target_tp_cov, target_tp_rho [B, P, Q, L, H, W]                      row S
+      member_tp_rho [B, S, P, Q, L, H, W]                                  every member's rho (per_member=True only)
+      tp_line_x [B, S + 1, P, Q, L, W], tp_line_y [B, S + 1, P, Q, L, H]    rho of every row on the probe's field row and column
+      tp_len [B, S + 1, P, Q, 4]         integral lengths from the lag-0 lines in the directions (+x, -x, +y, -y) (corr_lengths with
+                                         step = dx, dy of grid); tp_len_mean, tp_len_std [B, P, Q, 4] over the members, target_tp_len
+      tp_shift [B, S + 1, P, Q, L, 2]    the displacement (along x, along y) in pixels of the maximum of each line (corr_shift)
+      tp_speed [B, S + 1, P, Q, L, 2]    tp_shift * (dx, dy) / (tau_l step_dt), NaN at tau = 0; tp_speed_mean, tp_speed_std
+                                         [B, P, Q, L, 2] over the members, target_tp_speed
+      tp_probes, tp_pairs, tp_lags       the arguments as used.
+    Not supported: probes off the pixel grid, pixel-box averages of probes, negative lags (exchange ci and cj), more than 8 probes,
+    4 pairs or 8 lags or a lag over 64, the full two-point tensor, non-finite members."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, grid=(1.0, 1.0), probes=None,
+                 pairs=((0, 0), (1, 1)), lags=(0, 1, 2, 4), mean=None, per_member=False, step_dt=1.0):
+        noun, why = "ensemble two-point correlations", "the fluctuations scale with u * out_std"
+        _ens_members(noun, members)
+        self.probes, self.pairs, self.lags = corr_args(probes, pairs, lags, C, Hh, Ww)
+        real = lambda v: not isinstance(v, bool) and isinstance(v, numbers.Real) and math.isfinite(float(v)) and float(v) > 0   # noqa: E731
+        try:
+            g = tuple(grid)
+        except TypeError:
+            raise ValueError("grid must hold (dx, dy), got %r" % (grid,))
+        if len(g) != 2 or not all(real(v) for v in g):
+            raise ValueError("grid must hold two positive finite sizes (dx, dy), got %r" % (grid,))
+        if not real(step_dt):
+            raise ValueError("step_dt must be finite and > 0, got %r" % (step_dt,))
+        self.grid, self.step_dt = (float(g[0]), float(g[1])), float(step_dt)
+        sd, _mu = _ens_tables(3, why, out_std, out_mu)
+        u = _ens_u(u, B, 3, why)
+        if int(steps) < 1 or int(B) < 1:
+            raise ValueError("%s need steps, B >= 1, got %d, %d" % (noun, steps, B))
+        if mean is not None:
+            mean = torch.as_tensor(mean).detach()
+            if tuple(mean.shape) != (int(B), 3, int(Hh), int(Ww)) or not bool(torch.isfinite(mean).all()):
+                raise ValueError("mean is a finite array [%d, 3, %d, %d], got shape %s" % (B, Hh, Ww, tuple(mean.shape)))
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, 3, Hh, Ww, steps)
+        HW = self.H * self.W
+        self.per_member = bool(per_member)
+        self.a = _ens_scale(sd, u, self.B, torch.float64).to(torch.float32).to(dev).contiguous()
+        self.m = None if mean is None else mean.to(torch.float32).reshape(self.B, 3, HW).to(dev).contiguous()
+        P, Q, L = len(self.probes), len(self.pairs), len(self.lags)
+        self.plan = H.ens_corr_plan(self.S, self.B, self.H, self.W, P, Q, L, len(set(cj for _ci, cj in self.pairs)))
+        self.series = torch.empty((self.S + 1, self.B, self.Tk, P, 3), device=dev, dtype=torch.float32)
+        self.raw = torch.empty((self.S + 1, self.B, self.plan["planes"], HW), device=dev, dtype=torch.float32)
+
+    def add(self, y, m0, target, time=True):
+        """Add the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, 3, H, W], any strides whose channels-last view is an NHWC
+        channel-slice; rows member-major); target: the step's normalised target [B, 3, H, W] under the same stride rule, added as
+        row S with the step's last chunk.  A step fed with time=False launches nothing."""
+        yn, tn, k, t_before, last = self.open_chunk(y, m0, time, target, required=True)
+        _on_device(yn, tn)
+        if time:
+            cfg = (self.probes, self.pairs, self.lags)
+            H.ens_corr_probe(yn, self.a, self.m, self.series, *cfg, k, m0, t_before)
+            H.ens_corr_accum(yn, self.a, self.m, self.series, self.raw, *cfg, k, m0, t_before)
+            if last:
+                H.ens_corr_probe(tn, self.a, self.m, self.series, *cfg, 1, self.S, t_before)
+                H.ens_corr_accum(tn, self.a, self.m, self.series, self.raw, *cfg, 1, self.S, t_before)
+        self.close_chunk(m0, k, time, last)
+
+    def finalize(self):
+        """-> dict of the outputs over the steps folded with time=True."""
+        T = self.finalize_guard()
+        B, S, Hh, Ww = self.B, self.S, self.H, self.W
+        HW, dev = Hh * Ww, self.raw.device
+        P, Q, L = len(self.probes), len(self.pairs), len(self.lags)
+        pm, pv = corr_probe_stats(self.series[:, :, :T], self.pairs, self.lags, T)
+        outs = [torch.empty((B, P, Q, L, HW), device=dev, dtype=torch.float32) for _ in range(6)]
+        lines = [torch.empty((B, S + 1, P, Q, L, n), device=dev, dtype=torch.float32) for n in (Ww, Hh)]
+        mr = torch.empty((B, S, P, Q, L, HW), device=dev, dtype=torch.float32) if self.per_member else None
+        H.ens_corr_finalize(self.raw, pm.to(dev), pv.to(dev), outs, mr, lines, self.probes, self.pairs, self.lags, Hh, Ww, T)
+        o = {}
+        for key, t in zip(("tp_cov_mean", "tp_cov_std", "tp_rho_mean", "tp_rho_std", "target_tp_cov", "target_tp_rho"), outs):
+            o[key] = t.view(B, P, Q, L, Hh, Ww)
+        if mr is not None:
+            o["member_tp_rho"] = mr.view(B, S, P, Q, L, Hh, Ww)
+        o["tp_line_x"], o["tp_line_y"] = lines
+        # the derived scalars, fp64 on the host from the lines
+        lx, ly = lines[0].cpu().double(), lines[1].cpu().double()
+        dx, dy = self.grid
+        ln = torch.empty((B, S + 1, P, Q, 4), dtype=torch.float64)
+        sh = torch.empty((B, S + 1, P, Q, L, 2), dtype=torch.float64)
+        for p, (h0, w0) in enumerate(self.probes):
+            ln[:, :, p, :, 0:2] = corr_lengths(lx[:, :, p, :, 0], w0, dx)
+            ln[:, :, p, :, 2:4] = corr_lengths(ly[:, :, p, :, 0], h0, dy)
+            sh[:, :, p, :, :, 0] = corr_shift(lx[:, :, p], w0)
+            sh[:, :, p, :, :, 1] = corr_shift(ly[:, :, p], h0)
+        tau = torch.tensor([float(v) if v > 0 else float("nan") for v in self.lags], dtype=torch.float64) * self.step_dt
+        sp = sh * torch.tensor([dx, dy], dtype=torch.float64) / tau.view(L, 1)
+        o["tp_len"], o["tp_len_mean"], o["tp_len_std"], o["target_tp_len"] = ln, ln[:, :S].mean(1), ln[:, :S].std(1, unbiased=False), ln[:, S]
+        o["tp_shift"] = sh
+        o["tp_speed"], o["tp_speed_mean"], o["tp_speed_std"], o["target_tp_speed"] = sp, sp[:, :S].mean(1), sp[:, :S].std(1, unbiased=False), sp[:, S]
+        o["tp_probes"], o["tp_pairs"], o["tp_lags"] = self.probes, self.pairs, self.lags
+        return o
+
+
 STRUCTURE_MAX_LAGS = 16
 STRUCTURE_MAX_LAG = 64
 

@@ -794,3 +794,74 @@ def modelPredSpod(args, model, testing_loader, log, samples=1, stride=1, tmax=1,
                                                  channels=channels, window=window, dt=step_dt, loo=loo),
                target=True, window=True, meta=("spod_bins", "spod_freq"))
     return _ensembleStats("modelPredSpod", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
+
+
+def _corr_factory(stride, t_start, grid, probes, pairs, lags, per_member, step_dt):
+    """The make of modelPredCorrelation's record: the target's time mean over the kept steps from t_start on, back in normalised
+    units (fp64, as _budget_factory forms it), and the tmg_ops.EnsembleCorrelation about it."""
+    def make(mb, members, steps):
+        import tmg_ops as ops
+        B, C = mb.B, mb.C
+        tk = mb.tgt[:, t_start * stride:(steps - 1) * stride + 1:stride].double()
+        u, sd, mu = mb.u.double(), mb.out_std.double()[:C], mb.out_mu.double()[:C]
+        xn = (tk / u.view(B, 1, C, 1, 1) - mu.view(1, 1, C, 1, 1)) / sd.view(1, 1, C, 1, 1)
+        return ops.EnsembleCorrelation(members, B, C, mb.H, mb.W, steps, mb.dev, mb.out_mu, mb.out_std, u=mb.u, grid=grid, probes=probes,
+                                       pairs=pairs, lags=lags, mean=xn.mean(1), per_member=per_member, step_dt=step_dt)
+    return make
+
+
+def modelPredCorrelation(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, probes=None,
+                         pairs=((0, 0), (1, 1)), lags=(0, 1, 2, 4), per_member=False, dt=None):
+    """modelPredStats plus the two-point space-time correlations of every member and of the target about probe points, still without
+    forming modelPred's [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleCorrelation):
+
+      R(x0; x, tau) = < u'_i(x0, t) u'_j(x, t + tau) >
+
+    On an inhomogeneous domain it is the one statistic that shows the size and shape of the structure that passes a chosen point (the
+    integral length scales), where that structure is tau later, and from that displacement the convection velocity: a surrogate that
+    gets it wrong sheds vortices of the right energy at the wrong speed.  Same roll-outs as modelPredStats: under the same host RNG
+    state the keys both return are identical.  The grid is (args.dx along W, args.dy along H).  The target of kept step j is series
+    step j * stride.  dt=None counts time in kept steps, else a kept step lasts stride * dt.
+
+    Rows are the S members and the target.  A row's fluctuation is d = (u0, u0, u0^2) out_std (y - m) about the TARGET's time mean m
+    over the kept steps from t_start on.  probes: at most 8 pixels (h, w) inside the field, duplicates allowed (None: (H // 2, W // 4),
+    (H // 2, W // 2), (H // 2, 3 W // 4)); pairs: at most 4 pairs (ci, cj) of channels in 0..2, ci taken at the probe and cj in the
+    field; lags: at most 8 strictly increasing integers in kept steps, the first 0, the largest <= 64.  t = 0, 1, .. numbers the timed
+    steps (kept steps t_start..Tk-1); after T of them lag l has n_l = T - tau_l pairs (probe at t - tau_l, field at t).  The state
+    holds the rows' d at the probes at every timed step and, with J the distinct cj, NPL = P Q L + 2 |J| L fp32 planes per row: the
+    sums of d_ci(x0, t - tau) d_cj(x, t), of d_j(x, t) and of d_j(x, t)^2 over t >= tau_l.  It takes NPL * 4 bytes per element of
+    [S + 1, N, HW], 40 planes or 160 bytes at the defaults; it is bitwise reproducible and independent of max_rows.  From it, in fp64
+    on the device, cov = X / n - pm mf and the Pearson coefficient rho = cov / sqrt(pv vf) of the n = n_l paired samples (pm, pv the
+    mean and population variance of the probe's first n values, mf, vf those of the field's last n), NaN where pv or vf is not
+    positive and for lags with n_l < 2.  |rho| <= 1 up to rounding, and it is 1 at the displaced point of a frozen pattern convected
+    by whole pixels.
+
+    Returns modelPredStats' dict plus (CPU tensors; P probes, Q pairs, L lags, S = samples):
+      tp_cov_mean, tp_cov_std, tp_rho_mean, tp_rho_std [N, P, Q, L, H, W]   mean / population std (ddof 0) over the members
+      target_tp_cov, target_tp_rho [N, P, Q, L, H, W]                      the target through the same kernels
+      member_tp_rho [N, S, P, Q, L, H, W]                                  every member's rho (per_member=True only)
+      tp_line_x [N, S + 1, P, Q, L, W], tp_line_y [N, S + 1, P, Q, L, H]    rho of every row (the target last) on the probe's field
+                                                                           row and field column
+      tp_len [N, S + 1, P, Q, 4]        integral lengths from the lag-0 lines in the directions (+x, -x, +y, -y): with rho_i the value
+                                        i pixels from the probe and k the first i >= 1 that is outside the field or has rho_i <= 0 or
+                                        NaN, len = step (rho_0 / 2 + sum_{i=1}^{k-1} rho_i), the trapezoid to a zero at k, step = dx
+                                        or dy; tp_len_mean, tp_len_std [N, P, Q, 4] over the members, target_tp_len [N, P, Q, 4]
+      tp_shift [N, S + 1, P, Q, L, 2]   the displacement (along x, along y) in pixels of the maximum of each line from the probe,
+                                        refined by the parabola through the peak and its two neighbours when the peak is interior
+                                        and all three are finite; NaN for an all-NaN line
+      tp_speed [N, S + 1, P, Q, L, 2]   tp_shift * (dx, dy) / (tau_l step_dt), NaN at tau = 0; tp_speed_mean, tp_speed_std
+                                        [N, P, Q, L, 2] over the members, target_tp_speed [N, P, Q, L, 2]
+      tp_probes, tp_pairs, tp_lags      the arguments as used.
+    Not supported: probes off the pixel grid, pixel-box averages of probes, negative lags (exchange ci and cj), more than 8 probes,
+    4 pairs or 8 lags or a lag over 64, the full two-point tensor, non-finite members."""
+    step_dt = 1.0 if dt is None else float(stride) * float(dt)
+    if not (math.isfinite(step_dt) and step_dt > 0):
+        raise ValueError("dt must be a positive finite time between two model steps, got %r" % (dt,))
+    import tmg_ops as ops
+    if probes is not None:                                                    # (the default probes need the field's size)
+        ops.corr_args(probes, pairs, lags, 3, 1 << 30, 1 << 30)
+    else:
+        ops.corr_args(((0, 0),), pairs, lags, 3, 1, 1)
+    acc = _Acc(_corr_factory(stride, t_start, (args.dx, args.dy), probes, pairs, lags, bool(per_member), step_dt), target=True,
+               meta=("tp_probes", "tp_pairs", "tp_lags"))
+    return _ensembleStats("modelPredCorrelation", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
