@@ -402,6 +402,15 @@ static inline bool tmg_bad_seg_count(int64_t nin, int64_t nout) {
 struct TmgD2 { int stride, off; };
 static inline TmgD2 tmg_opt_d2(const void* p, const int64_t* d) { return p ? TmgD2{(int)d[0], (int)d[1]} : TmgD2{0, 0}; }
 
+// The pixel slices of the kernels that write one partial per slice (symgram_plan, pod_plan, sfun_slices): for a wish of P slices the
+// slice length SL is ceil(HW / P) rounded up to a multiple of q, and P becomes the slices that are then left, so that
+// (P - 1) SL < HW <= P SL.
+struct TmgSlices { int64_t SL, P; };
+static inline TmgSlices tmg_slices(int64_t HW, int64_t P, int64_t q) {
+    const int64_t SL = ((HW + P - 1) / P + q - 1) / q * q;
+    return TmgSlices{SL, (HW + SL - 1) / SL};
+}
+
 #define TMG_CHECK_LAUNCH()                          \
     do {                                            \
         hipError_t e__ = hipGetLastError();         \

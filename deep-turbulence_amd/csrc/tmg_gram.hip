@@ -7,69 +7,29 @@
 // a_c = u[b][c] out_std[c] > 0; out_mu cancels.  Centring changes no distance: it makes G_mm + G_nn - 2 G_mn cancel against the spread
 // of the members, not against the magnitude of the field.
 //   ens_gram_mean_kernel       r [B][C][HW] = (x_0 + x_1 + .. + x_{S-1}, sequential fp32 in member order) * fl(1 / S)
-//   ens_gram_kernel<DIAG>      one block per (case, channel), pixel slice and pair of 64-row macro-tiles I <= J (DIAG: I == J): its
-//                              partial Gram block into the workspace, no atomics
-//   ens_gram_reduce_kernel     P > 1: the P slices' partials added in slice order (fp32)
+//   ens_gram_kernel<DIAG>      the Gram blocks of tmg_symgram.h over the planes (case, channel): the walk over this file's rows between
+//                              that header's pair decode and its hand-over and store; partial blocks into the workspace, no atomics
+//   symgram_reduce_kernel      (tmg_symgram.h) P > 1: the P slices' partials added in slice order (fp32)
 //   ens_gram_finalize_kernel   d2, dist = sqrt(d2), the means of the distances (fp64), the two argmins, traj_dist2 += d2 on timed steps;
 //                              <true>: the same sums and argmins on sqrt(traj_dist2)
 //
-// Layout of ens_gram_kernel.  v_mfma_f32_16x16x4_f32 with the lane maps of tmg_tspec.hip: A[i = l & 15][k = l >> 4], B[k = l >> 4][j = l & 15],
-// D column l & 15, rows 4 (l >> 4) + 0..3.  A is a 16-row tile of e and B the transpose of another, so both operands are held the same
-// way: lane l has row l & 15 of its tile and pixel group kq = l >> 4.  The sum over the pixels may run in any order as long as A and B of
-// one instruction agree on it: a wave takes 64 consecutive pixels at a time, lane (row, kq) owns the 16 CONSECUTIVE pixels kq 16 .. kq 16
-// + 15 of them (64 bytes: four float4 loads when HW is a multiple of 4) and MFMA step s = 0..15 contracts element s of every lane's run.
-// A row's fragment is loaded once per 64 pixels and used for every tile pair it is part of; on a diagonal tile pair A and B are the same
-// registers.  Rows > S and pixels >= HW are never loaded and their lanes hold 0 (xs comes from torch.empty: 0 * NaN is NaN); tile
-// pairs without a valid row issue no MFMA.  r is subtracted when the fragment is built (one rounding per operand).
-//
-// Sum order, which the tests' rounding count is derived from (tests/energy_cases.py).  The pixels are cut into P slices of SL pixels
-// (SL a multiple of 256, the host's choice: tmg_ens_gram_plan).  Inside a slice wave w of the block's 4 takes the 64-pixel chunks w,
-// w + 4, .. in order; an MFMA is a k-ordered fmaf chain onto its C input, so one accumulator is a chain of at most SL / 4 fmaf.  Waves
-// 1..3 hand their accumulators over through LDS and wave 0 adds them in wave order (3 additions), then the slices are added in slice
-// order (P - 1 additions).  The plan reports L = SL, the fmaf terms of one partial (the four waves' chains end to end, >= SL / 4 + 3,
-// the longest dependent chain inside a partial), so that L P >= HW.  Roundings of one d2 entry beside L + P: 2 operand roundings (x - r),
-// 2 combining additions (G_mm + G_nn, then - 2 G_mn; the doubling is exact), 2 for the scale (a_c^2 rounded once from fp64, one product),
-// up to 3 additions over the channels of a group, 1 for the second-order terms: c = 10.  The sums over dist are fp64.
+// Layout and sum order of ens_gram_kernel: tmg_symgram.h, with Z = R rows per plane and one pass over the pixels, so that the plan
+// (tmg_ens_gram_plan) reports L = SL.  What is this file's own: a row's run of 16 pixels is four float4 loads when HW is a multiple of 4;
+// the mean's run is loaded once per chunk and serves every row; r is subtracted when the fragment is built (one rounding per operand).
+// Roundings of one d2 entry beside L + P, which the tests' rounding count is derived from (tests/energy_cases.py): 2 operand roundings
+// (x - r), 2 combining additions (G_mm + G_nn, then - 2 G_mn; the doubling is exact), 2 for the scale (a_c^2 rounded once from fp64, one
+// product), up to 3 additions over the channels of a group, 1 for the second-order terms: c = 10.  The sums over dist are fp64.
 // No float atomics anywhere: the same inputs give the same bits, for every chunking of the members.
-#include "tmg_common.h"
+#include "tmg_symgram.h"
 #include "tmglow_hip.h"
 
 #define GRAM_MAXC 4
 #define GRAM_MAXS 1024
-#define GRAM_MT 64                       // rows of a macro-tile
-#define GRAM_PART (GRAM_MT * GRAM_MT)    // floats of one partial: [16 tile pairs x 4 D registers][64 lanes]; 256 when R <= 16 (one tile)
-#define GRAM_CHUNK 64                    // pixels a wave contracts per step
-#define GRAM_SLQ 256                     // slice granularity: 4 waves x one chunk
-#define GRAM_TARGET_BLOCKS 768           // the grid the slice count aims at: 256 CUs x 3 blocks (48 KB of LDS each)
-#define GRAM_WS_CAP (1ll << 24)          // floats of workspace beyond which the slice count is cut (P = 1 may exceed it)
 
 struct GramGroups {
     int cnt[GRAM_MAXC];
     int ch[GRAM_MAXC][GRAM_MAXC];
 };
-
-struct GramPlan {
-    int64_t P, L, NP, ws, SL, NT, part;
-};
-
-static GramPlan gram_plan(int64_t S, int64_t B, int64_t C, int64_t HW) {
-    GramPlan g;
-    g.NT = (S + 1 + GRAM_MT - 1) / GRAM_MT;
-    g.NP = g.NT * (g.NT + 1) / 2;
-    g.part = S + 1 <= 16 ? 256 : GRAM_PART;                                 // one 16-row tile: the small instance
-    const int64_t base = B * C * g.NP;
-    const int64_t maxp = (HW + GRAM_SLQ - 1) / GRAM_SLQ;
-    int64_t P = (GRAM_TARGET_BLOCKS + base - 1) / base;
-    const int64_t pcap = GRAM_WS_CAP / (base * g.part) - 1;              // P partials and their sum
-    if (P > pcap) P = pcap;
-    if (P > maxp) P = maxp;
-    if (P < 1) P = 1;
-    g.SL = ((HW + P - 1) / P + GRAM_SLQ - 1) / GRAM_SLQ * GRAM_SLQ;
-    g.P = (HW + g.SL - 1) / g.SL;
-    g.L = g.SL;
-    g.ws = base * g.part * (g.P + (g.P > 1 ? 1 : 0));
-    return g;
-}
 
 __global__ __launch_bounds__(256) void ens_gram_mean_kernel(const float* __restrict__ xs, float* __restrict__ r, int S, size_t ms, int HW,
                                                             float inv_s) {
@@ -117,22 +77,11 @@ template <bool DIAG, int NTL>
 __global__ __launch_bounds__(256) void ens_gram_kernel(const float* __restrict__ xs, const float* __restrict__ tgt, int tps,
                                                        const float* __restrict__ r, float* __restrict__ ws, int S, int B, int C, int HW,
                                                        int SL, int P, int NT, int vec) {
-    __shared__ float red[3][NTL * NTL * 4][64];                                  // waves 1..3: [accumulator register][lane]
     const int wave = threadIdx.x >> 6, l = threadIdx.x & 63, l16 = l & 15, kq = l >> 4;
     const int slice = blockIdx.x, bc = blockIdx.z;
     const int b = bc / C, c = bc - b * C;
-    int I = blockIdx.y, J = blockIdx.y;
-    if (!DIAG) {                                                           // the q-th pair I < J, rows of the upper triangle in order
-        int q = blockIdx.y;
-        I = 0;
-        while (q >= NT - 1 - I) {
-            q -= NT - 1 - I;
-            ++I;
-        }
-        J = I + 1 + q;
-    }
-    const int R = S + 1;
-    const int nti = min(NTL, (R - I * GRAM_MT + 15) >> 4), ntj = min(NTL, (R - J * GRAM_MT + 15) >> 4);   // valid 16-row tiles (>= 1)
+    const SymgramTile tl = symgram_tile<DIAG, NTL>(S + 1, NT);
+    const int I = tl.I, J = tl.J, nti = tl.nti, ntj = tl.ntj;
     const size_t hw = (size_t)HW, ms = (size_t)B * C * hw;
     const float* xbc = xs + ((size_t)b * C + c) * hw;                      // member 0 of (b, c)
     const float* tbc = tgt + (size_t)b * hw * tps + c;
@@ -143,7 +92,7 @@ __global__ __launch_bounds__(256) void ens_gram_kernel(const float* __restrict__
 #pragma unroll
         for (int jt = 0; jt < NTL; ++jt) acc[it][jt] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int pbeg = slice * SL, pend = min(HW, pbeg + SL);
-    for (int pc = pbeg + wave * GRAM_CHUNK; pc < pend; pc += 4 * GRAM_CHUNK) {
+    for (int pc = pbeg + wave * SYMGRAM_CHUNK; pc < pend; pc += 4 * SYMGRAM_CHUNK) {
         const int p0 = pc + kq * 16;
         float rv[16];
 #pragma unroll
@@ -165,7 +114,7 @@ __global__ __launch_bounds__(256) void ens_gram_kernel(const float* __restrict__
         float fa[NTL][16];
 #pragma unroll
         for (int it = 0; it < NTL; ++it) {
-            const int row = I * GRAM_MT + 16 * it + l16;
+            const int row = I * SYMGRAM_MT + 16 * it + l16;
             gram_frag(fa[it], xbc + (size_t)min(row, S - 1) * ms, tbc, tps, it < nti ? row : S + 1, S, p0, HW, vec != 0, rv);
         }
 #pragma unroll
@@ -175,7 +124,7 @@ __global__ __launch_bounds__(256) void ens_gram_kernel(const float* __restrict__
 #pragma unroll
                 for (int s = 0; s < 16; ++s) fb[s] = fa[jt][s];
             } else {
-                const int row = J * GRAM_MT + 16 * jt + l16;
+                const int row = J * SYMGRAM_MT + 16 * jt + l16;
                 gram_frag(fb, xbc + (size_t)min(row, S - 1) * ms, tbc, tps, jt < ntj ? row : S + 1, S, p0, HW, vec != 0, rv);
             }
 #pragma unroll
@@ -187,54 +136,7 @@ __global__ __launch_bounds__(256) void ens_gram_kernel(const float* __restrict__
             }
         }
     }
-    if (wave > 0) {
-#pragma unroll
-        for (int it = 0; it < NTL; ++it)
-#pragma unroll
-            for (int jt = 0; jt < NTL; ++jt)
-                if ((!DIAG || it <= jt) && it < nti && jt < ntj) {
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) red[wave - 1][(it * NTL + jt) * 4 + v][l] = acc[it][jt][v];
-                }
-    }
-    __syncthreads();
-    if (wave == 0) {
-        const int pidx = I * NT - I * (I - 1) / 2 + (J - I);
-        const int NP = NT * (NT + 1) / 2;
-        float* wp = ws + (((size_t)bc * NP + pidx) * P + slice) * (NTL * NTL * 256) + l;
-#pragma unroll
-        for (int it = 0; it < NTL; ++it)
-#pragma unroll
-            for (int jt = 0; jt < NTL; ++jt) {
-                const bool live = (!DIAG || it <= jt) && it < nti && jt < ntj;
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int a = (it * NTL + jt) * 4 + v;
-                    float t = acc[it][jt][v];
-                    if (live) t = ((t + red[0][a][l]) + red[1][a][l]) + red[2][a][l];
-                    wp[a * 64] = t;                                        // every float of the partial is written: 0 where nothing is live
-                }
-            }
-    }
-}
-
-// G[i] = ws[i][0] + ws[i][1] + .. in slice order; i over [B C][NP] partial blocks of `part` floats
-__global__ __launch_bounds__(256) void ens_gram_reduce_kernel(const float* __restrict__ ws, float* __restrict__ G, int P, int part) {
-#pragma clang fp contract(off)
-    const size_t blk = blockIdx.x;
-    const int e = blockIdx.y * 256 + threadIdx.x;                          // < part
-    const float* wp = ws + blk * P * part + e;
-    float a = wp[0];
-    for (int s = 1; s < P; ++s) a += wp[(size_t)s * part];
-    G[blk * part + e] = a;
-}
-
-// offset of G[m][n], m <= n, inside the (b, c) plane [NP][part]
-__device__ __forceinline__ size_t gram_at(int m, int n, int NT, int part) {
-    const int I = m >> 6, J = n >> 6;
-    const int pidx = I * NT - I * (I - 1) / 2 + (J - I);
-    const int it = (m >> 4) & 3, jt = (n >> 4) & 3, i = m & 15, j = n & 15;
-    return (size_t)pidx * part + (size_t)(((it * 4 + jt) * 4 + (i & 3)) * 64 + j + 16 * (i >> 2));
+    symgram_store<DIAG, NTL>(acc, tl, ws, P, NT);
 }
 
 // One block per (group, case).  Thread m owns row m of the distance matrix (rows m, m + 256, ..): the sum of its distances to the
@@ -266,7 +168,7 @@ __global__ __launch_bounds__(256) void ens_gram_finalize_kernel(const float* __r
             if (k < cnt) {
                 sc[k] = a2[b * C + ch[k]];
                 const float* Gc = G + ((size_t)b * C + ch[k]) * NP * part;
-                for (int m = threadIdx.x; m < R; m += 256) dg[k][m] = Gc[gram_at(m, m, NT, part)];
+                for (int m = threadIdx.x; m < R; m += 256) dg[k][m] = Gc[symgram_at(m, m, NT, part)];
             }
         __syncthreads();
     }
@@ -280,7 +182,7 @@ __global__ __launch_bounds__(256) void ens_gram_finalize_kernel(const float* __r
             } else {
                 if (n != m) {
                     const int lo = min(m, n), hi = max(m, n);
-                    const size_t at = gram_at(lo, hi, NT, part);
+                    const size_t at = symgram_at(lo, hi, NT, part);
                     float d = 0.f;
 #pragma unroll
                     for (int k = 0; k < GRAM_MAXC; ++k)
@@ -344,9 +246,9 @@ extern "C" int tmg_ens_gram_plan(const int64_t* dims, int64_t* plan) {
     if (S < 1 || B < 1 || HW < 1 || C < 2 || C > GRAM_MAXC) return -1;
     if (S > GRAM_MAXS || HW >= (1ll << 31) - 256 || B * C > 65535 || S * B * C * HW >= (1ll << 40)) return -2;
     if (!plan) return -3;
-    const GramPlan g = gram_plan(S, B, C, HW);
+    const SymgramPlan g = symgram_plan(S + 1, B * C, HW);
     plan[0] = g.P;
-    plan[1] = g.L;
+    plan[1] = g.SL;                                                        // L: one pass over the slice
     plan[2] = g.NP;
     plan[3] = g.ws;
     plan[4] = g.SL;
@@ -388,7 +290,7 @@ extern "C" int tmg_ens_gram_step(const void* xs, const void* target, const int64
     if (S > GRAM_MAXS || HW >= (1ll << 31) - 256 || B * C > 65535 || S * B * C * HW >= (1ll << 40)) return -2;
     if (t_d && (t_d[0] >= (1ll << 31) || B * HW * t_d[0] >= (1ll << 40))) return -2;
     if (B * Tk * Gn >= (1ll << 40)) return -2;
-    const GramPlan g = gram_plan(S, B, C, HW);
+    const SymgramPlan g = symgram_plan(S + 1, B * C, HW);
     if (g.ws >= (1ll << 40) || Gn * B * (S + 1) * (S + 1) >= (1ll << 40)) return -2;
     if (ws_floats < g.ws) return -1;
     if (!xs || !target || !t_d || !a2 || !grp || !r || !ws || !outf || !outi) return -3;
@@ -398,26 +300,10 @@ extern "C" int tmg_ens_gram_step(const void* xs, const void* target, const int64
                        (float*)r, (int)S, (size_t)(B * C * HW), (int)HW, (float)(1.0 / (double)S));
     TMG_CHECK_LAUNCH();
     const float* tg = (const float*)target + t_d[1];
-    const dim3 gd((unsigned)g.P, (unsigned)g.NT, (unsigned)(B * C)), go((unsigned)g.P, (unsigned)(g.NP - g.NT), (unsigned)(B * C));
-#define GRAM_LAUNCH(DIAG_, NTL_, GRID_)                                                                                              \
-    hipLaunchKernelGGL((ens_gram_kernel<DIAG_, NTL_>), GRID_, dim3(256), 0, st, (const float*)xs, tg, (int)t_d[0], (const float*)r, \
-                       (float*)ws, (int)S, (int)B, (int)C, (int)HW, (int)g.SL, (int)g.P, (int)g.NT, vec)
-    if (g.part == 256) GRAM_LAUNCH(true, 1, gd);
-    else GRAM_LAUNCH(true, 4, gd);
+    SYMGRAM_LAUNCH(ens_gram_kernel, g, B * C, st, (const float*)xs, tg, (int)t_d[0], (const float*)r, (float*)ws, (int)S, (int)B, (int)C,
+                   (int)HW, (int)g.SL, (int)g.P, (int)g.NT, vec);
+    const float* G = symgram_reduce(g, B * C, (float*)ws, st);
     TMG_CHECK_LAUNCH();
-    if (g.NT > 1) {
-        GRAM_LAUNCH(false, 4, go);
-        TMG_CHECK_LAUNCH();
-    }
-#undef GRAM_LAUNCH
-    const float* G = (const float*)ws;
-    if (g.P > 1) {
-        float* Gs = (float*)ws + B * C * g.NP * g.P * g.part;
-        hipLaunchKernelGGL(ens_gram_reduce_kernel, dim3((unsigned)(B * C * g.NP), (unsigned)(g.part / 256)), dim3(256), 0, st, (const float*)ws,
-                           Gs, (int)g.P, (int)g.part);
-        TMG_CHECK_LAUNCH();
-        G = Gs;
-    }
     hipLaunchKernelGGL(ens_gram_finalize_kernel<false>, dim3((unsigned)Gn, (unsigned)B), dim3(256), 0, st, G, (const float*)a2,
                        (float*)traj, (float*)outf, (long long*)outi, (int)S, (int)B, (int)C, (int)g.NT, (int)Tk, (int)t, (int)t_before,
                        timed ? 1 : 0, (int)g.part, gr);

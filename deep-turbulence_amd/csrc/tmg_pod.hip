@@ -9,7 +9,7 @@
 //   ens_pod_kernel<NTL>   one block per (pixel slice, group of 64 members, case): its partial sums, no atomics
 //   ens_pod_fold_kernel   P > 1: the P slices' partials added in slice order (fp32); P = 1: the block writes the outputs itself
 //
-// Layout.  v_mfma_f32_16x16x4_f32 with the lane maps of tmg_gram.hip: A[i = l & 15][k = l >> 4], B[k = l >> 4][j = l & 15], D column
+// Layout.  v_mfma_f32_16x16x4_f32 with the lane maps of tmg_symgram.h: A[i = l & 15][k = l >> 4], B[k = l >> 4][j = l & 15], D column
 // l & 15, rows 4 (l >> 4) + 0..3.  The members are the M rows in tiles of 16, the modes the one N tile, pixels x channels the reduction.
 // A wave takes 64 consecutive pixels of one channel at a time; lane (row, kq) holds the 16 CONSECUTIVE pixels kq 16 .. kq 16 + 15 of
 // them and MFMA step s = 0..15 contracts element s of every lane's run (the order of the sum is free as long as A and B agree).
@@ -55,8 +55,9 @@ static PodPlan pod_plan(int64_t S, int64_t B, int64_t Cg, int64_t HW) {
     PodPlan g;
     int64_t P = (HW + POD_SLQ - 1) / POD_SLQ;
     if (P > POD_MAXP) P = POD_MAXP;
-    g.SL = ((HW + P - 1) / P + POD_SLQ - 1) / POD_SLQ * POD_SLQ;
-    g.P = (HW + g.SL - 1) / g.SL;
+    const TmgSlices s = tmg_slices(HW, P, POD_SLQ);
+    g.SL = s.SL;
+    g.P = s.P;
     g.L = g.SL * Cg;
     g.ws = g.P > 1 ? g.P * S * B * POD_ROW : 0;
     return g;

@@ -78,8 +78,9 @@ static void sfun_slices(int64_t S, int64_t B, int64_t C, int64_t HW, int64_t L, 
     if (P > pcap) P = pcap;
     if (P > maxp) P = maxp;
     if (P < 1) P = 1;
-    g.SL = ((HW + P - 1) / P + SFUN_SLQ - 1) / SFUN_SLQ * SFUN_SLQ;
-    g.P = (HW + g.SL - 1) / g.SL;
+    const TmgSlices s = tmg_slices(HW, P, SFUN_SLQ);
+    g.SL = s.SL;
+    g.P = s.P;
     g.Lc = g.SL / SFUN_SLQ + 9;
     g.ws = per * g.P;
 }

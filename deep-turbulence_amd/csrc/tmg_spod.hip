@@ -3,39 +3,30 @@
 // bin k, channel c and pixel p the Fourier coefficient of the windowed series, formed exactly as tspec_finalize_kernel forms it
 // (no contraction):
 //   xbar = acc[2 NF] * fl(1 / Tn),  Re X_m = acc[k] - xbar G_re,  Im X_m = acc[NF + k] - xbar G_im
-//   spod_csd_kernel<DIAG>   one block per (case, bin), pixel slice and pair of 64-row macro-tiles I <= J (DIAG: I == J) of the real Gram
+//   spod_csd_kernel<DIAG>   the Gram blocks of tmg_symgram.h over the planes (case, bin), the walk over this file's rows: the real Gram
 //                           matrix of the 2 R rows Z = [Re X_0 .. Re X_{R-1}; Im X_0 .. Im X_{R-1}] over the Cg HW elements of the
-//                           selected channels: its partial block into the workspace, no atomics.  The upper triangle holds RR, II and
+//                           selected channels, its partial blocks into the workspace, no atomics.  The upper triangle holds RR, II and
 //                           the full RI block
-//   spod_reduce_kernel      P > 1: the P slices' partials added in slice order (fp32)
+//   symgram_reduce_kernel   (tmg_symgram.h) P > 1: the P slices' partials added in slice order (fp32)
 //   spod_combine_kernel     csd_raw [B][NB][2][R][R]: raw0[m][n] = RR[lo][hi] + II[lo][hi] (lo, hi = min, max of m, n),
 //                           raw1[m][n] = RI[m][n] - RI[n][m], one fp32 addition each: raw0 is bitwise symmetric, raw1 bitwise
 //                           antisymmetric with an exactly zero diagonal
 //   spod_modes_kernel       modes [B][NB][2 J][Cg][HW] = w [16 x 2 SP] Z [2 SP rows], the weights built on the host from the
 //                           eigenvectors
 //
-// Layout of spod_csd_kernel: ens_gram_kernel's (tmg_gram.hip).  v_mfma_f32_16x16x4_f32, A[i = l & 15][k = l >> 4],
-// B[k = l >> 4][j = l & 15], D column l & 15, rows 4 (l >> 4) + 0..3; A is a 16-row tile of Z and B the transpose of another, so lane l
-// holds row l & 15 of its tile and the 16 CONSECUTIVE pixels kq 16 .. kq 16 + 15 (kq = l >> 4) of the wave's 64, and MFMA step s
-// contracts element s of every lane's run.  A row's fragment is loaded once per 64 pixels (the coefficient plane and the sum plane: two
-// 64-byte runs, float4 loads when the rows are 16-byte aligned) and used for every tile pair it is part of; on a diagonal pair A and B
-// are the same registers.  Rows >= 2 R and pixels >= HW are never loaded and their lanes hold 0 (acc comes from torch.empty: 0 * NaN is
-// NaN); tile pairs without a valid row issue no MFMA.  The row pointers are formed before the loops: the inner loop holds loads, the
-// correction and MFMAs only.
-//
-// Sum order (tests/spod_cases.py counts the roundings from it).  The pixels are cut into P slices of SL pixels (SL a multiple of 256:
-// tmg_ens_spod_plan).  Inside a slice a block walks the selected channels in the order given and, per channel, wave w of 4 takes the
-// 64-pixel chunks w, w + 4, ..; an MFMA is a k-ordered fmaf chain onto its C input.  Waves 1..3 hand their accumulators over through
-// LDS and wave 0 adds them in wave order (3 additions), then the slices are added in slice order (P - 1 additions).  L = Cg SL is the
-// fmaf terms of one partial.  Roundings of one csd_raw entry beside L + P: 2 per operand for the correction (xbar G, then the
-// subtraction; xbar itself is one more, counted with them as 3 per operand in the tests' bound) and 1 for the combine.
+// Layout and sum order of spod_csd_kernel: tmg_symgram.h, with Z = 2 R rows per plane and one pass per selected channel, in the order
+// given, so that the plan (tmg_ens_spod_plan) reports L = Cg SL.  What is this file's own: a row's fragment is formed from the
+// coefficient plane and the sum plane (two 64-byte runs, float4 loads when the rows are 16-byte aligned); the row pointers are formed
+// before the loops, so that the inner loop holds loads, the correction and MFMAs only.  Roundings of one csd_raw entry beside L + P
+// (tests/spod_cases.py counts them): 2 per operand for the correction (xbar G, then the subtraction; xbar itself is one more, counted
+// with them as 3 per operand in the tests' bound) and 1 for the combine.
 //
 // spod_modes_kernel has tspec_block_kernel's shape: the weights are the A fragment (A[i = row r][k = q]), Z the B fragment, the D
 // columns are consecutive pixels, so the stores run in 64-byte runs.  A wave owns 64 consecutive pixels of one channel (four column
 // tiles); step qs contracts q = 4 qs .. 4 qs + 3, lane group lq holding q = 4 qs + lq: first the SP / 4 steps of the real parts, then
 // those of the imaginary parts, the row pointers advanced by one constant per step.  Every output element is one fmaf chain in q order.
 // No float atomics anywhere: the same inputs give the same bits.
-#include "tmg_common.h"
+#include "tmg_symgram.h"
 #include "tmglow_hip.h"
 #include "tmglow_hip_spod.h"
 
@@ -43,42 +34,25 @@
 #define SPOD_MAXS 255
 #define SPOD_MAXB 16                     // bins of one call
 #define SPOD_MAXJ 8
-#define SPOD_MT 64                       // rows of a macro-tile
-#define SPOD_PART (SPOD_MT * SPOD_MT)    // floats of one partial: [16 tile pairs x 4 D registers][64 lanes]; 256 when 2 R <= 16
-#define SPOD_CHUNK 64                    // pixels a wave contracts per step
-#define SPOD_SLQ 256                     // slice granularity: 4 waves x one chunk
-#define SPOD_TARGET_BLOCKS 768           // the grid the slice count aims at: 256 CUs x 3 blocks
-#define SPOD_WS_CAP (1ll << 24)          // floats of workspace beyond which the slice count is cut (P = 1 may exceed it)
 
 struct SpodSel {
     int bin[SPOD_MAXB];
     int ch[SPOD_MAXC];
 };
 
+// the shared plan for the 2 R rows and the B NB planes, and what this file adds: L, vec, MB
 struct SpodPlan {
-    int64_t P, L, NP, ws, SL, NT, part, vec, MB;
+    SymgramPlan g;
+    int64_t L, vec, MB;
 };
 
 static SpodPlan spod_plan(int64_t S, int64_t B, int64_t Cg, int64_t HW, int64_t NB, int64_t addr) {
-    SpodPlan g;
-    const int64_t Z = 2 * (S + 1);
-    g.NT = (Z + SPOD_MT - 1) / SPOD_MT;
-    g.NP = g.NT * (g.NT + 1) / 2;
-    g.part = Z <= 16 ? 256 : SPOD_PART;
-    const int64_t base = B * NB * g.NP;
-    const int64_t maxp = (HW + SPOD_SLQ - 1) / SPOD_SLQ;
-    int64_t P = (SPOD_TARGET_BLOCKS + base - 1) / base;
-    const int64_t pcap = SPOD_WS_CAP / (base * g.part) - 1;               // P partials and their sum
-    if (P > pcap) P = pcap;
-    if (P > maxp) P = maxp;
-    if (P < 1) P = 1;
-    g.SL = ((HW + P - 1) / P + SPOD_SLQ - 1) / SPOD_SLQ * SPOD_SLQ;
-    g.P = (HW + g.SL - 1) / g.SL;
-    g.L = Cg * g.SL;
-    g.ws = base * g.part * (g.P + (g.P > 1 ? 1 : 0));
-    g.vec = (HW % 4 == 0 && (addr & 15) == 0) ? 1 : 0;
-    g.MB = (HW + 255) / 256;
-    return g;
+    SpodPlan q;
+    q.g = symgram_plan(2 * (S + 1), B * NB, HW);
+    q.L = Cg * q.g.SL;
+    q.vec = (HW % 4 == 0 && (addr & 15) == 0) ? 1 : 0;
+    q.MB = (HW + 255) / 256;
+    return q;
 }
 
 // The fragment of one row of Z for this lane's run of 16 pixels p0 .. p0 + 15: x - (s inv_t) g, 0 beyond HW and for a row that does not
@@ -111,7 +85,6 @@ template <bool DIAG, int NTL>
 __global__ __launch_bounds__(256) void spod_csd_kernel(const float* __restrict__ acc, const float* __restrict__ cst, float* __restrict__ ws,
                                                        int R, int B, int C, int HW, int NF, int NB, int Cg, int SL, int P, int NT, int vec,
                                                        float inv_t, SpodSel sel) {
-    __shared__ float red[3][NTL * NTL * 4][64];                            // waves 1..3: [accumulator register][lane]
     const int wave = threadIdx.x >> 6, l = threadIdx.x & 63, l16 = l & 15, kq = l >> 4;
     const int slice = blockIdx.x, bz = blockIdx.z;
     const int b = bz / NB, kb = bz - b * NB;
@@ -119,18 +92,9 @@ __global__ __launch_bounds__(256) void spod_csd_kernel(const float* __restrict__
 #pragma unroll
     for (int q = 0; q < SPOD_MAXB; ++q)
         if (q == kb) k = sel.bin[q];
-    int I = blockIdx.y, J = blockIdx.y;
-    if (!DIAG) {                                                           // the q-th pair I < J, rows of the upper triangle in order
-        int q = blockIdx.y;
-        I = 0;
-        while (q >= NT - 1 - I) {
-            q -= NT - 1 - I;
-            ++I;
-        }
-        J = I + 1 + q;
-    }
     const int Z = 2 * R;
-    const int nti = min(NTL, (Z - I * SPOD_MT + 15) >> 4), ntj = min(NTL, (Z - J * SPOD_MT + 15) >> 4);   // valid 16-row tiles (>= 1)
+    const SymgramTile tl = symgram_tile<DIAG, NTL>(Z, NT);
+    const int I = tl.I, J = tl.J, nti = tl.nti, ntj = tl.ntj;
     const size_t hw = (size_t)HW, E = (size_t)R * B * C * hw;
     const float gre = cst[k], gim = cst[NF + k];
     const float* sum0 = acc + (size_t)(2 * NF) * E;
@@ -145,7 +109,7 @@ __global__ __launch_bounds__(256) void spod_csd_kernel(const float* __restrict__
     bool lb[NTL];
 #pragma unroll
     for (int t = 0; t < NTL; ++t) {
-        const int za = I * SPOD_MT + 16 * t + l16, zb = J * SPOD_MT + 16 * t + l16;
+        const int za = I * SYMGRAM_MT + 16 * t + l16, zb = J * SYMGRAM_MT + 16 * t + l16;
         la[t] = t < nti && za < Z;
         lb[t] = t < ntj && zb < Z;
         const int zac = la[t] ? za : 0, zbc = lb[t] ? zb : 0;
@@ -170,7 +134,7 @@ __global__ __launch_bounds__(256) void spod_csd_kernel(const float* __restrict__
         for (int q = 0; q < SPOD_MAXC; ++q)
             if (q == cg) c = sel.ch[q];
         const size_t co = (size_t)c * hw;
-        for (int pc = pbeg + wave * SPOD_CHUNK; pc < pend; pc += 4 * SPOD_CHUNK) {
+        for (int pc = pbeg + wave * SYMGRAM_CHUNK; pc < pend; pc += 4 * SYMGRAM_CHUNK) {
             const int p0 = pc + kq * 16;
             float fa[NTL][16];
 #pragma unroll
@@ -194,54 +158,7 @@ __global__ __launch_bounds__(256) void spod_csd_kernel(const float* __restrict__
             }
         }
     }
-    if (wave > 0) {
-#pragma unroll
-        for (int it = 0; it < NTL; ++it)
-#pragma unroll
-            for (int jt = 0; jt < NTL; ++jt)
-                if ((!DIAG || it <= jt) && it < nti && jt < ntj) {
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) red[wave - 1][(it * NTL + jt) * 4 + v][l] = d[it][jt][v];
-                }
-    }
-    __syncthreads();
-    if (wave == 0) {
-        const int pidx = I * NT - I * (I - 1) / 2 + (J - I);
-        const int NP = NT * (NT + 1) / 2;
-        float* wp = ws + (((size_t)bz * NP + pidx) * P + slice) * (NTL * NTL * 256) + l;
-#pragma unroll
-        for (int it = 0; it < NTL; ++it)
-#pragma unroll
-            for (int jt = 0; jt < NTL; ++jt) {
-                const bool live = (!DIAG || it <= jt) && it < nti && jt < ntj;
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int a = (it * NTL + jt) * 4 + v;
-                    float t = d[it][jt][v];
-                    if (live) t = ((t + red[0][a][l]) + red[1][a][l]) + red[2][a][l];
-                    wp[a * 64] = t;                                        // every float of the partial is written: 0 where nothing is live
-                }
-            }
-    }
-}
-
-// G[i] = ws[i][0] + ws[i][1] + .. in slice order; i over [B NB][NP] partial blocks of `part` floats
-__global__ __launch_bounds__(256) void spod_reduce_kernel(const float* __restrict__ ws, float* __restrict__ G, int P, int part) {
-#pragma clang fp contract(off)
-    const size_t blk = blockIdx.x;
-    const int e = blockIdx.y * 256 + threadIdx.x;                          // < part
-    const float* wp = ws + blk * P * part + e;
-    float a = wp[0];
-    for (int s = 1; s < P; ++s) a += wp[(size_t)s * part];
-    G[blk * part + e] = a;
-}
-
-// offset of G[m][n], m <= n < 2 R, inside the (b, bin) plane [NP][part]
-__device__ __forceinline__ size_t spod_at(int m, int n, int NT, int part) {
-    const int I = m >> 6, J = n >> 6;
-    const int pidx = I * NT - I * (I - 1) / 2 + (J - I);
-    const int it = (m >> 4) & 3, jt = (n >> 4) & 3, i = m & 15, j = n & 15;
-    return (size_t)pidx * part + (size_t)(((it * 4 + jt) * 4 + (i & 3)) * 64 + j + 16 * (i >> 2));
+    symgram_store<DIAG, NTL>(d, tl, ws, P, NT);
 }
 
 // one thread per entry (m, n) of a (b, bin) plane: csd_raw [B NB][2][R][R]
@@ -253,8 +170,8 @@ __global__ __launch_bounds__(256) void spod_combine_kernel(const float* __restri
     const int NP = NT * (NT + 1) / 2;
     const float* Gp = G + (size_t)blockIdx.y * NP * part;
     const int lo = min(m, n), hi = max(m, n);
-    const float rr = Gp[spod_at(lo, hi, NT, part)], ii = Gp[spod_at(R + lo, R + hi, NT, part)];
-    const float rimn = Gp[spod_at(m, R + n, NT, part)], rinm = Gp[spod_at(n, R + m, NT, part)];
+    const float rr = Gp[symgram_at(lo, hi, NT, part)], ii = Gp[symgram_at(R + lo, R + hi, NT, part)];
+    const float rimn = Gp[symgram_at(m, R + n, NT, part)], rinm = Gp[symgram_at(n, R + m, NT, part)];
     float* o = raw + (size_t)blockIdx.y * 2 * R * R + e;
     o[0] = rr + ii;
     o[(size_t)R * R] = rimn - rinm;
@@ -316,16 +233,16 @@ extern "C" int tmg_ens_spod_plan(const int64_t* dims, int64_t* plan) {
     if (S < 1 || S > SPOD_MAXS || B < 1 || HW < 1 || Cg < 1 || Cg > SPOD_MAXC || NB < 1 || NB > SPOD_MAXB) return -1;
     if (HW >= (1ll << 31) - 256 || B * NB > 65535 || (S + 1) * B * SPOD_MAXC * HW >= (1ll << 40)) return -2;
     if (!plan) return -3;
-    const SpodPlan g = spod_plan(S, B, Cg, HW, NB, addr);
-    plan[0] = g.P;
-    plan[1] = g.L;
-    plan[2] = g.NP;
-    plan[3] = g.ws;
-    plan[4] = g.SL;
-    plan[5] = g.NT;
-    plan[6] = g.part;
-    plan[7] = g.vec;
-    plan[8] = g.MB;
+    const SpodPlan q = spod_plan(S, B, Cg, HW, NB, addr);
+    plan[0] = q.g.P;
+    plan[1] = q.L;
+    plan[2] = q.g.NP;
+    plan[3] = q.g.ws;
+    plan[4] = q.g.SL;
+    plan[5] = q.g.NT;
+    plan[6] = q.g.part;
+    plan[7] = q.vec;
+    plan[8] = q.MB;
     return 0;
 }
 
@@ -361,31 +278,16 @@ extern "C" int tmg_ens_spod_csd(const void* acc, const void* cst, const int64_t*
     const int64_t S = dims[0], B = dims[1], C = dims[2], HW = dims[3], NF = dims[4], Tn = dims[5], NB = dims[6], Cg = dims[7],
                   ws_floats = dims[8];
     const int64_t R = S + 1;
-    const SpodPlan g = spod_plan(S, B, Cg, HW, NB, (int64_t)((uintptr_t)acc & 15));
+    const SpodPlan q = spod_plan(S, B, Cg, HW, NB, (int64_t)((uintptr_t)acc & 15));
+    const SymgramPlan& g = q.g;
     if (g.ws >= (1ll << 40)) return -2;
     if (ws_floats < g.ws) return -1;
     if (!acc || !cst || !ws || !csd_raw) return -3;
     const float inv_t = (float)(1.0 / (double)Tn);
-    const dim3 gd((unsigned)g.P, (unsigned)g.NT, (unsigned)(B * NB)), go((unsigned)g.P, (unsigned)(g.NP - g.NT), (unsigned)(B * NB));
-#define SPOD_LAUNCH(DIAG_, NTL_, GRID_)                                                                                              \
-    hipLaunchKernelGGL((spod_csd_kernel<DIAG_, NTL_>), GRID_, dim3(256), 0, st, (const float*)acc, (const float*)cst, (float*)ws,   \
-                       (int)R, (int)B, (int)C, (int)HW, (int)NF, (int)NB, (int)Cg, (int)g.SL, (int)g.P, (int)g.NT, (int)g.vec, inv_t, sel)
-    if (g.part == 256) SPOD_LAUNCH(true, 1, gd);
-    else SPOD_LAUNCH(true, 4, gd);
+    SYMGRAM_LAUNCH(spod_csd_kernel, g, B * NB, st, (const float*)acc, (const float*)cst, (float*)ws, (int)R, (int)B, (int)C, (int)HW, (int)NF,
+                   (int)NB, (int)Cg, (int)g.SL, (int)g.P, (int)g.NT, (int)q.vec, inv_t, sel);
+    const float* G = symgram_reduce(g, B * NB, (float*)ws, st);
     TMG_CHECK_LAUNCH();
-    if (g.NT > 1) {
-        SPOD_LAUNCH(false, 4, go);
-        TMG_CHECK_LAUNCH();
-    }
-#undef SPOD_LAUNCH
-    const float* G = (const float*)ws;
-    if (g.P > 1) {
-        float* Gs = (float*)ws + B * NB * g.NP * g.P * g.part;
-        hipLaunchKernelGGL(spod_reduce_kernel, dim3((unsigned)(B * NB * g.NP), (unsigned)(g.part / 256)), dim3(256), 0, st, (const float*)ws,
-                           Gs, (int)g.P, (int)g.part);
-        TMG_CHECK_LAUNCH();
-        G = Gs;
-    }
     hipLaunchKernelGGL(spod_combine_kernel, dim3((unsigned)((R * R + 255) / 256), (unsigned)(B * NB)), dim3(256), 0, st, G, (float*)csd_raw,
                        (int)R, (int)g.NT, (int)g.part);
     TMG_CHECK_LAUNCH();

@@ -8,6 +8,8 @@ exact in fp32, so the mean plane, d2 and traj_dist2 must EQUAL the integer refer
 workspace, traj_dist2 and the outputs pre-filled with NaN.
 
 Worst share of the bound reached on an MI355X (the tests print it; LAB_NOTES.md): 0.0036 integer, 0.017 real data, 0.0064 end to end."""
+import hashlib
+import json
 import os
 import sys
 from types import SimpleNamespace
@@ -123,6 +125,41 @@ def test_real_data_stays_in_the_rounding_bound(idx):
     assert bool((rerr <= (S + 1) * K.U24 * np.abs(x64).sum(1) / S).all()), "%s mean plane" % what
     worst = K.check(got, ref, bnd, S, t_start, what)
     print("%s: cnt = %d + %d + %d; worst share of the bound %.4f" % (what, plan["L"], plan["P"], K.C_ROUND, worst))
+
+
+# ---- the bits of the commit before the Gram engine moved to csrc/tmg_symgram.h ----------------------------------------------------------
+# The code promises the same bits for the same inputs and has no float atomics, so the outputs of these cases are pinned by their
+# SHA-256 (tests/golden/symgram_bits.json, written by tests/golden/make_symgram_golden.py on an MI355X from the commit before).  Rows of
+# REAL_TABLE run as the test above runs them, and the 70-member case of the feed test as row 8: between them the one-tile instance,
+# NT = 1 with four tiles, the off-diagonal instance, P = 1 and P > 1, float4 and scalar loads and HW that is no multiple of 16
+# (tests/test_symgram_cpu.py asserts that coverage from the recorded plans).
+BITS = os.path.join(C.GOLDEN, "symgram_bits.json")
+BITS_ROWS = [K.REAL_TABLE[i] + (i,) for i in (0, 2, 3, 4, 5, 7)] + [(70, 3, 2, K.HWS[65], K.G2, "gauss", True, 8)]
+
+
+def bits_name(row):
+    return "S%d_B%d_C%d_hw%d_%s" % (row[0], row[1], row[2], row[3][0] * row[3][1], row[5])
+
+
+def energy_bits(S, B, Cc, hw, groups, kind, with_u, idx):
+    """-> (name -> SHA-256 of every output array: the scores of outf, the argmins of outi, traj_dist2 after every step and the mean
+    plane; what the plan says of the engine's branches)."""
+    xs, tgt = K.real_inputs(S, B, Cc, hw, kind, 6000 + idx)
+    sd = torch.tensor(K.SD[:Cc])
+    u = (0.5 + torch.rand(B, Cc, generator=torch.Generator().manual_seed(11))) if with_u else None
+    got, plan = run_energy(xs, tgt, K.chunk_sizes(S, idx % 3), idx % 2 == 0, idx % 2, sd=sd, u=u, groups=groups)
+    HW = hw[0] * hw[1]
+    return ({k: hashlib.sha256(np.ascontiguousarray(v).tobytes()).hexdigest() for k, v in sorted(got.items())},
+            {"part": plan["part"], "NT": plan["NT"], "P": plan["P"], "vec": HW % 4 == 0, "HW": HW, "Cg": 1})
+
+
+@pytest.mark.parametrize("row", BITS_ROWS, ids=bits_name)
+def test_real_data_gives_the_bits_of_the_commit_before_the_shared_engine(row):
+    gold = json.load(open(BITS))["gram"][bits_name(row)]
+    sha, plan = energy_bits(*row)
+    assert plan == gold["plan"]
+    assert set(sha) == set(gold["sha256"])
+    assert sha == gold["sha256"], [k for k in sha if sha[k] != gold["sha256"][k]]
 
 
 # ---- exact properties ------------------------------------------------------------------------------------------------------------------

@@ -10,6 +10,8 @@ with the reference's leading mode 1 - O(1e-9), target_captured 0.999979 for a ta
 0.000000) for psi_2's pattern in bin k1.
 Durations (pytest --durations): 32 tests in 3.7 s; modelPredSpod end to end 0.86 s, the first kernel call 0.27 s, every end-to-end
 case under 0.25 s, everything else 0.01 s or less."""
+import hashlib
+import json
 import math
 import os
 import sys
@@ -98,6 +100,35 @@ def test_csd_real_data_inside_the_counted_bound(name, offset):
     print("%s offset %g: cnt %d (L %d, P %d), max err %.3e, %.4f of the bound" % (name, offset, cnt, plan["L"], plan["P"], float(err.max()), share))
     assert bool((err <= bound).all()), (name, share)
     check_symmetry(raw)
+
+
+# ---- 2b. the CSD kernel: the bits of the commit before the Gram engine moved to csrc/tmg_symgram.h --------------------------------------
+# The same inputs give the same bits and there are no float atomics, so csd_raw of the real-data cases above, and of the two-macro-tile
+# case on the scalar load path, is pinned by its SHA-256 (tests/golden/symgram_bits.json, written by
+# tests/golden/make_symgram_golden.py on an MI355X from the commit before).
+BITS = os.path.join(C.GOLDEN, "symgram_bits.json")
+BITS_CASES = [(n, o, 0) for n, o in K.REAL_CASES] + [("r33_hw272_16bins", 0.0, 1)]
+
+
+def bits_name(c):
+    return "%s_offset%g_shift%d" % c
+
+
+def csd_bits(name, offset, shift):
+    """-> (SHA-256 of csd_raw, what the plan says of the engine's branches)"""
+    case = K.CSD_BY_NAME[name]
+    acc, cst = K.gauss_acc(case, 90 + K.CSD_CASES.index(case), offset)
+    raw, plan = run_csd(acc, cst, case, shift)
+    return (hashlib.sha256(raw.contiguous().numpy().tobytes()).hexdigest(),
+            {"part": plan["part"], "NT": plan["NT"], "P": plan["P"], "vec": plan["vec"], "HW": acc.shape[4], "Cg": len(case["channels"])})
+
+
+@pytest.mark.parametrize("c", BITS_CASES, ids=bits_name)
+def test_csd_real_data_gives_the_bits_of_the_commit_before_the_shared_engine(c):
+    gold = json.load(open(BITS))["spod"][bits_name(c)]
+    sha, plan = csd_bits(*c)
+    assert plan == gold["plan"]
+    assert sha == gold["sha256"]
 
 
 # ---- 3. the modes kernel -----------------------------------------------------------------------------------------------------------------
