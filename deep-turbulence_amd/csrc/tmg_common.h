@@ -73,6 +73,20 @@ __device__ __forceinline__ float out_scale_of(const float* kappa) {
         if (C_ >= ARR[1].n) { C_ -= ARR[1].n; PTR_ = ARR[2].p; STRIDE_ = ARR[2].stride; OFF_ = ARR[2].off; } \
     }
 #define TMG_PICK_OSEG(ARR, NL_, PTR_, STRIDE_, OFF_) TMG_PICK_SEG(float*, ARR, NL_, PTR_, STRIDE_, OFF_)
+// The staging form: concatenated input channel C_ of the kernel argument P_ -> two new locals, the base pointer of that channel
+// (segment pointer + offset + channel within the segment) and the segment's pixel stride; (ZERO_, 0) for a channel past P_.Cin or
+// when the caller's extra condition GUARD_ (`true` for none) fails, so that the loads built on them need no control flow.
+#define TMG_PICK_IN_CHANNEL(P_, C_, GUARD_, ZERO_, PTR_, STRIDE_)                                         \
+    const float* PTR_ = ZERO_;                                                                            \
+    int STRIDE_ = 0;                                                                                      \
+    {                                                                                                     \
+        int cl_ = (C_);                                                                                   \
+        if ((GUARD_) && cl_ < P_.Cin) {                                                                   \
+            TMG_PICK_SEG(const float*, P_.in, cl_, sp_, ss_, so_)                                         \
+            PTR_ = sp_ + so_ + cl_;                                                                       \
+            STRIDE_ = ss_;                                                                                \
+        }                                                                                                 \
+    }
 
 // 4 consecutive (concatenated) input channels c..c+3 of pixel (b,iy,ix), after padding rule,
 // optional affine and optional ReLU.

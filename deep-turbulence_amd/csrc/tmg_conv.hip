@@ -333,25 +333,7 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_kernel(ConvP p) {
         if (k + 2 < nst) {
             const int b_ = ti_b, oy0_ = ti_y * TH, ox0_ = ti_x * TW;
             const int c0 = ci * KCH, kch = min(KCH, p.Cin_pad - c0);
-            const float* tptr = zero_page;
-            int tss = 0;
-            {
-                int cl = c0 + 4 * pc4;
-                if (4 * pc4 < kch && cl < p.Cin) {
-                    const float* sp = p.in[0].p;
-                    int ss = p.in[0].stride, so = p.in[0].off;
-                    if (cl >= p.in[0].n) {
-                        cl -= p.in[0].n;
-                        sp = p.in[1].p; ss = p.in[1].stride; so = p.in[1].off;
-                        if (cl >= p.in[1].n) {
-                            cl -= p.in[1].n;
-                            sp = p.in[2].p; ss = p.in[2].stride; so = p.in[2].off;
-                        }
-                    }
-                    tptr = sp + so + cl;
-                    tss = ss;
-                }
-            }
+            TMG_PICK_IN_CHANNEL(p, c0 + 4 * pc4, 4 * pc4 < kch, zero_page, tptr, tss)
             const int iy0 = oy0_ - halo, ix0 = ox0_ - halo;
             const int tbv = b_ * p.Hin * p.Win * tss;
             oobm = 0;

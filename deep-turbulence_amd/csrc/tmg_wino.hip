@@ -90,6 +90,139 @@ extern "C" int tmg_conv_wino_pack(const void* w, void* U, int64_t Cout, int64_t 
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Stages shared by the Winograd forwards (wino_fwd_kernel, wino_fwdp_kernel, wino_fwd3_kernel, wino_nn_kernel), each written once.
+// A new kernel of the family uses these and writes only its input transform and its MFMA loop.  They are macros on purpose (as
+// TMG_PICK_SEG: text keeps every instance's code object what it was) and name the locals of the kernel they expand in: the kernel
+// argument p, lds, tid, the stage counter k of `for (k = -2; k < nst; ++k)`, and what the stages before them declare.
+// ---------------------------------------------------------------------------------------------------------------------------------
+constexpr int NT = 512;                    // threads that stage (and, except in wino_fwdp_kernel, multiply)
+constexpr int TH = 8, TW = 16, PH = TH + 2, PW = TW + 2, PP = PH * PW;   // output tile, raw patch (halo 1)
+constexpr int KC = 32, CS = KC + 8;        // channels per chunk, raw-patch pixel stride (words)
+constexpr int RAWW = PP * CS;              // words per raw buffer
+constexpr int UPI = (PP * (KC / 4) + NT - 1) / NT;   // raw float4 items per thread (3)
+constexpr int VS = KC + 8;                 // V row stride (words): a fragment read is a float4 per lane at li * VS + 4 q
+constexpr int VPL = 32 * VS;               // words per V position plane (32 Winograd tiles)
+
+// pixel tile T_ of the batch -> b_, ty_, tx_ (t_ is scratch)
+#define TMG_WN_TILE(T_)                                                                                               \
+    int t_ = (T_);                                                                                                    \
+    const int tx_ = t_ % p.tiles_x; t_ /= p.tiles_x;                                                                  \
+    const int ty_ = t_ % p.tiles_y;                                                                                   \
+    const int b_ = t_ / p.tiles_y;
+// persistent grid: block x owns the pixel tiles x, x + G, ..: nmine tiles of nchunks 32-channel chunks = nst stages
+#define TMG_WN_CURSORS                                                                                                \
+    const int G = gridDim.x;                                                                                          \
+    const int nmine = (int)blockIdx.x < p.ntiles ? (p.ntiles - (int)blockIdx.x + G - 1) / G : 0;                      \
+    const int nchunks = p.nchunks, nst = nmine * nchunks;
+// ---- lean staging state: a thread owns channel quad pc4 of every 64th patch pixel; pv holds the loads in flight ---------------
+#define TMG_WN_PATCH_TABLE                                                                                            \
+    const int pc4 = tid & 7, ppix0 = tid >> 3;                                                                        \
+    unsigned pyx[UPI];                                                                                                \
+    _Pragma("unroll") for (int u = 0; u < UPI; ++u) {                                                                 \
+        const int pix = min(ppix0 + u * 64, PP - 1);                                                                  \
+        const int py = pix / PW, px = pix - py * PW;                                                                  \
+        pyx[u] = ((unsigned)py << 16) | (unsigned)px;                                                                 \
+    }                                                                                                                 \
+    float4 pv[UPI];
+// ---- commit stage k+1: the loads issued two rounds ago, ReLU applied, into the raw buffer nobody reads in this round ----------
+#define TMG_WN_COMMIT                                                                                                 \
+    if (k >= -1 && k + 1 < nst) {                                                                                     \
+        float* rb_ = lds + ((k + 1) & 1) * RAWW;                                                                      \
+        _Pragma("unroll") for (int u = 0; u < UPI; ++u) {                                                             \
+            if (ppix0 + u * 64 < PP) {                                                                                \
+                float4 v = pv[u];                                                                                     \
+                if (p.relu_in) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); } \
+                *reinterpret_cast<float4*>(rb_ + (ppix0 + u * 64) * CS + 4 * pc4) = v;                                \
+            }                                                                                                         \
+        }                                                                                                             \
+    }
+// ---- issue the loads of stage k+2 (cursors: chunk ci of pixel tile ti) ---------------------------------------------------------
+// head: the tile's patch origin and this thread's channel -> (tptr, tss); tail: advance the cursor
+#define TMG_WN_ISSUE_HEAD                                                                                             \
+    TMG_WN_TILE(ti)                                                                                                   \
+    const int iy0 = ty_ * TH - 1, ix0 = tx_ * TW - 1;                                                                 \
+    TMG_PICK_IN_CHANNEL(p, ci * KC + 4 * pc4, true, tmg_zero_page, tptr, tss)
+#define TMG_WN_ISSUE_TAIL if (++ci == nchunks) { ci = 0; ti += G; }
+// tbv: pixel index of image b_'s first pixel;  item U_ under the padding rule.  TMG_WN_PXI: its pixel index in the batch (32 bits: the launcher refuses B H W >= 2^31);
+// TMG_WN_DEAD: it reads the zero page (zero padding, or an item past the patch).  Both are expressions, not locals of
+// TMG_WN_PIXEL, on purpose: as locals (the index computed in front of the select instead of in its arm, the condition as a named
+// bool) they compiled to other code in wino_fwd_kernel, wino_fwd3_kernel and wino_nn_kernel.
+#define TMG_WN_PIXEL(U_)                                                                                              \
+    const int iy = iy0 + (int)(pyx[U_] >> 16), ix = ix0 + (int)(pyx[U_] & 0xffffu);                                   \
+    const int iyc = min(max(iy, 0), p.Hin - 1), ixc = min(max(ix, 0), p.Win - 1);                                     \
+    const bool oob = !p.pad_rep && (iy != iyc || ix != ixc);
+#define TMG_WN_TBV const unsigned tbv = (unsigned)b_ * (unsigned)(p.Hin * p.Win);
+#define TMG_WN_PXI (tbv + (unsigned)iyc * (unsigned)p.Win + (unsigned)ixc)
+#define TMG_WN_DEAD(U_) (oob || ppix0 + U_ * 64 >= PP)
+// LOAD_(dst float4, address): TMG_WN_LD (plain) or TMG_WN_LD_NT
+#define TMG_WN_ISSUE(LOAD_)                                                                                           \
+    if (k + 2 < nst) {                                                                                                \
+        TMG_WN_ISSUE_HEAD                                                                                             \
+        TMG_WN_TBV                                                                                                    \
+        _Pragma("unroll") for (int u = 0; u < UPI; ++u) {                                                             \
+            TMG_WN_PIXEL(u)                                                                                           \
+            const float* a_ = TMG_WN_DEAD(u) ? tmg_zero_page : tptr + (size_t)TMG_WN_PXI * (unsigned)tss;             \
+            LOAD_(pv[u], a_)                                                                                          \
+        }                                                                                                             \
+        TMG_WN_ISSUE_TAIL                                                                                             \
+    }
+#define TMG_WN_LD(D_, A_) D_ = *reinterpret_cast<const float4*>(A_);
+// streamed once: non-temporal, so that the activations do not push the U operand (re-read by every tile) out of L2
+#define TMG_WN_LD_NT(D_, A_)                                                                                          \
+    {                                                                                                                 \
+        const f32x4 nt_ = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(A_));                             \
+        D_ = make_float4(nt_[0], nt_[1], nt_[2], nt_[3]);                                                             \
+    }
+// float4 arithmetic of the input transforms
+#define TMG_W4(OP, A_, B_) make_float4(A_.x OP B_.x, A_.y OP B_.y, A_.z OP B_.z, A_.w OP B_.w)
+// ---- bias and the four output tiles Y[output pixel of the 2x2 tile][m-tile][n-tile] of a lane (ntile0, ntt, q of the kernel) ----
+// The bias of this lane's channels, loaded ONCE and branch-free (no bias / channels past the end: the zero page): a load inside the
+// epilogue's conditional blocks makes the compiler put `s_waitcnt vmcnt(0)` in front of EVERY store there - each of the 16 stores
+// of a tile then waits for the one before it and for the whole prefetched U ring (round 6: 6-14 % of the launch).  Y starts at
+// the bias instead of adding it in the epilogue, and returns to it after every epilogue.
+#define TMG_WN_Y_RESET                                                                                                \
+    _Pragma("unroll") for (int o = 0; o < 4; ++o) _Pragma("unroll") for (int m = 0; m < 2; ++m)                       \
+        _Pragma("unroll") for (int n = 0; n < NPW; ++n) Y[o][m][n] = bvr[n];
+#define TMG_WN_BIAS_Y                                                                                                 \
+    f32x4 bvr[NPW];                                                                                                   \
+    _Pragma("unroll") for (int n = 0; n < NPW; ++n) {                                                                 \
+        const int n0 = (ntile0 + n) * 16 + 4 * q;                                                                     \
+        const float* bp = (p.bias != nullptr && ntile0 + n < ntt && n0 < p.Cout) ? p.bias + n0 : tmg_zero_page;       \
+        const float4 b4 = *reinterpret_cast<const float4*>(bp);                                                       \
+        bvr[n] = (f32x4){b4.x, b4.y, b4.z, b4.w};                                                                     \
+    }                                                                                                                 \
+    f32x4 Y[4][2][NPW];                                                                                               \
+    TMG_WN_Y_RESET
+// ---- epilogue of pixel tile tm (after TMG_WN_TILE(tm)): lane (LI_, Q_) holds channels 4 Q_ .. 4 Q_ + 3 (of each n-tile) of Winograd
+//      tile 16 m + LI_; Y -> NHWC float4 stores, Y back to the bias, cursor to the next tile.  STORE_(f32x4, address): TMG_WN_ST or
+//      TMG_WN_ST_NT.
+#define TMG_WN_EPILOGUE(LI_, Q_, STORE_)                                                                              \
+    {                                                                                                                 \
+        _Pragma("unroll") for (int m = 0; m < 2; ++m) {                                                               \
+            const int wt = 16 * m + LI_;                                                                              \
+            const int oyb = ty_ * TH + 2 * (wt >> 3), oxb = tx_ * TW + 2 * (wt & 7);                                  \
+            _Pragma("unroll") for (int n = 0; n < NPW; ++n) {                                                         \
+                const int n0 = (ntile0 + n) * 16 + 4 * Q_;                                                            \
+                if (ntile0 + n < ntt && n0 < p.Cout) {                                                                \
+                    int nl = n0;                                                                                      \
+                    TMG_PICK_OSEG(p.out, nl, optr, ostride, ooff)                                                     \
+                    _Pragma("unroll") for (int o = 0; o < 4; ++o) {                                                   \
+                        const int oy = oyb + (o >> 1), ox = oxb + (o & 1);                                            \
+                        if (oy < p.Hin && ox < p.Win) {                                                               \
+                            const unsigned opx = ((unsigned)b_ * (unsigned)p.Hin + (unsigned)oy) * (unsigned)p.Win + (unsigned)ox; \
+                            STORE_(Y[o][m][n], optr + (size_t)opx * (unsigned)ostride + ooff + nl)                    \
+                        }                                                                                             \
+                    }                                                                                                 \
+                }                                                                                                     \
+            }                                                                                                         \
+        }                                                                                                             \
+        TMG_WN_Y_RESET                                                                                                \
+        cm = 0; tm += G;                                                                                              \
+    }
+#define TMG_WN_ST(V_, A_) *reinterpret_cast<float4*>(A_) = make_float4(V_[0], V_[1], V_[2], V_[3]);
+#define TMG_WN_ST_NT(V_, A_) __builtin_nontemporal_store(V_, reinterpret_cast<f32x4*>(A_));
+
 // NPW: 16-channel output tiles per wave.  2: a block covers up to 256 output channels (wave w: n-tiles 2w, 2w+1).  1: up to 128 -
 // the contractions with 64..128 output channels (the ConvLSTM block's out-conv input gradient, 40 -> 104 at the first level) would leave
 // waves 4-7 of the 2-tile form multiplying repeated tiles; with one tile per wave all eight waves carry live work.
@@ -153,20 +286,24 @@ extern "C" int tmg_conv_wino_pack(const void* w, void* U, int64_t Cout, int64_t 
         }                                                                                                             \
     }
 #define TMG_WN_ULOAD(DST, PTR, BOFF) DST = tmg_bload4(urs, BOFF, (unsigned)(((PTR) - p.U) * 4));
+// ring slot R <- the U fragments of position POS of the chunk whose operand starts at UB and has KGN 16-channel groups (1 or 2: the
+// second set repeats the first when there is one group)
+#define TMG_WN_LOADB(R, UB, KGN, POS)                                                                                 \
+    {                                                                                                                 \
+        const float* up_ = (UB) + (size_t)(POS) * pos_stride;                                                         \
+        _Pragma("unroll") for (int n = 0; n < NPW; ++n) {                                                             \
+            TMG_WN_ULOAD(bfr[R][0][n], up_, boff[n])                                                                  \
+            TMG_WN_ULOAD(bfr[R][1][n], up_ + (size_t)((KGN) - 1) * kb_stride, boff[n])                                \
+        }                                                                                                             \
+    }
 // (TMG_PACKED_F32: this kernel keeps the packed-fp32 instructions the rest of the file is built without - its float4 input transform and
 // the tile additions of the output transform halve their instruction count: gate conv 2.045 -> 2.023 ms, conditioning contraction
 // 0.663 -> 0.636 ms; wino_fwdp_kernel, wino_nn_kernel (+3 %) and wino_wgrad_kernel (+-0) measured no better with them, round 6)
 template <int NPW>
 __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd_kernel(WinoP p) {
+    static_assert(NPW == 2, "the one-tile shapes run on wino_fwdp_kernel");
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int NT = 512;
-    constexpr int TH = 8, TW = 16, PH = TH + 2, PW = TW + 2, PP = PH * PW;   // output tile, raw patch (halo 1)
-    constexpr int KC = 32, CS = KC + 8;        // channels per chunk, raw-patch pixel stride (words)
-    constexpr int VS = KC + 8;                 // V row stride (words): a fragment read is a float4 per lane at li * VS + 4 q
-    constexpr int RAWW = PP * CS;              // words per raw buffer
-    constexpr int VPL = 32 * VS;               // words per V position plane (32 Winograd tiles)
     float* Vb = lds + 2 * RAWW;                // [16][32][VS]
-    constexpr int UPI = (PP * (KC / 4) + NT - 1) / NT;   // raw float4 items per thread (3)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, q = lane >> 4;
@@ -179,16 +316,7 @@ __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd_kernel(WinoP p
 #pragma unroll
     for (int n = 0; n < NPW; ++n) boff[n] = 4u * (unsigned)(li * 16 + 4 * q + min(ntile0 + n, ntt - 1) * 256);
 
-    // ---- lean staging state: a thread owns channel quad pc4 of every 64th patch pixel -------------------------------------
-    const int pc4 = tid & 7, ppix0 = tid >> 3;
-    unsigned pyx[UPI];
-#pragma unroll
-    for (int u = 0; u < UPI; ++u) {
-        const int pix = min(ppix0 + u * 64, PP - 1);
-        const int py = pix / PW, px = pix - py * PW;
-        pyx[u] = ((unsigned)py << 16) | (unsigned)px;
-    }
-    float4 pv[UPI];
+    TMG_WN_PATCH_TABLE
 
     // ---- transform mapping: item = (Winograd tile t, channel quad c4), rows xi = 2 h, 2 h + 1 of the 4x4 result; the two halves
     //      live in different waves (no intra-wave bank conflicts between them)
@@ -197,94 +325,25 @@ __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd_kernel(WinoP p
     const int traw = ((2 * tty) * PW + 2 * ttx) * CS + 4 * tc4;   // word offset of patch pixel (0, 0) of the tile in a raw buffer
     const int tv = tt * VS + 4 * tc4;                             // word offset inside a V plane
 
-    const int G = gridDim.x;
-    const int nmine = (int)blockIdx.x < p.ntiles ? (p.ntiles - (int)blockIdx.x + G - 1) / G : 0;
-    const int nchunks = p.nchunks, nst = nmine * nchunks;
-    // cursors: ci/ti = chunk / tile of the stage being issued, cc = chunk being committed, cm/tm = chunk / tile being computed
-    int ci = 0, cc = 0, cm = 0;
+    TMG_WN_CURSORS
+    // cursors: ci/ti = chunk / tile of the stage being issued, cm/tm = chunk / tile being computed
+    int ci = 0, cm = 0;
     int ti = blockIdx.x, tm = blockIdx.x;
 
     // U through a buffer descriptor: scalar byte offset (position, channel group) + the lane's constant 32-bit offset - no vector
     // address arithmetic per load (flat global loads cost a 64-bit vector add each: the fp32 MFMA shares the vector ALUs)
     const __amdgpu_buffer_rsrc_t urs = tmg_make_rsrc(p.U, 16u * (unsigned)pos_stride * 4u);
-    // The bias of this lane's channels, loaded ONCE and branch-free (no bias / channels past the end: the zero page): a load inside the
-    // epilogue's conditional blocks makes the compiler put `s_waitcnt vmcnt(0)` in front of EVERY store there - each of the 16 stores
-    // of a tile then waits for the one before it and for the whole prefetched U ring (round 6: 6-14 % of the launch).  Y starts at
-    // the bias instead of adding it in the epilogue.
-    f32x4 bvr[NPW];
-#pragma unroll
-    for (int n = 0; n < NPW; ++n) {
-        const int n0 = (ntile0 + n) * 16 + 4 * q;
-        const float* bp = (p.bias != nullptr && ntile0 + n < ntt && n0 < p.Cout) ? p.bias + n0 : tmg_zero_page;
-        const float4 b4 = *reinterpret_cast<const float4*>(bp);
-        bvr[n] = (f32x4){b4.x, b4.y, b4.z, b4.w};
-    }
-    f32x4 Y[4][2][NPW];   // [output pixel of the 2x2 tile][m-tile][n-tile]
+    TMG_WN_BIAS_Y
     f32x4 T0[2][NPW], T1[2][NPW];   // column sums of a middle row (TMG_WN_POSITION)
-#pragma unroll
-    for (int o = 0; o < 4; ++o)
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int n = 0; n < NPW; ++n) Y[o][m][n] = bvr[n];
 
-    float4 bfr[4][2][NPW];   // U fragments [ring][16-channel group][n-tile], three positions ahead of the MFMAs
+    float4 bfr[4][2][NPW];   // U fragments [ring][16-channel group][n-tile], LEAD positions ahead of the MFMAs
     for (int k = -2; k < nst; ++k) {
-        // ---- commit stage k+1 --------------------------------------------------------------------------------------------------
-        if (k >= -1 && k + 1 < nst) {
-            float* rb = lds + ((k + 1) & 1) * RAWW;
-#pragma unroll
-            for (int u = 0; u < UPI; ++u) {
-                if (ppix0 + u * 64 < PP) {
-                    float4 v = pv[u];
-                    if (p.relu_in) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-                    *reinterpret_cast<float4*>(rb + (ppix0 + u * 64) * CS + 4 * pc4) = v;
-                }
-            }
-            if (++cc == nchunks) cc = 0;
-        }
-        // ---- issue the loads of stage k+2 -------------------------------------------------------------------------------------
-        if (k + 2 < nst) {
-            int t_ = ti;
-            const int tx_ = t_ % p.tiles_x; t_ /= p.tiles_x;
-            const int ty_ = t_ % p.tiles_y;
-            const int b_ = t_ / p.tiles_y;
-            const int iy0 = ty_ * TH - 1, ix0 = tx_ * TW - 1;
-            const float* tptr = tmg_zero_page;
-            int tss = 0;
-            {
-                int cl = ci * KC + 4 * pc4;
-                if (cl < p.Cin) {
-                    const float* sp = p.in[0].p;
-                    int ss = p.in[0].stride, so = p.in[0].off;
-                    if (cl >= p.in[0].n) {
-                        cl -= p.in[0].n;
-                        sp = p.in[1].p; ss = p.in[1].stride; so = p.in[1].off;
-                        if (cl >= p.in[1].n) {
-                            cl -= p.in[1].n;
-                            sp = p.in[2].p; ss = p.in[2].stride; so = p.in[2].off;
-                        }
-                    }
-                    tptr = sp + so + cl;
-                    tss = ss;
-                }
-            }
-            const unsigned tbv = (unsigned)b_ * (unsigned)(p.Hin * p.Win);   // 32-bit pixel index: the launcher refuses B H W >= 2^31
-#pragma unroll
-            for (int u = 0; u < UPI; ++u) {
-                const int iy = iy0 + (int)(pyx[u] >> 16), ix = ix0 + (int)(pyx[u] & 0xffffu);
-                const int iyc = min(max(iy, 0), p.Hin - 1), ixc = min(max(ix, 0), p.Win - 1);
-                const bool oob = !p.pad_rep && (iy != iyc || ix != ixc);
-                const float* a_ = (oob || ppix0 + u * 64 >= PP) ? tmg_zero_page : tptr + (size_t)(tbv + (unsigned)iyc * (unsigned)p.Win + (unsigned)ixc) * (unsigned)tss;
-                pv[u] = *reinterpret_cast<const float4*>(a_);
-            }
-            if (++ci == nchunks) { ci = 0; ti += G; }
-        }
+        TMG_WN_COMMIT
+        TMG_WN_ISSUE(TMG_WN_LD)
         if (k >= 0) {
             // ---- input transform of stage k: V = B^T d B,  B^T = [[1,0,-1,0],[0,1,1,0],[0,-1,1,0],[0,1,0,-1]] ----------------------
             {
                 const float* rb = lds + (k & 1) * RAWW + traw;
-#define TMG_W4(OP, A_, B_) make_float4(A_.x OP B_.x, A_.y OP B_.y, A_.z OP B_.z, A_.w OP B_.w)
                 // row pass, one patch column at a time (12 registers of raw data live instead of 48):
                 // th = 0: xi 0 = row0 - row2, xi 1 = row1 + row2 ; th = 1 (rows 1, 2, 3 loaded): xi 2 = row2 - row1, xi 3 = row1 - row3
                 float4 t[2][4];
@@ -304,7 +363,6 @@ __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd_kernel(WinoP p
                     *reinterpret_cast<float4*>(vb + 2 * VPL) = TMG_W4(-, t[e][2], t[e][1]);
                     *reinterpret_cast<float4*>(vb + 3 * VPL) = TMG_W4(-, t[e][3], t[e][1]);      // -V at nu = 3 (TMG_WN_POSITION)
                 }
-#undef TMG_W4
             }
             __syncthreads();
             // ---- 16 position GEMMs over this chunk, output transform folded in ---------------------------------------------------
@@ -313,21 +371,14 @@ __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd_kernel(WinoP p
                 const int kgn = min(KC, p.Cin_pad - c0) >> 4;   // 16-channel groups in this chunk (1 or 2)
                 const float* ub = p.U + (size_t)(c0 >> 4) * kb_stride;
                 const float4* v4 = reinterpret_cast<const float4*>(Vb) + (li * VS + 4 * q) / 4;
-#define TMG_WN_LOADB(R, UB, KGN, POS)                                                                                 \
-                {                                                                                                     \
-                    const float* up_ = (UB) + (size_t)(POS) * pos_stride;                                             \
-                    _Pragma("unroll") for (int n = 0; n < NPW; ++n) {                                                 \
-                        TMG_WN_ULOAD(bfr[R][0][n], up_, boff[n])                                                    \
-                        TMG_WN_ULOAD(bfr[R][1][n], up_ + (size_t)((KGN) - 1) * kb_stride, boff[n])                  \
-                    }                                                                                                 \
-                }
                 // LEAD: how many positions ahead of the MFMAs the U fragments are fetched.  One position is 2 x 1 024 matrix cycles on a
                 // SIMD and U is L2-resident.  With two n-tiles per wave a lead of two positions keeps three ring slots live instead of
                 // four: 238 registers against 254 with the column sums of TMG_WN_POSITION; measured equal over the step's shapes (gate
-                // conv 2.045 / 2.081 ms, conditioning contraction 0.663 / 0.642 ms at a lead of 2 / 3).
-                constexpr int LEAD = NPW == 2 ? 2 : 3;
-                if (k == 0) { TMG_WN_LOADB(0, ub, kgn, 0) TMG_WN_LOADB(1, ub, kgn, 1) if (LEAD == 3) TMG_WN_LOADB(2, ub, kgn, 2) }
-                // (every later stage gets its first three fragment sets from the previous stage's last positions)
+                // conv 2.045 / 2.081 ms, conditioning contraction 0.663 / 0.642 ms at a lead of 2 / 3).  (wino_fwdp_kernel, one n-tile
+                // per wave, leads by three.)
+                constexpr int LEAD = 2;
+                if (k == 0) { TMG_WN_LOADB(0, ub, kgn, 0) TMG_WN_LOADB(1, ub, kgn, 1) }
+                // (every later stage gets its first LEAD fragment sets from the previous stage's last positions)
                 // operand of the next stage (the next chunk of this tile, or chunk 0 of the next tile: every tile uses the same U)
                 const int c0n = (cm + 1 == nchunks) ? 0 : c0 + KC;
                 const int kgn_n = min(KC, p.Cin_pad - c0n) >> 4;
@@ -340,7 +391,7 @@ __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd_kernel(WinoP p
                     constexpr int R = pos & 3;
                     // (without the scheduling fences the compiler hoists all 16 positions' LDS reads to the top and spills)
                     __builtin_amdgcn_sched_barrier(0);
-                    // U fragments three positions ahead (a position is only 32 MFMAs per wave: one position of lead does not cover
+                    // U fragments LEAD positions ahead (a position is only 32 MFMAs per wave: one position of lead does not cover
                     // the L2 latency), V fragments of this position from LDS
                     if (pos + LEAD < 16) TMG_WN_LOADB((pos + LEAD) & 3, ub, kgn, pos + LEAD)
                     else TMG_WN_LOADB((pos + LEAD) & 3, ubn, kgn_n, pos + LEAD - 16)
@@ -357,43 +408,10 @@ __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd_kernel(WinoP p
                 TMG_WN_P(0) TMG_WN_P(1) TMG_WN_P(2) TMG_WN_P(3) TMG_WN_P(4) TMG_WN_P(5) TMG_WN_P(6) TMG_WN_P(7)
                 TMG_WN_P(8) TMG_WN_P(9) TMG_WN_P(10) TMG_WN_P(11) TMG_WN_P(12) TMG_WN_P(13) TMG_WN_P(14) TMG_WN_P(15)
 #undef TMG_WN_P
-#undef TMG_WN_LOADB
             }
             if (cm + 1 == nchunks) {
-                // ---- epilogue: lane (li, q) holds channels 4 q .. 4 q + 3 (of each n-tile) of Winograd tile 16 m + li -------------
-                int t_ = tm;
-                const int tx_ = t_ % p.tiles_x; t_ /= p.tiles_x;
-                const int ty_ = t_ % p.tiles_y;
-                const int b_ = t_ / p.tiles_y;
-#pragma unroll
-                for (int m = 0; m < 2; ++m) {
-                    const int wt = 16 * m + li;
-                    const int oyb = ty_ * TH + 2 * (wt >> 3), oxb = tx_ * TW + 2 * (wt & 7);
-#pragma unroll
-                    for (int n = 0; n < NPW; ++n) {
-                        const int n0 = (ntile0 + n) * 16 + 4 * q;
-                        if (ntile0 + n < ntt && n0 < p.Cout) {
-                            int nl = n0;
-                            TMG_PICK_OSEG(p.out, nl, optr, ostride, ooff)
-#pragma unroll
-                            for (int o = 0; o < 4; ++o) {
-                                const int oy = oyb + (o >> 1), ox = oxb + (o & 1);
-                                if (oy < p.Hin && ox < p.Win) {
-                                    const unsigned opx = ((unsigned)b_ * (unsigned)p.Hin + (unsigned)oy) * (unsigned)p.Win + (unsigned)ox;
-                                    *reinterpret_cast<float4*>(optr + (size_t)opx * (unsigned)ostride + ooff + nl) =
-                                        make_float4(Y[o][m][n][0], Y[o][m][n][1], Y[o][m][n][2], Y[o][m][n][3]);
-                                }
-                            }
-                        }
-                    }
-                }
-#pragma unroll
-                for (int o = 0; o < 4; ++o)
-#pragma unroll
-                    for (int m = 0; m < 2; ++m)
-#pragma unroll
-                        for (int n = 0; n < NPW; ++n) Y[o][m][n] = bvr[n];
-                cm = 0; tm += G;
+                TMG_WN_TILE(tm)
+                TMG_WN_EPILOGUE(li, q, TMG_WN_ST)
             } else {
                 ++cm;
             }
@@ -417,16 +435,10 @@ __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd_kernel(WinoP p
 template <int NPW>
 __global__ __launch_bounds__(768, 1) void wino_fwdp_kernel(WinoP p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int TH = 8, TW = 16;
-    constexpr int KC = 32;
-    constexpr int VS = KC + 8;                 // V row stride (words): a fragment read is a float4 per lane at li * VS + 4 q
-    constexpr int VPL = 32 * VS;               // words per V position plane (32 Winograd tiles)
     constexpr int VBUF = 16 * VPL;             // words per V buffer
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int G = gridDim.x;
-    const int nmine = (int)blockIdx.x < p.ntiles ? (p.ntiles - (int)blockIdx.x + G - 1) / G : 0;
-    const int nchunks = p.nchunks, nst = nmine * nchunks;
+    TMG_WN_CURSORS
     if (wave >= 8) {
         // ================================================= producers =================================================
         const int ptid = tid - 512;
@@ -435,31 +447,10 @@ __global__ __launch_bounds__(768, 1) void wino_fwdp_kernel(WinoP p) {
         const int tv = tt * VS + 4 * tc4;
         int ci = 0, ti = blockIdx.x;
         for (int k = 0; k < nst; ++k) {
-            int t_ = ti;
-            const int tx_ = t_ % p.tiles_x; t_ /= p.tiles_x;
-            const int ty_ = t_ % p.tiles_y;
-            const int b_ = t_ / p.tiles_y;
+            TMG_WN_TILE(ti)
             const int iy0 = ty_ * TH - 1 + 2 * tty, ix0 = tx_ * TW - 1 + 2 * ttx;
-            const float* tptr = tmg_zero_page;
-            int tss = 0;
-            {
-                int cl = ci * KC + 4 * tc4;
-                if (cl < p.Cin) {
-                    const float* sp = p.in[0].p;
-                    int ss = p.in[0].stride, so = p.in[0].off;
-                    if (cl >= p.in[0].n) {
-                        cl -= p.in[0].n;
-                        sp = p.in[1].p; ss = p.in[1].stride; so = p.in[1].off;
-                        if (cl >= p.in[1].n) {
-                            cl -= p.in[1].n;
-                            sp = p.in[2].p; ss = p.in[2].stride; so = p.in[2].off;
-                        }
-                    }
-                    tptr = sp + so + cl;
-                    tss = ss;
-                }
-            }
-            const unsigned tbv = (unsigned)b_ * (unsigned)(p.Hin * p.Win);
+            TMG_PICK_IN_CHANNEL(p, ci * KC + 4 * tc4, true, tmg_zero_page, tptr, tss)
+            TMG_WN_TBV
             float4 d[4][4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -483,7 +474,6 @@ __global__ __launch_bounds__(768, 1) void wino_fwdp_kernel(WinoP p) {
                         d[r][c].z = fmaxf(d[r][c].z, 0.f); d[r][c].w = fmaxf(d[r][c].w, 0.f);
                     }
             }
-#define TMG_W4(OP, A_, B_) make_float4(A_.x OP B_.x, A_.y OP B_.y, A_.z OP B_.z, A_.w OP B_.w)
             float* vbuf = lds + (k & 1) * VBUF + tv;
 #pragma unroll
             for (int xi = 0; xi < 4; ++xi) {
@@ -501,8 +491,7 @@ __global__ __launch_bounds__(768, 1) void wino_fwdp_kernel(WinoP p) {
                 *reinterpret_cast<float4*>(vb + 2 * VPL) = TMG_W4(-, t[2], t[1]);
                 *reinterpret_cast<float4*>(vb + 3 * VPL) = TMG_W4(-, t[3], t[1]);                 // -V at nu = 3
             }
-#undef TMG_W4
-            if (++ci == nchunks) { ci = 0; ti += G; }
+            TMG_WN_ISSUE_TAIL
             __syncthreads();       // stage k is in V[k & 1]; the multipliers have left V[(k + 1) & 1]
         }
         return;
@@ -518,35 +507,13 @@ __global__ __launch_bounds__(768, 1) void wino_fwdp_kernel(WinoP p) {
     for (int n = 0; n < NPW; ++n) boff[n] = 4u * (unsigned)(li * 16 + 4 * q + min(ntile0 + n, ntt - 1) * 256);
     const __amdgpu_buffer_rsrc_t urs = tmg_make_rsrc(p.U, 16u * (unsigned)pos_stride * 4u);
     int cm = 0, tm = blockIdx.x;
-    f32x4 bvr[NPW];       // bias in registers, Y starts from it: no load between the epilogue's stores (see wino_fwd_kernel)
-#pragma unroll
-    for (int n = 0; n < NPW; ++n) {
-        const int n0 = (ntile0 + n) * 16 + 4 * q;
-        const float* bp = (p.bias != nullptr && ntile0 + n < ntt && n0 < p.Cout) ? p.bias + n0 : tmg_zero_page;
-        const float4 b4 = *reinterpret_cast<const float4*>(bp);
-        bvr[n] = (f32x4){b4.x, b4.y, b4.z, b4.w};
-    }
-    f32x4 Y[4][2][NPW];
-#pragma unroll
-    for (int o = 0; o < 4; ++o)
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int n = 0; n < NPW; ++n) Y[o][m][n] = bvr[n];
+    TMG_WN_BIAS_Y
     f32x4 T0[2][NPW], T1[2][NPW];
     float4 bfr[4][2][NPW];
     for (int k = 0; k < nst; ++k) {
         const int c0 = cm * KC;
         const int kgn = min(KC, p.Cin_pad - c0) >> 4;
         const float* ub = p.U + (size_t)(c0 >> 4) * kb_stride;
-#define TMG_WN_LOADB(R, UB, KGN, POS)                                                                                 \
-        {                                                                                                             \
-            const float* up_ = (UB) + (size_t)(POS) * pos_stride;                                                     \
-            _Pragma("unroll") for (int n = 0; n < NPW; ++n) {                                                         \
-                TMG_WN_ULOAD(bfr[R][0][n], up_, boff[n])                                                              \
-                TMG_WN_ULOAD(bfr[R][1][n], up_ + (size_t)((KGN) - 1) * kb_stride, boff[n])                            \
-            }                                                                                                         \
-        }
         if (k == 0) { TMG_WN_LOADB(0, ub, kgn, 0) TMG_WN_LOADB(1, ub, kgn, 1) TMG_WN_LOADB(2, ub, kgn, 2) }
         __syncthreads();           // stage k has been produced
         {
@@ -570,41 +537,9 @@ __global__ __launch_bounds__(768, 1) void wino_fwdp_kernel(WinoP p) {
                 TMG_WN_POSITION
             }
         }
-#undef TMG_WN_LOADB
         if (cm + 1 == nchunks) {
-            int t_ = tm;
-            const int tx_ = t_ % p.tiles_x; t_ /= p.tiles_x;
-            const int ty_ = t_ % p.tiles_y;
-            const int b_ = t_ / p.tiles_y;
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                const int wt = 16 * m + li;
-                const int oyb = ty_ * TH + 2 * (wt >> 3), oxb = tx_ * TW + 2 * (wt & 7);
-#pragma unroll
-                for (int n = 0; n < NPW; ++n) {
-                    const int n0 = (ntile0 + n) * 16 + 4 * q;
-                    if (ntile0 + n < ntt && n0 < p.Cout) {
-                        int nl = n0;
-                        TMG_PICK_OSEG(p.out, nl, optr, ostride, ooff)
-#pragma unroll
-                        for (int o = 0; o < 4; ++o) {
-                            const int oy = oyb + (o >> 1), ox = oxb + (o & 1);
-                            if (oy < p.Hin && ox < p.Win) {
-                                const unsigned opx = ((unsigned)b_ * (unsigned)p.Hin + (unsigned)oy) * (unsigned)p.Win + (unsigned)ox;
-                                *reinterpret_cast<float4*>(optr + (size_t)opx * (unsigned)ostride + ooff + nl) =
-                                    make_float4(Y[o][m][n][0], Y[o][m][n][1], Y[o][m][n][2], Y[o][m][n][3]);
-                            }
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int o = 0; o < 4; ++o)
-#pragma unroll
-                for (int m = 0; m < 2; ++m)
-#pragma unroll
-                    for (int n = 0; n < NPW; ++n) Y[o][m][n] = bvr[n];
-            cm = 0; tm += G;
+            TMG_WN_TILE(tm)
+            TMG_WN_EPILOGUE(li, q, TMG_WN_ST)
         } else {
             ++cm;
         }
@@ -799,37 +734,23 @@ __device__ __forceinline__ tmg_bf16x8 tmg_as_bf(uint4 u) {
 template <int NPW>
 __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd3_kernel(WinoP p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int NT = 512;
-    constexpr int TH = 8, TW = 16, PH = TH + 2, PW = TW + 2, PP = PH * PW;   // output tile, raw patch (halo 1)
-    constexpr int KC = 32, CS = KC + 8;        // channels per chunk, raw-patch pixel stride (words)
-    constexpr int RAWW = PP * CS;              // words per raw buffer
     constexpr int VQ = 32 * 16;                // bytes of one [32 tiles][8 bf16] plane
     constexpr int VPART = 4 * VQ, VPOS = 3 * VPART;   // bytes of one part (4 k-quarters) / one position (3 parts)
     char* Vb = reinterpret_cast<char*>(lds + 2 * RAWW);    // [16][3][4][32][16 bytes]
-    constexpr int UPI = (PP * (KC / 4) + NT - 1) / NT;   // raw float4 items per thread (3)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, q = lane >> 4;
     const int ntt = p.Npad >> 4;
-    const int nch = p.nchunks;
     const int ntile0 = (int)blockIdx.y * (8 * NPW) + NPW * wave;
-    // U addressing (bytes): fragment = 1 KB; [pos][chunk][n-tile][part]
-    const unsigned upart = 1024u, unt = 3u * upart, uch = (unsigned)ntt * unt, upos = (unsigned)nch * uch;
+    // U addressing (bytes): fragment = 1 KB; [pos][chunk][n-tile][part]  (p.nchunks here and TMG_WN_CURSORS below the transform
+    // mapping: with the cursors declared up here the prologue of both instances is scheduled differently)
+    const unsigned upart = 1024u, unt = 3u * upart, uch = (unsigned)ntt * unt, upos = (unsigned)p.nchunks * uch;
     unsigned boff[NPW];
 #pragma unroll
     for (int n = 0; n < NPW; ++n) boff[n] = (unsigned)min(ntile0 + n, ntt - 1) * unt + (unsigned)lane * 16u;
     const char* Ub = reinterpret_cast<const char*>(p.U);
 
-    // ---- lean staging state: a thread owns channel quad pc4 of every 64th patch pixel -------------------------------------
-    const int pc4 = tid & 7, ppix0 = tid >> 3;
-    unsigned pyx[UPI];
-#pragma unroll
-    for (int u = 0; u < UPI; ++u) {
-        const int pix = min(ppix0 + u * 64, PP - 1);
-        const int py = pix / PW, px = pix - py * PW;
-        pyx[u] = ((unsigned)py << 16) | (unsigned)px;
-    }
-    float4 pv[UPI];
+    TMG_WN_PATCH_TABLE
 
     // ---- transform mapping: item = (Winograd tile tt, channel octet tc8, row xi of the 4x4 position grid) -------------------------------
     const int tc8 = tid & 3, tt = (tid >> 2) & 31, txi = tid >> 7;
@@ -839,27 +760,11 @@ __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd3_kernel(WinoP 
     const int tra = (txi == 0) ? 0 : (txi == 2 ? 2 : 1), trb = (txi == 0) ? 2 : (txi == 1 ? 2 : (txi == 2 ? 1 : 3));
     const float tsb = (txi == 1) ? 1.f : -1.f;
 
-    const int G = gridDim.x;
-    const int nmine = (int)blockIdx.x < p.ntiles ? (p.ntiles - (int)blockIdx.x + G - 1) / G : 0;
-    const int nst = nmine * nch;
-    int ci = 0, cc = 0, cm = 0;
+    TMG_WN_CURSORS
+    int ci = 0, cm = 0;
     int ti = blockIdx.x, tm = blockIdx.x;
 
-    f32x4 bvr[NPW];       // bias in registers, Y starts from it: no load between the epilogue's stores (see wino_fwd_kernel)
-#pragma unroll
-    for (int n = 0; n < NPW; ++n) {
-        const int n0 = (ntile0 + n) * 16 + 4 * q;
-        const float* bp = (p.bias != nullptr && ntile0 + n < ntt && n0 < p.Cout) ? p.bias + n0 : tmg_zero_page;
-        const float4 b4 = *reinterpret_cast<const float4*>(bp);
-        bvr[n] = (f32x4){b4.x, b4.y, b4.z, b4.w};
-    }
-    f32x4 Y[4][2][NPW];   // [output pixel of the 2x2 tile][m-tile][n-tile]
-#pragma unroll
-    for (int o = 0; o < 4; ++o)
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int n = 0; n < NPW; ++n) Y[o][m][n] = bvr[n];
+    TMG_WN_BIAS_Y
 
     // U fragments run in STEPS of (position, n-tile) - 32 or 16 per stage, 12 MFMAs each - through a ring of four slots, three steps
     // ahead of their MFMAs (slot = step & 3: the stage length is a multiple of four, one unrolled body).  [A ring of whole positions
@@ -867,60 +772,8 @@ __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd3_kernel(WinoP 
     constexpr int NSTEP = 16 * NPW, LD = 3;
     uint4 bfr[4][3];
     for (int k = -2; k < nst; ++k) {
-        // ---- commit stage k+1 --------------------------------------------------------------------------------------------------
-        if (k >= -1 && k + 1 < nst) {
-            float* rb = lds + ((k + 1) & 1) * RAWW;
-#pragma unroll
-            for (int u = 0; u < UPI; ++u) {
-                if (ppix0 + u * 64 < PP) {
-                    float4 v = pv[u];
-                    if (p.relu_in) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-                    *reinterpret_cast<float4*>(rb + (ppix0 + u * 64) * CS + 4 * pc4) = v;
-                }
-            }
-            if (++cc == nch) cc = 0;
-        }
-        // ---- issue the loads of stage k+2 -------------------------------------------------------------------------------------
-        if (k + 2 < nst) {
-            int t_ = ti;
-            const int tx_ = t_ % p.tiles_x; t_ /= p.tiles_x;
-            const int ty_ = t_ % p.tiles_y;
-            const int b_ = t_ / p.tiles_y;
-            const int iy0 = ty_ * TH - 1, ix0 = tx_ * TW - 1;
-            const float* tptr = tmg_zero_page;
-            int tss = 0;
-            {
-                int cl = ci * KC + 4 * pc4;
-                if (cl < p.Cin) {
-                    const float* sp = p.in[0].p;
-                    int ss = p.in[0].stride, so = p.in[0].off;
-                    if (cl >= p.in[0].n) {
-                        cl -= p.in[0].n;
-                        sp = p.in[1].p; ss = p.in[1].stride; so = p.in[1].off;
-                        if (cl >= p.in[1].n) {
-                            cl -= p.in[1].n;
-                            sp = p.in[2].p; ss = p.in[2].stride; so = p.in[2].off;
-                        }
-                    }
-                    tptr = sp + so + cl;
-                    tss = ss;
-                }
-            }
-            const unsigned tbv = (unsigned)b_ * (unsigned)(p.Hin * p.Win);
-#pragma unroll
-            for (int u = 0; u < UPI; ++u) {
-                const int iy = iy0 + (int)(pyx[u] >> 16), ix = ix0 + (int)(pyx[u] & 0xffffu);
-                const int iyc = min(max(iy, 0), p.Hin - 1), ixc = min(max(ix, 0), p.Win - 1);
-                const bool oob = !p.pad_rep && (iy != iyc || ix != ixc);
-                const float* a_ = (oob || ppix0 + u * 64 >= PP) ? tmg_zero_page : tptr + (size_t)(tbv + (unsigned)iyc * (unsigned)p.Win + (unsigned)ixc) * (unsigned)tss;
-                // streamed once: non-temporal, so that the activations do not push the U operand (re-read by every tile) out of L2
-                {
-                    const f32x4 nt_ = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a_));
-                    pv[u] = make_float4(nt_[0], nt_[1], nt_[2], nt_[3]);
-                }
-            }
-            if (++ci == nch) { ci = 0; ti += G; }
-        }
+        TMG_WN_COMMIT
+        TMG_WN_ISSUE(TMG_WN_LD_NT)
         if (k >= 0) {
             // ---- input transform of stage k: V = B^T d B in fp32, split into three bf16 parts on the way to LDS -----------------------------
             {
@@ -963,7 +816,7 @@ __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd3_kernel(WinoP 
                     bfr[(ST) & 3][2] = *reinterpret_cast<const uint4*>(up_ + 2048);                                   \
                 }
                 // operand of the next stage (the next chunk of this tile, or chunk 0 of the next tile: every tile uses the same U)
-                const char* ubn = Ub + (size_t)((unsigned)((cm + 1 == nch) ? 0 : cm + 1) * uch);
+                const char* ubn = Ub + (size_t)((unsigned)((cm + 1 == nchunks) ? 0 : cm + 1) * uch);
                 if (k == 0) { TMG_W3_LOADB(0) TMG_W3_LOADB(1) TMG_W3_LOADB(2) }
                 // two accumulator sets: the output-transform additions of position p - 1 (vector ALU) sit between the MFMAs of position
                 // p - with six 16-cycle MFMAs per accumulator tile a position is only 24 x 16 pipe cycles, and additions that wait for
@@ -1026,45 +879,13 @@ __global__ __launch_bounds__(512, 1) TMG_PACKED_F32 void wino_fwd3_kernel(WinoP 
 #undef TMG_W3_YUPD
 #undef TMG_W3_LOADB
             }
-            if (cm + 1 == nch) {
-                // ---- epilogue: lane (li, q) holds channels 4 q .. 4 q + 3 (of each n-tile) of Winograd tile 16 m + li -------------
-                int t_ = tm;
-                const int tx_ = t_ % p.tiles_x; t_ /= p.tiles_x;
-                const int ty_ = t_ % p.tiles_y;
-                const int b_ = t_ / p.tiles_y;
+            if (cm + 1 == nchunks) {
+                TMG_WN_TILE(tm)
                 // (opaque copies per epilogue: the tile-invariant output offsets built on them are otherwise hoisted out of the stage loop
                 // and spilled at two n-tiles per wave)
                 int lie = li, qe = q;
                 asm volatile("" : "+v"(lie), "+v"(qe));
-#pragma unroll
-                for (int m = 0; m < 2; ++m) {
-                    const int wt = 16 * m + lie;
-                    const int oyb = ty_ * TH + 2 * (wt >> 3), oxb = tx_ * TW + 2 * (wt & 7);
-#pragma unroll
-                    for (int n = 0; n < NPW; ++n) {
-                        const int n0 = (ntile0 + n) * 16 + 4 * qe;
-                        if (ntile0 + n < ntt && n0 < p.Cout) {
-                            int nl = n0;
-                            TMG_PICK_OSEG(p.out, nl, optr, ostride, ooff)
-#pragma unroll
-                            for (int o = 0; o < 4; ++o) {
-                                const int oy = oyb + (o >> 1), ox = oxb + (o & 1);
-                                if (oy < p.Hin && ox < p.Win) {
-                                    const unsigned opx = ((unsigned)b_ * (unsigned)p.Hin + (unsigned)oy) * (unsigned)p.Win + (unsigned)ox;
-                                    __builtin_nontemporal_store(Y[o][m][n],
-                                                                reinterpret_cast<f32x4*>(optr + (size_t)opx * (unsigned)ostride + ooff + nl));
-                                }
-                            }
-                        }
-                    }
-                }
-#pragma unroll
-                for (int o = 0; o < 4; ++o)
-#pragma unroll
-                    for (int m = 0; m < 2; ++m)
-#pragma unroll
-                        for (int n = 0; n < NPW; ++n) Y[o][m][n] = bvr[n];
-                cm = 0; tm += G;
+                TMG_WN_EPILOGUE(lie, qe, TMG_WN_ST_NT)
             } else {
                 ++cm;
             }
@@ -1144,12 +965,8 @@ struct WinoNP {
 template <int NTN, int SKEW = 1>
 __global__ __launch_bounds__(512, 1) void wino_nn_kernel(WinoNP p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int NT = 512;
-    constexpr int TH = 8, TW = 16, PH = TH + 2, PW = TW + 2, PP = PH * PW;
-    constexpr int KC = 32, CS = KC + 8, RAWW = PP * CS;
     constexpr int NC = NTN * 16 + (NTN < 3 ? 4 : 0);   // row stride (words) of the M buffer [16 pos][32 tiles][NC] (3 tiles: no room to pad)
     float* Mb = lds + 2 * RAWW;
-    constexpr int UPI = (PP * (KC / 4) + NT - 1) / NT;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, q = lane >> 4;
@@ -1175,15 +992,7 @@ __global__ __launch_bounds__(512, 1) void wino_nn_kernel(WinoNP p) {
         offb[m] = ((2 * ty + rb) * PW + 2 * tx) * CS + 4 * q;
     }
 
-    const int pc4 = tid & 7, ppix0 = tid >> 3;
-    unsigned pyx[UPI];
-#pragma unroll
-    for (int u = 0; u < UPI; ++u) {
-        const int pix = min(ppix0 + u * 64, PP - 1);
-        const int py = pix / PW, px = pix - py * PW;
-        pyx[u] = ((unsigned)py << 16) | (unsigned)px;
-    }
-    float4 pv[UPI];
+    TMG_WN_PATCH_TABLE
     // Pixel part of the staging addresses: the same for every 32-channel chunk of a pixel tile (8-60 chunks here), so it is computed when
     // the issue cursor enters a tile and kept (one register per item + a mask of the zero-padded ones): ~9 vector instructions per load
     // and chunk less - this kernel issues only 64-96 MFMAs per wave and chunk, and vector cycles add to matrix cycles.
@@ -1193,13 +1002,11 @@ __global__ __launch_bounds__(512, 1) void wino_nn_kernel(WinoNP p) {
     unsigned pxo[UPI];
     unsigned pzm = 0;
 
-    const int G = gridDim.x;
-    const int nmine = (int)blockIdx.x < p.ntiles ? (p.ntiles - (int)blockIdx.x + G - 1) / G : 0;
-    const int nchunks = p.nchunks, nst = nmine * nchunks;
+    TMG_WN_CURSORS
     int ci = 0, cm = 0;
     int ti = blockIdx.x, tm = blockIdx.x;
 
-    f32x4 acc[2][2][NTN];   // [position of the wave][m-tile][n-tile]
+    f32x4 acc[2][2][NTN];  // [position of the wave][m-tile][n-tile]
 #pragma unroll
     for (int e = 0; e < 2; ++e)
 #pragma unroll
@@ -1235,58 +1042,25 @@ __global__ __launch_bounds__(512, 1) void wino_nn_kernel(WinoNP p) {
         const float* bp = (p.bias != nullptr && tid < 32 * QN && n0 < p.Cout) ? p.bias + n0 : tmg_zero_page;
         bvq = *reinterpret_cast<const float4*>(bp);
     }
-#define TMG_WN_STAGE \
-        if (k >= -1 && k + 1 < nst) { \
-            float* rb_ = lds + ((k + 1) & 1) * RAWW; \
-            _Pragma("unroll") for (int u = 0; u < UPI; ++u) { \
-                if (ppix0 + u * 64 < PP) { \
-                    float4 v = pv[u]; \
-                    if (p.relu_in) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); } \
-                    *reinterpret_cast<float4*>(rb_ + (ppix0 + u * 64) * CS + 4 * pc4) = v; \
-                } \
-            } \
-        } \
-        if (k + 2 < nst) { \
-            int t_ = ti; \
-            const int tx_ = t_ % p.tiles_x; t_ /= p.tiles_x; \
-            const int ty_ = t_ % p.tiles_y; \
-            const int b_ = t_ / p.tiles_y; \
-            const int iy0 = ty_ * TH - 1, ix0 = tx_ * TW - 1; \
-            const float* tptr = tmg_zero_page; \
-            int tss = 0; \
-            { \
-                int cl = ci * KC + 4 * pc4; \
-                if (cl < p.Cin) { \
-                    const float* sp = p.in[0].p; \
-                    int ss = p.in[0].stride, so = p.in[0].off; \
-                    if (cl >= p.in[0].n) { \
-                        cl -= p.in[0].n; \
-                        sp = p.in[1].p; ss = p.in[1].stride; so = p.in[1].off; \
-                        if (cl >= p.in[1].n) { \
-                            cl -= p.in[1].n; \
-                            sp = p.in[2].p; ss = p.in[2].stride; so = p.in[2].off; \
-                        } \
-                    } \
-                    tptr = sp + so + cl; \
-                    tss = ss; \
-                } \
-            } \
-            if (ci == 0 || !PXC) { \
-                const unsigned tbv = (unsigned)b_ * (unsigned)(p.Hin * p.Win); \
-                pzm = 0; \
-                _Pragma("unroll") for (int u = 0; u < UPI; ++u) { \
-                    const int iy = iy0 + (int)(pyx[u] >> 16), ix = ix0 + (int)(pyx[u] & 0xffffu); \
-                    const int iyc = min(max(iy, 0), p.Hin - 1), ixc = min(max(ix, 0), p.Win - 1); \
-                    const bool oob = !p.pad_rep && (iy != iyc || ix != ixc); \
-                    pxo[u] = tbv + (unsigned)iyc * (unsigned)p.Win + (unsigned)ixc; \
-                    pzm |= ((oob || ppix0 + u * 64 >= PP) ? 1u : 0u) << u; \
-                } \
-            } \
-            _Pragma("unroll") for (int u = 0; u < UPI; ++u) { \
-                const float* a_ = ((pzm >> u) & 1u) ? tmg_zero_page : tptr + (size_t)pxo[u] * (unsigned)tss; \
-                pv[u] = *reinterpret_cast<const float4*>(a_); \
-            } \
-            if (++ci == nchunks) { ci = 0; ti += G; } \
+    // commit + issue of a round: TMG_WN_ISSUE with the pixel indices (pxo) and dead-item mask (pzm) kept across a tile's chunks
+#define TMG_WN_STAGE                                                                                                  \
+        TMG_WN_COMMIT                                                                                                 \
+        if (k + 2 < nst) {                                                                                            \
+            TMG_WN_ISSUE_HEAD                                                                                         \
+            if (ci == 0 || !PXC) {                                                                                    \
+                TMG_WN_TBV                                                                                            \
+                pzm = 0;                                                                                              \
+                _Pragma("unroll") for (int u = 0; u < UPI; ++u) {                                                     \
+                    TMG_WN_PIXEL(u)                                                                                   \
+                    pxo[u] = TMG_WN_PXI;                                                                              \
+                    pzm |= (TMG_WN_DEAD(u) ? 1u : 0u) << u;                                                           \
+                }                                                                                                     \
+            }                                                                                                         \
+            _Pragma("unroll") for (int u = 0; u < UPI; ++u) {                                                         \
+                const float* a_ = ((pzm >> u) & 1u) ? tmg_zero_page : tptr + (size_t)pxo[u] * (unsigned)tss;          \
+                TMG_WN_LD(pv[u], a_)                                                                                  \
+            }                                                                                                         \
+            TMG_WN_ISSUE_TAIL                                                                                         \
         }
     for (int k = -2; k < nst; ++k) {
         if (!late || k < 0) { TMG_WN_STAGE }
@@ -1349,10 +1123,7 @@ __global__ __launch_bounds__(512, 1) void wino_nn_kernel(WinoNP p) {
                             acc[e][m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
                         }
                 __syncthreads();
-                int t_ = tm;
-                const int tx_ = t_ % p.tiles_x; t_ /= p.tiles_x;
-                const int ty_ = t_ % p.tiles_y;
-                const int b_ = t_ / p.tiles_y;
+                TMG_WN_TILE(tm)
                 static_assert(32 * QN <= NT, "one epilogue item per thread");
                 for (int it = tid; it < 32 * QN; it += NT) {
                     const int wt = it / QN, c4 = it - wt * QN;
