@@ -20,7 +20,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmglow_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip", "tmg_phase.hip", "tmg_spod.hip", "tmg_budget.hip", "tmg_corr.hip"]
+SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip", "tmg_phase.hip", "tmg_spod.hip", "tmg_budget.hip", "tmg_corr.hip", "tmg_flux.hip"]
 # Sources compiled WITHOUT the packed-fp32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32): beside MFMAs a packed
 # f32 instruction costs ~13 cycles more than the two scalar ones it replaces (MI355X_MICROARCH.md, cycle constants, 'price of one
 # filler beside MFMAs'), and the compiler SLP-packs adjacent scalar adds / multiplies by itself under -O3.  The matrix-core kernels'
@@ -88,6 +88,15 @@ BUDGET_EXPORTS = ["tmg_ens_budget_plan", "tmg_ens_budget_accum", "tmg_ens_budget
 # The two-point space-time correlations about probe points (csrc/tmg_corr.hip), declared in include/tmglow_hip_corr.h, a header of its
 # own: ens_corr_plan / ens_corr_probe / ens_corr_accum / ens_corr_finalize below.
 CORR_EXPORTS = ["tmg_ens_corr_plan", "tmg_ens_corr_probe", "tmg_ens_corr_accum", "tmg_ens_corr_finalize"]
+# The scale-to-scale energy flux and the sub-filter stresses (csrc/tmg_flux.hip), declared in include/tmglow_hip_flux.h, a header of its
+# own: ens_flux_plan / ens_flux_accum / ens_flux_terms below.
+FLUX_EXPORTS = ["tmg_ens_flux_plan", "tmg_ens_flux_accum", "tmg_ens_flux_terms"]
+_P64 = ctypes.POINTER(ctypes.c_int64)
+FLUX_ARGTYPES = {
+    "tmg_ens_flux_plan": [_P64, _P64, _P64],
+    "tmg_ens_flux_accum": [ctypes.c_void_p, _P64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _P64, _P64, ctypes.c_void_p],
+    "tmg_ens_flux_terms": [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, _P64, _P64, ctypes.c_void_p],
+}
 # Every export returns int except the workspace sizes, which the header declares int64_t (read through a 32-bit return a request of
 # 2^31 floats or more would be truncated and the kernel handed a buffer smaller than it planned for).
 RET_I64 = ("tmg_conv_wgrad_ws_floats", "tmg_conv_wgrad_grouped_ws_floats", "tmg_conv_wino_wgrad_ws_floats",
@@ -104,7 +113,7 @@ def build(force=False, verbose=False):
                os.path.join(inc, "tmglow_hip_gram.h"), os.path.join(inc, "tmglow_hip_sfun.h"),
                os.path.join(inc, "tmglow_hip_event.h"), os.path.join(inc, "tmglow_hip_pdf.h"), os.path.join(inc, "tmglow_hip_pod.h"),
                os.path.join(inc, "tmglow_hip_phase.h"), os.path.join(inc, "tmglow_hip_spod.h"), os.path.join(inc, "tmglow_hip_layout.h"),
-               os.path.join(inc, "tmglow_hip_budget.h"), os.path.join(inc, "tmglow_hip_corr.h")]
+               os.path.join(inc, "tmglow_hip_budget.h"), os.path.join(inc, "tmglow_hip_corr.h"), os.path.join(inc, "tmglow_hip_flux.h")]
     hmt = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -160,6 +169,9 @@ def lib():
             getattr(_lib, name).argtypes = PLAN_ARGTYPES[name]
         for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS + SFUN_EXPORTS + EVENT_EXPORTS + PDF_EXPORTS + POD_EXPORTS + PHASE_EXPORTS + SPOD_EXPORTS + LAYOUT_EXPORTS + BUDGET_EXPORTS + CORR_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
+        for name in FLUX_EXPORTS:
+            getattr(_lib, name).restype = ctypes.c_int
+            getattr(_lib, name).argtypes = FLUX_ARGTYPES[name]
     return _lib
 
 
@@ -1512,6 +1524,71 @@ def ens_budget_terms(raw, M, fl, outs, member_budget, Hh, Ww, T):
             raise RuntimeError("ens_budget_terms: member_budget is %s, not a contiguous %s" % (tuple(member_budget.shape), (B, R - 1, 7, HW)))
     _chk(lib().tmg_ens_budget_terms(_ptr(raw), _ptr(M), (ctypes.c_double * 4)(*[float(v) for v in fl]), *[_ptr(t) for t in outs],
                                     _ptr(member_budget), _i64(R - 1, B, Hh, Ww, T), _stream()), "tmg_ens_budget_terms")
+
+
+def ens_flux_plan(S, B, Hh, Ww, widths):
+    """The launch plan of ens_flux_accum for S members of B cases of [H, W] and the box widths `widths` (tmg_ens_flux_plan; nothing is
+    launched) -> dict: tile (TH, TW) pixels per block, halo = r_max + 1, tiles (NTY, NTX) per field over the valid region of the
+    smallest width, lds bytes of dynamic LDS, optin: True when that exceeds 64 KB, blocks = NTY NTX B per fed row.  A function of
+    (H, W, widths); B only scales the blocks."""
+    plan = (c_i64 * 8)()
+    _chk(lib().tmg_ens_flux_plan(_i64(S, B, Hh, Ww, len(widths)), _i64(*widths), plan), "tmg_ens_flux_plan")
+    th, tw, halo, nty, ntx, lds, optin, blocks = [int(v) for v in plan]
+    return {"tile": (th, tw), "halo": halo, "tiles": (nty, ntx), "lds": lds, "optin": bool(optin), "blocks": blocks}
+
+
+def ens_flux_accum(y, a, kk, raw, widths, k, row0, t_before):
+    """Add one chunk of k rows (y: NHWC [k*B, H, W, 2..4] or a channel-slice view, rows member-major; channels 0 and 1 are read) to
+    the planes of the rows row0 .. row0 + k - 1 of the state raw [S + 1, B, L, 7, HW] (the target: k = 1, row0 = S) with the scales
+    a [B, 2] and the flux factors kk [L, 2] (device fp32); t_before == 0 stores instead of adding (tmg_ens_flux_accum)."""
+    kB, Hh, Ww, Cc = y.shape
+    ptr, ps, co, _ = seg(y)
+    check_device(y)
+    check_act(raw)
+    check_device(raw)
+    check_act(a)
+    check_act(kk)
+    if raw.dim() != 5:
+        raise RuntimeError("ens_flux_accum: raw is [S + 1, B, L, 7, HW], got %s" % (tuple(raw.shape),))
+    R, B, L, Q, HW = raw.shape
+    if not 2 <= Cc <= 4 or Q != 7 or L != len(widths) or HW != Hh * Ww or kB != k * B or tuple(a.shape) != (B, 2) or tuple(kk.shape) != (L, 2):
+        raise RuntimeError("ens_flux_accum: raw %s, a %s, kk %s do not fit %d rows of %s and %d widths" % (
+            tuple(raw.shape), tuple(a.shape), tuple(kk.shape), k, tuple(y.shape), len(widths)))
+    if not (raw.is_contiguous() and a.is_contiguous() and kk.is_contiguous()):
+        raise RuntimeError("ens_flux_accum: contiguous fp32 device tables")
+    _chk(lib().tmg_ens_flux_accum(c_vp(ptr), _i64(ps, co), _ptr(a), _ptr(kk), _ptr(raw), _i64(*widths),
+                                  _i64(k, R - 1, B, Hh, Ww, row0, t_before, L), _stream()), "tmg_ens_flux_accum")
+
+
+FLUX_OUTS = ("flux_mean", "flux_std", "target_flux", "flux_tstd_mean", "target_flux_tstd", "backscatter_mean", "backscatter_std",
+             "target_backscatter", "sgs_mean", "sgs_std", "target_sgs", "member_flux", "flux_curve", "sgs_energy_curve")
+
+
+def ens_flux_terms(raw, k64, outs, widths, Hh, Ww, T):
+    """The time-mean flux, its temporal std, the backscatter fraction, the sub-filter stresses and the two curves of every row of the
+    state raw [S + 1, B, L, 7, HW] after T timed steps: outs = the 14 arrays of FLUX_OUTS in that order (fp32 on the device; the
+    fields [B, L, HW], the stresses [B, L, 3, HW], member_flux [B, S, L, HW] or None, the curves [B, S + 1, L]); k64 [L, 2] fp64 on the
+    device (tmg_ens_flux_terms)."""
+    check_act(raw)
+    check_device(raw)
+    if raw.dim() != 5 or raw.shape[3] != 7 or raw.shape[2] != len(widths) or raw.shape[4] != Hh * Ww or not raw.is_contiguous() or \
+            len(outs) != len(FLUX_OUTS):
+        raise RuntimeError("ens_flux_terms: raw is [S + 1, B, %d, 7, %d] fp32 on the device, got %s" % (len(widths), Hh * Ww, tuple(raw.shape)))
+    R, B, L, _, HW = raw.shape
+    if tuple(k64.shape) != (L, 2) or k64.dtype != torch.float64 or not (k64.is_cuda and k64.is_contiguous()):
+        raise RuntimeError("ens_flux_terms: k64 is [L, 2] fp64 on the device, got %s" % (tuple(k64.shape),))
+    want = [(B, L, HW)] * 8 + [(B, L, 3, HW)] * 3 + [(B, R - 1, L, HW)] + [(B, R, L)] * 2
+    for name, t, shp in zip(FLUX_OUTS, outs, want):
+        if t is None and name == "member_flux":
+            continue
+        check_act(t)
+        if tuple(t.shape) != shp or not t.is_contiguous():
+            raise RuntimeError("ens_flux_terms: %s is %s, not a contiguous %s" % (name, tuple(t.shape), shp))
+    nw = 4 * ((HW + 255) // 256)
+    ws = torch.empty((B * R * L * 2 * nw,), device=raw.device, dtype=torch.float64)
+    table = (c_vp * len(outs))(*[None if t is None else t.data_ptr() for t in outs])
+    _chk(lib().tmg_ens_flux_terms(_ptr(raw), _ptr(k64), table, _ptr(ws), _i64(*widths), _i64(R - 1, B, Hh, Ww, T, L), _stream()),
+         "tmg_ens_flux_terms")
 
 
 def ens_corr_cfg(probes, pairs, lags):

@@ -3068,6 +3068,138 @@ class EnsembleBudget(EnsembleFeed):
         return o
 
 
+FLUX_WIDTHS = (3, 5, 9, 17, 33)
+FLUX_MAX_WIDTHS = 8
+FLUX_MAX_WIDTH = 33
+FLUX_PLANES = 7
+
+
+def flux_args(widths, C, Hh, Ww, grid):
+    """The checks and the defaults of the flux arguments: 2 <= C <= 4 (channels 0 and 1 are read), H, W >= 5 (one valid pixel of
+    width 3), grid two positive finite sizes; widths (None: FLUX_WIDTHS without those over min(H, W) - 2) at most 8 odd integers in
+    3 .. 33, strictly increasing, none over min(H, W) - 2.  H = W = None (the field is not known yet) skips the field's limits.
+    -> (widths, dx, dy)."""
+    real = lambda v: not isinstance(v, bool) and isinstance(v, numbers.Real) and math.isfinite(float(v))   # noqa: E731
+    if not 2 <= int(C) <= 4:
+        raise ValueError("the energy flux needs 2 <= C <= 4 channels (ux, uy first), got %d" % int(C))
+    known = Hh is not None and Ww is not None
+    if known and (int(Hh) < 5 or int(Ww) < 5):
+        raise ValueError("the energy flux needs H, W >= 5 (a 3 x 3 box and the ring of the stencils), got %d x %d" % (int(Hh), int(Ww)))
+    try:
+        g = tuple(grid)
+    except TypeError:
+        raise ValueError("grid must hold (dx, dy), got %r" % (grid,))
+    if len(g) != 2 or not all(real(v) and float(v) > 0 for v in g):
+        raise ValueError("grid must hold two positive finite sizes (dx, dy), got %r" % (grid,))
+    lim = min(int(Hh), int(Ww)) - 2 if known else FLUX_MAX_WIDTH
+    if widths is None:
+        ws = tuple(w for w in FLUX_WIDTHS if w <= lim)
+    else:
+        try:
+            ws = tuple(widths)
+        except TypeError:
+            raise ValueError("widths must hold odd box widths in pixels, got %r" % (widths,))
+        if not 1 <= len(ws) <= FLUX_MAX_WIDTHS:
+            raise ValueError("widths must hold 1 .. %d box widths, got %d" % (FLUX_MAX_WIDTHS, len(ws)))
+        if not all(isinstance(w, numbers.Integral) and not isinstance(w, bool) for w in ws):
+            raise ValueError("widths must be integers, got %r" % (widths,))
+        ws = tuple(int(w) for w in ws)
+        if any(w < 3 or w > FLUX_MAX_WIDTH or w % 2 == 0 for w in ws):
+            raise ValueError("widths must be odd and in 3 .. %d, got %r" % (FLUX_MAX_WIDTH, ws))
+        if any(b <= a for a, b in zip(ws, ws[1:])):
+            raise ValueError("widths must be strictly increasing, got %r" % (ws,))
+        if ws[-1] > lim:
+            raise ValueError("width %d does not fit a %s x %s field: a width is at most min(H, W) - 2 = %d" % (ws[-1], Hh, Ww, lim))
+    return ws, float(g[0]), float(g[1])
+
+
+def flux_factors(widths, dx, dy):
+    """k [L, 2] fp64 (CPU): 1 / (8 dx N^3), 1 / (8 dy N^3), N = w^2: Pi = -(A kx + B ky) with the un-normalised sums A, B."""
+    return torch.tensor([[1.0 / ((8.0 * d) * float((w * w) ** 3)) for d in (float(dx), float(dy))] for w in widths], dtype=torch.float64)
+
+
+class EnsembleFlux(EnsembleFeed):
+    """On-device scale-to-scale energy flux and sub-filter stresses of sampled roll-outs of B cases, and of the target
+    (tmg_ens_flux_accum / tmg_ens_flux_terms): the coarse-graining analysis of Germano, Eyink and Aluie.  For a box filter of width
+    l = w pixels, tau_ij(l) = bar(u_i u_j) - bar(u_i) bar(u_j) is the sub-filter stress and Pi_l(x, t) = -tau_ij d bar(u_i) / dx_j the
+    local flux of energy across l: positive for a forward cascade, negative for backscatter.
+
+    Rows are the S members plus the target as row S.  The filtered field of a row is f_c = fl(a_c y_c), c = (ux, uy), a = u * out_std
+    (formed in fp64, rounded once); out_mu never enters: tau and the gradients of bar(u) are exactly invariant to a constant
+    velocity, and leaving it out shrinks the cancellation.  For a width w, r = w // 2, N = w^2, the state holds un-normalised
+    quantities (integers on integer data): the box sums Sg of f_u, f_v, f_u f_u, f_u f_v, f_v f_v (a row pass, then a column pass, both
+    added from the centre outwards; no running window, no summed-area table), Q_ij = N Sg_ij - Sg_i Sg_j = N^2 tau_ij,
+    A = Q_uu Sx Sg_u + Q_uv Sx Sg_v, B = Q_uv Sy Sg_u + Q_vv Sy Sg_v with the un-scaled 3x3 stencils of pc/ applied to the box sums of
+    the eight neighbours, and Pi_s = -(A kx + B ky), kx = 1 / (8 dx N^3), ky = 1 / (8 dy N^3).  A pixel is valid for w when the box and
+    the ring of the stencils lie inside the field, r + 1 <= h <= H - 2 - r and the same in w: no padding, no one-sided filter, NaN
+    outside.  Every timed step adds 7 fp32 quantities per row, width and valid pixel to `raw` [S + 1, B, L, 7, HW]: A, B, Pi_s^2,
+    [Pi_s < 0], Q_uu, Q_uv, Q_vv.  An element is touched by one thread once per call: the state is bitwise reproducible, independent of
+    the chunking, and needs no memset (the first timed step stores; invalid pixels are neither written nor read).  It takes 28 L
+    bytes per element of [S + 1, B, HW].
+
+    finalize() forms, in fp64 on the device, per row and width: Pi = -(sum A kx + sum B ky) / T, the temporal std of Pi_s
+    sqrt(max(sum Pi_s^2 / T - Pi^2, 0)), the backscatter fraction count / T, tau = sum Q / (N^2 T).
+
+    Feeding protocol of EnsembleFeed, with the step's target on every chunk; a step fed with time=False launches nothing.
+    finalize() -> dict:
+      flux_mean, flux_std, target_flux [B, L, H, W]        Welford mean / population std (ddof 0) over the members, and the target's
+      flux_tstd_mean, target_flux_tstd [B, L, H, W]        the same of the temporal std of Pi_s
+      backscatter_mean, backscatter_std, target_backscatter [B, L, H, W]
+      sgs_mean, sgs_std, target_sgs [B, L, 3, H, W]        the same of tau (uu, uv, vv)
+      member_flux [B, S, L, H, W]                          every member's Pi (per_member=True only)
+      flux_curve, sgs_energy_curve [B, S + 1, L]           per row, the target last: the mean over the width's valid region of Pi and
+                                                           of (tau_uu + tau_vv) / 2 (fp64, partials folded in a fixed order)
+      flux_widths [L], flux_lengths [L, 2]                 the widths in pixels and as lengths (w dx, w dy)."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, grid=(1.0, 1.0), widths=None, per_member=False):
+        noun, why = "ensemble energy fluxes", "the filtered velocity scales with u * out_std"
+        _ens_members(noun, members)
+        self.widths, self.dx, self.dy = flux_args(widths, C, Hh, Ww, grid)
+        sd, _mu = _ens_tables(int(C), why, out_std, out_mu)
+        u = _ens_u(u, B, int(C), why)
+        if int(steps) < 1 or int(B) < 1:
+            raise ValueError("%s need steps, B >= 1, got %d, %d" % (noun, steps, B))
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, C, Hh, Ww, steps)
+        self.per_member = bool(per_member)
+        self.L = len(self.widths)
+        self.a = _ens_scale(sd, u, self.B, torch.float64)[:, :2].to(torch.float32).to(dev).contiguous()
+        k64 = flux_factors(self.widths, self.dx, self.dy)
+        self.k64 = k64.to(dev)
+        self.kk = k64.to(torch.float32).to(dev)
+        self.plan = H.ens_flux_plan(self.S, self.B, self.H, self.W, self.widths)
+        self.raw = torch.empty((self.S + 1, self.B, self.L, FLUX_PLANES, self.H * self.W), device=dev, dtype=torch.float32)
+
+    def add(self, y, m0, target, time=True):
+        """Add the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
+        channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride rule, added as
+        row S with the step's last chunk.  A step fed with time=False launches nothing."""
+        yn, tn, k, t_before, last = self.open_chunk(y, m0, time, target, required=True)
+        _on_device(yn, tn)
+        if time:
+            H.ens_flux_accum(yn, self.a, self.kk, self.raw, self.widths, k, m0, t_before)
+            if last:
+                H.ens_flux_accum(tn, self.a, self.kk, self.raw, self.widths, 1, self.S, t_before)
+        self.close_chunk(m0, k, time, last)
+
+    def finalize(self):
+        """-> dict of the outputs over the steps folded with time=True."""
+        T = self.finalize_guard()
+        B, S, L, Hh, Ww = self.B, self.S, self.L, self.H, self.W
+        HW, dev = Hh * Ww, self.raw.device
+        new = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)   # noqa: E731
+        outs = [new(B, L, HW) for _ in range(8)] + [new(B, L, 3, HW) for _ in range(3)]
+        outs += [new(B, S, L, HW) if self.per_member else None, new(B, S + 1, L), new(B, S + 1, L)]
+        H.ens_flux_terms(self.raw, self.k64, outs, self.widths, Hh, Ww, T)
+        o = {}
+        for key, t in zip(H.FLUX_OUTS, outs):
+            if t is not None:
+                o[key] = t if key.endswith("curve") else t.view(tuple(t.shape[:-1]) + (Hh, Ww))
+        o["flux_widths"] = torch.tensor(self.widths, dtype=torch.int64)
+        o["flux_lengths"] = torch.tensor([[w * self.dx, w * self.dy] for w in self.widths], dtype=torch.float64)
+        return o
+
+
 CORR_MAX_PROBES = 8
 CORR_MAX_PAIRS = 4
 CORR_MAX_LAGS = 8

@@ -747,6 +747,54 @@ def modelPredBudget(args, model, testing_loader, log, samples=1, stride=1, tmax=
     return _ensembleStats("modelPredBudget", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
 
 
+def _flux_factory(grid, widths, per_member):
+    """The make of modelPredFlux's record: the tmg_ops.EnsembleFlux of one mini-batch (its constructor checks the widths against the
+    field before it touches the device)."""
+    def make(mb, members, steps):
+        import tmg_ops as ops
+        return ops.EnsembleFlux(members, mb.B, mb.C, mb.H, mb.W, steps, mb.dev, mb.out_mu, mb.out_std, u=mb.u, grid=grid, widths=widths,
+                                per_member=per_member)
+    return make
+
+
+def modelPredFlux(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, widths=None, per_member=False):
+    """modelPredStats plus the scale-to-scale energy flux and the sub-filter stresses of every member and of the target, still
+    without forming modelPred's [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleFlux): per location, does energy go from the large
+    scales to the small ones, at what rate, and how often does it go backwards?  The coarse-graining (filtering) analysis of Germano,
+    Eyink and Aluie, which needs no homogeneity: for a box filter of width l, tau_ij(l) = bar(u_i u_j) - bar(u_i) bar(u_j) is the
+    sub-filter stress and Pi_l(x, t) = -tau_ij d bar(u_i) / dx_j the local flux across l, positive for a forward cascade, negative for
+    backscatter.  Same roll-outs as modelPredStats: under the same host RNG state the keys both return are identical.  The grid is
+    (args.dx along W, args.dy along H).
+
+    widths: at most 8 odd box widths in pixels, strictly increasing, each in 3 .. 33 (None: (3, 5, 9, 17, 33) without those over
+    min(H, W) - 2; an explicit width over that is a ValueError).  Rows are the S members and the target.  The filtered field is
+    (u0, u0) out_std y (out_mu never enters: tau and the gradients of bar(u) are exactly invariant to a constant velocity).  Every
+    timed step (kept steps t_start..Tk-1) adds, per row, width and valid pixel, 7 fp32 sums of un-normalised quantities: with the box
+    sums Sg over the w x w box (N = w^2; separable, added from the centre outwards, no running window and no summed-area table),
+    Q_ij = N Sg_ij - Sg_i Sg_j = N^2 tau_ij, A = Q_uu Sx Sg_u + Q_uv Sx Sg_v, B = Q_uv Sy Sg_u + Q_vv Sy Sg_v (the un-scaled 3x3 stencils of
+    pc/ on the box sums of the eight neighbours) and Pi_s = -(A / (8 dx N^3) + B / (8 dy N^3)), the sums of A, B, Pi_s^2, [Pi_s < 0],
+    Q_uu, Q_uv, Q_vv.  The state takes 28 L bytes per element of [S + 1, N, HW] for L widths; it is bitwise reproducible and
+    independent of max_rows.  A pixel is valid for a width when the box and the ring of the stencils lie inside the field
+    (r + 1 <= h <= H - 2 - r, r = w // 2, and the same in w); every output is NaN outside.
+
+    Returns modelPredStats' dict plus (CPU tensors):
+      flux_mean, flux_std, target_flux [N, L, H, W]         mean / population std (ddof 0) over the members of each member's
+                                                            time-mean Pi, and the target's through the same kernels
+      flux_tstd_mean, target_flux_tstd [N, L, H, W]         the same of the temporal std of Pi_s
+      backscatter_mean, backscatter_std, target_backscatter [N, L, H, W]   ... of the fraction of timed steps with Pi_s < 0
+      sgs_mean, sgs_std, target_sgs [N, L, 3, H, W]         ... of the time-mean tau (uu, uv, vv)
+      member_flux [N, S, L, H, W]                           every member's Pi (per_member=True only)
+      flux_curve, sgs_energy_curve [N, S + 1, L]            per row, the target last: the mean over the width's valid region of Pi
+                                                            and of (tau_uu + tau_vv) / 2
+      flux_widths [L], flux_lengths [L, 2]                  the widths in pixels and as lengths (w dx, w dy).
+    Not supported: Gaussian or spectral filters, the boundary strip (one-sided filters), widths over 33, more than 8 widths, pixel
+    boxes, the pressure and the three-dimensional terms, a per-step flux series, non-finite members."""
+    import tmg_ops as ops
+    ws, dx, dy = ops.flux_args(widths, 3, None, None, (args.dx, args.dy))
+    acc = _Acc(_flux_factory((dx, dy), None if widths is None else ws, bool(per_member)), target=True, meta=("flux_widths", "flux_lengths"))
+    return _ensembleStats("modelPredFlux", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
+
+
 def modelPredSpod(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, bins=None, modes=4, channels=(0, 1),
                   window="hann", loo=True, dt=None):
     """modelPredStats plus the spectral POD (SPOD; Towne, Schmidt & Colonius 2018) of the members over the kept steps t_start..Tk-1
