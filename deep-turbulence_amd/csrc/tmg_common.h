@@ -55,11 +55,24 @@ __device__ __forceinline__ float block_sum_256(float v, float* red /* >= 4 float
     return red[0] + red[1] + red[2] + red[3];
 }
 
+// ---- Non-finite values ("Non-finite values") ------------------------------------------------------------------------
+// fmaxf / fminf return the operand that is NOT NaN: a ReLU or a clamp written with them turns a NaN into 0 / the lower limit and a
+// diverged run goes on with finite, wrong numbers.  These propagate it, as nn.ReLU / torch.clamp / nn.Hardtanh do; finite values
+// (and +-Inf) map exactly as before.  IEEE 754-2019 maximum / minimum: one v_maximum3_f32 / v_minimum3_f32 on gfx950, where fmaxf
+// is a canonicalising v_max_f32 plus the v_max_f32 itself.  Every rectifier and clip whose operand comes from data or from a
+// parameter goes through them.
+__device__ __forceinline__ float tmg_relu(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+__device__ __forceinline__ float tmg_clamp(float v, float lo, float hi) {
+    return __builtin_elementwise_minimum(__builtin_elementwise_maximum(v, lo), hi);
+}
+__device__ __forceinline__ float4 tmg_relu4(float4 v) { return make_float4(tmg_relu(v.x), tmg_relu(v.y), tmg_relu(v.z), tmg_relu(v.w)); }
+__device__ __forceinline__ float4 tmg_clamp4(float4 v, float lo, float hi) {
+    return make_float4(tmg_clamp(v.x, lo, hi), tmg_clamp(v.y, lo, hi), tmg_clamp(v.z, lo, hi), tmg_clamp(v.w, lo, hi));
+}
+
 __device__ __forceinline__ float out_scale_of(const float* kappa) {
     if (!kappa) return 1.0f;
-    float k = *kappa;
-    k = fminf(fmaxf(k, -4.0f), 1.3862943611198906f);
-    return expf(k);
+    return expf(tmg_clamp(*kappa, -4.0f, 1.3862943611198906f));
 }
 
 // Select the segment (of <= 3) holding concatenated channel C_ BY VALUE into three new locals (taking a pointer into the
@@ -125,12 +138,7 @@ __device__ __forceinline__ float4 load_in4(const P& p, int b, int iy, int ix, in
         for (int e = 0; e < 4; ++e)
             if (c + e < p.Cin) f[e] = f[e] * p.in_scale[c + e] + p.in_shift[c + e];
     }
-    if (p.relu_in) {
-        v.x = fmaxf(v.x, 0.f);
-        v.y = fmaxf(v.y, 0.f);
-        v.z = fmaxf(v.z, 0.f);
-        v.w = fmaxf(v.w, 0.f);
-    }
+    if (p.relu_in) v = tmg_relu4(v);
     return v;
 }
 
@@ -279,10 +287,7 @@ __device__ __forceinline__ void stage_patch_bf(const P& p, float* lds, int b, in
                 for (int e = 0; e < 4; ++e)
                     if (c + e < p.Cin) f[e] = f[e] * p.in_scale[c + e] + p.in_shift[c + e];
             }
-            if (p.relu_in) {
-                v[u].x = fmaxf(v[u].x, 0.f); v[u].y = fmaxf(v[u].y, 0.f);
-                v[u].z = fmaxf(v[u].z, 0.f); v[u].w = fmaxf(v[u].w, 0.f);
-            }
+            if (p.relu_in) v[u] = tmg_relu4(v[u]);
             if (dst[u] >= 0) *reinterpret_cast<float4*>(lds + dst[u]) = v[u];
         }
     }

@@ -186,7 +186,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvP p) {
                     float v = acc[i][j][r] + bv;
                     if (p.add.p) v += p.add.p[opx * p.add.stride + p.add.off + n];
                     v *= osc;
-                    if (p.relu_out) v = fmaxf(v, 0.f);
+                    if (p.relu_out) v = tmg_relu(v);
                     float* dst = obase + opx * ostride;
                     if (p.accumulate) v += *dst;
                     *dst = v;
@@ -323,7 +323,7 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_kernel(ConvP p) {
                         v.x = v.x * isc.x + ish.x; v.y = v.y * isc.y + ish.y;
                         v.z = v.z * isc.z + ish.z; v.w = v.w * isc.w + ish.w;
                     }
-                    if (p.relu_in) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+                    if (p.relu_in) v = tmg_relu4(v);
                     *reinterpret_cast<float4*>(bb + u * pstep * CS * 4) = v;
                 }
             }
@@ -452,7 +452,7 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_kernel(ConvP p) {
 #pragma unroll
                                     for (int r = 0; r < 4; ++r) {
                                         v[r] *= osc;
-                                        if (p.relu_out) v[r] = fmaxf(v[r], 0.f);
+                                        if (p.relu_out) v[r] = tmg_relu(v[r]);
                                     }
                                     int nl = n0;
                                     TMG_PICK_OSEG(p.out, nl, op_, ostride, ooff)
@@ -490,7 +490,7 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_kernel(ConvP p) {
 #pragma unroll
                                     for (int r = 0; r < 4; ++r) {
                                         v[r] *= osc;
-                                        if (p.relu_out) v[r] = fmaxf(v[r], 0.f);
+                                        if (p.relu_out) v[r] = tmg_relu(v[r]);
                                     }
                                     if (p.accumulate) {
                                         const float4 o4 = *dst;
@@ -507,7 +507,7 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_kernel(ConvP p) {
                                             float x = v[r];
                                             if (p.add.p) x += p.add.p[(size_t)opx * (unsigned)p.add.stride + p.add.off + n];
                                             x *= osc;
-                                            if (p.relu_out) x = fmaxf(x, 0.f);
+                                            if (p.relu_out) x = tmg_relu(x);
                                             float* dst = op_ + (size_t)opx * (unsigned)ostride + ooff + nl;
                                             if (p.accumulate) x += *dst;
                                             *dst = x;
@@ -823,7 +823,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_kernel(WgradP p) {
                     v.x = v.x * isc.x + ish.x; v.y = v.y * isc.y + ish.y;                                         \
                     v.z = v.z * isc.z + ish.z; v.w = v.w * isc.w + ish.w;                                         \
                 }                                                                                                 \
-                if (p.relu_in) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); } \
+                if (p.relu_in) v = tmg_relu4(v); \
                 *reinterpret_cast<float4*>(reinterpret_cast<char*>(lds) + 4u * (BW) + pdst0 + u * pstep * 64) = v; \
             }                                                                                                     \
         }                                                                                                         \

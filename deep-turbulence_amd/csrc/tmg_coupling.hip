@@ -171,9 +171,9 @@ __global__ __launch_bounds__(256, CT == 1 ? 3 : 2) void cpl_fwd_kernel(CplFP p) 
                 const int pp = i / K4, s = i - pp * K4;
                 const int py = pp / PW, px = pp - py * PW;
                 const float4 v = pv[u];
-                *reinterpret_cast<float2*>(XQ + ((2 * s) * PP + pp) * 2) = make_float2(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f));
+                *reinterpret_cast<float2*>(XQ + ((2 * s) * PP + pp) * 2) = make_float2(tmg_relu(v.x), tmg_relu(v.y));
                 if (s < CH4) {
-                    *reinterpret_cast<float2*>(XQ + ((2 * s + 1) * PP + pp) * 2) = make_float2(fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
+                    *reinterpret_cast<float2*>(XQ + ((2 * s + 1) * PP + pp) * 2) = make_float2(tmg_relu(v.z), tmg_relu(v.w));
                     const int cy = py - 1, cx = px - 1;
                     if (cy >= 0 && cy < 16 && cx >= 0 && cx < 16) {
                         const int cp = cy * 16 + cx;
@@ -665,7 +665,7 @@ __global__ __launch_bounds__(256, CT == 1 ? 2 : 2) void cpl_bwd_kernel(CplBP p) 
 #undef TMG_CPLB_TAP
             if constexpr (SUM) {
                 // the pixel's mask word: this lane's four bits at its channels, gathered over the pixel's four lanes (li + 16 q')
-                unsigned mb = ((xm.x > 0.f ? 1u : 0u) | (xm.y > 0.f ? 2u : 0u) | (xm.z > 0.f ? 4u : 0u) | (xm.w > 0.f ? 8u : 0u)) << (4 * q);
+                unsigned mb = ((!(xm.x <= 0.f) ? 1u : 0u) | (!(xm.y <= 0.f) ? 2u : 0u) | (!(xm.z <= 0.f) ? 4u : 0u) | (!(xm.w <= 0.f) ? 8u : 0u)) << (4 * q);
                 mb |= (unsigned)__shfl_xor((int)mb, 16);
                 mb |= (unsigned)__shfl_xor((int)mb, 32);
                 if (pin) {
@@ -676,8 +676,8 @@ __global__ __launch_bounds__(256, CT == 1 ? 2 : 2) void cpl_bwd_kernel(CplBP p) 
                         if (c < ch) {
                             const float4 t = *reinterpret_cast<const float4*>(T1 + ((row0 + nt) * 16 + li) * ch + c);
                             *reinterpret_cast<float4*>(p.dtin + TMG_PXO(gp, p.dts) + c) =
-                                make_float4(t.x + (xm.x > 0.f ? acc[mt][0] : 0.f), t.y + (xm.y > 0.f ? acc[mt][1] : 0.f),
-                                            t.z + (xm.z > 0.f ? acc[mt][2] : 0.f), t.w + (xm.w > 0.f ? acc[mt][3] : 0.f));
+                                make_float4(t.x + (!(xm.x <= 0.f) ? acc[mt][0] : 0.f), t.y + (!(xm.y <= 0.f) ? acc[mt][1] : 0.f),
+                                            t.z + (!(xm.z <= 0.f) ? acc[mt][2] : 0.f), t.w + (!(xm.w <= 0.f) ? acc[mt][3] : 0.f));
                         } else if (c == ch)
                             *reinterpret_cast<float4*>(p.GD + TMG_PXO(gp, 4)) = make_float4(acc[mt][0], acc[mt][1], __uint_as_float(mb), 0.f);
                     }
@@ -689,7 +689,8 @@ __global__ __launch_bounds__(256, CT == 1 ? 2 : 2) void cpl_bwd_kernel(CplBP p) 
                     const int c = 16 * mt + 4 * q;
                     const float4 v = make_float4(acc[mt][0], acc[mt][1], acc[mt][2], acc[mt][3]);
                     if (c < ch) *reinterpret_cast<float4*>(p.G0 + TMG_PXO(gp, ch) + c) = v;
-                    else if (c == ch) *reinterpret_cast<float4*>(p.GD + TMG_PXO(gp, 4)) = v;   // (d1, d2, 0, 0): rows past ch + 1 carry zero weights
+                    // (d1, d2, 0, 0): rows past ch + 1 carry zero weights, and 0 * NaN is not 0: the padding is written as zeros
+                    else if (c == ch) *reinterpret_cast<float4*>(p.GD + TMG_PXO(gp, 4)) = make_float4(v.x, v.y, 0.f, 0.f);
                 }
             }
         }

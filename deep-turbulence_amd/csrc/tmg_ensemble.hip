@@ -98,11 +98,11 @@ __global__ __launch_bounds__(256) void ens_accum_kernel(const float* __restrict_
             if (c < C) {
                 const size_t o = (size_t)b * ocs + (size_t)c * hw + p;
                 mean_out[o] = mean[c];
-                std_out[o] = sqrtf(fmaxf(m2[c], 0.f) * rn);
+                std_out[o] = sqrtf(tmg_relu(m2[c]) * rn);
             }
         }
         mag_mean[(size_t)b * mcs + p] = mean[ENS_MAXC];
-        mag_std[(size_t)b * mcs + p] = sqrtf(fmaxf(m2[ENS_MAXC], 0.f) * rn);
+        mag_std[(size_t)b * mcs + p] = sqrtf(tmg_relu(m2[ENS_MAXC]) * rn);
     } else {
 #pragma unroll
         for (int c = 0; c <= ENS_MAXC; ++c) {
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256) void ens_time_finalize_kernel(const float* __r
         for (int m = 0; m < S; ++m) {
             const size_t i = (size_t)m * n + e;
             const float tv = tmean[i];
-            const float rv = sqrtf(fmaxf(tm2[i], 0.f) * rT);
+            const float rv = sqrtf(tmg_relu(tm2[i]) * rT);
             const float rn = 1.f / (float)(m + 1);
             float d = tv - am;
             am += d * rn;
@@ -157,9 +157,9 @@ __global__ __launch_bounds__(256) void ens_time_finalize_kernel(const float* __r
         }
         const float rs = 1.f / (float)S;
         tm_mean[e] = am;
-        tm_std[e] = sqrtf(fmaxf(aq, 0.f) * rs);
+        tm_std[e] = sqrtf(tmg_relu(aq) * rs);
         rms_mean[e] = rm;
-        rms_std[e] = sqrtf(fmaxf(rq, 0.f) * rs);
+        rms_std[e] = sqrtf(tmg_relu(rq) * rs);
     }
 }
 
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(256) void ens_turb_accum_kernel(const float* __rest
     }
     if (flags & 2) {
         vort_mean[(size_t)b * vcs + p] = mean;
-        vort_std[(size_t)b * vcs + p] = sqrtf(fmaxf(m2, 0.f) * (1.f / n));
+        vort_std[(size_t)b * vcs + p] = sqrtf(tmg_relu(m2) * (1.f / n));
     } else {
         vmean[si] = mean;
         vm2[si] = m2;
@@ -337,11 +337,11 @@ __global__ __launch_bounds__(256) void ens_turb_finalize_kernel(const float* __r
         }
         const float rs = 1.f / (float)S;
         uv_mean[e] = am[0];
-        uv_std[e] = sqrtf(fmaxf(aq[0], 0.f) * rs);
+        uv_std[e] = sqrtf(tmg_relu(aq[0]) * rs);
         tke_mean[e] = am[1];
-        tke_std[e] = sqrtf(fmaxf(aq[1], 0.f) * rs);
+        tke_std[e] = sqrtf(tmg_relu(aq[1]) * rs);
         tv_mean[e] = am[2];
-        tv_std[e] = sqrtf(fmaxf(aq[2], 0.f) * rs);
+        tv_std[e] = sqrtf(tmg_relu(aq[2]) * rs);
     }
 }
 

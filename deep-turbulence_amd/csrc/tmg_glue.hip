@@ -93,12 +93,8 @@ __global__ __launch_bounds__(256) void gauss_sample_kernel(const float* __restri
             const int j = (int)(i - pl * (unsigned)Ch);
             float4 mean = *reinterpret_cast<const float4*>(hz + pix * hs + j);
             float4 lsd = *reinterpret_cast<const float4*>(hz + pix * hs + Ch + j);
-            if (clip_mean) {
-                mean.x = fminf(fmaxf(mean.x, mlo), mhi); mean.y = fminf(fmaxf(mean.y, mlo), mhi);
-                mean.z = fminf(fmaxf(mean.z, mlo), mhi); mean.w = fminf(fmaxf(mean.w, mlo), mhi);
-            }
-            lsd.x = fminf(fmaxf(lsd.x, slo), shi); lsd.y = fminf(fmaxf(lsd.y, slo), shi);
-            lsd.z = fminf(fmaxf(lsd.z, slo), shi); lsd.w = fminf(fmaxf(lsd.w, slo), shi);
+            if (clip_mean) mean = tmg_clamp4(mean, mlo, mhi);
+            lsd = tmg_clamp4(lsd, slo, shi);
             float4 v = make_float4(nrm[0], nrm[1], nrm[2], nrm[3]);
             if (eps_in) v = *reinterpret_cast<const float4*>(eps_in + pix * es + j);
             lp += -0.5f * (4.f * LOG2PI_G + 2.f * (lsd.x + lsd.y + lsd.z + lsd.w) + v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w);
@@ -117,8 +113,8 @@ __global__ __launch_bounds__(256) void gauss_sample_kernel(const float* __restri
             const int j = (int)(i - pl * (unsigned)Ch);
             float mean = hz[pix * hs + j];
             float lsd = hz[pix * hs + Ch + j];
-            if (clip_mean) mean = fminf(fmaxf(mean, mlo), mhi);
-            lsd = fminf(fmaxf(lsd, slo), shi);
+            if (clip_mean) mean = tmg_clamp(mean, mlo, mhi);
+            lsd = tmg_clamp(lsd, slo, shi);
             const float v = eps_in ? eps_in[pix * es + j] : nrm[e];
             lp += -0.5f * (LOG2PI_G + 2.f * lsd + v * v);
             out[pix * os + oo + j] = mean + expf(lsd) * v;

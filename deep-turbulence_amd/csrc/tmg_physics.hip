@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void phys_fwd_kernel(PhysP p) {
         ux_x /= p.dx; uy_x /= p.dx; ux_y /= p.dy; uy_y /= p.dy;
         const float raw_p = p.dx * p.dy * ((pxx / (p.dx * p.dx) + pyy / (p.dy * p.dy)) / p.rho + ux_x * ux_x + 2.f * ux_y * uy_x + uy_y * uy_y);
         const float raw_d = p.dx * (dvy / p.dy + dux / p.dx);
-        const float ps = fminf(fmaxf(raw_p, -1.f), 1.f), us = fminf(fmaxf(raw_d, -1.f), 1.f);
+        const float ps = tmg_clamp(raw_p, -1.f, 1.f), us = tmg_clamp(raw_d, -1.f, 1.f);
         if (p.pstar_out) p.pstar_out[(size_t)n * plane + (size_t)i * p.W + j] = ps;
         if (p.ustar_out) p.ustar_out[((size_t)n * p.H + i) * (p.W + 2) + j + 1] = us;
         const bool rin = (i >= 1 && i <= p.H - 2);
@@ -115,7 +115,7 @@ __global__ void phys_div_edge_kernel(PhysP p) {
                 dvy += g1w(b, a) * V;
             }
         const float raw_d = p.dx * (dvy / p.dy + dux / p.dx);
-        p.ustar_out[((size_t)n * p.H + i) * (p.W + 2) + c] = fminf(fmaxf(raw_d, -1.f), 1.f);
+        p.ustar_out[((size_t)n * p.H + i) * (p.W + 2) + c] = tmg_clamp(raw_d, -1.f, 1.f);
     }
 }
 
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256) void phys_rms_kernel(const float* __restrict__
         acc += d * d;
         if (mean_out) {
             mean_out[k] = m;
-            coef_out[k] = rms > 0.f ? d / (T * rms) : 0.f;
+            coef_out[k] = rms <= 0.f ? 0.f : d / (T * rms);            // a NaN rms stays NaN ("Non-finite values")
         }
     }
     const float tot = block_sum_256(acc, red);
@@ -205,10 +205,11 @@ __global__ __launch_bounds__(256) void phys_bwd_kernel(PhysBP p) {
             const float raw_p = p.dx * p.dy_ * ((pxx / (p.dx * p.dx) + pyy / (p.dy_ * p.dy_)) / p.rho + ux_x * ux_x + 2.f * ux_y * uy_x + uy_y * uy_y);
             const float raw_d = p.dx * (dvy / p.dy_ + dux / p.dx);
             const bool rin = (i >= 1 && i <= p.H - 2);
-            if (rin && j >= 1 && j <= p.W - 2 && raw_p >= -1.f && raw_p <= 1.f) {
-                const float a_p = cp_ * raw_p * p.dx * p.dy_;
-                s1 = a_p * 2.f * ux_x; s2 = a_p * 2.f * uy_x; s3 = a_p * 2.f * ux_y; s4 = a_p * 2.f * uy_y; s5 = a_p / p.rho;
-            }
+            // The clamp's gradient is a select (0 outside [-1, 1], outside the interior and at a NaN residual), but the products with
+            // the velocity derivatives are formed all the same, as autograd forms 2 ux_x * 0: a non-finite derivative stays visible
+            // in the velocity gradients, a non-finite pressure (which enters linearly) does not ("Non-finite values").
+            const float a_p = (rin && j >= 1 && j <= p.W - 2 && raw_p >= -1.f && raw_p <= 1.f) ? cp_ * raw_p * p.dx * p.dy_ : 0.f;
+            s1 = a_p * 2.f * ux_x; s2 = a_p * 2.f * uy_x; s3 = a_p * 2.f * ux_y; s4 = a_p * 2.f * uy_y; s5 = a_p / p.rho;
             if (rin && raw_d >= -1.f && raw_d <= 1.f) s6 = cd_ * raw_d * p.dx;
         }
         S[0][li][lj] = s1; S[1][li][lj] = s2; S[2][li][lj] = s3; S[3][li][lj] = s4; S[4][li][lj] = s5; S[5][li][lj] = s6;
@@ -322,7 +323,7 @@ __global__ void phys_fields_kernel(const float* __restrict__ u, const float* __r
                     dvy += w1(b, a) * V[(size_t)ii * W + jc];
                 }
             const float raw = sd * (dvy / dy + dux / dx);
-            ustar[idx] = fminf(fmaxf(raw, -1.f), 1.f);
+            ustar[idx] = tmg_clamp(raw, -1.f, 1.f);
         }
         if (pstar && jw < W) {
             const int j = jw;
@@ -349,7 +350,7 @@ __global__ void phys_fields_kernel(const float* __restrict__ u, const float* __r
                 }
             ux_x /= dx; uy_x /= dx; ux_y /= dy; uy_y /= dy;
             const float raw = sp * ((pxx / (dx * dx) + pyy / (dy * dy)) / rho + ux_x * ux_x + 2.f * ux_y * uy_x + uy_y * uy_y);
-            pstar[((size_t)n * H + i) * W + j] = fminf(fmaxf(raw, -1.f), 1.f);
+            pstar[((size_t)n * H + i) * W + j] = tmg_clamp(raw, -1.f, 1.f);
         }
     }
 }
@@ -612,7 +613,7 @@ __global__ __launch_bounds__(256) void adam_step_kernel(const long long* __restr
             m[i] = mi; v[i] = vi;
             float den;
             if (amsgrad) {
-                const float vx = fmaxf(vm[i], vi);
+                const float vx = __builtin_elementwise_maximum(vm[i], vi);     // torch.maximum: a NaN v stays in vmax
                 vm[i] = vx;
                 den = sqrtf(vx) / bc2s + eps;
             } else {

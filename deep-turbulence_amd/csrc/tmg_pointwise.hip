@@ -263,8 +263,8 @@ __global__ __launch_bounds__(256) void gauss_fwd_kernel(const float* __restrict_
         const int j = (int)(i - pl * (unsigned)Ch);
         float mean = hz[pix * hs + ho + j];
         float lsd = hz[pix * hs + ho + Ch + j];
-        if (clip_mean) mean = fminf(fmaxf(mean, mlo), mhi);
-        lsd = fminf(fmaxf(lsd, slo), shi);
+        if (clip_mean) mean = tmg_clamp(mean, mlo, mhi);
+        lsd = tmg_clamp(lsd, slo, shi);
         const float v = zin[pix * zs + zo + j];
         if (mode == 0) {
             const float e = (v - mean) * expf(-lsd);
@@ -291,10 +291,10 @@ __global__ void gauss_bwd_kernel(const float* __restrict__ hz, int hs, int ho, c
         const int j = i % Ch;
         const int b = (int)(pix / pix_per_img);
         const float mraw = hz[pix * hs + ho + j], sraw = hz[pix * hs + ho + Ch + j];
-        float mean = mraw, lsd = fminf(fmaxf(sraw, slo), shi);
+        float mean = mraw, lsd = tmg_clamp(sraw, slo, shi);
         bool mpass = true;
         if (clip_mean) {
-            mean = fminf(fmaxf(mraw, mlo), mhi);
+            mean = tmg_clamp(mraw, mlo, mhi);
             mpass = (mraw > mlo) && (mraw < mhi);
         }
         const bool spass = (sraw > slo) && (sraw < shi);
@@ -594,7 +594,7 @@ __global__ __launch_bounds__(256) void chan_reduce_kernel(const float* __restric
                         a1 += d * d;
                     } else {
                         const float uu = xv[u] * v0[c] + v1[c];
-                        const float du = uu > 0.f ? gv[u] : 0.f;
+                        const float du = !(uu <= 0.f) ? gv[u] : 0.f;
                         a0 += du;
                         a1 += du * (xv[u] - v2[c]) * v3[c];
                     }
@@ -707,7 +707,7 @@ __global__ void bn_finalize_kernel(const float* __restrict__ sum, const float* _
 }
 
 // BatchNorm(+ReLU) input gradient:  u = x*a_c + b_c,  du = g*[u>0],
-//   dx = gamma_c * rstd_c * (du - m0_c - xhat * m1_c)     (m0 = mean du, m1 = mean du*xhat)
+//   dx = gamma_c * rstd_c * (du - m0_c - xhat * m1_c)     (m0 = mean du, m1 = mean du*xhat; both NULL: dx = gamma_c * rstd_c * du)
 __global__ void bn_bwd_apply_kernel(const float* __restrict__ x, int xs, int xo, const float* __restrict__ g, int gs, int go,
                                     const float* __restrict__ a, const float* __restrict__ bsh, const float* __restrict__ mean,
                                     const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ m0,
@@ -719,9 +719,11 @@ __global__ void bn_bwd_apply_kernel(const float* __restrict__ x, int xs, int xo,
         const int c = i % C;
         const float xv = x[pix * xs + xo + c];
         const float u = xv * a[c] + bsh[c];
-        const float du = u > 0.f ? g[pix * gs + go + c] : 0.f;
+        const float du = !(u <= 0.f) ? g[pix * gs + go + c] : 0.f;
         const float xh = (xv - mean[c]) * rstd[c];
-        const float v = gamma[c] * rstd[c] * (du - m0[c] * m_scale - xh * m1[c] * m_scale);
+        // m0 == nullptr: the statistics are constants (eval mode) and dx = gamma rstd du; the correction terms are absent, not
+        // 0 * xhat, which would turn a non-finite x into a non-finite dx that the reference does not have ("Non-finite values")
+        const float v = gamma[c] * rstd[c] * (m0 ? du - m0[c] * m_scale - xh * m1[c] * m_scale : du);
         float* d = dx + pix * ds + dof + c;
         *d = accumulate ? (*d + v) : v;
     }
@@ -738,7 +740,7 @@ __global__ void masked_add_kernel(const float* __restrict__ src, int ss, int so,
         const size_t pix = i / n;
         const int c = i % n;
         float v = src ? src[pix * ss + so + c] : 0.f;
-        if (ref && !(ref[pix * rs_ + ro + c] > 0.f)) v = 0.f;
+        if (ref && ref[pix * rs_ + ro + c] <= 0.f) v = 0.f;
         if (add) v += add[pix * as + ao + c];
         float* d = dst + pix * ds + dof + c;
         *d = accumulate ? (*d + v) : v;
@@ -757,10 +759,10 @@ __global__ __launch_bounds__(256) void masked_add4_kernel(const float* __restric
         float4 v = src ? *reinterpret_cast<const float4*>(src + (size_t)pix * ss + so + c) : make_float4(0.f, 0.f, 0.f, 0.f);
         if (ref) {
             const float4 r = *reinterpret_cast<const float4*>(ref + (size_t)pix * rs_ + ro + c);
-            if (!(r.x > 0.f)) v.x = 0.f;
-            if (!(r.y > 0.f)) v.y = 0.f;
-            if (!(r.z > 0.f)) v.z = 0.f;
-            if (!(r.w > 0.f)) v.w = 0.f;
+            if (r.x <= 0.f) v.x = 0.f;
+            if (r.y <= 0.f) v.y = 0.f;
+            if (r.z <= 0.f) v.z = 0.f;
+            if (r.w <= 0.f) v.w = 0.f;
         }
         if (add) {
             const float4 a = *reinterpret_cast<const float4*>(add + (size_t)pix * as + ao + c);
@@ -969,7 +971,7 @@ __global__ __launch_bounds__(256) void c1x2_fwd_kernel(C1X2P p) {
     if (lead) {
 #pragma unroll
         for (int u = 0; u < 2; ++u)
-            if (rok[u]) ld1[ry[u] * RW + rx[u]] = rin[u] ? fmaxf(acc1[u] + a1v[u], 0.f) : 0.f;
+            if (rok[u]) ld1[ry[u] * RW + rx[u]] = rin[u] ? tmg_relu(acc1[u] + a1v[u]) : 0.f;
     }
     const float d1own = acc1[0] + a1v[0];   // raw d1 of the own pixel
     __syncthreads();
@@ -1037,7 +1039,7 @@ __global__ __launch_bounds__(256) void c1_bwd_kernel(C1BP p) {
             if (y >= 0 && y < p.Hin && x >= 0 && x < p.Win) {
                 const size_t pix = ((size_t)b * p.Hin + y) * p.Win + x;
                 v = p.dd[pix * p.dd_stride + p.dd_off];
-                if (p.dref && !(p.dref[pix * p.dref_stride + p.dref_off] > 0.f)) v = 0.f;
+                if (p.dref && p.dref[pix * p.dref_stride + p.dref_off] <= 0.f) v = 0.f;
             }
             ldd[i] = v;
         }
@@ -1235,7 +1237,7 @@ __global__ __launch_bounds__(256) void dense2_bwd_kernel(D2BP p) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int i = tid + u * 256;
-            if (i < QH * QW) A2[i] = (a2in[u] && a2d[u] > 0.f) ? a2g[u] : 0.f;
+            if (i < QH * QW) A2[i] = (a2in[u] && !(a2d[u] <= 0.f)) ? a2g[u] : 0.f;
         }
         __syncthreads();
 #pragma unroll
@@ -1244,7 +1246,7 @@ __global__ __launch_bounds__(256) void dense2_bwd_kernel(D2BP p) {
             if (i < PH * PW) {
                 const int py = i / PW, px = i - py * PW;
                 float v = 0.f;
-                if (a1in[u] && a1d[u] > 0.f) {
+                if (a1in[u] && !(a1d[u] <= 0.f)) {
                     v = a1g[u];
 #pragma unroll
                     for (int tap = 0; tap < 9; ++tap) {
@@ -1303,10 +1305,10 @@ __global__ __launch_bounds__(256) void dense2_bwd_kernel(D2BP p) {
                         ad = (p.add0 && !sgi) ? *reinterpret_cast<const float4*>(p.add0 + opix * p.add0_stride + nl) : make_float4(0.f, 0.f, 0.f, 0.f); \
                     }                                                                                                     \
                     float4 o;                                                                                             \
-                    o.x = (m.x > 0.f ? g.x + v.x : 0.f) + ad.x;                                                           \
-                    o.y = (m.y > 0.f ? g.y + v.y : 0.f) + ad.y;                                                           \
-                    o.z = (m.z > 0.f ? g.z + v.z : 0.f) + ad.z;                                                           \
-                    o.w = (m.w > 0.f ? g.w + v.w : 0.f) + ad.w;                                                           \
+                    o.x = (!(m.x <= 0.f) ? g.x + v.x : 0.f) + ad.x;                                                       \
+                    o.y = (!(m.y <= 0.f) ? g.y + v.y : 0.f) + ad.y;                                                       \
+                    o.z = (!(m.z <= 0.f) ? g.z + v.z : 0.f) + ad.z;                                                       \
+                    o.w = (!(m.w <= 0.f) ? g.w + v.w : 0.f) + ad.w;                                                       \
                     *reinterpret_cast<float4*>(op) = o;                                                                   \
                 } else {                                                                                                  \
                     const float vv[4] = {v.x, v.y, v.z, v.w};                                                             \
@@ -1317,7 +1319,7 @@ __global__ __launch_bounds__(256) void dense2_bwd_kernel(D2BP p) {
                             const int sgi = (nl >= p.g0[0].n) ? 1 : 0;                                                    \
                             if (sgi) nl -= p.g0[0].n;                                                                     \
                             const float g = (sgi ? p.g0[1].p : p.g0[0].p)[opix * (sgi ? p.g0[1].stride : p.g0[0].stride) + (sgi ? p.g0[1].off : p.g0[0].off) + nl]; \
-                            float o = mm[e] > 0.f ? g + vv[e] : 0.f;                                                      \
+                            float o = !(mm[e] <= 0.f) ? g + vv[e] : 0.f;                                                  \
                             if (p.add0 && !sgi) o += p.add0[opix * p.add0_stride + nl];                                   \
                             (sgi ? p.out[1].p : p.out[0].p)[opix * (sgi ? p.out[1].stride : p.out[0].stride) + (sgi ? p.out[1].off : p.out[0].off) + nl] = o; \
                         }                                                                                                 \
@@ -1454,7 +1456,7 @@ __global__ __launch_bounds__(256, NQ <= 2 ? 4 : 3) void dense2_bwd_lean_kernel(D
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int i = tidl + u * 256;
-            if (i < QH * QW) A2[i] = (a2in[u] && a2d[u] > 0.f) ? a2g[u] : 0.f;
+            if (i < QH * QW) A2[i] = (a2in[u] && !(a2d[u] <= 0.f)) ? a2g[u] : 0.f;
         }
         __syncthreads();
 #pragma unroll
@@ -1463,7 +1465,7 @@ __global__ __launch_bounds__(256, NQ <= 2 ? 4 : 3) void dense2_bwd_lean_kernel(D
             if (i < PH * PW) {
                 const int py = i / PW, px = i - py * PW;
                 float v = 0.f;
-                if (a1in[u] && a1d[u] > 0.f) {
+                if (a1in[u] && !(a1d[u] <= 0.f)) {
                     v = a1g[u];
 #pragma unroll
                     for (int tap = 0; tap < 9; ++tap) {
@@ -1510,10 +1512,10 @@ __global__ __launch_bounds__(256, NQ <= 2 ? 4 : 3) void dense2_bwd_lean_kernel(D
                         o.z = gq[j].z + ((m4 & 4u) ? v.z : 0.f);
                         o.w = gq[j].w + ((m4 & 8u) ? v.w : 0.f);
                     } else {
-                    o.x = (mq[j].x > 0.f ? gq[j].x + v.x : 0.f) + aq[j].x;
-                    o.y = (mq[j].y > 0.f ? gq[j].y + v.y : 0.f) + aq[j].y;
-                    o.z = (mq[j].z > 0.f ? gq[j].z + v.z : 0.f) + aq[j].z;
-                    o.w = (mq[j].w > 0.f ? gq[j].w + v.w : 0.f) + aq[j].w;
+                    o.x = (!(mq[j].x <= 0.f) ? gq[j].x + v.x : 0.f) + aq[j].x;
+                    o.y = (!(mq[j].y <= 0.f) ? gq[j].y + v.y : 0.f) + aq[j].y;
+                    o.z = (!(mq[j].z <= 0.f) ? gq[j].z + v.z : 0.f) + aq[j].z;
+                    o.w = (!(mq[j].w <= 0.f) ? gq[j].w + v.w : 0.f) + aq[j].w;
                     }
                     *reinterpret_cast<float4*>(ob + (opix * os4 + 16u * j)) = o;
                 }

@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void wgrad_thin_kernel(ThinP p) {
                 else if (c < n0 + n1) a_ = sp1 + pix * ss1 + (c - n0);
                 else a_ = sp2 + pix * ss2 + (c - n0 - n1);
                 v = tmg_ldg4(a_);
-                if (p.relu_in) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+                if (p.relu_in) v = tmg_relu4(v);
             }
             *reinterpret_cast<float4*>(X + (row * PWp + col) * CS + 4 * qd) = v;
         }

@@ -132,7 +132,7 @@ constexpr int VPL = 32 * VS;               // words per V position plane (32 Win
         _Pragma("unroll") for (int u = 0; u < UPI; ++u) {                                                             \
             if (ppix0 + u * 64 < PP) {                                                                                \
                 float4 v = pv[u];                                                                                     \
-                if (p.relu_in) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); } \
+                if (p.relu_in) v = tmg_relu4(v); \
                 *reinterpret_cast<float4*>(rb_ + (ppix0 + u * 64) * CS + 4 * pc4) = v;                                \
             }                                                                                                         \
         }                                                                                                             \
@@ -469,10 +469,7 @@ __global__ __launch_bounds__(768, 1) void wino_fwdp_kernel(WinoP p) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        d[r][c].x = fmaxf(d[r][c].x, 0.f); d[r][c].y = fmaxf(d[r][c].y, 0.f);
-                        d[r][c].z = fmaxf(d[r][c].z, 0.f); d[r][c].w = fmaxf(d[r][c].w, 0.f);
-                    }
+                    for (int c = 0; c < 4; ++c) d[r][c] = tmg_relu4(d[r][c]);
             }
             float* vbuf = lds + (k & 1) * VBUF + tv;
 #pragma unroll
@@ -1151,7 +1148,7 @@ __global__ __launch_bounds__(512, 1) void wino_nn_kernel(WinoNP p) {
                             float4 y = ox == 0 ? make_float4(za.x + zb.x + zc.x, za.y + zb.y + zc.y, za.z + zb.z + zc.z, za.w + zb.w + zc.w)
                                                : make_float4(zb.x - zc.x - zd.x, zb.y - zc.y - zd.y, zb.z - zc.z - zd.z, zb.w - zc.w - zd.w);
                             y.x += bv.x; y.y += bv.y; y.z += bv.z; y.w += bv.w;
-                            if (p.relu_out) { y.x = fmaxf(y.x, 0.f); y.y = fmaxf(y.y, 0.f); y.z = fmaxf(y.z, 0.f); y.w = fmaxf(y.w, 0.f); }
+                            if (p.relu_out) y = tmg_relu4(y);
                             const int py = ty_ * TH + 2 * (wt >> 3) + oy, px = tx_ * TW + 2 * (wt & 7) + ox;
                             if (py < p.Hin && px < p.Win)
                                 *reinterpret_cast<float4*>(optr + (size_t)(((unsigned)b_ * (unsigned)p.Hin + (unsigned)py) * (unsigned)p.Win + (unsigned)px) * (unsigned)ostride + ooff + nl) = y;
@@ -1365,7 +1362,7 @@ __global__ __launch_bounds__(512, 1) void wino_wgrad_kernel(WinoWP p) {
         _Pragma("unroll") for (int u = 0; u < UX; ++u) {                                                               \
             if (xc4 < CIT * 4 && xpix0 + u * xstep < PP) {                                                             \
                 float4 v = xv[u];                                                                                      \
-                if (p.relu_in) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); } \
+                if (p.relu_in) v = tmg_relu4(v); \
                 *reinterpret_cast<float4*>((XRB) + (xpix0 + u * xstep) * CSX + 4 * xc4) = v;                           \
             }                                                                                                          \
         }                                                                                                              \

@@ -1862,8 +1862,9 @@ def chan_reduce(x, g, v0, v1, v2, v3, s0, s1, mode, divisor=0):
 
 
 def bn_bwd_apply(x, g, a, bsh, mean, rstd, gamma, m0, m1, dx, accumulate, divisor=0):
-    """divisor > 0: m0, m1 are sums and are divided by it inside the kernel."""
+    """divisor > 0: m0, m1 are sums and are divided by it inside the kernel.  m0 = m1 = None: the statistics are constants (eval mode)."""
     B, H, W, C = x.shape
+    assert (m0 is None) == (m1 is None)
     _chk(lib().tmg_bn_bwd_apply(_ptr(x), _d2(x), _ptr(g), _d2(g), _ptr(a), _ptr(bsh), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(m0),
                                 _ptr(m1), _ptr(dx), _d2(dx), _i64(B * H * W, C, accumulate, divisor), _stream()), "tmg_bn_bwd_apply")
 

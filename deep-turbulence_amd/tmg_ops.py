@@ -409,7 +409,7 @@ class BNReLUConvFn(torch.autograd.Function):
         wpk_t = H.conv_pack(weight, 1)
         G = empty((B, Hh, Ww, C), x.device)
         H.conv_fwd([dy], wpk_t, C, 3, 1, [G])
-        s = zeros((3, C), x.device)  # sums of du, du*xhat, and a zero row for the eval-mode call
+        s = zeros((2, C), x.device)  # sums of du, du*xhat
         s0, s1 = s[0], s[1]
         H.chan_reduce(x, G, a, bsh, mean, rstd, s0, s1, 1)
         dgamma, dbeta = s1, s0
@@ -417,7 +417,7 @@ class BNReLUConvFn(torch.autograd.Function):
         if ctx.training:
             H.bn_bwd_apply(x, G, a, bsh, mean, rstd, gamma, s0, s1, dx, False, divisor=n)
         else:
-            H.bn_bwd_apply(x, G, a, bsh, mean, rstd, gamma, s[2], s[2], dx, False)
+            H.bn_bwd_apply(x, G, a, bsh, mean, rstd, gamma, None, None, dx, False)
         return (dx,) + _defer((gamma, None, weight), (dgamma, dbeta, dW)) + (None, None, None, None, None)
 
 
@@ -487,12 +487,12 @@ class DenseBlockFn(torch.autograd.Function):
             H.conv_wgrad([xin], dy, dW, None, 3, 1, in_scale=a, in_shift=bsh, relu_in=True)
             G = empty((B, Hh, Ww, c), buf.device)
             H.conv_fwd([dy], ctx.packs_t[i], c, 3, 1, [G])
-            s = zeros((3, c), buf.device)   # sums of du, du*xhat, and a zero row for the eval-mode call
+            s = zeros((2, c), buf.device)   # sums of du, du*xhat
             H.chan_reduce(xin, G, a, bsh, mean, rstd, s[0], s[1], 1)
             if use_batch[i]:
                 H.bn_bwd_apply(xin, G, a, bsh, mean, rstd, gamma, s[0], s[1], dbuf[..., :c], True, divisor=n)
             else:
-                H.bn_bwd_apply(xin, G, a, bsh, mean, rstd, gamma, s[2], s[2], dbuf[..., :c], True)
+                H.bn_bwd_apply(xin, G, a, bsh, mean, rstd, gamma, None, None, dbuf[..., :c], True)
             grads[3 * i:3 * i + 3] = [s[1], s[0], dW]
         ctx.stats = None
         ctx.packs_t = None

@@ -197,7 +197,7 @@ int tmg_upsample_bwd(const void* dout, void* din, const int64_t* dims, tmg_strea
 /* Per-channel sums over pixels: BatchNorm batch moments (mode 0) and backward sums (mode 1)
  * (nn.BatchNorm2d at denseBlock.py:49).  dims = {npix, C, mode, divisor}: mode 0 subtracts v0[c]/divisor before summing
  * (divisor 0: v0 as is) - the centred second pass takes the first pass's sums directly.  tmg_bn_bwd_apply: dims = {npix, C,
- * accumulate, divisor} with m0, m1 divided by divisor. */
+ * accumulate, divisor} with m0, m1 divided by divisor; m0 = m1 = NULL: constant statistics (eval mode), dx = gamma rstd du. */
 int tmg_chan_reduce(const void* x, const int64_t* x_d, const void* g, const int64_t* g_d, const void* v0, const void* v1,
                     const void* v2, const void* v3, void* s0, void* s1, const int64_t* dims, tmg_stream_t st);
 int tmg_bn_bwd_apply(const void* x, const int64_t* x_d, const void* g, const int64_t* g_d, const void* a, const void* bsh,
