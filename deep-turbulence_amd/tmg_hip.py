@@ -20,7 +20,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmglow_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip", "tmg_phase.hip", "tmg_spod.hip", "tmg_budget.hip", "tmg_corr.hip", "tmg_flux.hip"]
+SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip", "tmg_phase.hip", "tmg_spod.hip", "tmg_budget.hip", "tmg_corr.hip", "tmg_flux.hip", "tmg_lagr.hip"]
 # Sources compiled WITHOUT the packed-fp32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32): beside MFMAs a packed
 # f32 instruction costs ~13 cycles more than the two scalar ones it replaces (MI355X_MICROARCH.md, cycle constants, 'price of one
 # filler beside MFMAs'), and the compiler SLP-packs adjacent scalar adds / multiplies by itself under -O3.  The matrix-core kernels'
@@ -91,6 +91,9 @@ CORR_EXPORTS = ["tmg_ens_corr_plan", "tmg_ens_corr_probe", "tmg_ens_corr_accum",
 # The scale-to-scale energy flux and the sub-filter stresses (csrc/tmg_flux.hip), declared in include/tmglow_hip_flux.h, a header of its
 # own: ens_flux_plan / ens_flux_accum / ens_flux_terms below.
 FLUX_EXPORTS = ["tmg_ens_flux_plan", "tmg_ens_flux_accum", "tmg_ens_flux_terms"]
+# The Lagrangian transport: pathlines, FTLE, residence time (csrc/tmg_lagr.hip), declared in include/tmglow_hip_lagr.h, a header of its
+# own: ens_lagr_plan / ens_lagr_advect / ens_lagr_store / ens_lagr_finalize below.
+LAGR_EXPORTS = ["tmg_ens_lagr_plan", "tmg_ens_lagr_advect", "tmg_ens_lagr_store", "tmg_ens_lagr_finalize"]
 _P64 = ctypes.POINTER(ctypes.c_int64)
 FLUX_ARGTYPES = {
     "tmg_ens_flux_plan": [_P64, _P64, _P64],
@@ -113,7 +116,8 @@ def build(force=False, verbose=False):
                os.path.join(inc, "tmglow_hip_gram.h"), os.path.join(inc, "tmglow_hip_sfun.h"),
                os.path.join(inc, "tmglow_hip_event.h"), os.path.join(inc, "tmglow_hip_pdf.h"), os.path.join(inc, "tmglow_hip_pod.h"),
                os.path.join(inc, "tmglow_hip_phase.h"), os.path.join(inc, "tmglow_hip_spod.h"), os.path.join(inc, "tmglow_hip_layout.h"),
-               os.path.join(inc, "tmglow_hip_budget.h"), os.path.join(inc, "tmglow_hip_corr.h"), os.path.join(inc, "tmglow_hip_flux.h")]
+               os.path.join(inc, "tmglow_hip_budget.h"), os.path.join(inc, "tmglow_hip_corr.h"), os.path.join(inc, "tmglow_hip_flux.h"),
+               os.path.join(inc, "tmglow_hip_lagr.h")]
     hmt = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -167,7 +171,7 @@ def lib():
         for name in PLAN_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
             getattr(_lib, name).argtypes = PLAN_ARGTYPES[name]
-        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS + SFUN_EXPORTS + EVENT_EXPORTS + PDF_EXPORTS + POD_EXPORTS + PHASE_EXPORTS + SPOD_EXPORTS + LAYOUT_EXPORTS + BUDGET_EXPORTS + CORR_EXPORTS:
+        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS + SFUN_EXPORTS + EVENT_EXPORTS + PDF_EXPORTS + POD_EXPORTS + PHASE_EXPORTS + SPOD_EXPORTS + LAYOUT_EXPORTS + BUDGET_EXPORTS + CORR_EXPORTS + LAGR_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
         for name in FLUX_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
@@ -1589,6 +1593,115 @@ def ens_flux_terms(raw, k64, outs, widths, Hh, Ww, T):
     table = (c_vp * len(outs))(*[None if t is None else t.data_ptr() for t in outs])
     _chk(lib().tmg_ens_flux_terms(_ptr(raw), _ptr(k64), table, _ptr(ws), _i64(*widths), _i64(R - 1, B, Hh, Ww, T, L), _stream()),
          "tmg_ens_flux_terms")
+
+
+LAGR_OUTS = ("ftle_mean", "ftle_std", "target_ftle", "ftle_count", "disp_mean", "disp_std", "target_disp", "alive_frac", "target_alive",
+             "res_time_mean", "res_time_std", "target_res_time", "end_err_mean", "end_spread", "member_ftle", "member_end", "member_exit")
+LAGR_INT_OUTS = ("ftle_count", "member_exit")
+
+
+def ens_lagr_seeds(lattice, boxes, substeps):
+    """The host integers the advection and the finalize share: {Gh, Gw, oy, ox, sy, sx, R, n, then (h0, h1, w0, w1) of 4 boxes};
+    lattice = (Gh, Gw, oy, ox, sy, sx)."""
+    flat = [int(v) for v in lattice] + [len(boxes), int(substeps)]
+    for r in range(4):
+        flat += [int(v) for v in boxes[r]] if r < len(boxes) else [0, 0, 0, 0]
+    return _i64(*flat)
+
+
+def ens_lagr_steps(substeps):
+    """The host floats of one advection of n = substeps Heun steps: s_j = float32(j / n), j = 0 .. 8 (0 past n), h = float32(1 / n),
+    hh = float32(0.5 / n); each is one rounding of the fp64 quotient."""
+    n = int(substeps)
+    return _flts([j / n if j <= n else 0.0 for j in range(9)] + [1.0 / n, 0.5 / n])
+
+
+def ens_lagr_plan(S, B, Hh, Ww, P):
+    """The launch plans of ens_lagr_advect and ens_lagr_store for S members of B cases of [H, W] and P particles (tmg_ens_lagr_plan;
+    nothing is launched) -> dict: tile particles per advect block, tiles blocks per row and case (the advect grid is tiles x B x k),
+    store_tile pixels per store block, store_tiles blocks per row and case, vec: True when the planes of prev are written with
+    16-byte stores (W % 4 == 0 and an aligned state), bytes of pos, exit and prev."""
+    plan = (c_i64 * 6)()
+    _chk(lib().tmg_ens_lagr_plan(_i64(S, B, Hh, Ww, P), plan), "tmg_ens_lagr_plan")
+    tile, tiles, stile, stiles, vec, nbytes = [int(v) for v in plan]
+    return {"tile": tile, "tiles": tiles, "grid": (tiles, int(B)), "store_tile": stile, "store_tiles": stiles, "vec": bool(vec),
+            "bytes": nbytes}
+
+
+def _lagr_feed(name, y, a, o, prev, k):
+    kB, Hh, Ww, Cc = y.shape
+    ptr, ps, co, _ = seg(y)
+    check_device(y)
+    check_act(prev)
+    check_device(prev)
+    check_act(a)
+    check_act(o)
+    if prev.dim() != 4:
+        raise RuntimeError("%s: prev is [S + 1, B, 2, HW], got %s" % (name, tuple(prev.shape)))
+    R, B, two, HW = prev.shape
+    if not 2 <= Cc <= 4 or two != 2 or HW != Hh * Ww or kB != k * B or tuple(a.shape) != (B, 2) or tuple(o.shape) != (B, 2):
+        raise RuntimeError("%s: prev %s, a %s, o %s do not fit %d rows of %s" % (name, tuple(prev.shape), tuple(a.shape), tuple(o.shape),
+                                                                                k, tuple(y.shape)))
+    if not (prev.is_contiguous() and a.is_contiguous() and o.is_contiguous()):
+        raise RuntimeError("%s: contiguous fp32 device tables" % name)
+    return ptr, ps, co, R, B, Hh, Ww
+
+
+def ens_lagr_advect(y, a, o, prev, pos, exit_, res, lattice, boxes, substeps, k, row0, t_before):
+    """Seed (t_before == 0) or advect by one kept step the particles of one chunk of k rows (y: NHWC [k*B, H, W, 2..4] or a
+    channel-slice view, rows member-major; channels 0 and 1 are read): rows row0 .. row0 + k - 1 of the state pos [S + 1, B, 2, P]
+    fp32, exit [S + 1, B, P] int32, res [S + 1, B, R, P] int32, through the planes prev [S + 1, B, 2, HW] of the previous timed step
+    and the chunk's own rows, with the velocity tables a, o [B, 2] (device fp32) (tmg_ens_lagr_advect).  Before ens_lagr_store of the
+    same rows, on the same stream."""
+    ptr, ps, co, R, B, Hh, Ww = _lagr_feed("ens_lagr_advect", y, a, o, prev, k)
+    P = int(lattice[0]) * int(lattice[1])
+    check_act(pos)
+    check_device(pos)
+    for t, shp in ((exit_, (R, B, P)), (res, (R, B, len(boxes), P))):
+        if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()) or tuple(t.shape) != shp:
+            raise RuntimeError("ens_lagr_advect: exit and res are contiguous int32 %s on the device, got %s %s" % (shp, t.dtype, tuple(t.shape)))
+    if tuple(pos.shape) != (R, B, 2, P) or not pos.is_contiguous():
+        raise RuntimeError("ens_lagr_advect: pos is %s, not a contiguous %s" % (tuple(pos.shape), (R, B, 2, P)))
+    _chk(lib().tmg_ens_lagr_advect(c_vp(ptr), _i64(ps, co), _ptr(a), _ptr(o), _ptr(prev), _ptr(pos), _ptr(exit_), _ptr(res),
+                                   ens_lagr_seeds(lattice, boxes, substeps), ens_lagr_steps(substeps),
+                                   _i64(k, R - 1, B, Hh, Ww, row0, t_before), _stream()), "tmg_ens_lagr_advect")
+
+
+def ens_lagr_store(y, a, o, prev, k, row0):
+    """Write the converted velocity planes fl(fl(a y) + o) of one chunk of k rows into the rows row0 .. row0 + k - 1 of prev
+    [S + 1, B, 2, HW] (tmg_ens_lagr_store).  After ens_lagr_advect of the same rows, on the same stream."""
+    ptr, ps, co, R, B, Hh, Ww = _lagr_feed("ens_lagr_store", y, a, o, prev, k)
+    _chk(lib().tmg_ens_lagr_store(c_vp(ptr), _i64(ps, co), _ptr(a), _ptr(o), _ptr(prev), _i64(k, R - 1, B, Hh, Ww, row0), _stream()),
+         "tmg_ens_lagr_store")
+
+
+def ens_lagr_finalize(pos, exit_, res, fl, outs, lattice, boxes, Hh, Ww):
+    """The transport diagnostics of the state pos [S + 1, B, 2, P], exit [S + 1, B, P], res [S + 1, B, R, P]: outs = the 17 arrays of
+    LAGR_OUTS in that order (fp32 on the device, ftle_count and member_exit int32; the res_time_* None without boxes, the member_*
+    all three or None; shapes in include/tmglow_hip_lagr.h); fl = (dx, dy, step_dt, T_int) (tmg_ens_lagr_finalize)."""
+    check_act(pos)
+    check_device(pos)
+    if pos.dim() != 4 or len(outs) != len(LAGR_OUTS) or len(fl) != 4:
+        raise RuntimeError("ens_lagr_finalize: pos is [S + 1, B, 2, P] fp32 on the device, got %s" % (tuple(pos.shape),))
+    R, B, two, P = pos.shape
+    S, nb = R - 1, len(boxes)
+    if two != 2 or P != int(lattice[0]) * int(lattice[1]) or not pos.is_contiguous():
+        raise RuntimeError("ens_lagr_finalize: pos %s does not fit the lattice %s" % (tuple(pos.shape), tuple(lattice[:2])))
+    for t, shp in ((exit_, (R, B, P)), (res, (R, B, nb, P))):
+        if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()) or tuple(t.shape) != shp:
+            raise RuntimeError("ens_lagr_finalize: exit and res are contiguous int32 %s on the device, got %s %s" % (shp, t.dtype, tuple(t.shape)))
+    want = [(B, P)] * 4 + [(B, 2, P)] * 3 + [(B, P)] * 2 + [(B, nb, P)] * 3 + [(B, P)] * 2 + [(B, S, P), (B, S, 2, P), (B, S, P)]
+    for name, t, shp in zip(LAGR_OUTS, outs, want):
+        if t is None and (name.startswith("member_") or (nb == 0 and "res_time" in name)):
+            continue
+        if t is None or not t.is_cuda or t.dtype != (torch.int32 if name in LAGR_INT_OUTS else torch.float32) or tuple(t.shape) != shp \
+                or not t.is_contiguous():
+            raise RuntimeError("ens_lagr_finalize: %s is not a contiguous %s device array of its type" % (name, shp))
+    if len({outs[i] is None for i in (14, 15, 16)}) != 1:
+        raise RuntimeError("ens_lagr_finalize: member_ftle, member_end and member_exit come all three or not at all")
+    table = (c_vp * len(outs))(*[None if t is None else t.data_ptr() for t in outs])
+    _chk(lib().tmg_ens_lagr_finalize(_ptr(pos), _ptr(exit_), _ptr(res), (ctypes.c_double * 4)(*[float(v) for v in fl]), table,
+                                     ens_lagr_seeds(lattice, boxes, 1), _i64(S, B, Hh, Ww), _stream()), "tmg_ens_lagr_finalize")
 
 
 def ens_corr_cfg(probes, pairs, lags):

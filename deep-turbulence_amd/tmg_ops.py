@@ -3068,6 +3068,196 @@ class EnsembleBudget(EnsembleFeed):
         return o
 
 
+TRANSPORT_MAX_SUBSTEPS = 8
+TRANSPORT_MAX_BOXES = 4
+TRANSPORT_FIELDS = ("ftle_mean", "ftle_std", "target_ftle", "ftle_count", "disp_mean", "disp_std", "target_disp", "alive_frac",
+                    "target_alive", "res_time_mean", "res_time_std", "target_res_time", "end_err_mean", "end_spread")
+TRANSPORT_MEMBER_FIELDS = ("member_ftle", "member_end", "member_exit")
+
+
+def transport_args(seed_stride, seed_origin, substeps, boxes, C, Hh, Ww, grid, step_dt):
+    """The checks and the defaults of the transport arguments, without a device: 2 <= C <= 4 (channels 0 and 1 are the velocity),
+    H, W >= 2, grid two positive finite sizes (dx, dy), step_dt a positive finite time between two kept steps; seed_stride two
+    integers (sy, sx) >= 1 (along H, along W); seed_origin two integers (oy, ox) >= 0 inside the field (None: (sy // 2, sx // 2));
+    substeps an integer in 1 .. 8; boxes at most 4 tuples (h0, h1, w0, w1) of integers, inclusive, 0 <= h0 <= h1 <= H - 1 and
+    0 <= w0 <= w1 <= W - 1.  H = W = None (the field is not known yet) skips the field's limits and returns Gh = Gw = None.
+    -> (lattice, substeps, boxes, dx, dy, step_dt) with lattice = (Gh, Gw, oy, ox, sy, sx): the seeds are the pixels
+    (oy + i sy, ox + j sx), i < Gh, j < Gw, every one of that lattice that lies inside the field."""
+    real = lambda v: not isinstance(v, bool) and isinstance(v, numbers.Real) and math.isfinite(float(v))   # noqa: E731
+    whole = lambda v: isinstance(v, numbers.Integral) and not isinstance(v, bool)                         # noqa: E731
+    if not 2 <= int(C) <= 4:
+        raise ValueError("the transport needs 2 <= C <= 4 channels (ux, uy first), got %d" % int(C))
+    known = Hh is not None and Ww is not None
+    if known and (int(Hh) < 2 or int(Ww) < 2):
+        raise ValueError("the transport needs H, W >= 2 (one bilinear cell), got %d x %d" % (int(Hh), int(Ww)))
+    try:
+        g = tuple(grid)
+    except TypeError:
+        raise ValueError("grid must hold (dx, dy), got %r" % (grid,))
+    if len(g) != 2 or not all(real(v) and float(v) > 0 for v in g):
+        raise ValueError("grid must hold two positive finite sizes (dx, dy), got %r" % (grid,))
+    if not real(step_dt) or float(step_dt) <= 0:
+        raise ValueError("step_dt must be a positive finite time between two kept steps, got %r" % (step_dt,))
+    try:
+        st = tuple(seed_stride)
+    except TypeError:
+        raise ValueError("seed_stride must hold (sy, sx), got %r" % (seed_stride,))
+    if len(st) != 2 or not all(whole(v) and int(v) >= 1 for v in st):
+        raise ValueError("seed_stride must hold two integers (sy, sx) >= 1, got %r" % (seed_stride,))
+    sy, sx = int(st[0]), int(st[1])
+    if seed_origin is None:
+        og = (sy // 2, sx // 2)
+    else:
+        try:
+            og = tuple(seed_origin)
+        except TypeError:
+            raise ValueError("seed_origin must hold (oy, ox), got %r" % (seed_origin,))
+        if len(og) != 2 or not all(whole(v) and int(v) >= 0 for v in og):
+            raise ValueError("seed_origin must hold two integers (oy, ox) >= 0, got %r" % (seed_origin,))
+    oy, ox = int(og[0]), int(og[1])
+    if not whole(substeps) or not 1 <= int(substeps) <= TRANSPORT_MAX_SUBSTEPS:
+        raise ValueError("substeps must be an integer in 1 .. %d, got %r" % (TRANSPORT_MAX_SUBSTEPS, substeps))
+    try:
+        bx = tuple(tuple(b) for b in boxes)
+    except TypeError:
+        raise ValueError("boxes must hold tuples (h0, h1, w0, w1), got %r" % (boxes,))
+    if len(bx) > TRANSPORT_MAX_BOXES:
+        raise ValueError("at most %d boxes, got %d" % (TRANSPORT_MAX_BOXES, len(bx)))
+    for b in bx:
+        if len(b) != 4 or not all(whole(v) for v in b) or not (0 <= b[0] <= b[1] and 0 <= b[2] <= b[3]):
+            raise ValueError("a box is (h0, h1, w0, w1) in pixels, inclusive, 0 <= h0 <= h1 and 0 <= w0 <= w1, got %r" % (b,))
+        if known and (b[1] > int(Hh) - 1 or b[3] > int(Ww) - 1):
+            raise ValueError("box %r does not fit a %d x %d field" % (b, int(Hh), int(Ww)))
+    bx = tuple(tuple(int(v) for v in b) for b in bx)
+    Gh = Gw = None
+    if known:
+        if oy > int(Hh) - 1 or ox > int(Ww) - 1:
+            raise ValueError("seed_origin %r is outside the %d x %d field" % ((oy, ox), int(Hh), int(Ww)))
+        Gh, Gw = (int(Hh) - 1 - oy) // sy + 1, (int(Ww) - 1 - ox) // sx + 1
+    return (Gh, Gw, oy, ox, sy, sx), int(substeps), bx, float(g[0]), float(g[1]), float(step_dt)
+
+
+class EnsembleTransport(EnsembleFeed):
+    """On-device Lagrangian transport of sampled roll-outs of B cases, and of the target (tmg_ens_lagr_advect / tmg_ens_lagr_store /
+    tmg_ens_lagr_finalize): pathlines of a lattice of seed particles through every row's own velocity field, the forward finite-time
+    Lyapunov exponent of the flow map (its ridges are the repelling Lagrangian coherent structures: Haller; Shadden, Lekien & Marsden
+    2005), the residence time in pixel boxes, and the spread of a parcel's endpoint over the members against its error to the
+    target's endpoint.
+
+    Rows are the S members plus the target as row S.  Positions are in pixels: px along W, py along H, pixel (h, w) at (w, h); a
+    position is inside when 0 <= px <= W - 1 and 0 <= py <= H - 1.  The velocity in pixels per kept step is fl(fl(a_c y_c) + o_c),
+    c = (ux, uy), a = u out_std step_dt / d, o = u out_mu step_dt / d, d = (dx, dy) (formed in fp64 as ((u sd) step_dt) / d, rounded
+    once), bilinear in space, linear in time between the previous timed step and the current one.  Seeds are the pixels
+    (oy + i sy, ox + j sx).  The first timed step seeds every row's particles and stores its velocity planes; every later one runs
+    one advection of `substeps` Heun steps (predictor x* = x + h k1, corrector x + h (k1 + k2) / 2, h = 1 / substeps) and then
+    overwrites the planes: Tn timed steps give Tn - 1 advections over T_int = (Tn - 1) step_dt, and Tn >= 2 is needed.  A particle
+    whose predictor or corrector leaves the field dies: it keeps its last inside position and the index of that advection
+    (member_exit; -1 while alive).  At every timed step an alive particle inside box r adds 1 to its counter.  The operation order is
+    stated in include/tmglow_hip_lagr.h; an element of the state is touched by one thread once per call: the state (pos
+    [S + 1, B, 2, P], exit [S + 1, B, P], res [S + 1, B, R, P], prev [S + 1, B, 2, HW]) is bitwise reproducible, independent of the
+    chunking, and needs no memset.
+
+    Feeding protocol of EnsembleFeed, with the step's target on every chunk; a step fed with time=False launches nothing.
+    finalize() -> dict (fields over the lattice [Gh, Gw]; mean / population std (ddof 0) by Welford over the members valid at the
+    node, in member order, NaN where none is):
+      ftle_mean, ftle_std, target_ftle [B, Gh, Gw]   ln(lam) / (2 T_int), lam the largest eigenvalue of C = F^T F, F the central
+                                                     differences of the final physical positions (px dx, py dy) over the seeds'
+                                                     physical spacing; valid where the node and its four lattice neighbours are
+                                                     alive in that row (never on the lattice's frame)
+      ftle_count [B, Gh, Gw] int32                   the members valid there
+      disp_mean, disp_std, target_disp [B, 2, Gh, Gw]   final minus seed position (along x, along y), over the alive members
+      alive_frac, target_alive [B, Gh, Gw]           the share of the members alive at the end; 1 / 0 for the target
+      res_time_mean, res_time_std, target_res_time [B, R, Gh, Gw]   counter * step_dt over all members (only with boxes)
+      end_err_mean [B, Gh, Gw]                       the mean, over the members alive together with the target, of the distance
+                                                     between their endpoints
+      end_spread [B, Gh, Gw]                         sqrt(var_x + var_y) of the alive members' endpoints about their mean; read it
+                                                     beside end_err_mean: a calibrated ensemble has them of one size
+      member_ftle [B, S, Gh, Gw], member_end [B, S, 2, Gh, Gw] (pixels), member_exit [B, S, Gh, Gw] int32   (per_member=True only)
+      paths [B, S + 1, Tn, 2, Gh, Gw]                the positions in pixels after every timed step (keep_paths=True only; plain
+                                                     copies of pos)
+      transport_seeds [Gh, Gw, 2] int64 (h, w), transport_boxes, transport_time = T_int."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, grid=(1.0, 1.0), step_dt=1.0, seed_stride=(2, 2),
+                 seed_origin=None, substeps=1, boxes=(), per_member=False, keep_paths=False):
+        noun, why = "ensemble transport diagnostics", "the velocity scales with u * out_std"
+        _ens_members(noun, members)
+        self.lattice, self.n, self.boxes, self.dx, self.dy, self.step_dt = transport_args(seed_stride, seed_origin, substeps, boxes, C,
+                                                                                          Hh, Ww, grid, step_dt)
+        sd, mu = _ens_tables(int(C), why, out_std, out_mu)
+        u = _ens_u(u, B, int(C), why)
+        if int(steps) < 2 or int(B) < 1:
+            raise ValueError("%s need steps >= 2 and B >= 1, got %d, %d" % (noun, steps, B))
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, int(C), Hh, Ww, steps)
+        HW = self.H * self.W
+        self.Gh, self.Gw = self.lattice[:2]
+        self.P = self.Gh * self.Gw
+        self.per_member, self.keep_paths = bool(per_member), bool(keep_paths)
+        d = torch.tensor([self.dx, self.dy], dtype=torch.float64).view(1, 2)
+        self.a = ((_ens_scale(sd, u, self.B, torch.float64)[:, :2] * self.step_dt) / d).to(torch.float32).to(dev).contiguous()
+        self.o = ((_ens_scale(mu, u, self.B, torch.float64)[:, :2] * self.step_dt) / d).to(torch.float32).to(dev).contiguous()
+        self.plan = H.ens_lagr_plan(self.S, self.B, self.H, self.W, self.P)
+        R = self.S + 1
+        self.pos = torch.empty((R, self.B, 2, self.P), device=dev, dtype=torch.float32)
+        self.exit = torch.empty((R, self.B, self.P), device=dev, dtype=torch.int32)
+        self.res = torch.empty((R, self.B, len(self.boxes), self.P), device=dev, dtype=torch.int32)
+        self.prev = torch.empty((R, self.B, 2, HW), device=dev, dtype=torch.float32)
+        self._paths = []
+
+    def _feed(self, yn, k, row0, t_before):
+        H.ens_lagr_advect(yn, self.a, self.o, self.prev, self.pos, self.exit, self.res, self.lattice, self.boxes, self.n, k, row0, t_before)
+        H.ens_lagr_store(yn, self.a, self.o, self.prev, k, row0)             # after the advection: it reads what this overwrites
+
+    def add(self, y, m0, target, time=True):
+        """Advect the particles of the step's members m0 .. m0 + k - 1 through y (API-shaped [k*B, C, H, W], any strides whose
+        channels-last view is an NHWC channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the
+        same stride rule, advected as row S with the step's last chunk.  A step fed with time=False launches nothing."""
+        yn, tn, k, t_before, last = self.open_chunk(y, m0, time, target, required=True)
+        _on_device(yn, tn)
+        if time:
+            self._feed(yn, k, m0, t_before)
+            if last:
+                self._feed(tn, 1, self.S, t_before)
+                if self.keep_paths:
+                    self._paths.append(self.pos.clone())
+        self.close_chunk(m0, k, time, last)
+
+    def finalize(self):
+        """-> dict of the outputs over the steps folded with time=True (at least two)."""
+        T = self.finalize_guard()
+        if T < 2:
+            raise RuntimeError("the transport needs at least 2 timed steps (one advection), got %d" % T)
+        B, S, P, Gh, Gw, nb = self.B, self.S, self.P, self.Gh, self.Gw, len(self.boxes)
+        dev = self.pos.device
+        T_int = (T - 1) * self.step_dt
+        shapes = {"ftle_count": (B, P), "disp_mean": (B, 2, P), "disp_std": (B, 2, P), "target_disp": (B, 2, P),
+                  "res_time_mean": (B, nb, P), "res_time_std": (B, nb, P), "target_res_time": (B, nb, P),
+                  "member_ftle": (B, S, P), "member_end": (B, S, 2, P), "member_exit": (B, S, P)}
+        outs = []
+        for name in H.LAGR_OUTS:
+            if (name in TRANSPORT_MEMBER_FIELDS and not self.per_member) or ("res_time" in name and nb == 0):
+                outs.append(None)
+            else:
+                outs.append(torch.empty(shapes.get(name, (B, P)), device=dev,
+                                        dtype=torch.int32 if name in H.LAGR_INT_OUTS else torch.float32))
+        H.ens_lagr_finalize(self.pos, self.exit, self.res, (self.dx, self.dy, self.step_dt, T_int), outs, self.lattice, self.boxes,
+                            self.H, self.W)
+        o = {}
+        for name, t in zip(H.LAGR_OUTS, outs):
+            if t is not None:
+                o[name] = t.view(tuple(t.shape[:-1]) + (Gh, Gw))
+        if self.keep_paths:
+            # [Tn, S + 1, B, 2, P] -> [B, S + 1, Tn, 2, Gh, Gw]
+            o["paths"] = torch.stack(self._paths).permute(2, 1, 0, 3, 4).reshape(B, S + 1, T, 2, Gh, Gw).contiguous()
+        _, _, oy, ox, sy, sx = self.lattice
+        hh = (oy + sy * torch.arange(Gh)).view(Gh, 1).expand(Gh, Gw)
+        ww = (ox + sx * torch.arange(Gw)).view(1, Gw).expand(Gh, Gw)
+        o["transport_seeds"] = torch.stack((hh, ww), dim=-1).contiguous()
+        o["transport_boxes"] = self.boxes
+        o["transport_time"] = T_int
+        return o
+
+
 FLUX_WIDTHS = (3, 5, 9, 17, 33)
 FLUX_MAX_WIDTHS = 8
 FLUX_MAX_WIDTH = 33

@@ -795,6 +795,69 @@ def modelPredFlux(args, model, testing_loader, log, samples=1, stride=1, tmax=1,
     return _ensembleStats("modelPredFlux", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
 
 
+def _transport_factory(grid, step_dt, seed_stride, seed_origin, substeps, boxes, per_member, keep_paths):
+    """The make of modelPredTransport's record: the tmg_ops.EnsembleTransport of one mini-batch (its constructor checks the seeds and
+    the boxes against the field before it touches the device)."""
+    def make(mb, members, steps):
+        import tmg_ops as ops
+        return ops.EnsembleTransport(members, mb.B, mb.C, mb.H, mb.W, steps, mb.dev, mb.out_mu, mb.out_std, u=mb.u, grid=grid,
+                                     step_dt=step_dt, seed_stride=seed_stride, seed_origin=seed_origin, substeps=substeps, boxes=boxes,
+                                     per_member=per_member, keep_paths=keep_paths)
+    return make
+
+
+def modelPredTransport(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, dt=None, seed_stride=(2, 2),
+                       seed_origin=None, substeps=1, boxes=(), per_member=False, keep_paths=False):
+    """modelPredStats plus the Lagrangian transport of every member and of the target, still without forming modelPred's
+    [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleTransport): what does the recirculation trap and for how long, where do the shear
+    layer and the wake stretch and fold material, does a parcel released at a point end up where the reference simulation puts it?
+    Every other diagnostic here looks at fixed pixels; a pathline integrates the velocity along a moving point, so a small phase or
+    convection-speed error accumulates instead of averaging out.  Same roll-outs as modelPredStats: under the same host RNG state
+    the keys both return are identical.  The grid is (args.dx along W, args.dy along H); dt, the time between two model steps, is
+    required (a kept step lasts step_dt = stride * dt); the target of kept step j is series step j * stride.
+
+    Rows are the S members and the target.  Positions are in pixels, px along W and py along H, pixel (h, w) at (w, h); a position is
+    inside when 0 <= px <= W - 1 and 0 <= py <= H - 1.  The velocity (u0, u0) (out_std y + out_mu) step_dt / (dx, dy) in pixels per
+    kept step is bilinear in space and linear in time between two kept steps.  seed_stride = (sy, sx) and seed_origin = (oy, ox)
+    (None: (sy // 2, sx // 2)) place the seeds on the pixels (oy + i sy, ox + j sx) inside the field, a lattice [Gh, Gw].  The first
+    timed step (kept step t_start) seeds; each of the Tn - 1 later ones advects every particle by `substeps` (1 .. 8) Heun steps, over
+    T_int = (Tn - 1) step_dt in all; Tn = Tk - t_start >= 2.  A particle whose predictor or corrector leaves the field dies: it keeps
+    its last inside position and the index of that advection.  boxes: at most 4 pixel boxes (h0, h1, w0, w1), inclusive; at every
+    timed step an alive particle inside a box adds one step_dt to its residence time there.  The state takes 12 + 4 R bytes per
+    particle and 8 bytes per pixel of every row and case; it is bitwise reproducible and independent of max_rows.
+
+    Returns modelPredStats' dict plus (CPU tensors; mean / population std (ddof 0) over the members valid at the node, NaN where
+    none is):
+      ftle_mean, ftle_std, target_ftle [N, Gh, Gw]   the forward finite-time Lyapunov exponent ln(lam) / (2 T_int), lam the largest
+                                                     eigenvalue of F^T F, F the central differences of the final physical positions
+                                                     over the seeds' physical spacing; valid where the node and its four lattice
+                                                     neighbours are alive in that row
+      ftle_count [N, Gh, Gw] int32                   the members valid there
+      disp_mean, disp_std, target_disp [N, 2, Gh, Gw]   final minus seed position in physical units, over the alive members
+      alive_frac, target_alive [N, Gh, Gw]           the share of the members still alive; 1 / 0 for the target
+      res_time_mean, res_time_std, target_res_time [N, R, Gh, Gw]   the residence times, all members (only with boxes)
+      end_err_mean [N, Gh, Gw]                       the mean distance of the members' endpoints to the target's, over the members
+                                                     alive together with the target
+      end_spread [N, Gh, Gw]                         sqrt(var_x + var_y) of the alive members' endpoints; read beside end_err_mean
+      member_ftle [N, S, Gh, Gw], member_end [N, S, 2, Gh, Gw] (pixels), member_exit [N, S, Gh, Gw] int32   (per_member=True only)
+      paths [N, S + 1, Tn, 2, Gh, Gw]                the positions in pixels after every timed step (keep_paths=True only)
+      transport_seeds [Gh, Gw, 2] (h, w), transport_boxes, transport_time = T_int.
+    Not supported: backward-time (attracting) FTLE, sub-pixel or non-lattice seeds, re-seeding of dead particles, RK4, periodic
+    domains, a per-step FTLE series, non-finite members (they only kill the particles that touch them)."""
+    import tmg_ops as ops
+    if dt is None:
+        raise ValueError("modelPredTransport needs dt, the time between two model steps: a pathline is an integral over time")
+    step_dt = float(stride) * float(dt)
+    _, n, bx, dx, dy, step_dt = ops.transport_args(seed_stride, seed_origin, substeps, boxes, 3, None, None, (args.dx, args.dy), step_dt)
+    nkeep = tmax // stride
+    if nkeep >= 1 and 0 <= t_start < nkeep and nkeep - t_start < 2:            # (else _ensembleStats words the error)
+        raise ValueError("modelPredTransport needs at least 2 kept steps from t_start on (one advection), got %d (tmax=%d, stride=%d, "
+                         "t_start=%d)" % (nkeep - t_start, tmax, stride, t_start))
+    acc = _Acc(_transport_factory((dx, dy), step_dt, tuple(seed_stride), seed_origin, n, bx, bool(per_member), bool(keep_paths)),
+               target=True, meta=("transport_seeds", "transport_boxes", "transport_time"))
+    return _ensembleStats("modelPredTransport", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
+
+
 def modelPredSpod(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, bins=None, modes=4, channels=(0, 1),
                   window="hann", loo=True, dt=None):
     """modelPredStats plus the spectral POD (SPOD; Towne, Schmidt & Colonius 2018) of the members over the kept steps t_start..Tk-1
