@@ -20,7 +20,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmglow_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip", "tmg_phase.hip", "tmg_spod.hip", "tmg_budget.hip", "tmg_corr.hip", "tmg_flux.hip", "tmg_lagr.hip"]
+SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip", "tmg_phase.hip", "tmg_spod.hip", "tmg_budget.hip", "tmg_corr.hip", "tmg_flux.hip", "tmg_vortex.hip", "tmg_lagr.hip"]
 # Sources compiled WITHOUT the packed-fp32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32): beside MFMAs a packed
 # f32 instruction costs ~13 cycles more than the two scalar ones it replaces (MI355X_MICROARCH.md, cycle constants, 'price of one
 # filler beside MFMAs'), and the compiler SLP-packs adjacent scalar adds / multiplies by itself under -O3.  The matrix-core kernels'
@@ -94,6 +94,9 @@ FLUX_EXPORTS = ["tmg_ens_flux_plan", "tmg_ens_flux_accum", "tmg_ens_flux_terms"]
 # The Lagrangian transport: pathlines, FTLE, residence time (csrc/tmg_lagr.hip), declared in include/tmglow_hip_lagr.h, a header of its
 # own: ens_lagr_plan / ens_lagr_advect / ens_lagr_store / ens_lagr_finalize below.
 LAGR_EXPORTS = ["tmg_ens_lagr_plan", "tmg_ens_lagr_advect", "tmg_ens_lagr_store", "tmg_ens_lagr_finalize"]
+# The vortex census: Okubo-Weiss classes, connected-component labels, int64 measures (csrc/tmg_vortex.hip), declared in
+# include/tmglow_hip_vortex.h, a header of its own: ens_vortex_plan / ens_vortex_classify / ens_vortex_label / ens_vortex_census below.
+VORTEX_EXPORTS = ["tmg_ens_vortex_plan", "tmg_ens_vortex_classify", "tmg_ens_vortex_label", "tmg_ens_vortex_census"]
 _P64 = ctypes.POINTER(ctypes.c_int64)
 FLUX_ARGTYPES = {
     "tmg_ens_flux_plan": [_P64, _P64, _P64],
@@ -117,7 +120,7 @@ def build(force=False, verbose=False):
                os.path.join(inc, "tmglow_hip_event.h"), os.path.join(inc, "tmglow_hip_pdf.h"), os.path.join(inc, "tmglow_hip_pod.h"),
                os.path.join(inc, "tmglow_hip_phase.h"), os.path.join(inc, "tmglow_hip_spod.h"), os.path.join(inc, "tmglow_hip_layout.h"),
                os.path.join(inc, "tmglow_hip_budget.h"), os.path.join(inc, "tmglow_hip_corr.h"), os.path.join(inc, "tmglow_hip_flux.h"),
-               os.path.join(inc, "tmglow_hip_lagr.h")]
+               os.path.join(inc, "tmglow_hip_lagr.h"), os.path.join(inc, "tmglow_hip_vortex.h")]
     hmt = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -171,7 +174,7 @@ def lib():
         for name in PLAN_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
             getattr(_lib, name).argtypes = PLAN_ARGTYPES[name]
-        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS + SFUN_EXPORTS + EVENT_EXPORTS + PDF_EXPORTS + POD_EXPORTS + PHASE_EXPORTS + SPOD_EXPORTS + LAYOUT_EXPORTS + BUDGET_EXPORTS + CORR_EXPORTS + LAGR_EXPORTS:
+        for name in TSPEC_EXPORTS + QUANT_EXPORTS + GRAM_EXPORTS + SFUN_EXPORTS + EVENT_EXPORTS + PDF_EXPORTS + POD_EXPORTS + PHASE_EXPORTS + SPOD_EXPORTS + LAYOUT_EXPORTS + BUDGET_EXPORTS + CORR_EXPORTS + LAGR_EXPORTS + VORTEX_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
         for name in FLUX_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
@@ -1702,6 +1705,81 @@ def ens_lagr_finalize(pos, exit_, res, fl, outs, lattice, boxes, Hh, Ww):
     table = (c_vp * len(outs))(*[None if t is None else t.data_ptr() for t in outs])
     _chk(lib().tmg_ens_lagr_finalize(_ptr(pos), _ptr(exit_), _ptr(res), (ctypes.c_double * 4)(*[float(v) for v in fl]), table,
                                      ens_lagr_seeds(lattice, boxes, 1), _i64(S, B, Hh, Ww), _stream()), "tmg_ens_lagr_finalize")
+
+
+VORTEX_PLAN_KEYS = ("TH", "TW", "NTH", "NTW", "tile_blocks", "merge_blocks", "pixel_blocks", "threads", "lds_label", "lds_census",
+                    "ws_bytes", "state_bytes")
+VORTEX_WORDS = 8
+
+
+def ens_vortex_plan(k, S, B, Hh, Ww, K, Tn, code=False):
+    """The launch plans of the vortex census for chunks of k rows of S members of B cases of [H, W], K table slots and Tn timed steps
+    (tmg_ens_vortex_plan; nothing is launched) -> dict of VORTEX_PLAN_KEYS (include/tmglow_hip_vortex.h).  code=True: the C
+    return code instead of raising (0 with the plan as second element)."""
+    plan = (c_i64 * len(VORTEX_PLAN_KEYS))()
+    rc = lib().tmg_ens_vortex_plan(_i64(k, S, B, Hh, Ww, K, Tn), plan)
+    out = dict(zip(VORTEX_PLAN_KEYS, [int(v) for v in plan]))
+    if code:
+        return rc, out
+    _chk(rc, "tmg_ens_vortex_plan")
+    return out
+
+
+def _vortex_planes(name, n, HW, dev, **planes):
+    """Every plane is a contiguous [n, HW] device array of its dtype."""
+    for key, (t, dt) in planes.items():
+        if not t.is_cuda or t.dtype != dt or tuple(t.shape) != (n, HW) or not t.is_contiguous() or t.device != dev:
+            raise RuntimeError("%s: %s is a contiguous [%d, %d] %s array on %s, got %s %s" % (name, key, n, HW, dt, dev, t.dtype, tuple(t.shape)))
+        check_device(t)
+
+
+def ens_vortex_classify(y, u, out_mu, out_std, thr, qscale, omega, cls, rejected, grid, k):
+    """Classify one chunk of k rows (y: NHWC [k*B, H, W, 2..4] or a channel-slice view, rows member-major): omega [k*B, HW] fp32, cls
+    [k*B, HW] int8 and rejected [k*B] int32 (set, not added to), with the device tables u [B, C] or None, out_mu, out_std [C], thr,
+    qscale [B] and grid = (dx, dy) (tmg_ens_vortex_classify)."""
+    kB, Hh, Ww, Cc = y.shape
+    ptr, ps, co, _ = seg(y)
+    check_device(y)
+    B = kB // k
+    _vortex_planes("ens_vortex_classify", kB, Hh * Ww, y.device, omega=(omega, torch.float32), cls=(cls, torch.int8))
+    if kB != k * B or tuple(thr.shape) != (B,) or tuple(qscale.shape) != (B,) or rejected.dtype != torch.int32 or rejected.numel() != kB \
+            or not rejected.is_contiguous() or (u is not None and tuple(u.shape) != (B, Cc)):
+        raise RuntimeError("ens_vortex_classify: the tables do not fit %d rows of %s" % (k, tuple(y.shape)))
+    for t in (u, out_mu, out_std, thr, qscale):
+        if t is not None:
+            check_act(t)
+    _chk(lib().tmg_ens_vortex_classify(c_vp(ptr), _i64(ps, co), _ptr(u), _ptr(out_mu), _ptr(out_std), _ptr(thr), _ptr(qscale), _ptr(omega),
+                                       _ptr(cls), _ptr(rejected), _flts(grid), _i64(k, B, Hh, Ww, Cc), _stream()), "tmg_ens_vortex_classify")
+
+
+def ens_vortex_label(cls, label, status, Hh, Ww):
+    """cls [n, HW] int8 -> label [n, HW] int32: the smallest linear index of the pixel's 4-connected component of one non-zero class,
+    -1 on the background; status: one int32 on the device that receives a non-zero code when a loop reaches its trip bound
+    (tmg_ens_vortex_label)."""
+    n = cls.shape[0]
+    _vortex_planes("ens_vortex_label", n, Hh * Ww, cls.device, cls=(cls, torch.int8), label=(label, torch.int32))
+    if not status.is_cuda or status.dtype != torch.int32 or status.numel() != 1:
+        raise RuntimeError("ens_vortex_label: status is one int32 on the device")
+    _chk(lib().tmg_ens_vortex_label(_ptr(cls), _ptr(label), _ptr(status), _i64(n, Hh, Ww), _stream()), "tmg_ens_vortex_label")
+
+
+def ens_vortex_census(label, cls, omega, qscale, area, slot, table, found, core, Hh, Ww, k, min_area):
+    """The census of one chunk of k rows: label, cls, omega [k*B, HW] -> table [k*B, K, 8] int64 and found [k*B, 2] int32 (both
+    overwritten) and core [B, 2, HW] int32 (added to); area, slot [k*B, HW] int32 are workspace (tmg_ens_vortex_census)."""
+    kB, HW = label.shape
+    B = kB // k
+    i32 = torch.int32
+    _vortex_planes("ens_vortex_census", kB, HW, label.device, label=(label, i32), cls=(cls, torch.int8), omega=(omega, torch.float32),
+                   area=(area, i32), slot=(slot, i32))
+    K = table.shape[1] if table.dim() == 3 else 0
+    if HW != Hh * Ww or kB != k * B or table.dtype != torch.int64 or tuple(table.shape) != (kB, K, VORTEX_WORDS) or not table.is_contiguous() \
+            or found.dtype != i32 or tuple(found.shape) != (kB, 2) or not found.is_contiguous() or core.dtype != i32 \
+            or tuple(core.shape) != (B, 2, HW) or not core.is_contiguous() or tuple(qscale.shape) != (B,):
+        raise RuntimeError("ens_vortex_census: table %s, found %s, core %s do not fit %d rows of %d cases of %d pixels"
+                           % (tuple(table.shape), tuple(found.shape), tuple(core.shape), k, B, HW))
+    check_act(qscale)
+    _chk(lib().tmg_ens_vortex_census(_ptr(label), _ptr(cls), _ptr(omega), _ptr(qscale), _ptr(area), _ptr(slot), _ptr(table), _ptr(found),
+                                     _ptr(core), _i64(k, B, Hh, Ww, K, min_area), _stream()), "tmg_ens_vortex_census")
 
 
 def ens_corr_cfg(probes, pairs, lags):

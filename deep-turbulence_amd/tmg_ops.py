@@ -3258,6 +3258,280 @@ class EnsembleTransport(EnsembleFeed):
         return o
 
 
+VORTEX_MAX_K = 256
+VORTEX_MAX_CIRC_BINS = 32
+VORTEX_AREA_BINS = 19
+VORTEX_MAX_SIDE = 512
+
+
+def vortex_args(threshold, qscale, min_area, max_vortices, circ_bins, circ_range, C, Hh, Ww, grid, B=None):
+    """The checks and the defaults of the vortex census arguments, without a device: 2 <= C <= 4 (channels 0 and 1 are the velocity),
+    3 <= H, W <= 512, grid two positive finite sizes (dx, dy); threshold None, one finite number >= 0 or one per case, in physical
+    1/s^2; qscale None, one positive power of two or one per case; min_area an integer >= 1; max_vortices an integer in 1 .. 256;
+    circ_bins an integer in 1 .. 32; circ_range None, one (lo, hi) with 0 <= lo < hi or one per case.  H = W = None (the field is not
+    known yet) skips the field's limits; B = None the lengths of the per-case arrays.
+    -> (thr, qs, min_area, K, nb, cr, dx, dy): thr, qs [B] and cr [B, 2] fp64 CPU tensors, or None where None was given."""
+    real = lambda v: not isinstance(v, bool) and isinstance(v, numbers.Real) and math.isfinite(float(v))   # noqa: E731
+    whole = lambda v: isinstance(v, numbers.Integral) and not isinstance(v, bool)                         # noqa: E731
+    if not 2 <= int(C) <= 4:
+        raise ValueError("the vortex census needs 2 <= C <= 4 channels (ux, uy first), got %d" % int(C))
+    known = Hh is not None and Ww is not None
+    if known and not (3 <= int(Hh) <= VORTEX_MAX_SIDE and 3 <= int(Ww) <= VORTEX_MAX_SIDE):
+        raise ValueError("the vortex census needs 3 <= H, W <= %d, got %d x %d" % (VORTEX_MAX_SIDE, int(Hh), int(Ww)))
+    try:
+        g = tuple(grid)
+    except TypeError:
+        raise ValueError("grid must hold (dx, dy), got %r" % (grid,))
+    if len(g) != 2 or not all(real(v) and float(v) > 0 for v in g):
+        raise ValueError("grid must hold two positive finite sizes (dx, dy), got %r" % (grid,))
+
+    def per_case(v, name, width, ok, rule):
+        if v is None:
+            return None
+        try:
+            t = torch.as_tensor(v, dtype=torch.float64).detach().cpu()
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError("%s must be %s, got %r" % (name, rule, v))
+        if t.dim() == width:
+            t = t.unsqueeze(0).expand((1 if B is None else int(B),) + tuple(t.shape)).contiguous()
+        if t.dim() != width + 1 or (width and t.shape[-1] != 2) or (B is not None and t.shape[0] != int(B)) or not bool(ok(t).all()):
+            raise ValueError("%s must be %s, got %r" % (name, rule, v))
+        return t
+
+    thr = per_case(threshold, "threshold", 0, lambda t: torch.isfinite(t) & (t >= 0), "None, one finite number >= 0 or one per case")
+    pow2 = lambda t: torch.isfinite(t) & (t > 0) & (torch.frexp(t.clamp(min=1e-300))[0] == 0.5) & (t >= 2.0 ** -100) & (t <= 2.0 ** 100)   # noqa: E731
+    qs = per_case(qscale, "qscale", 0, pow2, "None, one positive power of two (2^-100 .. 2^100) or one per case")
+    cr = per_case(circ_range, "circ_range", 1, lambda t: (torch.isfinite(t) & (t >= 0)) & (t[..., 1:] > t[..., :1]),
+                  "None, one (lo, hi) with 0 <= lo < hi or one per case")
+    if not whole(min_area) or int(min_area) < 1:
+        raise ValueError("min_area must be an integer >= 1, got %r" % (min_area,))
+    if not whole(max_vortices) or not 1 <= int(max_vortices) <= VORTEX_MAX_K:
+        raise ValueError("max_vortices must be an integer in 1 .. %d, got %r" % (VORTEX_MAX_K, max_vortices))
+    if not whole(circ_bins) or not 1 <= int(circ_bins) <= VORTEX_MAX_CIRC_BINS:
+        raise ValueError("circ_bins must be an integer in 1 .. %d, got %r" % (VORTEX_MAX_CIRC_BINS, circ_bins))
+    return thr, qs, int(min_area), int(max_vortices), int(circ_bins), cr, float(g[0]), float(g[1])
+
+
+def vortex_defaults(tp, grid):
+    """tp [B, T, 2.., H, W]: the physical target series at the timed steps -> (threshold, qscale) [B] fp64 (CPU), the defaults of the
+    census: 0.2 times the population std, over the interior pixels and the steps, of ow = w^2 - sn^2 - ss^2 (the 0.2 sigma of
+    Isern-Fontanet et al.), and 2^(20 - ceil(log2(max |w|))), so that the largest vorticity lands in (2^19, 2^20] fixed-point steps.
+    Plain torch in fp64: this only chooses two numbers per case.  A target whose ow does not vary, or without vorticity, raises."""
+    tp = tp.double()
+    U, V = tp[:, :, 0], tp[:, :, 1]
+    ddx = lambda q: 2 * q[..., 1:-1, 2:] + q[..., :-2, 2:] + q[..., 2:, 2:] - 2 * q[..., 1:-1, :-2] - q[..., :-2, :-2] - q[..., 2:, :-2]   # noqa: E731
+    ddy = lambda q: 2 * q[..., 2:, 1:-1] + q[..., 2:, :-2] + q[..., 2:, 2:] - 2 * q[..., :-2, 1:-1] - q[..., :-2, :-2] - q[..., :-2, 2:]   # noqa: E731
+    rdx, rdy = 0.125 / float(grid[0]), 0.125 / float(grid[1])
+    ux, uy, vx, vy = ddx(U) * rdx, ddy(U) * rdy, ddx(V) * rdx, ddy(V) * rdy
+    w, sn, ss = vx - uy, ux - vy, vx + uy
+    ow = (w * w - sn * sn - ss * ss).reshape(tp.shape[0], -1)
+    sig = ow.std(1, unbiased=False).cpu()
+    wmax = w.abs().reshape(tp.shape[0], -1).max(1).values.cpu()
+    bad = ~(torch.isfinite(sig) & (sig > 0) & torch.isfinite(wmax) & (wmax > 0))
+    if bool(bad.any()):
+        raise ValueError("the Okubo-Weiss field of the target of case %d does not vary (std %r, max |vorticity| %r): give threshold and "
+                         "qscale" % (int(bad.nonzero()[0]), float(sig[bad][0]), float(wmax[bad][0])))
+    return 0.2 * sig, torch.pow(2.0, 20.0 - torch.ceil(torch.log2(wmax)))
+
+
+def _vortex_w1(p, q, h):
+    """The Wasserstein-1 distance between the distributions of the counts p, q [..., nb] with each bin's mass at its centre:
+    h sum_{j < nb - 1} |F_j - G_j|, F, G the cumulative shares, in fp64; NaN when either holds no sample."""
+    F = p.cumsum(-1)[..., :-1].double() / p.sum(-1, keepdim=True).double()
+    G = q.cumsum(-1)[..., :-1].double() / q.sum(-1, keepdim=True).double()
+    out = (F - G).abs().sum(-1) * h
+    return torch.where((p.sum(-1) > 0) & (q.sum(-1) > 0), out, torch.full_like(out, float("nan")))
+
+
+def vortex_finalize(tab, found, S, Hh, Ww, dx, dy, qscale, nb, circ_range):
+    """The statistics of the integer tables: tab [B, S + 1, T, K, 8] int64 (the target last), found [B, S + 1, T, 2] (CPU), qscale [B]
+    fp64, circ_range [B, 2] fp64 or None -> dict of fp64 CPU tensors (EnsembleVortices.finalize documents them).  Plain torch."""
+    B, R, T, K = tab.shape[:4]
+    cell = dx * dy
+    valid = tab[..., 0] >= 0
+    n, sq = tab[..., 1], tab[..., 4]
+    sgn = torch.stack((valid & (sq > 0), valid & (sq < 0)), dim=-1)                       # [B, R, T, K, 2]
+    gamma = sq.double() * cell / qscale.view(B, 1, 1, 1)
+    den = torch.where(sq != 0, sq, torch.ones_like(sq)).double()
+    cx, cy = tab[..., 5].double() / den * dx, tab[..., 6].double() / den * dy              # physical centroids
+    sd = sgn.double()
+    o = {}
+    per_row = {"count": found.double(), "area_frac": (n.double().unsqueeze(-1) * sd).sum(3) / float((Hh - 2) * (Ww - 2)),
+               "circ_sum": (gamma.unsqueeze(-1) * sd).sum(3)}
+    for key, v in per_row.items():                                                        # [B, R, T, 2]
+        o[key + "_mean"], o[key + "_std"], o["target_" + key] = v[:, :S].mean(1), v[:, :S].std(1, unbiased=False), v[:, S]
+    # the distributions, pooled over the timed steps
+    abin = sum((n >= (1 << j)).long() for j in range(1, VORTEX_AREA_BINS))
+    if circ_range is None:
+        top = (gamma[:, S].abs() * valid[:, S].double()).reshape(B, -1).max(1).values
+        circ_range = torch.stack((torch.zeros(B, dtype=torch.float64), torch.where(top > 0, 1.25 * top, torch.ones_like(top))), dim=1)
+    lo, hi = circ_range[:, 0].view(B, 1, 1, 1), circ_range[:, 1].view(B, 1, 1, 1)
+    cbin = torch.floor((gamma.abs() - lo) / (hi - lo) * nb).clamp(0, nb - 1).long()
+    ah, ch = torch.zeros(B, R, 2, VORTEX_AREA_BINS, dtype=torch.int64), torch.zeros(B, R, 2, nb, dtype=torch.int64)
+    for s in range(2):
+        wgt = sgn[..., s].reshape(B, R, T * K).long()
+        ah[:, :, s].scatter_add_(2, abin.reshape(B, R, T * K), wgt)
+        ch[:, :, s].scatter_add_(2, cbin.reshape(B, R, T * K), wgt)
+    o["area_hist"], o["circ_hist"] = ah, ch
+    hc = ((circ_range[:, 1] - circ_range[:, 0]) / nb).view(B, 1)
+    o["time_area_w1"] = _vortex_w1(ah[:, :S].sum(1), ah[:, S], 1.0)
+    o["time_circ_w1"] = _vortex_w1(ch[:, :S].sum(1), ch[:, S], hc)
+    o["time_member_circ_w1"] = _vortex_w1(ch[:, :S], ch[:, S:], hc.view(B, 1, 1))
+    o["vortex_circ_edges"] = circ_range[:, :1] + (circ_range[:, 1:] - circ_range[:, :1]) * torch.arange(nb + 1, dtype=torch.float64).view(1, -1) / nb
+    # object matching: every kept target vortex against the nearest kept vortex of its sign in every member
+    nan = float("nan")
+    md, mf = torch.full((B, T, 2), nan, dtype=torch.float64), torch.full((B, T, 2), nan, dtype=torch.float64)
+    for t in range(T):
+        for s in range(2):
+            tm, mm = sgn[:, S, t, :, s], sgn[:, :S, t, :, s]                              # [B, K], [B, S, K]
+            if not bool(tm.any()):
+                continue
+            ddx_ = cx[:, S, t].view(B, 1, K, 1) - cx[:, :S, t].view(B, S, 1, K)
+            ddy_ = cy[:, S, t].view(B, 1, K, 1) - cy[:, :S, t].view(B, S, 1, K)
+            D = torch.sqrt(ddx_ * ddx_ + ddy_ * ddy_).masked_fill(~mm.view(B, S, 1, K), float("inf"))
+            dmin = D.min(-1).values                                                       # [B, S, K]
+            has = mm.any(-1).view(B, S, 1)
+            hit, miss = tm.view(B, 1, K) & has, tm.view(B, 1, K) & ~has
+            nh, nm = hit.sum((1, 2)).double(), miss.sum((1, 2)).double()
+            dsum = torch.where(hit, dmin, torch.zeros_like(dmin)).sum((1, 2))
+            any_t = tm.any(-1)
+            md[:, t, s] = torch.where(any_t & (nh > 0), dsum / nh.clamp(min=1), torch.full_like(dsum, nan))
+            mf[:, t, s] = torch.where(any_t, nm / (nh + nm).clamp(min=1), torch.full_like(dsum, nan))
+    o["match_dist_mean"], o["match_miss_frac"] = md, mf
+    return o
+
+
+class EnsembleVortices(EnsembleFeed):
+    """On-device vortex census of sampled roll-outs of B cases, and of the target (tmg_ens_vortex_classify / tmg_ens_vortex_label /
+    tmg_ens_vortex_census): how many vortices does a field hold, how big and how strong are they, where do they live, and are the
+    target's vortices present in the members at the right place?  The Okubo-Weiss / Q-criterion census of McWilliams (1990) with the
+    0.2 sigma threshold of Isern-Fontanet et al., and the object-based verification of meteorology (SAL, MODE).
+
+    Rows are the S members plus the target as row S.  At every timed step a pixel of a row gets the class sign(w) when it is not on
+    the one-pixel frame, ow = w^2 - sn^2 - ss^2 > threshold[b] (w the vorticity, sn and ss the strains, from the un-scaled 3x3 stencils
+    of pc/ on u (out_std y + out_mu); w is bit for bit the `vort` of EnsemblePdfs), |qf| <= 2^31 and q != 0 with the fixed-point
+    vorticity qf = fl(w qscale[b]), q = rint(qf); else 0.  An interior pixel whose ow is NaN or whose qf alone fails is counted in
+    vortex_rejected.  A vortex is a maximal 4-connected set of pixels of one non-zero class; its label is its smallest linear index.
+    Its measures are 8 int64 words (root, n, sum w, sum h, sum q, sum q w, sum q h, max |q|): exact and independent of any order.
+    The table of a row, case and step holds the vortices with n >= min_area in increasing root order, the first K = max_vortices of
+    them; vortex_found counts them all.  The operation order is stated in include/tmglow_hip_vortex.h.  The state (the tables, 64 K
+    bytes per row, case and step, and two occupancy planes of 8 bytes per pixel and case) holds integers only: bitwise reproducible
+    and independent of the chunking; the workspace (17 bytes per pixel of the largest chunk) is transient.
+
+    threshold and qscale are one number or one per case (vortex_defaults gives the target's own); circ_range None: [0, 1.25 max |G|]
+    of the target's table per case.  Feeding protocol of EnsembleFeed, with the step's target on every chunk; a step fed with
+    time=False launches nothing.  finalize() raises RuntimeError when a labelling loop reached its trip bound (the status word);
+    else -> dict (fp32 unless stated; mean / population std (ddof 0) over the members; the sign axis is (+, -); G = circulation):
+      target_vortex_table [B, Tn, K, 8] int64           the target's tables; an empty slot is (-1, 0, ..)
+      vortex_table [B, S + 1, Tn, K, 8] int64           every row's (per_member=True only)
+      vortex_found [B, S + 1, Tn, 2] int32              the vortices with n >= min_area, before the truncation to K
+      vortex_rejected [B, S + 1, Tn] int32, vortex_truncated [B] int64 (the tables of the case with found(+) + found(-) > K)
+      count_mean, count_std, target_count [B, Tn, 2]    of vortex_found
+      area_frac_mean, area_frac_std, target_area_frac   the share of the interior pixels in kept vortices
+      circ_sum_mean, circ_sum_std, target_circ_sum      the sum of G = sum q dx dy / qscale over the kept vortices
+      area_hist [B, S + 1, 2, 19] int64                 the kept vortices of all timed steps by floor(log2 n)
+      circ_hist [B, S + 1, 2, circ_bins] int64          ... by |G| over circ_range (what lies outside goes to the end bins)
+      time_area_w1, time_circ_w1 [B, 2]                 the Wasserstein-1 distance between the pooled members' distribution and the
+                                                        target's (in bins of log2 n / in units of G); NaN when either is empty
+      time_member_circ_w1 [B, S, 2]                     each member's against the target's
+      core_prob, target_core_freq [B, 2, H, W]          the share of (member, step) / of steps at which the pixel lies in a vortex
+                                                        with n >= min_area, truncated or not
+      match_dist_mean [B, Tn, 2]                        the mean, over the members and the kept target vortices, of the physical
+                                                        distance from the target vortex' w-weighted centroid (sum q w / sum q,
+                                                        sum q h / sum q) to the nearest kept vortex of its sign in the member
+      match_miss_frac [B, Tn, 2]                        the share of (member, target vortex) pairs without any vortex of that sign;
+                                                        both NaN where the target has none
+      vortex_threshold, vortex_qscale [B], vortex_circ_edges [B, circ_bins + 1] float64; vortex_args, the dict (min_area,
+      max_vortices, circ_bins)."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, grid=(1.0, 1.0), threshold=None, qscale=None,
+                 min_area=4, max_vortices=64, circ_bins=16, circ_range=None, per_member=False):
+        noun, why = "ensemble vortex censuses", "the velocity scales with u * out_std"
+        _ens_members(noun, members)
+        thr, qs, self.min_area, self.K, self.nb, self.circ_range, self.dx, self.dy = vortex_args(
+            threshold, qscale, min_area, max_vortices, circ_bins, circ_range, C, Hh, Ww, grid, B=int(B))
+        if thr is None or qs is None:
+            raise ValueError("%s need threshold and qscale: they come from the target's series (vortex_defaults), which an accumulator "
+                             "does not see before it is fed" % noun)
+        sd, mu = _ens_tables(int(C), why, out_std, out_mu)
+        u = _ens_u(u, B, int(C), why)
+        if int(steps) < 1 or int(B) < 1:
+            raise ValueError("%s need steps, B >= 1, got %d, %d" % (noun, steps, B))
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, int(C), Hh, Ww, steps)
+        self.per_member = bool(per_member)
+        self.mu, self.sd = mu.to(dev).contiguous(), sd.to(dev).contiguous()
+        self.u = None if u is None else u.to(dev).contiguous()
+        self.thr = thr.to(torch.float32).to(dev).contiguous()
+        self.qs = qs.to(torch.float32).to(dev).contiguous()
+        R, HW = self.S + 1, self.H * self.W
+        self.plan = H.ens_vortex_plan(1, self.S, self.B, self.H, self.W, self.K, self.Tk)
+        self.table = torch.empty((self.Tk, R, self.B, self.K, H.VORTEX_WORDS), device=dev, dtype=torch.int64)
+        self.found = torch.empty((self.Tk, R, self.B, 2), device=dev, dtype=torch.int32)
+        self.rejected = torch.empty((self.Tk, R, self.B), device=dev, dtype=torch.int32)
+        self.core = torch.zeros((2, self.B, 2, HW), device=dev, dtype=torch.int32)          # the members', the target's
+        self.status = torch.zeros((1,), device=dev, dtype=torch.int32)
+        self.ws = None
+
+    def reserve(self, k):
+        """The workspace of chunks of up to k rows (17 bytes per pixel; grown when a larger chunk arrives; its content never matters)."""
+        need = 17 * int(k) * self.B * self.H * self.W
+        if self.ws is None or self.ws.numel() < need:
+            self.ws = torch.empty((need,), device=self.table.device, dtype=torch.uint8)
+        return self.ws
+
+    def _planes(self, k):
+        n, HW = k * self.B * self.H * self.W, self.H * self.W
+        ws = self.reserve(k)
+        i32 = lambda j: ws[4 * j * n:4 * (j + 1) * n].view(torch.int32).view(k * self.B, HW)   # noqa: E731
+        return ws[:4 * n].view(torch.float32).view(k * self.B, HW), i32(1), i32(2), i32(3), ws[16 * n:17 * n].view(torch.int8).view(k * self.B, HW)
+
+    def _feed(self, yn, k, row0, t, core):
+        om, lab, area, slot, cls = self._planes(k)
+        H.ens_vortex_classify(yn, self.u, self.mu, self.sd, self.thr, self.qs, om, cls, self.rejected[t, row0:row0 + k], (self.dx, self.dy), k)
+        H.ens_vortex_label(cls, lab, self.status, self.H, self.W)
+        H.ens_vortex_census(lab, cls, om, self.qs, area, slot, self.table[t, row0:row0 + k].view(k * self.B, self.K, H.VORTEX_WORDS),
+                            self.found[t, row0:row0 + k].view(k * self.B, 2), core, self.H, self.W, k, self.min_area)
+
+    def add(self, y, m0, target, time=True):
+        """Take the census of the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last
+        view is an NHWC channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride
+        rule, taken as row S with the step's last chunk.  A step fed with time=False launches nothing."""
+        yn, tn, k, t_before, last = self.open_chunk(y, m0, time, target, required=True)
+        _on_device(yn, tn)
+        if time:
+            self._feed(yn, k, m0, t_before, self.core[0])
+            if last:
+                self._feed(tn, 1, self.S, t_before, self.core[1])
+        self.close_chunk(m0, k, time, last)
+
+    def finalize(self):
+        """-> dict of the outputs over the steps folded with time=True."""
+        T = self.finalize_guard()
+        code = int(self.status.item())
+        if code:
+            raise RuntimeError("the vortex labelling reached a loop's trip bound (status %d): the labels are not to be trusted" % code)
+        B, S, K, Hh, Ww = self.B, self.S, self.K, self.H, self.W
+        tab = self.table[:T].permute(2, 1, 0, 3, 4).contiguous().cpu()                    # [B, S + 1, T, K, 8]
+        found = self.found[:T].permute(2, 1, 0, 3).contiguous().cpu()
+        qs64 = self.qs.double().cpu()
+        f = vortex_finalize(tab, found, S, Hh, Ww, self.dx, self.dy, qs64, self.nb, self.circ_range)
+        o = {key: (v if v.dtype == torch.int64 else v.to(torch.float32)) for key, v in f.items() if key != "vortex_circ_edges"}
+        o["vortex_circ_edges"] = f["vortex_circ_edges"]
+        o["target_vortex_table"] = tab[:, S].contiguous()
+        if self.per_member:
+            o["vortex_table"] = tab
+        o["vortex_found"] = found
+        o["vortex_rejected"] = self.rejected[:T].permute(2, 1, 0).contiguous().cpu()
+        o["vortex_truncated"] = (found.long().sum(-1) > K).sum((1, 2))
+        core = self.core.cpu().double().view(2, B, 2, Hh, Ww)
+        o["core_prob"] = (core[0] / float(S * T)).to(torch.float32)
+        o["target_core_freq"] = (core[1] / float(T)).to(torch.float32)
+        o["vortex_threshold"], o["vortex_qscale"] = self.thr.double().cpu(), qs64
+        o["vortex_args"] = dict(min_area=self.min_area, max_vortices=K, circ_bins=self.nb)
+        return o
+
+
 FLUX_WIDTHS = (3, 5, 9, 17, 33)
 FLUX_MAX_WIDTHS = 8
 FLUX_MAX_WIDTH = 33

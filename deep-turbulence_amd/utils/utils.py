@@ -858,6 +858,65 @@ def modelPredTransport(args, model, testing_loader, log, samples=1, stride=1, tm
     return _ensembleStats("modelPredTransport", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
 
 
+def _vortex_factory(name, grid, stride, t_start, kw):
+    """The make of modelPredVortices' record.  kw: the keywords of tmg_ops.EnsembleVortices, with threshold / qscale None for the
+    defaults of the case's target series over the kept steps from t_start on (tmg_ops.vortex_defaults, plain torch in fp64); arrays
+    per case are cut to the mini-batch."""
+    def make(mb, members, steps):
+        import tmg_ops as ops
+        kw2 = dict(kw)
+        for key in ("threshold", "qscale", "circ_range"):
+            v = kw2[key]
+            if v is not None and torch.as_tensor(v).dim() == (2 if key == "circ_range" else 1):
+                kw2[key] = torch.as_tensor(v)[mb.case0:mb.case0 + mb.B]
+        if kw2["threshold"] is None or kw2["qscale"] is None:
+            tk = mb.tgt[:, t_start * stride:(steps - 1) * stride + 1:stride]
+            try:
+                thr, qs = ops.vortex_defaults(tk, grid)
+            except ValueError as e:
+                raise ValueError("%s: cases from %d on: %s" % (name, mb.case0, e))
+            kw2["threshold"] = thr if kw2["threshold"] is None else kw2["threshold"]
+            kw2["qscale"] = qs if kw2["qscale"] is None else kw2["qscale"]
+        return ops.EnsembleVortices(members, mb.B, mb.C, mb.H, mb.W, steps, mb.dev, mb.out_mu, mb.out_std, u=mb.u, grid=grid, **kw2)
+    return make
+
+
+def modelPredVortices(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, threshold=None, qscale=None,
+                      min_area=4, max_vortices=64, circ_bins=16, circ_range=None, per_member=False):
+    """modelPredStats plus the vortex census of every member and of the target, still without forming modelPred's
+    [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleVortices): how many vortices are in the field, how big and how strong are they,
+    where do they live, and are the reference's vortices present in the members at the right place?  Every other diagnostic here is a
+    statistic of fields at fixed pixels or of particles; a member can match them all and still shed vortices half as strong and
+    twice as many, or break every vortex into speckle with the right vorticity PDF.  The Okubo-Weiss / Q-criterion census (McWilliams
+    1990; the 0.2 sigma threshold of Isern-Fontanet et al.) and the object-based verification of meteorology (SAL, MODE).  Same
+    roll-outs as modelPredStats: under the same host RNG state the keys both return are identical.  The grid is (args.dx along W,
+    args.dy along H); the target of kept step j is series step j * stride.
+
+    Rows are the S members and the target; the timed steps are the kept steps t_start..Tk-1 (Tn of them).  A pixel that is not on the
+    field's one-pixel frame belongs to a vortex core of sign(w) when ow = w^2 - sn^2 - ss^2 > threshold (w the vorticity, sn, ss the
+    normal and shear strain, all by the 3x3 stencils of pc/ in fp32); a vortex is a maximal 4-connected set of core pixels of one sign.
+    threshold: physical 1/s^2, one number or [N]; None: per case 0.2 times the population std of the target's ow over the interior
+    pixels and the timed steps (a constant target raises).  qscale: the power of two that turns w into the fixed-point integers q the
+    measures sum, one or [N]; None: 2^(20 - ceil(log2(max |w| of the target))).  Pixels with |w qscale| > 2^31 or a NaN criterion are
+    counted in vortex_rejected, never silently dropped; non-finite members become background.  min_area (>= 1): smaller vortices are
+    neither listed nor counted.  max_vortices (<= 256): the slots K of a table, filled in increasing order of the vortex' first pixel;
+    vortex_found counts past K and vortex_truncated reports it.  circ_bins (<= 32) bins of |circulation| over circ_range ((lo, hi),
+    [N, 2], or None: [0, 1.25 max |G|] of the case's target table).  The state takes 64 K bytes per row, case and timed step and 16
+    bytes per pixel and case; it holds integers only and is bitwise reproducible and independent of max_rows.
+
+    Returns modelPredStats' dict plus the keys of tmg_ops.EnsembleVortices.finalize (CPU tensors, B = N), and vortex_args, the
+    dict (min_area, max_vortices, circ_bins).
+    Not supported: 8-connectivity, tracking identities across steps (the tables are returned for that), lambda-2 or swirling
+    strength, pixel boxes, more than 256 vortices per field, periodic domains, fields over 512 per side."""
+    import tmg_ops as ops
+    ops.vortex_args(threshold, qscale, min_area, max_vortices, circ_bins, circ_range, 3, None, None, (args.dx, args.dy))
+    kw = dict(threshold=threshold, qscale=qscale, min_area=min_area, max_vortices=max_vortices, circ_bins=circ_bins, circ_range=circ_range,
+              per_member=bool(per_member))
+    acc = _Acc(_vortex_factory("modelPredVortices", (float(args.dx), float(args.dy)), stride, t_start, kw), target=True,
+               meta=("vortex_args",))
+    return _ensembleStats("modelPredVortices", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
+
+
 def modelPredSpod(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, bins=None, modes=4, channels=(0, 1),
                   window="hann", loo=True, dt=None):
     """modelPredStats plus the spectral POD (SPOD; Towne, Schmidt & Colonius 2018) of the members over the kept steps t_start..Tk-1
