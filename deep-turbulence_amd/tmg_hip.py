@@ -20,7 +20,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmglow_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip", "tmg_phase.hip", "tmg_spod.hip", "tmg_budget.hip", "tmg_corr.hip", "tmg_flux.hip", "tmg_vortex.hip", "tmg_lagr.hip"]
+SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip", "tmg_phase.hip", "tmg_spod.hip", "tmg_budget.hip", "tmg_corr.hip", "tmg_flux.hip", "tmg_vortex.hip", "tmg_frank.hip", "tmg_lagr.hip"]
 # Sources compiled WITHOUT the packed-fp32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32): beside MFMAs a packed
 # f32 instruction costs ~13 cycles more than the two scalar ones it replaces (MI355X_MICROARCH.md, cycle constants, 'price of one
 # filler beside MFMAs'), and the compiler SLP-packs adjacent scalar adds / multiplies by itself under -O3.  The matrix-core kernels'
@@ -97,11 +97,19 @@ LAGR_EXPORTS = ["tmg_ens_lagr_plan", "tmg_ens_lagr_advect", "tmg_ens_lagr_store"
 # The vortex census: Okubo-Weiss classes, connected-component labels, int64 measures (csrc/tmg_vortex.hip), declared in
 # include/tmglow_hip_vortex.h, a header of its own: ens_vortex_plan / ens_vortex_classify / ens_vortex_label / ens_vortex_census below.
 VORTEX_EXPORTS = ["tmg_ens_vortex_plan", "tmg_ens_vortex_classify", "tmg_ens_vortex_label", "tmg_ens_vortex_census"]
+# The multivariate rank histograms: the average-rank and band-depth pre-ranks of every row (csrc/tmg_frank.hip), declared in
+# include/tmglow_hip_frank.h, a header of its own: ens_frank_plan / ens_frank_step below.
+FRANK_EXPORTS = ["tmg_ens_frank_plan", "tmg_ens_frank_step"]
 _P64 = ctypes.POINTER(ctypes.c_int64)
 FLUX_ARGTYPES = {
     "tmg_ens_flux_plan": [_P64, _P64, _P64],
     "tmg_ens_flux_accum": [ctypes.c_void_p, _P64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _P64, _P64, ctypes.c_void_p],
     "tmg_ens_flux_terms": [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, _P64, _P64, ctypes.c_void_p],
+}
+FRANK_ARGTYPES = {
+    "tmg_ens_frank_plan": [_P64, _P64],
+    "tmg_ens_frank_step": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _P64,
+                           ctypes.c_void_p],
 }
 # Every export returns int except the workspace sizes, which the header declares int64_t (read through a 32-bit return a request of
 # 2^31 floats or more would be truncated and the kernel handed a buffer smaller than it planned for).
@@ -120,7 +128,8 @@ def build(force=False, verbose=False):
                os.path.join(inc, "tmglow_hip_event.h"), os.path.join(inc, "tmglow_hip_pdf.h"), os.path.join(inc, "tmglow_hip_pod.h"),
                os.path.join(inc, "tmglow_hip_phase.h"), os.path.join(inc, "tmglow_hip_spod.h"), os.path.join(inc, "tmglow_hip_layout.h"),
                os.path.join(inc, "tmglow_hip_budget.h"), os.path.join(inc, "tmglow_hip_corr.h"), os.path.join(inc, "tmglow_hip_flux.h"),
-               os.path.join(inc, "tmglow_hip_lagr.h"), os.path.join(inc, "tmglow_hip_vortex.h")]
+               os.path.join(inc, "tmglow_hip_lagr.h"), os.path.join(inc, "tmglow_hip_vortex.h"),
+               os.path.join(inc, "tmglow_hip_frank.h")]
     hmt = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -179,6 +188,9 @@ def lib():
         for name in FLUX_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
             getattr(_lib, name).argtypes = FLUX_ARGTYPES[name]
+        for name in FRANK_EXPORTS:
+            getattr(_lib, name).restype = ctypes.c_int
+            getattr(_lib, name).argtypes = FRANK_ARGTYPES[name]
     return _lib
 
 
@@ -1780,6 +1792,45 @@ def ens_vortex_census(label, cls, omega, qscale, area, slot, table, found, core,
     check_act(qscale)
     _chk(lib().tmg_ens_vortex_census(_ptr(label), _ptr(cls), _ptr(omega), _ptr(qscale), _ptr(area), _ptr(slot), _ptr(table), _ptr(found),
                                      _ptr(core), _i64(k, B, Hh, Ww, K, min_area), _stream()), "tmg_ens_vortex_census")
+
+
+FRANK_PLAN_KEYS = ("nblk", "grid_x", "grid_y", "grid_z", "threads", "rec_words", "ws_words")
+
+
+def ens_frank_plan(S, B, C, HW, code=False):
+    """The launch plan of ens_frank_step for S members and the target of B cases of [C, HW] (tmg_ens_frank_plan; nothing is
+    launched) -> dict of FRANK_PLAN_KEYS (include/tmglow_hip_frank.h) plus grid = (nblk, C, B).  code=True: the C return code
+    instead of raising, as the second element of a pair."""
+    plan = (c_i64 * len(FRANK_PLAN_KEYS))()
+    rc = lib().tmg_ens_frank_plan(_i64(S, B, C, HW), plan)
+    out = dict(zip(FRANK_PLAN_KEYS, [int(v) for v in plan]))
+    out["grid"] = (out["grid_x"], out["grid_y"], out["grid_z"])
+    if code:
+        return out, rc
+    _chk(rc, "tmg_ens_frank_plan")
+    return out
+
+
+def ens_frank_step(xs, ws, pre_raw, outside, tout, t, t_before, flags):
+    """The average-rank and band-depth terms of one kept step whose S members and target are the rows of xs [S + 1, B, C, HW] (the
+    target last): their sums over the pixels into pre_raw [B, Tk, C, S + 1, 2] int64 and the count of pixels whose target lies
+    strictly outside the members' range into outside [B, Tk, C] int64, both at step t; ws: the int32 workspace (>= ens_frank_plan's
+    words).  flags & 1 adds the outside flags to the plane tout [B, C, HW] int32, which holds t_before steps (tmg_ens_frank_step)."""
+    R, B, Cc, HW = xs.shape
+    i32, i64 = torch.int32, torch.int64
+    if xs.dtype != torch.float32 or not xs.is_cuda or not xs.is_contiguous() or R < 2:
+        raise RuntimeError("ens_frank_step: xs is a contiguous fp32 [S + 1, B, C, HW] on the device, got %s %s" % (xs.dtype, tuple(xs.shape)))
+    check_device(xs)
+    Tk = pre_raw.shape[1] if pre_raw.dim() == 5 else 0
+    if pre_raw.dtype != i64 or tuple(pre_raw.shape) != (B, Tk, Cc, R, 2) or not pre_raw.is_contiguous() or outside.dtype != i64 \
+            or tuple(outside.shape) != (B, Tk, Cc) or not outside.is_contiguous() or ws.dtype != i32 or ws.dim() != 1 \
+            or not ws.is_contiguous() or pre_raw.device != xs.device or outside.device != xs.device or ws.device != xs.device:
+        raise RuntimeError("ens_frank_step: pre_raw %s, outside %s, ws %s do not fit %d rows of [%d, %d, %d]"
+                           % (tuple(pre_raw.shape), tuple(outside.shape), tuple(ws.shape), R, B, Cc, HW))
+    if tout is not None and (tout.dtype != i32 or tuple(tout.shape) != (B, Cc, HW) or not tout.is_contiguous() or tout.device != xs.device):
+        raise RuntimeError("ens_frank_step: tout is a contiguous int32 [%d, %d, %d] on the device, got %s" % (B, Cc, HW, tuple(tout.shape)))
+    _chk(lib().tmg_ens_frank_step(_ptr(xs), _ptr(ws), ws.numel(), _ptr(pre_raw), _ptr(outside), _ptr(tout),
+                                  _i64(R - 1, B, HW, Cc, Tk, t, t_before, flags), _stream()), "tmg_ens_frank_step")
 
 
 def ens_corr_cfg(probes, pairs, lags):

@@ -2564,6 +2564,141 @@ class EnsembleEnergy(EnsembleFeed):
         return o
 
 
+def fieldrank_hist(below, equal, S):
+    """The rank histogram of a target whose pre-rank lies above `below` members and ties with `equal` of them, over the steps of
+    dim 1: below, equal [B, Tn, G] integer tensors with 0 <= below, 0 <= equal, below + equal <= S -> [B, G, S + 1] float64.  Step
+    n adds 1 / (equal + 1) to every bin below .. below + equal: the expectation of random tie-breaking, which is deterministic.  The
+    steps are added in order, one elementwise fp64 addition each; every histogram sums to Tn.  Host work: no device is needed."""
+    S = int(S)
+    below, equal = torch.as_tensor(below).to(torch.int64).cpu(), torch.as_tensor(equal).to(torch.int64).cpu()
+    if S < 1 or below.dim() != 3 or below.shape != equal.shape:
+        raise ValueError("fieldrank_hist takes below and equal of one shape [B, Tn, G] and S >= 1, got %s, %s, S=%d"
+                         % (tuple(below.shape), tuple(equal.shape), S))
+    if below.numel() and (int(below.min()) < 0 or int(equal.min()) < 0 or int((below + equal).max()) > S):
+        raise ValueError("fieldrank_hist needs 0 <= below, 0 <= equal and below + equal <= S = %d" % S)
+    B, Tn, G = below.shape
+    bins = torch.arange(S + 1, dtype=torch.int64).view(1, 1, S + 1)
+    hist = torch.zeros((B, G, S + 1), dtype=torch.float64)
+    for n in range(Tn):
+        lo, k = below[:, n].unsqueeze(-1), equal[:, n].unsqueeze(-1)
+        hist += ((bins >= lo) & (bins <= lo + k)).to(torch.float64) / (k + 1).to(torch.float64)
+    return hist
+
+
+def _fieldrank_of_target(pre):
+    """pre [.., S + 1] int64, the target last -> (below, equal): the members whose pre-rank is under / equal to the target's."""
+    return (pre[..., :-1] < pre[..., -1:]).sum(-1), (pre[..., :-1] == pre[..., -1:]).sum(-1)
+
+
+def _fieldrank_median(pre):
+    """pre [.., S + 1] int64 -> the member m < S with the largest pre-rank, the smallest index on ties."""
+    m = pre[..., :-1]
+    S = m.shape[-1]
+    idx = torch.arange(S, dtype=torch.int64).expand(m.shape)
+    return torch.where(m == m.max(-1, keepdim=True).values, idx, torch.full_like(idx, S)).min(-1).values
+
+
+def fieldrank_outputs(pre_raw, outside_count, time_outside_count, groups, timed):
+    """The host side of EnsembleFieldRanks.finalize(): the device's integer sums pre_raw [B, Tk, C, S + 1, 2], outside_count
+    [B, Tk, C] and time_outside_count [B, C, H, W] (int64 CPU tensors), the channel groups and the list of timed steps -> the dict
+    of outputs of the class docstring.  int64 and fp64 only; no device is needed."""
+    raw = pre_raw
+    B, Tk, C, R, _ = raw.shape
+    timed = [int(t) for t in timed]
+    if raw.dtype != torch.int64 or raw.dim() != 5 or raw.shape[4] != 2 or R < 2 or tuple(outside_count.shape) != (B, Tk, C) \
+            or time_outside_count.dim() != 4 or tuple(time_outside_count.shape[:2]) != (B, C) or not timed \
+            or any(not 0 <= t < Tk for t in timed):
+        raise ValueError("fieldrank_outputs: pre_raw %s, outside_count %s, time_outside_count %s, timed %s do not fit"
+                         % (tuple(raw.shape), tuple(outside_count.shape), tuple(time_outside_count.shape), timed))
+    groups = energy_groups(groups, C)
+    HW = time_outside_count.shape[2] * time_outside_count.shape[3]
+    o = {"pre_raw": raw, "outside_count": outside_count, "outside_frac": outside_count.double() / float(HW),
+         "time_outside_count": time_outside_count, "time_outside_frac": time_outside_count.double() / float(len(timed))}
+    for j, kind in enumerate(("avg", "depth")):
+        pre = torch.stack([raw[..., j][:, :, list(g)].sum(dim=2) for g in groups], dim=2)                 # [B, Tk, Gn, S + 1]
+        o[kind + "_prerank"] = pre
+        o[kind + "_rank_below"], o[kind + "_rank_equal"] = _fieldrank_of_target(pre)
+        o[kind + "_rank_hist"] = fieldrank_hist(o[kind + "_rank_below"][:, timed], o[kind + "_rank_equal"][:, timed], R - 1)
+        traj = pre[:, timed].sum(dim=1)
+        o["traj_" + kind + "_prerank"] = traj
+        o["traj_" + kind + "_rank_below"], o["traj_" + kind + "_rank_equal"] = _fieldrank_of_target(traj)
+    o["depth_median"] = _fieldrank_median(o["depth_prerank"])
+    o["traj_depth_median"] = _fieldrank_median(o["traj_depth_prerank"])
+    return o
+
+
+class EnsembleFieldRanks(EnsembleFeed):
+    """On-device multivariate rank histograms of sampled roll-outs of B cases against the target (tmg_ens_score_store /
+    tmg_ens_frank_step): whether the spread of whole FIELDS is right, which a per-pixel rank histogram cannot see and a score (one
+    number) cannot separate from bias.  The average-rank and band-depth histograms of Thorarinsdottir, Scheuerer & Heinz (2016); the
+    depth is the modified band depth of Lopez-Pintado & Romo (2009).  For case b, kept step t, channel c and pixel p, with the rows
+    x_0..x_{S-1} (raw normalised members) and x_S (the normalised target), for row i over the S other rows j != i:
+      lt = #{j : x_j < x_i}, eq = #{j : x_j == x_i}, gt = S - lt - eq
+      A_i(p) = 2 lt + eq                              the average-rank term (twice the mid-rank minus a constant)
+      D_i(p) = C(S,2) - C(lt,2) - C(gt,2)             the band-depth term: the pairs of other rows whose closed band holds x_i
+      O(p)   = [lt_S == S or gt_S == S]               the target lies strictly outside the members' range
+    It takes no out_mu, out_std or u: ranks do not change under x -> u (out_std x + out_mu) with u out_std > 0, so the kernel
+    compares the raw values, and the channels of a group are combined as sums of integers, without any choice of norm or scale.
+    The device sums A, D and O over the pixels in int64; everything else is host work on these small integer tensors, in int64 or
+    fp64.  With the channel groups g (tuples of channels; default ((0, 1), (2,)): velocity and pressure) the pre-rank of row i is
+    the sum over the group's channels; the field rank of the target is below = #{m < S : pre_m < pre_S}, equal = #{m < S : pre_m ==
+    pre_S}.  A low average rank: the target field lies under the members; a low depth rank: the target is the most outlying row.
+    A U-shaped average-rank histogram, or a depth-rank histogram piled at its low end, means under-dispersion.
+    Non-finite rows are not supported: the outputs of a pixel that holds one are unspecified.  At most 1024 members.
+
+    Feeding protocol of EnsembleFeed: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
+    chunks before the next step's; every chunk comes with the step's target, and the last chunk's is the one that is ranked.
+    Outputs of finalize() (CPU tensors; Gn groups, Tn the steps folded with time=True, int64 unless stated):
+      pre_raw [B, Tk, C, S + 1, 2]          sum_p A_i(p), sum_p D_i(p) per channel, the target last
+      outside_count [B, Tk, C], outside_frac = outside_count / HW float64 (a calibrated continuous ensemble gives 2 / (S + 1))
+      time_outside_count [B, C, H, W]       O(p) summed over the timed steps; time_outside_frac = count / Tn float64
+      avg_prerank, depth_prerank [B, Tk, Gn, S + 1]
+      avg_rank_below, avg_rank_equal, depth_rank_below, depth_rank_equal [B, Tk, Gn]
+      avg_rank_hist, depth_rank_hist [B, Gn, S + 1] float64: fieldrank_hist over the timed steps; each sums to Tn
+      traj_avg_prerank, traj_depth_prerank [B, Gn, S + 1]: the pre-ranks summed over the timed steps (a pre-rank is additive over
+      pixels, so this is the pre-rank of the roll-out as one vector); traj_avg_rank_below, traj_avg_rank_equal,
+      traj_depth_rank_below, traj_depth_rank_equal [B, Gn]
+      depth_median [B, Tk, Gn], traj_depth_median [B, Gn]: the member with the largest depth pre-rank (the functional median),
+      the smallest index on ties."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, groups=((0, 1), (2,))):
+        noun = "ensemble field ranks"
+        _ens_channels(noun, C)
+        _ens_members(noun, members)
+        if int(steps) < 1 or int(B) < 1 or int(Hh) < 1 or int(Ww) < 1:
+            raise ValueError("%s need B, H, W, steps >= 1, got %d, %d, %d, %d" % (noun, int(B), int(Hh), int(Ww), int(steps)))
+        self.groups = energy_groups(groups, C)
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, C, Hh, Ww, steps)
+        HW = self.H * self.W
+        self.plan = H.ens_frank_plan(self.S, self.B, C, HW)
+        # rows 0 .. S - 1: the members; row S: the target, stored by the same kernel as a one-member chunk
+        self.xs = torch.empty((self.S + 1, self.B, C, HW), device=dev, dtype=torch.float32)
+        self.ws = torch.empty((self.plan["ws_words"],), device=dev, dtype=torch.int32)
+        self.tout = torch.empty((self.B, C, HW), device=dev, dtype=torch.int32)
+        self.pre_raw = torch.empty((self.B, self.Tk, C, self.S + 1, 2), device=dev, dtype=torch.int64)
+        self.outside = torch.empty((self.B, self.Tk, C), device=dev, dtype=torch.int64)
+
+    def add(self, y, m0, target, time=True):
+        """Store the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
+        channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride rule.  The step's
+        last chunk stores its target as the last row and ranks the step."""
+        yn, tn, k, t_before, last = self.open_chunk(y, m0, time, target, required=True)
+        _on_device(yn, tn)
+        H.ens_score_store(yn, self.xs[:self.S], k, m0)
+        if last:
+            H.ens_score_store(tn, self.xs[self.S:], 1, 0)                      # row S, through its one-row view
+            H.ens_frank_step(self.xs, self.ws, self.pre_raw, self.outside, self.tout, self._step, t_before, 1 if time else 0)
+        self.close_chunk(m0, k, time, last)
+
+    def finalize(self):
+        """-> dict of the outputs (CPU tensors); the histograms, the roll-out ranks and the time_ outputs cover the steps folded
+        with time=True."""
+        self.finalize_guard()
+        return fieldrank_outputs(self.pre_raw.cpu(), self.outside.cpu(), self.tout.view(self.B, self.C, self.H, self.W).to(torch.int64).cpu(),
+                                 self.groups, self._timed)
+
+
 POD_MAX_MODES = 16
 
 

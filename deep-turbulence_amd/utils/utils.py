@@ -461,6 +461,55 @@ def modelPredEnergy(args, model, testing_loader, log, samples=1, stride=1, tmax=
     return _ensembleStats("modelPredEnergy", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
 
 
+def modelPredFieldRanks(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, groups=((0, 1), (2,))):
+    """modelPredStats plus the multivariate rank histograms of the target among the members as whole fields, still without forming
+    modelPred's [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleFieldRanks): the average-rank and band-depth histograms of
+    Thorarinsdottir, Scheuerer & Heinz (2016), the depth being the modified band depth of Lopez-Pintado & Romo (2009).  rank_hist of
+    modelPredScores is per pixel: it can be flat while every member is too smooth, or while the members never bracket the target as
+    a field.  The energy score of modelPredEnergy is one number and cannot tell under-dispersion from bias.  These histograms do for
+    fields what rank_hist does for pixels.  The target of kept step j is series step j * stride; a series that is too short raises.
+    Ranks do not change under the un-normalisation (u0 out_std > 0), so no channel scale enters and the channels of a group combine
+    without a norm.  Same roll-outs as modelPredStats: under the same host RNG state the keys both return are identical.
+
+    groups: tuples of channels, each channel in at most one group; the default is velocity (0, 1) and pressure (2,).  With the rows
+    x_0..x_{S-1} (members) and x_S (target), per pixel p and row i over the S other rows: lt, eq, gt the rows below, equal to and
+    above x_i; A_i(p) = 2 lt + eq; D_i(p) = C(S,2) - C(lt,2) - C(gt,2), the pairs of other rows whose closed band holds x_i;
+    O(p) = [the target is strictly outside the members' range].  The pre-rank of row i is the sum of A (or D) over the pixels and the
+    group's channels; below / equal count the members whose pre-rank is under / equal to the target's.
+
+    Returns modelPredStats' dict plus (CPU tensors; Gn groups, S = samples, kept steps t_start..Tk-1 are the Tn timed ones; int64
+    unless stated):
+      pre_raw [N, Tk, C, S + 1, 2]      sum_p A_i(p) and sum_p D_i(p) per channel, the target last
+      avg_prerank, depth_prerank [N, Tk, Gn, S + 1]
+      avg_rank_below, avg_rank_equal, depth_rank_below, depth_rank_equal [N, Tk, Gn]
+                                        the field rank of the target.  Low average rank: the target lies under the members; low depth
+                                        rank: the target is the most outlying row
+      avg_rank_hist, depth_rank_hist [N, Gn, S + 1] float64
+                                        over the timed steps, each step adding 1 / (equal + 1) to the bins below .. below + equal
+                                        (the expectation of random tie-breaking); each sums to Tn.  Sum them over N to pool cases.
+                                        U-shaped average ranks, or depth ranks piled at the low end, mean under-dispersion
+      traj_avg_prerank, traj_depth_prerank [N, Gn, S + 1]
+                                        the pre-ranks summed over the timed steps: the roll-out as one vector
+      traj_avg_rank_below, traj_avg_rank_equal, traj_depth_rank_below, traj_depth_rank_equal [N, Gn]
+      depth_median [N, Tk, Gn], traj_depth_median [N, Gn]
+                                        the member with the largest depth pre-rank (the functional median; ties: the lowest member)
+      outside_count [N, Tk, C], outside_frac float64
+                                        the pixels whose target lies strictly outside the members' range, and their share of the
+                                        field; a calibrated continuous ensemble gives 2 / (S + 1)
+      time_outside_count [N, C, H, W], time_outside_frac float64
+                                        the timed steps at which the pixel's target lay outside, and their share of Tn
+      fieldrank_groups                  the groups as given.
+
+    Not supported: the minimum-spanning-tree rank histogram, the functional boxplot and central-region envelopes, pixel boxes or
+    thinning of the field, per-member field ranks beyond depth_median, pooling over cases, more than 1024 members, non-finite
+    members (the outputs of a pixel that holds one are unspecified)."""
+    import tmg_ops as ops
+    groups = ops.energy_groups(groups, 3)
+    acc = _Acc(lambda mb, S, T: ops.EnsembleFieldRanks(S, mb.B, mb.C, mb.H, mb.W, T, mb.dev, groups=groups), target=True,
+               extra={"fieldrank_groups": tuple(groups)})
+    return _ensembleStats("modelPredFieldRanks", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
+
+
 def modelPredStructure(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, lags=None, weights=None):
     """modelPredStats plus the structure functions of every member and of the target and the ensemble's variogram score, still without
     forming modelPred's [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleStructure, grid = (args.dx, args.dy)).  This is the
