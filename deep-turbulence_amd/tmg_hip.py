@@ -20,7 +20,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmglow_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip", "tmg_phase.hip", "tmg_spod.hip", "tmg_budget.hip", "tmg_corr.hip", "tmg_flux.hip", "tmg_vortex.hip", "tmg_frank.hip", "tmg_lagr.hip"]
+SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip", "tmg_phase.hip", "tmg_spod.hip", "tmg_budget.hip", "tmg_corr.hip", "tmg_flux.hip", "tmg_vortex.hip", "tmg_frank.hip", "tmg_xspec.hip", "tmg_lagr.hip"]
 # Sources compiled WITHOUT the packed-fp32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32): beside MFMAs a packed
 # f32 instruction costs ~13 cycles more than the two scalar ones it replaces (MI355X_MICROARCH.md, cycle constants, 'price of one
 # filler beside MFMAs'), and the compiler SLP-packs adjacent scalar adds / multiplies by itself under -O3.  The matrix-core kernels'
@@ -31,8 +31,9 @@ SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hi
 # MFMAs of the projection, exactly the filler position the list is about; its results do not depend on the choice (a packed
 # instruction rounds each half as the scalar one does).  tmg_spod.hip is listed for the same reason: the correction
 # x - xbar G of every fragment element is vector work between the MFMAs of the Gram product and of the synthesis.
+# tmg_xspec.hip is listed as tmg_spectrum.hip is: its column pass stores the accumulators between the MFMAs of the next row tile.
 NO_PACKED_F32 = ["tmg_wino.hip", "tmg_conv.hip", "tmg_coupling.hip", "tmg_thin.hip", "tmg_mix16.hip", "tmg_spectrum.hip", "tmg_tspec.hip",
-                 "tmg_pod.hip", "tmg_spod.hip"]
+                 "tmg_pod.hip", "tmg_spod.hip", "tmg_xspec.hip"]
 _lib = None
 
 c_i64 = ctypes.c_int64
@@ -100,6 +101,9 @@ VORTEX_EXPORTS = ["tmg_ens_vortex_plan", "tmg_ens_vortex_classify", "tmg_ens_vor
 # The multivariate rank histograms: the average-rank and band-depth pre-ranks of every row (csrc/tmg_frank.hip), declared in
 # include/tmglow_hip_frank.h, a header of its own: ens_frank_plan / ens_frank_step below.
 FRANK_EXPORTS = ["tmg_ens_frank_plan", "tmg_ens_frank_step"]
+# The spectral skill: coherence, error and spread spectra against the target (csrc/tmg_xspec.hip), declared in
+# include/tmglow_hip_xspec.h, a header of its own: ens_xspec_plan / ens_xspec_prep / ens_xspec_cols / ens_xspec_accum below.
+XSPEC_EXPORTS = ["tmg_ens_xspec_plan", "tmg_ens_xspec_prep", "tmg_ens_xspec_cols", "tmg_ens_xspec_accum"]
 _P64 = ctypes.POINTER(ctypes.c_int64)
 FLUX_ARGTYPES = {
     "tmg_ens_flux_plan": [_P64, _P64, _P64],
@@ -110,6 +114,14 @@ FRANK_ARGTYPES = {
     "tmg_ens_frank_plan": [_P64, _P64],
     "tmg_ens_frank_step": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _P64,
                            ctypes.c_void_p],
+}
+XSPEC_ARGTYPES = {
+    "tmg_ens_xspec_plan": [_P64, _P64],
+    "tmg_ens_xspec_prep": [ctypes.c_void_p, _P64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                           ctypes.c_void_p, _P64, ctypes.c_void_p],
+    "tmg_ens_xspec_cols": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _P64,
+                           ctypes.POINTER(ctypes.c_float), ctypes.c_void_p],
+    "tmg_ens_xspec_accum": [ctypes.c_void_p] * 10 + [_P64, ctypes.c_void_p],
 }
 # Every export returns int except the workspace sizes, which the header declares int64_t (read through a 32-bit return a request of
 # 2^31 floats or more would be truncated and the kernel handed a buffer smaller than it planned for).
@@ -129,7 +141,7 @@ def build(force=False, verbose=False):
                os.path.join(inc, "tmglow_hip_phase.h"), os.path.join(inc, "tmglow_hip_spod.h"), os.path.join(inc, "tmglow_hip_layout.h"),
                os.path.join(inc, "tmglow_hip_budget.h"), os.path.join(inc, "tmglow_hip_corr.h"), os.path.join(inc, "tmglow_hip_flux.h"),
                os.path.join(inc, "tmglow_hip_lagr.h"), os.path.join(inc, "tmglow_hip_vortex.h"),
-               os.path.join(inc, "tmglow_hip_frank.h")]
+               os.path.join(inc, "tmglow_hip_frank.h"), os.path.join(inc, "tmglow_hip_xspec.h")]
     hmt = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -191,6 +203,9 @@ def lib():
         for name in FRANK_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
             getattr(_lib, name).argtypes = FRANK_ARGTYPES[name]
+        for name in XSPEC_EXPORTS:
+            getattr(_lib, name).restype = ctypes.c_int
+            getattr(_lib, name).argtypes = XSPEC_ARGTYPES[name]
     return _lib
 
 
@@ -1831,6 +1846,56 @@ def ens_frank_step(xs, ws, pre_raw, outside, tout, t, t_before, flags):
         raise RuntimeError("ens_frank_step: tout is a contiguous int32 [%d, %d, %d] on the device, got %s" % (B, Cc, HW, tuple(tout.shape)))
     _chk(lib().tmg_ens_frank_step(_ptr(xs), _ptr(ws), ws.numel(), _ptr(pre_raw), _ptr(outside), _ptr(tout),
                                   _i64(R - 1, B, HW, Cc, Tk, t, t_before, flags), _stream()), "tmg_ens_frank_step")
+
+
+XSPEC_PLAN_KEYS = ("prep_grid", "cols_grid_x", "cols_grid_y", "cols_lds_bytes", "accum_grid_x", "accum_grid_y", "threads", "f_floats",
+                   "part_floats", "zt_floats", "part_t_floats")
+
+
+def ens_xspec_plan(k, B, Hh, Ww, NK, code=False):
+    """The grids, LDS bytes and buffer sizes of the spectral-skill launches for a chunk of k members of B cases of [H, W] with NK
+    shells (tmg_ens_xspec_plan; nothing is launched) -> dict of XSPEC_PLAN_KEYS (include/tmglow_hip_xspec.h).  code=True: the C
+    return code instead of raising, as the second element of a pair."""
+    plan = (c_i64 * len(XSPEC_PLAN_KEYS))()
+    rc = lib().tmg_ens_xspec_plan(_i64(k, B, Hh, Ww, NK), plan)
+    out = dict(zip(XSPEC_PLAN_KEYS, [int(v) for v in plan]))
+    if code:
+        return out, rc
+    _chk(rc, "tmg_ens_xspec_plan")
+    return out
+
+
+def ens_xspec_prep(y, u, out_mu, out_std, center, f, fsum, k, mode, S):
+    """f = u fmaf(out_std, y, out_mu) - center of channels 0 and 1 of the chunk's k members (y: NHWC [k*B, H, W, C] or a channel-slice
+    view) into the dense f [>= k*B, H, W, 2]; mode 0: f alone (the target), 1 / 2: the members also go into fsum [B, H, W, 2] (1: the
+    step's first chunk stores), 3: f = fsum / S, y is None (tmg_ens_xspec_prep)."""
+    B, Hh, Ww, _ = fsum.shape
+    if mode == 3:
+        ptr, ps, co, Cc = 0, 0, 0, 2
+    else:
+        ptr, ps, co, Cc = seg(y)
+    _chk(lib().tmg_ens_xspec_prep(c_vp(ptr), _i64(ps, co), _ptr(u), _ptr(out_mu), _ptr(out_std), _ptr(center), _ptr(f), _ptr(fsum),
+                                  _i64(k, B, Hh, Ww, Cc, mode, S, f.numel()), _stream()), "tmg_ens_xspec_prep")
+
+
+def ens_xspec_cols(ft_h, yw, perm, offs, zt, part, n, B, Hh, Ww, NK, cross):
+    """Column transform of the n images in yw (ft_h: [2, H, H]) and the shell sums of every 16-column tile in the order of the tiles'
+    shell lists (perm, offs).  cross False (n = B, the target): Z into zt [2, B, H, W], the sums of P into part [B, W/16, NK];
+    cross True: (P, X, D) against zt into part [n, W/16, 3, NK] (tmg_ens_xspec_cols)."""
+    _chk(lib().tmg_ens_xspec_cols(_ptr(ft_h), _ptr(yw), _ptr(perm), _ptr(offs), _ptr(zt), _ptr(part),
+                                  _i64(n, B, Hh, Ww, NK, 1 if cross else 0, yw.numel(), zt.numel(), part.numel()),
+                                  _flts([0.5 / (float(Hh) * float(Ww)) ** 2]), _stream()), "tmg_ens_xspec_cols")
+
+
+def ens_xspec_accum(part, part_t, part_b, step, tpow, sum_out, bar_out, tmem, ttgt, tbar, k, QT, t, n_before, m0, t_before, flags):
+    """Fold one chunk's partial sums (ens_xspec_cols) into the step sums `step` [B, 3, NK], the members' time sums tmem [B, S, 3, NK],
+    and at the step's first / last chunk the target's and the mean field's sums into tpow [B, Tk, NK], ttgt [B, NK], bar_out and
+    sum_out [B, Tk, 3, NK], tbar [B, 3, NK]; flags: 1 timed, 2 last (tmg_ens_xspec_accum)."""
+    B, S, _, NK = tmem.shape
+    Tk = tpow.shape[1]
+    _chk(lib().tmg_ens_xspec_accum(_ptr(part), _ptr(part_t), _ptr(part_b), _ptr(step), _ptr(tpow), _ptr(sum_out), _ptr(bar_out),
+                                   _ptr(tmem), _ptr(ttgt), _ptr(tbar), _i64(k, B, NK, QT, S, Tk, t, n_before, m0, t_before, flags),
+                                   _stream()), "tmg_ens_xspec_accum")
 
 
 def ens_corr_cfg(probes, pairs, lags):

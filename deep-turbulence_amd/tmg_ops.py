@@ -4313,6 +4313,253 @@ class EnsembleSpectrum(EnsembleFeed):
         return self.out
 
 
+def xspec_args(C, Hh, Ww, grid, window, level):
+    """The argument checks of the spectral skill (EnsembleSpectralSkill, utils.modelPredSpectralSkill), every failure a ValueError
+    before any device work, in this order: C, H and W, grid, window, level, the number of shells -> (grid as floats, bins, k) with
+    (bins, k) = spectrum_bins(H, W, dx, dy)."""
+    if isinstance(C, bool) or not isinstance(C, numbers.Integral):
+        raise ValueError("spectral skill needs an integer number of channels, got %r" % (C,))
+    _ens_channels("spectral skill", C, " (the velocity is channels 0 and 1)")
+    if any(isinstance(n, bool) or not isinstance(n, numbers.Integral) for n in (Hh, Ww)) \
+            or not all(16 <= n <= 512 and n % 16 == 0 for n in (Hh, Ww)):
+        raise ValueError("spectral skill needs H and W that are a multiple of 16 in [16, 512], got %r x %r" % (Hh, Ww))
+    try:
+        grid = tuple(float(g) for g in grid)
+    except (TypeError, ValueError):
+        raise ValueError("grid needs two positive finite cell sizes (dx, dy), got %r" % (grid,)) from None
+    if len(grid) != 2 or not all(math.isfinite(g) and g > 0 for g in grid):
+        raise ValueError("grid needs two positive finite cell sizes (dx, dy), got %s" % (grid,))
+    if window not in ("hann", None):
+        raise ValueError("window must be 'hann' or None, got %r" % (window,))
+    if isinstance(level, bool) or not isinstance(level, numbers.Real) or not 0.0 < float(level) < 1.0:
+        raise ValueError("level is the coherence that defines the cut-off wavenumber, a number in (0, 1), got %r" % (level,))
+    bins, k = spectrum_bins(int(Hh), int(Ww), grid[0], grid[1])
+    if k.numel() > SPECTRUM_MAX_SHELLS:
+        raise ValueError("grid %s gives %d shells on %d x %d modes, at most %d are supported" % (grid, k.numel(), Hh, Ww, SPECTRUM_MAX_SHELLS))
+    return grid, bins, k
+
+
+XSPEC_RAW_KEYS = ("xs_target_power", "xs_sum", "xs_mean_field", "xs_time_member", "xs_time_target", "xs_time_mean_field")
+
+
+def _xs_ratio(a, b):
+    """a / b in fp64, NaN where b == 0 (an empty shell, or no power at all)."""
+    ok = b != 0
+    return torch.where(ok, a / torch.where(ok, b, torch.ones_like(b)), torch.full_like(b, float("nan")))
+
+
+def _xs_forms(P, X, D, Pb, Xb, Db, PT, S, pre):
+    """The derived spectra of one set of sums (fp64; P, X, D: the members' means): the issue's formulas, keys with prefix pre."""
+    spread = D - Db
+    arg = _xs_ratio((S + 1.0) / S * spread, Db)
+    return {pre + "spec_corr": _xs_ratio(X, torch.sqrt(P * PT)), pre + "mean_field_corr": _xs_ratio(Xb, torch.sqrt(Pb * PT)),
+            pre + "err_spec": D, pre + "mean_err_spec": Db, pre + "spread_spec": spread,
+            pre + "spread_skill": torch.sqrt(torch.where(arg >= 0, arg, torch.full_like(arg, float("nan")))),
+            pre + "power_ratio": _xs_ratio(P, PT), pre + "rel_err": _xs_ratio(D, PT)}
+
+
+def _xs_cutoff(corr, k, level):
+    """corr [..., NK] fp64 -> the cut-off wavenumber [...]: over the shells s >= 1 whose corr is finite, the first with corr < level;
+    linearly interpolated in corr between the finite shell before it and itself, k of that shell when it is the first finite one,
+    inf when no shell is under level."""
+    flat = corr.reshape(-1, corr.shape[-1])
+    out = torch.full((flat.shape[0],), float("inf"), dtype=torch.float64)
+    kk = k.tolist()
+    for r, row in enumerate(flat.tolist()):
+        prev = None
+        for s in range(1, len(row)):
+            c = row[s]
+            if not math.isfinite(c):
+                continue
+            if c < level:
+                out[r] = kk[s] if prev is None else kk[prev] + (row[prev] - level) / (row[prev] - c) * (kk[s] - kk[prev])
+                break
+            prev = s
+    return out.reshape(corr.shape[:-1])
+
+
+def xspec_outputs(xs_target_power, xs_sum, xs_mean_field, xs_time_member, xs_time_target, xs_time_mean_field, S, k, level, timed):
+    """The derived outputs of the spectral skill from its raw shell sums (XSPEC_RAW_KEYS; shapes as EnsembleSpectralSkill returns
+    them): host fp64 work on CPU copies, no device.  S: the members; k [NK]: the shell centres; level: the coherence of the cut-off;
+    timed: the number of timed steps, which turns the time sums into time means.  With Pm = xs_sum[:, :, 0] / S and likewise Xm, Dm,
+    (P_bar, X_bar, D_bar) = xs_mean_field and P_T = xs_target_power -> dict of float64 CPU tensors:
+      spec_corr = Xm / sqrt(Pm P_T), mean_field_corr = X_bar / sqrt(P_bar P_T), err_spec = Dm, mean_err_spec = D_bar,
+      spread_spec = Dm - D_bar (the identity mean|Z_m - T|^2 = mean|Z_m - Zbar|^2 + |Zbar - T|^2 shifted by the target, which stays
+      well-conditioned when the members track it; small negative values from rounding are returned as they are),
+      spread_skill = sqrt((S + 1) / S spread_spec / D_bar) (near 1 for a calibrated ensemble: its square has the expectation
+      (S - 1) / S there, spread_spec being the population variance; NaN where its argument is negative),
+      power_ratio = Pm / P_T, rel_err = Dm / P_T (2 for a decorrelated member of the right energy)            all [N, Tk, NK]
+      time_* of all of these [N, NK], from the time sums over `timed`
+      time_member_corr [N, S, NK] and its mean and population std over the members time_corr_mean, time_corr_std [N, NK]
+      cutoff_k [N, S + 1] (the mean field last): over the shells s >= 1 with a finite time correlation the first with corr < level,
+      linearly interpolated in corr between the finite shell before it and itself, k[s] when it is the first, inf when there is
+      none; cutoff_len = 2 pi / cutoff_k; cutoff_k_mean, cutoff_k_std [N] over the members, ignoring inf (NaN when all are inf)
+      xs_k [NK].
+    A ratio with a zero denominator is NaN (the empty shells of a stretched grid)."""
+    f64 = lambda v: torch.as_tensor(v).detach().cpu().to(torch.float64)          # noqa: E731
+    PT, sm, bar, tm, tT, tb = (f64(v) for v in (xs_target_power, xs_sum, xs_mean_field, xs_time_member, xs_time_target, xs_time_mean_field))
+    k = f64(k).reshape(-1)
+    S, Tn, NK = int(S), int(timed), k.numel()
+    if S < 1 or Tn < 1:
+        raise ValueError("xspec_outputs needs S >= 1 members and timed >= 1 steps, got %d and %d" % (S, Tn))
+    if isinstance(level, bool) or not isinstance(level, numbers.Real) or not 0.0 < float(level) < 1.0:
+        raise ValueError("level is a coherence in (0, 1), got %r" % (level,))
+    if PT.dim() != 3 or PT.shape[2] != NK:
+        raise ValueError("xs_target_power is [N, Tk, %d], got %s" % (NK, tuple(PT.shape)))
+    N, Tk = PT.shape[:2]
+    for name, v, shp in (("xs_sum", sm, (N, Tk, 3, NK)), ("xs_mean_field", bar, (N, Tk, 3, NK)), ("xs_time_member", tm, (N, S, 3, NK)),
+                         ("xs_time_target", tT, (N, NK)), ("xs_time_mean_field", tb, (N, 3, NK))):
+        if tuple(v.shape) != shp:
+            raise ValueError("%s is %s, got %s" % (name, list(shp), tuple(v.shape)))
+    o = _xs_forms(sm[:, :, 0] / S, sm[:, :, 1] / S, sm[:, :, 2] / S, bar[:, :, 0], bar[:, :, 1], bar[:, :, 2], PT, S, "")
+    ms = tm.sum(1)                                                               # [N, 3, NK]: the members in member order
+    o.update(_xs_forms(ms[:, 0] / S / Tn, ms[:, 1] / S / Tn, ms[:, 2] / S / Tn, tb[:, 0] / Tn, tb[:, 1] / Tn, tb[:, 2] / Tn, tT / Tn, S,
+                       "time_"))
+    mc = _xs_ratio(tm[:, :, 1], torch.sqrt(tm[:, :, 0] * tT.unsqueeze(1)))       # (the 1 / Tn of numerator and denominator cancel)
+    o["time_member_corr"] = mc
+    o["time_corr_mean"] = mc.mean(1)
+    o["time_corr_std"] = mc.std(1, unbiased=False)
+    bc = _xs_ratio(tb[:, 1], torch.sqrt(tb[:, 0] * tT))
+    cut = _xs_cutoff(torch.cat((mc, bc.unsqueeze(1)), 1), k, float(level))
+    o["cutoff_k"] = cut
+    o["cutoff_len"] = 2.0 * math.pi / cut
+    mem = cut[:, :S]
+    fin = torch.isfinite(mem)
+    cnt = fin.sum(1).to(torch.float64)
+    mean = _xs_ratio(torch.where(fin, mem, torch.zeros_like(mem)).sum(1), cnt)
+    o["cutoff_k_mean"] = mean
+    o["cutoff_k_std"] = torch.sqrt(_xs_ratio(torch.where(fin, (mem - mean.unsqueeze(1)) ** 2, torch.zeros_like(mem)).sum(1), cnt))
+    o["xs_k"] = k
+    return o
+
+
+class EnsembleSpectralSkill(EnsembleFeed):
+    """On-device spectral skill of sampled roll-outs of B cases against the target (tmg_ens_xspec_prep / tmg_spec_rows /
+    tmg_ens_xspec_cols / tmg_ens_xspec_accum): down to which scale does a member reproduce the target field itself, and from which
+    scale on is it only statistically plausible.  Rows are the members m, the target T and the ensemble-mean field bar; per case and
+    kept step
+      f_c = u[b, c] (out_std[c] y_c + out_mu[c]) - M_c, c = 0, 1     M: the centre plane [B, 2, H, W] in physical units (fp32, one
+                                                                     separate rounding); center=None: nothing is subtracted.  The
+                                                                     mean flow is trivially coherent; the question is about the
+                                                                     fluctuations
+      z = g (f_0 + i f_1), Z = fft2(z)                               g: the separable periodic Hann window over its RMS, or 1 for
+                                                                     window=None; the dense DFT of EnsembleSpectrum on the fp32
+                                                                     matrix pipe, H and W multiples of 16 up to 512
+      P = sc |Z|^2, X = sc Re(conj(Z) Z_T), D = sc |Z - Z_T|^2       sc = 0.5 / (H W)^2, D from the differences (P + P_T - 2 X
+                                                                     cancels exactly where the members are good)
+    summed over the shells of spectrum_bins(H, W, dx, dy); the shells are symmetric under k -> -k, so the shell sum of X is the
+    vector co-spectrum Re sum(conj(U_m) U_T + conj(V_m) V_T).  fbar = (sum_m f_m) / S, the members added in member order, goes
+    through the same transform as one more image per case.
+
+    Feeding protocol of EnsembleFeed: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
+    chunks before the next step's; every chunk comes with the step's normalised target [B, C, H, W], which is transformed at m0 = 0.
+    Raw outputs (device tensors, fp32; every sum in a fixed order, so they are bitwise equal for every chunking):
+      xs_target_power [B, Tk, NK]      P_T
+      xs_sum [B, Tk, 3, NK]            sum_m (P, X, D) in member order
+      xs_mean_field [B, Tk, 3, NK]     (P_bar, X_bar, D_bar)
+      xs_time_member [B, S, 3, NK], xs_time_target [B, NK], xs_time_mean_field [B, 3, NK]
+                                       the sums over the steps folded with time=True, in step order (finalize())
+    finalize() adds what xspec_outputs derives from them on the host in fp64 (float64 CPU tensors): spec_corr, mean_field_corr,
+    err_spec, mean_err_spec, spread_spec, spread_skill, power_ratio, rel_err and their time_ forms, time_member_corr, time_corr_mean,
+    time_corr_std, cutoff_k, cutoff_len, cutoff_k_mean, cutoff_k_std, xs_k.
+
+    Not supported: a pressure or scalar coherence; quadrature and phase spectra (the imaginary part does not reduce to a phase under
+    the shells' symmetry); per-member per-step outputs; coherence with the low-fidelity input, which lives on a different grid; pixel
+    boxes; fields that are not multiples of 16; more than 1024 members; non-finite members (the outputs of an affected step are
+    unspecified; there is no data-dependent addressing, so nothing can fault)."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, grid=(1.0, 1.0), window="hann", center=None,
+                 level=0.5):
+        noun = "spectral skill"
+        grid, bins, k = xspec_args(C, Hh, Ww, grid, window, level)
+        _ens_members(noun, members)
+        if int(B) < 1 or int(steps) < 1:
+            raise ValueError("%s needs B >= 1 cases and steps >= 1, got %d and %d" % (noun, int(B), int(steps)))
+        sd, mu = _ens_tables(2, "the fields are un-normalised with it", out_std, out_mu)
+        if u is not None:
+            u = torch.as_tensor(u, dtype=torch.float32).detach().cpu()
+            if u.numel() % int(B) or u.numel() // int(B) < 2:
+                raise ValueError("u needs at least 2 entries per case")
+            u = _ens_u(u.reshape(int(B), -1)[:, :2].contiguous(), int(B), 2, "the fields are scaled with it")
+        if isinstance(center, str):
+            raise ValueError("center is a plane [B, >= 2, H, W] or None (the target's time mean is utils.modelPredSpectralSkill's), got %r" % (center,))
+        if center is not None:
+            center = torch.as_tensor(center).detach()
+            if center.dim() != 4 or center.shape[0] != int(B) or center.shape[1] < 2 or tuple(center.shape[2:]) != (int(Hh), int(Ww)):
+                raise ValueError("center is a plane [B, >= 2, H, W] in physical units, got %s" % (tuple(center.shape),))
+            center = center[:, :2].to(torch.float32)
+            if not bool(torch.isfinite(center).all()):
+                raise ValueError("center must be finite")
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, C, Hh, Ww, steps)
+        self.grid, self.window, self.level = grid, window, float(level)
+        self.k, self.bins, self.NK = k, bins, k.numel()
+        NK = self.NK
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.mu, self.sd = mu.to(dev).contiguous(), sd.to(dev).contiguous()
+        self.u = None if u is None else u.to(dev).contiguous()
+        self.cen = None if center is None else center.to(dev).contiguous()
+        # the row pass runs on the field the prep kernel has formed: unit tables, no scale
+        self.one, self.zero = torch.ones(2, **f32), torch.zeros(2, **f32)
+        perm, offs = _spectrum_lists(bins, NK)
+        self.perm, self.offs = perm.to(dev), offs.to(dev)
+        self.ft_w = _spectrum_operand(self.W, window).to(dev)
+        self.ft_h = self.ft_w if self.H == self.W else _spectrum_operand(self.H, window).to(dev)
+        self.plan = H.ens_xspec_plan(1, self.B, self.H, self.W, NK)
+        QT = self.W // 16
+        self.fsum = torch.empty((self.B, self.H, self.W, 2), **f32)
+        self.zt = torch.empty((2, self.B, self.H, self.W), **f32)
+        self.part_t = torch.empty((self.B, QT, NK), **f32)
+        self.part_b = torch.empty((self.B, QT, 3, NK), **f32)
+        self.step_state = torch.empty((self.B, 3, NK), **f32)
+        self.out = {"xs_target_power": torch.empty((self.B, self.Tk, NK), **f32), "xs_sum": torch.empty((self.B, self.Tk, 3, NK), **f32),
+                    "xs_mean_field": torch.empty((self.B, self.Tk, 3, NK), **f32),
+                    "xs_time_member": torch.empty((self.B, self.S, 3, NK), **f32), "xs_time_target": torch.empty((self.B, NK), **f32),
+                    "xs_time_mean_field": torch.empty((self.B, 3, NK), **f32)}
+        self._f = self._yw = self._part = None       # workspace of the largest chunk: the field, its row transform, the tiles' sums
+
+    def _transform(self, n, cross, part):
+        """Rows and columns of the n images at the front of the field buffer."""
+        f = self._f[:n]
+        H.spec_rows(f, None, self.zero, self.one, self.ft_w, self._yw, n // self.B)
+        H.ens_xspec_cols(self.ft_h, self._yw, self.perm, self.offs, self.zt, part, n, self.B, self.H, self.W, self.NK, cross)
+
+    def add(self, y, m0, target, time=True):
+        """Fold the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
+        channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride rule, transformed
+        at m0 = 0.  The step's last chunk also transforms the ensemble-mean field and writes the step's outputs."""
+        yn, tn, k, t_before, last = self.open_chunk(y, m0, time, target, required=True)
+        _on_device(yn, tn)
+        kB = k * self.B
+        QT = self.W // 16
+        dev = self.fsum.device
+        if self._f is None or self._f.shape[0] < kB:
+            self._f = torch.empty((kB, self.H, self.W, 2), device=dev, dtype=torch.float32)
+            self._yw = torch.empty(2 * kB * self.H * self.W, device=dev, dtype=torch.float32)
+            self._part = torch.empty(kB * QT * 3 * self.NK, device=dev, dtype=torch.float32)
+        if m0 == 0:
+            H.ens_xspec_prep(tn, self.u, self.mu, self.sd, self.cen, self._f, self.fsum, 1, 0, self.S)
+            self._transform(self.B, False, self.part_t)
+        H.ens_xspec_prep(yn, self.u, self.mu, self.sd, self.cen, self._f, self.fsum, k, 1 if m0 == 0 else 2, self.S)
+        self._transform(kB, True, self._part)
+        if last:
+            H.ens_xspec_prep(None, None, None, None, None, self._f, self.fsum, 1, 3, self.S)
+            self._transform(self.B, True, self.part_b)
+        o = self.out
+        H.ens_xspec_accum(self._part, self.part_t, self.part_b, self.step_state, o["xs_target_power"], o["xs_sum"], o["xs_mean_field"],
+                          o["xs_time_member"], o["xs_time_target"], o["xs_time_mean_field"], k, QT, self._step, self._n, m0, t_before,
+                          (1 if time else 0) | (2 if last else 0))
+        self.close_chunk(m0, k, time, last)
+
+    def finalize(self):
+        """-> dict of the raw sums (device) and of xspec_outputs' derived outputs (float64, CPU); the time forms cover the steps
+        folded with time=True."""
+        T = self.finalize_guard()
+        o = dict(self.out)
+        o.update(xspec_outputs(*[self.out[n] for n in XSPEC_RAW_KEYS], self.S, self.k, self.level, T))
+        return o
+
+
 def _tspec_window(Tn, window):
     """fp64 [Tn]: the periodic Hann window w_n = 0.5 - 0.5 cos(2 pi n / Tn) over sqrt(mean(w^2)), or ones."""
     n = torch.arange(Tn, dtype=torch.float64)

@@ -339,6 +339,73 @@ def modelPredSpectra(args, model, testing_loader, log, samples=1, stride=1, tmax
     return _ensembleStats("modelPredSpectra", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, True, [acc])
 
 
+def _xspec_factory(args, stride, t_start, window, center, level):
+    """The make of modelPredSpectralSkill's record.  center "target": the target's time mean over the kept steps from t_start on,
+    formed in fp64 on the physical target series and rounded once (as _pdf_factory); an array [N, >= 2, H, W] is cut to the
+    mini-batch; None: no centre."""
+    def make(mb, members, steps):
+        import tmg_ops as ops
+        cen = center
+        if isinstance(cen, str):
+            cen = mb.tgt[:, t_start * stride:(steps - 1) * stride + 1:stride].double().mean(1).float()
+        elif cen is not None:
+            cen = torch.as_tensor(cen)[mb.case0:mb.case0 + mb.B]
+        return ops.EnsembleSpectralSkill(members, mb.B, mb.C, mb.H, mb.W, steps, mb.dev, mb.out_mu, mb.out_std, u=mb.u,
+                                         grid=(args.dx, args.dy), window=window, center=cen, level=level)
+    return make
+
+
+def modelPredSpectralSkill(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, window="hann",
+                           center="target", level=0.5):
+    """modelPredStats plus the spectral skill of the velocity field (channels 0, 1) against the target on the grid (args.dx along W,
+    args.dy along H), still without forming modelPred's [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleSpectralSkill).  TM-Glow is
+    a conditional generator: the low-fidelity input pins the large scales of a member, the small scales are invented.  The question
+    here: down to which scale does a member reproduce the target field itself, and from which scale on is it only statistically
+    plausible?  modelPredSpectra's E(k) holds magnitudes only (a member whose small scales hold the right energy in the wrong places
+    has a perfect E(k)); crps, rank_hist, energy_score, fss and the field ranks verify in physical space with all scales mixed; and
+    spread against error is reported per scale nowhere else.  The target of kept step j is series step j * stride; a series that is
+    too short raises.  Same roll-outs as modelPredStats: under the same host RNG state the keys both return are identical.
+
+    Per case, kept step and row (member m, target T, ensemble-mean field bar = the mean of the members' fields):
+    f_c = yh_c - M_c (c = 0, 1; center "target": M is the target's time mean over the kept steps from t_start on, an array
+    [N, >= 2, H, W]: that plane, None: nothing is subtracted; the mean flow is trivially coherent, the question is about the
+    fluctuations), z = g (f_0 + i f_1) with g the periodic Hann window over its RMS (window=None: 1), Z = fft2(z), and per mode
+    P = sc |Z|^2, X = sc Re(conj(Z) Z_T), D = sc |Z - Z_T|^2 with sc = 0.5 / (H W)^2, summed over the shells of
+    tmg_ops.spectrum_bins.  H and W must be multiples of 16 up to 512.
+
+    Returns modelPredStats' dict plus (CPU tensors; S = samples, kept steps t_start..Tk-1 are the timed ones):
+      xs_target_power [N, Tk, NK], xs_sum, xs_mean_field [N, Tk, 3, NK], xs_time_member [N, S, 3, NK], xs_time_target [N, NK],
+      xs_time_mean_field [N, 3, NK]      float32: the raw shell sums of P_T, of sum_m (P, X, D), of (P_bar, X_bar, D_bar), and their
+                                         sums over the timed steps per member, for the target and for the mean field
+      spec_corr, mean_field_corr [N, Tk, NK]
+                                         float64 from here on: the spectral coherence with the target of the members (pooled:
+                                         Xm / sqrt(Pm P_T)) and of the ensemble-mean field
+      err_spec, mean_err_spec, spread_spec
+                                         the members' mean error spectrum Dm, the mean field's D_bar, and Dm - D_bar
+      spread_skill                       sqrt((S + 1) / S spread_spec / D_bar): 1 for a calibrated ensemble, per shell
+      power_ratio, rel_err               Pm / P_T and Dm / P_T (2 for a decorrelated member of the right energy)
+      time_spec_corr .. time_rel_err [N, NK]
+                                         the same from the sums over the timed steps
+      time_member_corr [N, S, NK], time_corr_mean, time_corr_std [N, NK]
+                                         each member's coherence over the timed steps, its mean and population std over the members
+      cutoff_k [N, S + 1], cutoff_len    the effective resolution: the wavenumber at which the time coherence first falls under
+                                         `level` (members, the mean field last; interpolated between shells, inf when it never
+                                         does), and 2 pi over it
+      cutoff_k_mean, cutoff_k_std [N]    over the members, ignoring inf
+      xs_k [NK]                          the shell centres s 2 pi / max(W dx, H dy).
+    A ratio with a zero denominator is NaN (the empty shells of a stretched grid).
+
+    Not supported: a pressure or scalar coherence; quadrature and phase spectra; per-member per-step outputs; coherence with the
+    low-fidelity input, which lives on a different grid; pixel boxes; fields that are not multiples of 16; non-finite members (the
+    outputs of an affected step are unspecified)."""
+    import tmg_ops as ops
+    if isinstance(center, str) and center != "target":
+        raise ValueError("center is 'target', None or a plane [N, >= 2, H, W], got %r" % (center,))
+    ops.xspec_args(3, 16, 16, (getattr(args, "dx", 1.0), getattr(args, "dy", 1.0)) if args is not None else (1.0, 1.0), window, level)
+    acc = _Acc(_xspec_factory(args, stride, t_start, window, center, level), target=True, meta=("xs_k",))
+    return _ensembleStats("modelPredSpectralSkill", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
+
+
 def modelPredScores(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64):
     """modelPredStats plus the ensemble's calibration scores against the target the loader carries, still without forming modelPred's
     [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleScores).  The target of kept step j is series step j * stride.  Same roll-outs
