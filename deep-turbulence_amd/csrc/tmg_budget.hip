@@ -3,11 +3,10 @@
 // time sums of products of every row's own fluctuations.  Rows are the S members plus the target as row S.
 //   ens_budget_accum_kernel<V>   one thread per pixel (V = 0) or per four consecutive pixels of one field row (V = 1) of a case; it
 //                                loops over the chunk's k members and adds 14 quantities to the member's own planes of
-//                                raw [S + 1][B][14][HW].  THE ORDER, stated once: with d_c = fl(a_c fl(y_c - m_c)), c = 0, 1, 2 (u, v, p;
-//                                one subtraction, one multiplication), f = 0 outside the field and
-//                                  Sx f = fl(fl(fl(f[h-1,w+1] - f[h-1,w-1]) + fl(2 fl(f[h,w+1] - f[h,w-1]))) + fl(f[h+1,w+1] - f[h+1,w-1]))
-//                                  Sy f = the same with the roles of h and w exchanged (row h + 1 minus row h - 1)
-//                                the planes are  0..2: d_u, d_v, d_p;  3..5: fl(d_u d_u), fl(d_u d_v), fl(d_v d_v);
+//                                raw [S + 1][B][14][HW].  The order: with d_c = fl(a_c fl(y_c - m_c)), c = 0, 1, 2 (u, v, p; one
+//                                subtraction, one multiplication), d = 0 outside the field, and Sx, Sy the tmg_sobel3 (tmg_field.h) of
+//                                the three column / row differences of the fluctuation d_c, the planes are
+//                                  0..2: d_u, d_v, d_p;  3..5: fl(d_u d_u), fl(d_u d_v), fl(d_v d_v);
 //                                  6..9: fl(fl(d_u d_u) d_u), fl(fl(d_u d_u) d_v), fl(fl(d_u d_v) d_v), fl(fl(d_v d_v) d_v);
 //                                  10, 11: fl(d_p d_u), fl(d_p d_v);
 //                                  12: fl(fl(Sx d_u Sx d_u) + fl(Sx d_v Sx d_v));  13: the same with Sy
@@ -28,7 +27,7 @@
 //                                central moments at the pixel and at its eight neighbours straight from raw (shift formulas, T the
 //                                timed steps, D_c = raw_c / T), the seven terms, and a Welford mean / M2 over the members in member
 //                                order.  No plane of intermediates is written.
-#include "tmg_common.h"
+#include "tmg_field.h"
 #include "tmglow_hip.h"
 #include "tmglow_hip_budget.h"
 
@@ -125,10 +124,10 @@ __global__ __launch_bounds__(BUDGET_THREADS) void ens_budget_accum_kernel(const 
             // window column j + 1 is the pixel's own
             const float xu0 = du[0][j + 2] - du[0][j], xu1 = du[1][j + 2] - du[1][j], xu2 = du[2][j + 2] - du[2][j];
             const float xv0 = dv[0][j + 2] - dv[0][j], xv1 = dv[1][j + 2] - dv[1][j], xv2 = dv[2][j + 2] - dv[2][j];
-            const float sxu = (xu0 + 2.f * xu1) + xu2, sxv = (xv0 + 2.f * xv1) + xv2;
+            const float sxu = tmg_sobel3(xu0, xu1, xu2), sxv = tmg_sobel3(xv0, xv1, xv2);
             const float yu0 = du[2][j] - du[0][j], yu1 = du[2][j + 1] - du[0][j + 1], yu2 = du[2][j + 2] - du[0][j + 2];
             const float yv0 = dv[2][j] - dv[0][j], yv1 = dv[2][j + 1] - dv[0][j + 1], yv2 = dv[2][j + 2] - dv[0][j + 2];
-            const float syu = (yu0 + 2.f * yu1) + yu2, syv = (yv0 + 2.f * yv1) + yv2;
+            const float syu = tmg_sobel3(yu0, yu1, yu2), syv = tmg_sobel3(yv0, yv1, yv2);
             const float gxu = sxu * sxu, gxv = sxv * sxv, gyu = syu * syu, gyv = syv * syv;
             t[12][j] = gxu + gxv;
             t[13][j] = gyu + gyv;

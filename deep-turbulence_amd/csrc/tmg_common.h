@@ -39,7 +39,10 @@ struct TmgOSeg {
     int n;
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
+// The sum over the 64 lanes, in every lane: xor butterfly in DESCENDING order, 32 down to 1 (a fixed order: the same bits every time).
+// T: float, int or double.
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;

@@ -13,7 +13,7 @@
 //                             over the members
 // Bandwidth kernels: one thread owns one pixel of one case, every state array is planar ([..][HW], lanes on consecutive pixels),
 // so all state traffic is coalesced.  fp32 Welford (no E[y^2] - E[y]^2 cancellation), no atomics: bitwise reproducible.
-#include "tmg_common.h"
+#include "tmg_field.h"
 #include "tmglow_hip.h"
 
 #define ENS_MAXC 4
@@ -186,16 +186,8 @@ extern "C" int tmg_ens_time_finalize(const void* tmean, const void* tm2, void* t
 // waves load anyway, and one member's two channels of a 256 x 256 case (<= 1.1 MB at pixel stride 4) stay in L1 / L2 between the three
 // row passes.  The input is NHWC with a run-time pixel stride, so an LDS tile would be filled by the same strided loads and save
 // only the re-reads the caches already serve, at the price of a barrier per member; the kernel stays bound by its state planes.
-// One thread per pixel of a case, state planar, no atomics: bitwise reproducible.
-__device__ __forceinline__ float ens_unnorm(const float* __restrict__ yp, int c, float sc, float sd, float mu) {
-    // ens_accum_kernel's yh, bit for bit: one fma, then one multiply whose ROUNDED product is the value.  Contraction is off so that
-    // the multiply is never fused into a later subtraction (yh - mean would then see the unrounded product, and a member that is
-    // constant in time would leave a co-moment of rounding size instead of exactly 0).
-#pragma clang fp contract(off)
-    const float t = __builtin_fmaf(sd, yp[c], mu);
-    return sc * t;
-}
-
+// One thread per pixel of a case, state planar, no atomics: bitwise reproducible.  The physical values are tmg_unnorm_fma's, which
+// are ens_accum_kernel's yh bit for bit.
 __global__ __launch_bounds__(256) void ens_turb_accum_kernel(const float* __restrict__ y, int ps, const float* __restrict__ u,
                                                              const float* __restrict__ out_mu, const float* __restrict__ out_std,
                                                              const float* __restrict__ tmean, float* __restrict__ vmean,
@@ -218,27 +210,8 @@ __global__ __launch_bounds__(256) void ens_turb_accum_kernel(const float* __rest
     for (int j = 0; j < k; ++j) {
         const float* yp = y + ((size_t)(j * B + b) * hw + p) * ps;
         // d/dx v: columns w +- 1 of rows h - 1, h, h + 1 weighted 1, 2, 1; d/dy u: rows h +- 1 of columns w - 1, w, w + 1 weighted 1, 2, 1
-        float vx = 0.f, uy = 0.f;
-        if (rt) {
-            vx += 2.f * ens_unnorm(yp + ps, 1, sc1, sd1, mu1);
-            if (up) vx += ens_unnorm(yp + ps - rs, 1, sc1, sd1, mu1);
-            if (dn) vx += ens_unnorm(yp + ps + rs, 1, sc1, sd1, mu1);
-        }
-        if (lf) {
-            vx -= 2.f * ens_unnorm(yp - ps, 1, sc1, sd1, mu1);
-            if (up) vx -= ens_unnorm(yp - ps - rs, 1, sc1, sd1, mu1);
-            if (dn) vx -= ens_unnorm(yp - ps + rs, 1, sc1, sd1, mu1);
-        }
-        if (dn) {
-            uy += 2.f * ens_unnorm(yp + rs, 0, sc0, sd0, mu0);
-            if (lf) uy += ens_unnorm(yp + rs - ps, 0, sc0, sd0, mu0);
-            if (rt) uy += ens_unnorm(yp + rs + ps, 0, sc0, sd0, mu0);
-        }
-        if (up) {
-            uy -= 2.f * ens_unnorm(yp - rs, 0, sc0, sd0, mu0);
-            if (lf) uy -= ens_unnorm(yp - rs - ps, 0, sc0, sd0, mu0);
-            if (rt) uy -= ens_unnorm(yp - rs + ps, 0, sc0, sd0, mu0);
-        }
+        const float vx = tmg_sx<true>(yp, ps, rs, 1, sc1, sd1, mu1, up, dn, lf, rt);
+        const float uy = tmg_sy<true>(yp, ps, rs, 0, sc0, sd0, mu0, up, dn, lf, rt);
         const float vort = vx * rdx - uy * rdy;      // rdx = 1 / (8 dx), rdy = 1 / (8 dy)
         const float rn = 1.f / (float)(j + 1);
         const float d = vort - mean;
@@ -249,7 +222,7 @@ __global__ __launch_bounds__(256) void ens_turb_accum_kernel(const float* __rest
             float cq = 0.f, tw = 0.f, du = 0.f, dv = 0.f;   // first step: mean_v_new = v, the co-moment starts at 0
             if (t_before > 0) {
                 const size_t tb = ((size_t)(m0 + j) * B + b) * C * hw + p;   // channel 0 of the member's tmean planes
-                const float uu = ens_unnorm(yp, 0, sc0, sd0, mu0), vv = ens_unnorm(yp, 1, sc1, sd1, mu1);
+                const float uu = tmg_unnorm_fma(yp[0], sc0, sd0, mu0), vv = tmg_unnorm_fma(yp[1], sc1, sd1, mu1);
                 const float mv_old = tmean[tb + hw];
                 du = uu - tmean[tb];
                 dv = vv - (mv_old + (vv - mv_old) * tn);   // v - mean_v_new

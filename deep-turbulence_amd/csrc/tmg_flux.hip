@@ -1,15 +1,15 @@
 // The scale-to-scale energy flux and the sub-filter stresses of sampled roll-outs and of the target (tmg_ops.EnsembleFlux /
 // utils.modelPredFlux): the coarse-graining analysis with a box filter of width w pixels, tau_ij = bar(u_i u_j) - bar(u_i) bar(u_j) and
 // Pi = -tau_ij d bar(u_i) / dx_j at every instant, summed over the timed steps.  Rows are the S members plus the target as row S.
-//   ens_flux_accum_kernel   one block of 1024 threads (a pixel each) per tile of 32 x 32 pixels of one row of one case.  THE ORDER, stated once: with
+//   ens_flux_accum_kernel   one block of 1024 threads (a pixel each) per tile of 32 x 32 pixels of one row of one case.  The order: with
 //                           f_c = fl(a_c y_c), c = 0, 1 (u, v), r = w / 2, N = w^2, the box sums
 //                             Sg_u, Sg_v, Sg_uu, Sg_uv, Sg_vv  of  f_u, f_v, fl(f_u f_u), fl(f_u f_v), fl(f_v f_v)
 //                           are a row pass followed by a column pass, both from the centre outwards:
 //                             s_0 = g[0],  s_j = fl(fl(s_{j-1} + g[-j]) + g[+j]),  j = 1 .. r
 //                           (row pass: g along W; column pass: g the row sums, along H).  Then
 //                             Q_uu = fl(fl(N Sg_uu) - fl(Sg_u Sg_u)),  Q_uv = fl(fl(N Sg_uv) - fl(Sg_u Sg_v)),  Q_vv likewise     (N^2 tau)
-//                             Sx g = fl(fl(fl(g[h-1,w+1] - g[h-1,w-1]) + fl(2 fl(g[h,w+1] - g[h,w-1]))) + fl(g[h+1,w+1] - g[h+1,w-1]))
-//                             Sy g = the same with the roles of h and w exchanged (row h + 1 minus row h - 1), on the box sums
+//                             Sx, Sy = tmg_sobel3's combination (tmg_field.h, which says why it is written out here) of the three
+//                             column / row differences of the box sums Sg_u, Sg_v
 //                             A = fl(fl(Q_uu Sx Sg_u) + fl(Q_uv Sx Sg_v)),  B = fl(fl(Q_uv Sy Sg_u) + fl(Q_vv Sy Sg_v))
 //                             Pi_s = -fl(fl(A kx) + fl(B ky)),  kx = 1 / (8 dx N^3), ky = 1 / (8 dy N^3) (fp32 tables from the host)
 //                           and the planes of raw [S + 1][B][L][7][HW] are  0: A, 1: B, 2: fl(Pi_s Pi_s), 3: [Pi_s < 0], 4..6: Q_uu, Q_uv,
@@ -213,12 +213,6 @@ __global__ __launch_bounds__(FLUX_THREADS) void ens_flux_accum_kernel(const floa
     }
 }
 
-__device__ __forceinline__ double flux_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
-    return v;
-}
-
 // the outputs of tmg_ens_flux_terms, in the order of its table `outs`
 enum { FO_FLUX_MEAN, FO_FLUX_STD, FO_TARGET_FLUX, FO_TSTD_MEAN, FO_TARGET_TSTD, FO_BS_MEAN, FO_BS_STD, FO_TARGET_BS, FO_SGS_MEAN, FO_SGS_STD,
        FO_TARGET_SGS, FO_MEMBER_FLUX, FO_FLUX_CURVE, FO_SGS_CURVE, FO_N };
@@ -262,7 +256,7 @@ __global__ __launch_bounds__(FLUX_FIN_THREADS) void ens_flux_terms_kernel(const 
 #pragma unroll
             for (int i = 0; i < 6; ++i) v[i] = nanv;
         }
-        const double cp = flux_wave_sum(valid ? v[0] : 0.0), ce = flux_wave_sum(valid ? 0.5 * (v[3] + v[5]) : 0.0);
+        const double cp = wave_sum(valid ? v[0] : 0.0), ce = wave_sum(valid ? 0.5 * (v[3] + v[5]) : 0.0);
         if (lane == 0) {
             double* pp = part + ((((size_t)b * (S + 1) + row) * L + l) * 2) * NWv + wv;
             pp[0] = cp;

@@ -40,12 +40,6 @@ __device__ __forceinline__ void frank_count(float v, const float (&r)[FRANK_R], 
     }
 }
 
-__device__ __forceinline__ int frank_wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void ens_frank_step_kernel(const float* __restrict__ xs, int* __restrict__ ws, int* __restrict__ tout,
                                                              int S, int B, int HW, int C, int nblk, int t_before, int timed) {
 #pragma clang fp contract(off)
@@ -122,7 +116,7 @@ __global__ __launch_bounds__(256) void ens_frank_step_kernel(const float* __rest
             }
         }
 #pragma unroll
-        for (int k = 0; k < FRANK_NV; ++k) val[k] = frank_wave_sum(val[k]);
+        for (int k = 0; k < FRANK_NV; ++k) val[k] = wave_sum(val[k]);
         __syncthreads();                                                       // the previous held block's sums are read
 #pragma unroll
         for (int k = 0; k < FRANK_NV; ++k)

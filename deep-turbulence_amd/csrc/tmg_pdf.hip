@@ -22,7 +22,7 @@
 // at most one, and the correction is two reads.
 // The 3x3 neighbours are read from global memory: tmg_ensemble.hip explains why an LDS tile does not pay for NHWC input with a
 // run-time stride.
-#include "tmg_common.h"
+#include "tmg_field.h"
 #include "tmglow_hip.h"
 
 #define PDF_MAXC 4
@@ -84,47 +84,6 @@ extern "C" int tmg_ens_pdf_plan(const int64_t* dims, int64_t* plan) {
 
 // Everything below rounds every operation on its own: the numpy float32 mirror of the tests reproduces the derived fields bit for bit.
 #pragma clang fp contract(off)
-
-// the physical value of channel c at yp: t = fl(fl(sd x) + mu), v = fl(u t)
-__device__ __forceinline__ float pdf_unnorm(const float* __restrict__ yp, int c, float sc, float sd, float mu) {
-    float t = sd * yp[c];
-    t = t + mu;
-    return sc * t;
-}
-
-// d/dx of channel c (times 8 dx): right column first, then left, each in the order centre * 2, up, down; zero padding
-__device__ __forceinline__ float pdf_ddx(const float* __restrict__ yp, long long ps, long long rs, int c, float sc, float sd, float mu,
-                                         bool up, bool dn, bool lf, bool rt) {
-    float a = 0.f;
-    if (rt) {
-        a += 2.f * pdf_unnorm(yp + ps, c, sc, sd, mu);
-        if (up) a += pdf_unnorm(yp + ps - rs, c, sc, sd, mu);
-        if (dn) a += pdf_unnorm(yp + ps + rs, c, sc, sd, mu);
-    }
-    if (lf) {
-        a -= 2.f * pdf_unnorm(yp - ps, c, sc, sd, mu);
-        if (up) a -= pdf_unnorm(yp - ps - rs, c, sc, sd, mu);
-        if (dn) a -= pdf_unnorm(yp - ps + rs, c, sc, sd, mu);
-    }
-    return a;
-}
-
-// d/dy of channel c (times 8 dy): lower row first, then upper, each in the order centre * 2, left, right; zero padding
-__device__ __forceinline__ float pdf_ddy(const float* __restrict__ yp, long long ps, long long rs, int c, float sc, float sd, float mu,
-                                         bool up, bool dn, bool lf, bool rt) {
-    float a = 0.f;
-    if (dn) {
-        a += 2.f * pdf_unnorm(yp + rs, c, sc, sd, mu);
-        if (lf) a += pdf_unnorm(yp + rs - ps, c, sc, sd, mu);
-        if (rt) a += pdf_unnorm(yp + rs + ps, c, sc, sd, mu);
-    }
-    if (up) {
-        a -= 2.f * pdf_unnorm(yp - rs, c, sc, sd, mu);
-        if (lf) a -= pdf_unnorm(yp - rs - ps, c, sc, sd, mu);
-        if (rt) a -= pdf_unnorm(yp - rs + ps, c, sc, sd, mu);
-    }
-    return a;
-}
 
 // idx(d) = #{j in 0..n : d >= e[j]} for strictly increasing e[0..n] (LDS): a guess, corrected until e[g - 1] <= d < e[g]
 __device__ __forceinline__ int pdf_index(const float* e, int n, float scale, float d) {
@@ -204,15 +163,15 @@ __global__ __launch_bounds__(PDF_THREADS) void ens_pdf_count_kernel(
         for (int c = 0; c < PDF_MAXC; ++c) x[c] = c < C ? yp[c] : 0.f;
         float speed = 0.f, vort = 0.f, dvg = 0.f;
         if (DER) {
-            const float U = pdf_unnorm(yp, 0, sc0, sd0, mu0), V = pdf_unnorm(yp, 1, sc1, sd1, mu1);
+            const float U = tmg_unnorm_split(yp[0], sc0, sd0, mu0), V = tmg_unnorm_split(yp[1], sc1, sd1, mu1);
             const float uu = U * U, vv = V * V;
             speed = sqrtf(uu + vv);                                        // correctly rounded (hipcc's default for fp32 sqrt)
             if (sten) {
                 const bool up = h > 0, dn = h + 1 < Hh, lf = w > 0, rt = w + 1 < Ww;
-                const float vx = pdf_ddx(yp, ps, rs, 1, sc1, sd1, mu1, up, dn, lf, rt);
-                const float uy = pdf_ddy(yp, ps, rs, 0, sc0, sd0, mu0, up, dn, lf, rt);
-                const float ux = pdf_ddx(yp, ps, rs, 0, sc0, sd0, mu0, up, dn, lf, rt);
-                const float vy = pdf_ddy(yp, ps, rs, 1, sc1, sd1, mu1, up, dn, lf, rt);
+                const float vx = tmg_sx<false>(yp, ps, rs, 1, sc1, sd1, mu1, up, dn, lf, rt);
+                const float uy = tmg_sy<false>(yp, ps, rs, 0, sc0, sd0, mu0, up, dn, lf, rt);
+                const float ux = tmg_sx<false>(yp, ps, rs, 0, sc0, sd0, mu0, up, dn, lf, rt);
+                const float vy = tmg_sy<false>(yp, ps, rs, 1, sc1, sd1, mu1, up, dn, lf, rt);
                 const float t0 = vx * rdx, t1 = uy * rdy, t2 = ux * rdx, t3 = vy * rdy;
                 vort = t0 - t1;
                 dvg = t2 + t3;

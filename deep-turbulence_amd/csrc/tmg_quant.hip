@@ -16,10 +16,10 @@
 // slot.  The slots start as NaN: a rank that no member takes (possible only with non-finite members) shows.
 // All register arrays (r, rank, slot, count) are indexed by compile-time constants in fully unrolled loops: no scratch.
 //   qraw_j = x_(lo) + w_j (x_(hi) - x_(lo))           subtraction, product, addition: three rounded operations (contraction off)
-//   quant  = sc * fmaf(out_std, qraw_j, out_mu)       the un-normalisation as tspec_store_kernel writes it
+//   quant  = sc * fmaf(out_std, qraw_j, out_mu)       tmg_unnorm_fma (tmg_field.h)
 //   exceed = float(count) * float(1 / S)              one rounded product; every member is counted once, while it is held
 //   tquant: fp32 running mean in place, m += (quant - m) * (1 / (t_before + 1)); tbelow += (y < qraw_j); texceed += count
-#include "tmg_common.h"
+#include "tmg_field.h"
 #include "tmglow_hip.h"
 
 #define QUANT_MAXC 4
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void ens_quant_step_kernel(const float* __rest
             const float d = hi - lo;
             const float wd = a.w[j] * d;
             const float qraw = lo + wd;
-            const float v = sc * fmaf(sd, qraw, mu);
+            const float v = tmg_unnorm_fma(qraw, sc, sd, mu);
             const size_t lv = (size_t)j * C * hw;
             qp[lv] = v;
             if (timed) {

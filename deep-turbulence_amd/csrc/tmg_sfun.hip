@@ -85,6 +85,7 @@ static void sfun_slices(int64_t S, int64_t B, int64_t C, int64_t HW, int64_t L, 
     g.ws = per * g.P;
 }
 
+// (not tmg_common.h's wave_sum: this one adds in ASCENDING xor order, 1 up to 32, which gives other bits for floats)
 __device__ __forceinline__ float sfun_wave_sum(float v) {
 #pragma clang fp contract(off)
 #pragma unroll

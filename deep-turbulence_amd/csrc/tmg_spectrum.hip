@@ -10,15 +10,12 @@
 //   spec_accum_kernel     one thread per (case, shell): the partial spectra of a member summed in tile order, Welford over the chunk's
 //                         members, Chan's merge with the chunks before, per member the running time mean (flags as ens_accum_kernel)
 //   spec_finalize_kernel  once at the end: mean and population std over the members of their time means
-// Operand matrix of an N-point transform: T[n][m] = w[n] exp(-2 pi i ((n m) mod N) / N), planes (re, im) of [n][m] floats, built on the
-// host in fp64 and rounded once.  The same layout is the row pass's B operand (k = n = x, column = m = q) and the column pass's A
-// operand (k = n = y, row = m = p): in both a lane reads 16 consecutive floats of a row of T, and T (<= 2 MB) stays in L2.
-// MFMA lane maps (16x16x4 f32): A[i = l & 15][k = l >> 4], B[k = l >> 4][j = l & 15], C/D column l & 15, rows 4 (l >> 4) + 0..3.
+// The operand matrices, the MFMA lane maps, the side limit and the column pass's product: tmg_dft.h.
 // No atomics anywhere (an LDS float atomic from four waves lands in arrival order): the same inputs give the same bits.
-#include "tmg_common.h"
+#include "tmg_dft.h"
+#include "tmg_field.h"
 #include "tmglow_hip.h"
 
-#define SPEC_MAXN 512
 #define SPEC_MAXNK 8192
 
 __global__ __launch_bounds__(256) void spec_rows_kernel(const float* __restrict__ y, int ps, const float* __restrict__ u,
@@ -36,8 +33,8 @@ __global__ __launch_bounds__(256) void spec_rows_kernel(const float* __restrict_
     for (int i = threadIdx.x; i < 16 * Ww; i += 256) {
         const int r = i / Ww, x = i - r * Ww;
         const float* q = yp + (size_t)i * ps;
-        lds[r * LS + x] = sc0 * fmaf(sd0, q[0], mu0);               // yh as EnsembleStats forms it
-        lds[(16 + r) * LS + x] = sc1 * fmaf(sd1, q[1], mu1);
+        lds[r * LS + x] = tmg_unnorm_fma(q[0], sc0, sd0, mu0);
+        lds[(16 + r) * LS + x] = tmg_unnorm_fma(q[1], sc1, sd1, mu1);
     }
     __syncthreads();
     const int wave = threadIdx.x >> 6, l = threadIdx.x & 63, l16 = l & 15, lq = l >> 4;
@@ -72,7 +69,7 @@ extern "C" int tmg_spec_rows(const void* y, const int64_t* y_d, const void* u, c
                              void* yw, const int64_t* dims, hipStream_t st) {
     const int64_t k = dims[0], B = dims[1], Hh = dims[2], Ww = dims[3], C = dims[4], yw_floats = dims[5];
     if (k < 1 || B < 1 || C < 2 || C > 4) return -1;
-    if (Hh < 16 || Hh > SPEC_MAXN || (Hh & 15) || Ww < 16 || Ww > SPEC_MAXN || (Ww & 15)) return -1;
+    if (!tmg_dft_side_ok(Hh) || !tmg_dft_side_ok(Ww)) return -1;
     if (y_d[0] < C || y_d[1] < 0 || y_d[1] + C > y_d[0]) return -1;
     if (k * B > 65535 || (k * B) * Hh * Ww * y_d[0] >= (1ll << 40)) return -2;
     if (!y || !out_mu || !out_std || !ft || !yw) return -3;
@@ -111,7 +108,7 @@ __global__ __launch_bounds__(256) void spec_cols_kernel(const float* __restrict_
         const float* fr = ft + (size_t)lq * Hh + pt * 16 + l16;
         const float* fi = fr + th;
         f32x4 zr = {0.f, 0.f, 0.f, 0.f}, zi = {0.f, 0.f, 0.f, 0.f};
-        for (int k0 = 0; k0 < Hh; k0 += 16)        // H is a multiple of 16
+        for (int k0 = 0; k0 < Hh; k0 += 16)        // H is a multiple of 16; the column product of tmg_dft.h
 #pragma unroll
         for (int k = k0; k < k0 + 16; k += 4) {
             const float a_r = fr[(size_t)k * Hh], a_i = fi[(size_t)k * Hh];
@@ -144,7 +141,7 @@ extern "C" int tmg_spec_cols(const void* ft, const void* yw, const void* perm, c
                              const float* fl, hipStream_t st) {
     const int64_t n = dims[0], Hh = dims[1], Ww = dims[2], NK = dims[3], yw_floats = dims[4], part_floats = dims[5];
     if (n < 1 || NK < 1) return -1;
-    if (Hh < 16 || Hh > SPEC_MAXN || (Hh & 15) || Ww < 16 || Ww > SPEC_MAXN || (Ww & 15)) return -1;
+    if (!tmg_dft_side_ok(Hh) || !tmg_dft_side_ok(Ww)) return -1;
     if (!(fl[0] > 0.f) || !(fl[0] <= 3.0e38f)) return -1;
     if (n > 65535 || NK > SPEC_MAXNK) return -2;
     if (!ft || !yw || !perm || !offs || !part) return -3;
@@ -204,7 +201,7 @@ extern "C" int tmg_spec_accum(const void* part, void* smean, void* sm2, void* tm
                               hipStream_t st) {
     const int64_t k = dims[0], B = dims[1], NK = dims[2], QT = dims[3], n_before = dims[4], m0 = dims[5], t_before = dims[6],
                   flags = dims[7], ocs = dims[8];
-    if (k < 1 || B < 1 || NK < 1 || QT < 1 || QT > SPEC_MAXN / 16 || n_before < 0 || m0 < 0 || t_before < 0) return -1;
+    if (k < 1 || B < 1 || NK < 1 || QT < 1 || QT > TMG_DFT_MAXN / 16 || n_before < 0 || m0 < 0 || t_before < 0) return -1;
     if ((flags & 2) && ocs < NK) return -1;
     if (k * B > 65535 || B > 65535 || NK > SPEC_MAXNK || m0 + k > (1ll << 30)) return -2;
     if (!part) return -3;

@@ -1,7 +1,7 @@
 // Spectral POD of sampled roll-outs (tmg_ops.EnsembleSpod / utils.modelPredSpod): the members stand where Welch's blocks stand.  The
 // operand is tmg_tspec_block's accumulator acc [2 NF + 1][R][B][C][HW] over R = S + 1 rows (the S members, then the target): per row m,
-// bin k, channel c and pixel p the Fourier coefficient of the windowed series, formed exactly as tspec_finalize_kernel forms it
-// (no contraction):
+// bin k, channel c and pixel p the Fourier coefficient of the windowed series, tmg_fourier_coef of tmg_dft.h (which is also
+// tspec_finalize_kernel's):
 //   xbar = acc[2 NF] * fl(1 / Tn),  Re X_m = acc[k] - xbar G_re,  Im X_m = acc[NF + k] - xbar G_im
 //   spod_csd_kernel<DIAG>   the Gram blocks of tmg_symgram.h over the planes (case, bin), the walk over this file's rows: the real Gram
 //                           matrix of the 2 R rows Z = [Re X_0 .. Re X_{R-1}; Im X_0 .. Im X_{R-1}] over the Cg HW elements of the
@@ -26,6 +26,7 @@
 // tiles); step qs contracts q = 4 qs .. 4 qs + 3, lane group lq holding q = 4 qs + lq: first the SP / 4 steps of the real parts, then
 // those of the imaginary parts, the row pointers advanced by one constant per step.  Every output element is one fmaf chain in q order.
 // No float atomics anywhere: the same inputs give the same bits.
+#include "tmg_dft.h"
 #include "tmg_symgram.h"
 #include "tmglow_hip.h"
 #include "tmglow_hip_spod.h"
@@ -68,15 +69,15 @@ __device__ __forceinline__ void spod_frag(float (&f)[16], const float* __restric
         for (int q = 0; q < 4; ++q) {
             const float4 v = *reinterpret_cast<const float4*>(xrow + p0 + 4 * q);
             const float4 t = *reinterpret_cast<const float4*>(srow + p0 + 4 * q);
-            f[4 * q] = v.x - (t.x * inv_t) * g;
-            f[4 * q + 1] = v.y - (t.y * inv_t) * g;
-            f[4 * q + 2] = v.z - (t.z * inv_t) * g;
-            f[4 * q + 3] = v.w - (t.w * inv_t) * g;
+            f[4 * q] = tmg_fourier_coef(v.x, t.x, inv_t, g);
+            f[4 * q + 1] = tmg_fourier_coef(v.y, t.y, inv_t, g);
+            f[4 * q + 2] = tmg_fourier_coef(v.z, t.z, inv_t, g);
+            f[4 * q + 3] = tmg_fourier_coef(v.w, t.w, inv_t, g);
         }
     } else {
 #pragma unroll
         for (int s = 0; s < 16; ++s)
-            if (p0 + s < HW) f[s] = xrow[p0 + s] - (srow[p0 + s] * inv_t) * g;
+            if (p0 + s < HW) f[s] = tmg_fourier_coef(xrow[p0 + s], srow[p0 + s], inv_t, g);
     }
 }
 
@@ -212,7 +213,7 @@ __global__ __launch_bounds__(256) void spod_modes_kernel(const float* __restrict
             const float a = *wrow;
             float bv[4];
 #pragma unroll
-            for (int ct = 0; ct < 4; ++ct) bv[ct] = (q < S && pv[ct]) ? xp[16 * ct] - (sp[16 * ct] * inv_t) * g : 0.f;
+            for (int ct = 0; ct < 4; ++ct) bv[ct] = (q < S && pv[ct]) ? tmg_fourier_coef(xp[16 * ct], sp[16 * ct], inv_t, g) : 0.f;
 #pragma unroll
             for (int ct = 0; ct < 4; ++ct) d[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv[ct], d[ct], 0, 0, 0);
             wrow += 4;

@@ -16,12 +16,13 @@
 //   tspec_finalize_kernel  one thread per (case, bin, channel, pixel): per member X_k = (re_k, im_k) - xbar G_k with the host-built
 //                          G_k = sum_n g_n exp(-2 pi i k n / Tn), P_k = (c_k / Tn^2) |X_k|^2, Welford over the members in order
 // The operand tm [Tn][RP] (RP = R rounded up to 16, the padding columns zero) is built on the host in fp64 with the argument reduced
-// in integers, (k n) mod Tn, and rounded once.  MFMA lane maps (16x16x4 f32, as tmg_spectrum.hip): A[i = l & 15][k = l >> 4],
+// in integers, (k n) mod Tn, and rounded once.  MFMA lane maps (16x16x4 f32, as tmg_dft.h): A[i = l & 15][k = l >> 4],
 // B[k = l >> 4][j = l & 15], C/D column l & 15, rows 4 (l >> 4) + 0..3: the D columns are consecutive elements (pixels), so every
 // accumulator row is read and written in 64-byte runs.  An MFMA is a k-ordered fmaf chain onto its C input: acc after a block is the
 // chain over the block's steps in order, started from acc before it.
 // No atomics anywhere: the same inputs give the same bits.
-#include "tmg_common.h"
+#include "tmg_dft.h"
+#include "tmg_field.h"
 #include "tmglow_hip.h"
 
 #define TSPEC_MAXC 4
@@ -38,7 +39,10 @@ __global__ __launch_bounds__(256) void tspec_store_kernel(const float* __restric
     float* xp = ring + ((size_t)(m0 + j) * B + b) * C * hw + p;
 #pragma unroll
     for (int c = 0; c < TSPEC_MAXC; ++c)
-        if (c < C) xp[(size_t)c * hw] = (u ? u[b * C + c] : 1.f) * fmaf(out_std[c], yp[c], out_mu[c]);   // yh as spec_rows_kernel forms it
+        if (c < C) {
+            const float sc = u ? u[b * C + c] : 1.f;
+            xp[(size_t)c * hw] = tmg_unnorm_fma(yp[c], sc, out_std[c], out_mu[c]);
+        }
 }
 
 extern "C" int tmg_tspec_store(const void* y, const int64_t* y_d, const void* u, const void* out_mu, const void* out_std, void* ring,
@@ -133,8 +137,8 @@ __global__ __launch_bounds__(256) void tspec_finalize_kernel(const float* __rest
     float mean = 0.f, m2 = 0.f;
     for (int m = 0; m < S; ++m) {
         const size_t o = (size_t)m * ms;
-        const float xbar = asum[o] * inv_t;
-        const float re = are[o] - xbar * gr, im = aim[o] - xbar * gi;
+        const float sm = asum[o];
+        const float re = tmg_fourier_coef(are[o], sm, inv_t, gr), im = tmg_fourier_coef(aim[o], sm, inv_t, gi);
         const float P = ck * (re * re + im * im);
         const float d = P - mean;
         mean += d * (1.f / (float)(m + 1));

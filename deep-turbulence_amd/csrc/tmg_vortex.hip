@@ -1,9 +1,9 @@
 // Vortex census of sampled roll-outs and of the target (tmg_ops.EnsembleVortices / utils.modelPredVortices): the Okubo-Weiss class of
 // every pixel, the 4-connected components of each class, their int64 measures and a table of them per row, case and timed step.  The
 // definitions are stated once in include/tmglow_hip_vortex.h; every fp32 operation of the classification is rounded on its own.
-//   ens_vortex_classify_kernel  one thread per pixel of one plane (row, case): the 3x3 stencils from global memory (tmg_ensemble.hip
-//                               explains why an LDS tile does not pay for NHWC input with a run-time stride), omega, class, and one
-//                               integer atomicAdd per wave that holds a rejected pixel.
+//   ens_vortex_classify_kernel  one thread per pixel of one plane (row, case): the 3x3 stencils of tmg_field.h from global memory
+//                               (tmg_ensemble.hip explains why an LDS tile does not pay for NHWC input with a run-time stride), omega,
+//                               class, and one integer atomicAdd per wave that holds a rejected pixel.
 //   ens_vortex_tile_kernel      one block per 32 x 32 tile of one plane: a union-find over the tile in LDS.  parent[x] <= x always, so
 //                               the forest has no cycles and a root is the smallest index of its tree; a link is one LDS atomicMin of
 //                               the larger root onto the smaller, retried from the value it displaced when the larger one had stopped
@@ -23,8 +23,7 @@
 //   ens_vortex_fill_kernel      one block per 1024 pixels of one plane: the measures of its pixels into an LDS copy of the table
 //                               (64-bit LDS integer atomics), then one global 64-bit atomicAdd / atomicMax per non-zero word.
 // Integer sums and maxima do not depend on the order: every output is bitwise reproducible and independent of the chunking.
-// The stencil helpers repeat pdf_ddx / pdf_ddy of tmg_pdf.hip on purpose: omega must be that file's `vort` bit for bit.
-#include "tmg_common.h"
+#include "tmg_field.h"
 #include "tmglow_hip.h"
 #include "tmglow_hip_vortex.h"
 
@@ -80,46 +79,6 @@ extern "C" int tmg_ens_vortex_plan(const int64_t* dims, int64_t* plan) {
 // ---- classification -------------------------------------------------------------------------------------------------------------------
 #pragma clang fp contract(off)
 
-__device__ __forceinline__ float vx_unnorm(const float* __restrict__ yp, int c, float sc, float sd, float mu) {
-    float t = sd * yp[c];
-    t = t + mu;
-    return sc * t;
-}
-
-// Sx of channel c: right column first, then left, each in the order centre * 2, up, down; zero padding
-__device__ __forceinline__ float vx_ddx(const float* __restrict__ yp, long long ps, long long rs, int c, float sc, float sd, float mu,
-                                        bool up, bool dn, bool lf, bool rt) {
-    float a = 0.f;
-    if (rt) {
-        a += 2.f * vx_unnorm(yp + ps, c, sc, sd, mu);
-        if (up) a += vx_unnorm(yp + ps - rs, c, sc, sd, mu);
-        if (dn) a += vx_unnorm(yp + ps + rs, c, sc, sd, mu);
-    }
-    if (lf) {
-        a -= 2.f * vx_unnorm(yp - ps, c, sc, sd, mu);
-        if (up) a -= vx_unnorm(yp - ps - rs, c, sc, sd, mu);
-        if (dn) a -= vx_unnorm(yp - ps + rs, c, sc, sd, mu);
-    }
-    return a;
-}
-
-// Sy of channel c: lower row first, then upper, each in the order centre * 2, left, right; zero padding
-__device__ __forceinline__ float vx_ddy(const float* __restrict__ yp, long long ps, long long rs, int c, float sc, float sd, float mu,
-                                        bool up, bool dn, bool lf, bool rt) {
-    float a = 0.f;
-    if (dn) {
-        a += 2.f * vx_unnorm(yp + rs, c, sc, sd, mu);
-        if (lf) a += vx_unnorm(yp + rs - ps, c, sc, sd, mu);
-        if (rt) a += vx_unnorm(yp + rs + ps, c, sc, sd, mu);
-    }
-    if (up) {
-        a -= 2.f * vx_unnorm(yp - rs, c, sc, sd, mu);
-        if (lf) a -= vx_unnorm(yp - rs - ps, c, sc, sd, mu);
-        if (rt) a -= vx_unnorm(yp - rs + ps, c, sc, sd, mu);
-    }
-    return a;
-}
-
 __global__ __launch_bounds__(VX_THREADS) void ens_vortex_classify_kernel(
     const float* __restrict__ y, int ps, const float* __restrict__ u, const float* __restrict__ out_mu, const float* __restrict__ out_std,
     const float* __restrict__ thr, const float* __restrict__ qscale, float* __restrict__ omega, signed char* __restrict__ cls,
@@ -136,10 +95,10 @@ __global__ __launch_bounds__(VX_THREADS) void ens_vortex_classify_kernel(
         const long long rs = (long long)Ww * ps;
         const float* yp = y + ((size_t)row * HW + p) * ps;
         const bool up = h > 0, dn = h + 1 < Hh, lf = w > 0, rt = w + 1 < Ww;
-        const float sxv = vx_ddx(yp, ps, rs, 1, sc1, sd1, mu1, up, dn, lf, rt);
-        const float syu = vx_ddy(yp, ps, rs, 0, sc0, sd0, mu0, up, dn, lf, rt);
-        const float sxu = vx_ddx(yp, ps, rs, 0, sc0, sd0, mu0, up, dn, lf, rt);
-        const float syv = vx_ddy(yp, ps, rs, 1, sc1, sd1, mu1, up, dn, lf, rt);
+        const float sxv = tmg_sx<false>(yp, ps, rs, 1, sc1, sd1, mu1, up, dn, lf, rt);
+        const float syu = tmg_sy<false>(yp, ps, rs, 0, sc0, sd0, mu0, up, dn, lf, rt);
+        const float sxu = tmg_sx<false>(yp, ps, rs, 0, sc0, sd0, mu0, up, dn, lf, rt);
+        const float syv = tmg_sy<false>(yp, ps, rs, 1, sc1, sd1, mu1, up, dn, lf, rt);
         const float vx = sxv * rdx, uy = syu * rdy, ux = sxu * rdx, vy = syv * rdy;
         const float om = vx - uy;
         const float sn = ux - vy;

@@ -1,8 +1,8 @@
 // Spectral skill of sampled roll-outs against the target (tmg_ops.EnsembleSpectralSkill / utils.modelPredSpectralSkill): per wavenumber
 // shell the power P, the co-spectrum X with the target and the error power D of every member and of the ensemble-mean field
 // (definitions: include/tmglow_hip_xspec.h).  The 2-D DFT is tmg_spectrum.hip's: the row pass is tmg_spec_rows, called unchanged with
-// unit tables on the field this file's prep kernel forms; the column pass below repeats spec_cols_kernel's product lane for lane and
-// k for k, so that a member that equals the target gives the target's bits.
+// unit tables on the field this file's prep kernel forms; the column pass below has spec_cols_kernel's product, lane for lane and k
+// for k (tmg_dft.h states it and why it is written out in both kernels), so that a member that equals the target gives the target's bits.
 //   xspec_prep_kernel   one thread per element of [B][H][W][2]: f = u fmaf(out_std, y, out_mu) - M of channels 0 and 1 of every image
 //                       of the NHWC chunk (run-time pixel stride) into the dense buffer f [k*B][H][W][2]; the members' f added in
 //                       member order into fsum (the step's first chunk stores); mode 3 writes fbar = fsum / S instead
@@ -14,11 +14,11 @@
 //                       field and the step's outputs at its last
 // Every element of every state is owned by one thread per launch and every sum has a fixed order: the same inputs give the same bits
 // for every chunking.  No data-dependent addressing: the shell lists are host-built and checked by the caller.
-#include "tmg_common.h"
+#include "tmg_dft.h"
+#include "tmg_field.h"
 #include "tmglow_hip_xspec.h"
 
-#define XS_MAXN 512
-#define XS_MAXNK 8192
+#define XS_MAXSHELLS 8192
 #define XS_MAXS 1024
 
 // mode 0: f only (the target); 1: members, fsum stored; 2: members, fsum loaded, added to, stored; 3: f = fsum / S (no y)
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void xspec_prep_kernel(const float* __restrict
     float s = mode == 2 ? fsum[e] : 0.f;
     for (int j = 0; j < k; ++j) {
         const float q = y[((size_t)j * B * HW + pix) * ps + c];
-        float v = sc * fmaf(sd, q, mu);              // the un-normalisation of spec_rows_kernel
+        float v = tmg_unnorm_fma(q, sc, sd, mu);
         if (cen) v = v - m;                          // one separate rounding
         f[(size_t)j * n + e] = v;
         s = (mode == 1 && j == 0) ? v : s + v;
@@ -56,8 +56,8 @@ extern "C" int tmg_ens_xspec_plan(const int64_t* dims, int64_t* out) {
     if (!dims || !out) return -3;
     const int64_t k = dims[0], B = dims[1], Hh = dims[2], Ww = dims[3], NK = dims[4];
     if (k < 1 || B < 1 || NK < 1) return -1;
-    if (Hh < 16 || Hh > XS_MAXN || (Hh & 15) || Ww < 16 || Ww > XS_MAXN || (Ww & 15)) return -1;
-    if (k > XS_MAXS || 3 * B > 65535 || k * B > 65535 || NK > XS_MAXNK) return -2;
+    if (!tmg_dft_side_ok(Hh) || !tmg_dft_side_ok(Ww)) return -1;
+    if (k > XS_MAXS || 3 * B > 65535 || k * B > 65535 || NK > XS_MAXSHELLS) return -2;
     const int64_t QT = Ww / 16, img = Hh * Ww;
     out[0] = (B * img * 2 + 255) / 256;              // prep grid: one thread per element of [B][H][W][2]
     out[1] = QT;                                     // cols grid x: the 16-column tiles
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) void xspec_cols_kernel(const float* __restrict
         const float* fr = ft + (size_t)lq * Hh + pt * 16 + l16;
         const float* fi = fr + th;
         f32x4 zr = {0.f, 0.f, 0.f, 0.f}, zi = {0.f, 0.f, 0.f, 0.f};
-        for (int k0 = 0; k0 < Hh; k0 += 16)        // H is a multiple of 16; the order of spec_cols_kernel
+        for (int k0 = 0; k0 < Hh; k0 += 16)        // H is a multiple of 16; the column product of tmg_dft.h
 #pragma unroll
         for (int k = k0; k < k0 + 16; k += 4) {
             const float a_r = fr[(size_t)k * Hh], a_i = fi[(size_t)k * Hh];
@@ -202,10 +202,10 @@ extern "C" int tmg_ens_xspec_cols(const void* ft, const void* yw, const void* pe
     const int64_t n = dims[0], B = dims[1], Hh = dims[2], Ww = dims[3], NK = dims[4], cross = dims[5], yw_floats = dims[6],
                   zt_floats = dims[7], part_floats = dims[8];
     if (n < 1 || B < 1 || NK < 1 || (cross != 0 && cross != 1)) return -1;
-    if (Hh < 16 || Hh > XS_MAXN || (Hh & 15) || Ww < 16 || Ww > XS_MAXN || (Ww & 15)) return -1;
+    if (!tmg_dft_side_ok(Hh) || !tmg_dft_side_ok(Ww)) return -1;
     if (n % B || (!cross && n != B)) return -1;
     if (!(fl[0] > 0.f) || !(fl[0] <= 3.0e38f)) return -1;
-    if (n > 65535 || NK > XS_MAXNK) return -2;
+    if (n > 65535 || NK > XS_MAXSHELLS) return -2;
     if (!ft || !yw || !perm || !offs || !zt || !part) return -3;
     const int64_t plane = n * Hh * Ww, zplane = B * Hh * Ww, QT = Ww / 16;
     if (yw_floats < 2 * plane || zt_floats < 2 * zplane || part_floats < n * QT * NK * (cross ? 3 : 1)) return -4;
@@ -269,11 +269,11 @@ extern "C" int tmg_ens_xspec_accum(const void* part, const void* part_t, const v
     if (!dims) return -3;
     const int64_t k = dims[0], B = dims[1], NK = dims[2], QT = dims[3], S = dims[4], Tk = dims[5], t = dims[6], n_before = dims[7],
                   m0 = dims[8], t_before = dims[9], flags = dims[10];
-    if (k < 1 || B < 1 || NK < 1 || QT < 1 || QT > XS_MAXN / 16 || S < 1 || Tk < 1 || t < 0 || t >= Tk || n_before < 0 || m0 < 0
+    if (k < 1 || B < 1 || NK < 1 || QT < 1 || QT > TMG_DFT_MAXN / 16 || S < 1 || Tk < 1 || t < 0 || t >= Tk || n_before < 0 || m0 < 0
         || t_before < 0 || flags < 0 || flags > 3)
         return -1;
     if (m0 != n_before || m0 + k > S || ((flags & 2) != 0) != (m0 + k == S)) return -1;
-    if (S > XS_MAXS || 3 * B > 65535 || k * B > 65535 || NK > XS_MAXNK || B * Tk * 3 * NK >= (1ll << 40)) return -2;
+    if (S > XS_MAXS || 3 * B > 65535 || k * B > 65535 || NK > XS_MAXSHELLS || B * Tk * 3 * NK >= (1ll << 40)) return -2;
     if (!part || !step) return -3;
     if (n_before == 0 && (!part_t || !tpow)) return -3;
     if ((flags & 2) && (!part_b || !sum_out || !bar_out)) return -3;

@@ -134,7 +134,8 @@ def build(force=False, verbose=False):
     source or a header changed, all stale ones in parallel), then one link."""
     from concurrent.futures import ThreadPoolExecutor
     inc = os.path.join(os.path.dirname(_HERE), "include")
-    headers = [os.path.join(CSRC, "tmg_common.h"), os.path.join(CSRC, "tmg_symgram.h"), os.path.join(inc, "tmglow_hip.h"), os.path.join(inc, "tmglow_hip_plan.h"),
+    headers = [os.path.join(CSRC, "tmg_common.h"), os.path.join(CSRC, "tmg_symgram.h"), os.path.join(CSRC, "tmg_field.h"), os.path.join(CSRC, "tmg_dft.h"),
+               os.path.join(inc, "tmglow_hip.h"), os.path.join(inc, "tmglow_hip_plan.h"),
                os.path.join(inc, "tmglow_hip_tspec.h"), os.path.join(inc, "tmglow_hip_quant.h"),
                os.path.join(inc, "tmglow_hip_gram.h"), os.path.join(inc, "tmglow_hip_sfun.h"),
                os.path.join(inc, "tmglow_hip_event.h"), os.path.join(inc, "tmglow_hip_pdf.h"), os.path.join(inc, "tmglow_hip_pod.h"),
