@@ -2202,6 +2202,176 @@ class EnsembleEvents(EnsembleFeed):
         return o
 
 
+SPELL_MAX_LEN = 64
+SPELL_MAX_STEPS = 32767
+SPELL_MAX_CASES = 65535
+SPELL_TABLE_KEYS = ("spell_hist", "spell_len", "spell_cens", "spell_cens_len")
+SPELL_MAP_KEYS = ("time_in_count", "time_spell_count", "time_longest_sum", "time_longest_max", "target_in_count", "target_spell_count",
+                  "target_longest")
+
+
+def spell_args(events, max_len, C):
+    """The checks of EnsembleSpells' events and max_len arguments for C channels.  events: event_args' rules and messages (channel in
+    0..C-1, finite value, '>' or '<'; 1 to 4 of them).  max_len: the number of length bins L, an integer in 1..64 (no bools, no
+    floats).  -> (events as tuples, L)."""
+    ev, _ = event_args(events, (1,), C)
+    if isinstance(max_len, bool) or not isinstance(max_len, numbers.Integral) or not 1 <= max_len <= SPELL_MAX_LEN:
+        raise ValueError("max_len is an integer in 1..%d (the length bins), got %r" % (SPELL_MAX_LEN, max_len))
+    return ev, int(max_len)
+
+
+def spell_outputs(hist, length, cens, cens_len, S, Tn, HW):
+    """The duration statistics of the run tables of S members and the target (row S) over a window of Tn steps of HW pixels: hist
+    [..., S + 1, 2, L] (the complete runs by length, the last bin open), length [..., S + 1, 2] (the sum of their lengths), cens,
+    cens_len [..., S + 1, 2, 3] (the numbers and length sums of the left, right and both runs), int64 CPU tensors; the axis of 2 is
+    the polarity (0 gaps, 1 spells).  Host only, integers in int64 and ratios in fp64, every float rounded to fp32 once.  -> dict:
+      spell_mean [..., S + 1, 2]          length / sum(hist): the mean complete duration, NaN without a complete run
+      spell_survival [..., S + 1, 2, L]   entry j - 1: the share of the complete runs of length >= j
+      spell_p11, spell_p01 [..., S + 1]   n11 / (n11 + n10) and n01 / (n01 + n00), the step-to-step persistence and onset
+                                          probabilities of the two-state chain, the transition counts from the tables' identities
+                                          (n11 = t_in - n_s, n01 = n_s - left_1 - both_1, n10 = n_s - right_1 - both_1, n00 alike
+                                          from the gaps); NaN on an empty denominator
+      spell_markov_mean [..., S + 1]      1 / (1 - p11) = (n11 + n10) / n10: the mean spell a chain of this persistence would have
+      spell_w1 [..., S, 2], spell_w1_pooled [..., 2]   the Wasserstein-1 distance over the bin index between a member's (all members'
+                                          pooled) length distribution and the target's; NaN when either is empty
+      spell_mean_below, spell_mean_equal, spell_mean_valid [..., 2] int64   the members with at least one complete run (valid) whose
+                                          mean duration is strictly below / equal to the target's, by the integer products
+                                          len_m cnt_T against len_T cnt_m: the exact rank of the target's persistence; below and
+                                          equal are 0 when the target has no complete run."""
+    S, Tn, HW = int(S), int(Tn), int(HW)
+    hist, length, cens, cens_len = (torch.as_tensor(v) for v in (hist, length, cens, cens_len))
+    lead = tuple(hist.shape[:-3])
+    if S < 1 or Tn < 2 or HW < 1 or hist.dim() < 3 or tuple(hist.shape[-3:-1]) != (S + 1, 2) or hist.shape[-1] < 1 \
+            or any(v.dtype != torch.int64 for v in (hist, length, cens, cens_len)) or tuple(length.shape) != lead + (S + 1, 2) \
+            or tuple(cens.shape) != lead + (S + 1, 2, 3) or tuple(cens_len.shape) != lead + (S + 1, 2, 3):
+        raise ValueError("spell_outputs takes int64 tables [..., %d, 2, L], [..., %d, 2] and two of [..., %d, 2, 3], got %s, %s, %s, %s"
+                         % (S + 1, S + 1, S + 1, tuple(hist.shape), tuple(length.shape), tuple(cens.shape), tuple(cens_len.shape)))
+    if Tn * HW >= 2 ** 31:
+        raise ValueError("Tn HW = %d * %d does not stay under 2^31 (the int64 products of the duration ranks)" % (Tn, HW))
+    hist, length, cens, cens_len = hist.cpu(), length.cpu(), cens.cpu(), cens_len.cpu()
+    f32 = lambda v: v.to(torch.float32)                                        # noqa: E731
+    n = hist.sum(-1)
+    nd = n.double()
+    o = {"spell_mean": f32(length.double() / nd)}
+    o["spell_survival"] = f32(hist.flip(-1).cumsum(-1).flip(-1).double() / nd.unsqueeze(-1))
+    runs, tlen = n + cens.sum(-1), length + cens_len.sum(-1)                   # every run of the polarity and the steps it covers
+    n11, n00 = tlen[..., 1] - runs[..., 1], tlen[..., 0] - runs[..., 0]
+    n01 = runs[..., 1] - cens[..., 1, 0] - cens[..., 1, 2]
+    n10 = runs[..., 1] - cens[..., 1, 1] - cens[..., 1, 2]
+    o["spell_p11"] = f32(n11.double() / (n11 + n10).double())
+    o["spell_p01"] = f32(n01.double() / (n01 + n00).double())
+    o["spell_markov_mean"] = f32((n11 + n10).double() / n10.double())
+    cdf = lambda h: h.cumsum(-1).double() / h.sum(-1, keepdim=True).double()   # noqa: E731
+    ct = cdf(hist[..., S, :, :])
+    o["spell_w1"] = f32((cdf(hist[..., :S, :, :]) - ct.unsqueeze(-3)).abs().sum(-1))
+    o["spell_w1_pooled"] = f32((cdf(hist[..., :S, :, :].sum(-3)) - ct).abs().sum(-1))
+    lm, cm = length[..., :S, :], n[..., :S, :]
+    lt, ctg = length[..., S, :].unsqueeze(-2), n[..., S, :].unsqueeze(-2)
+    ok = (cm > 0) & (ctg > 0)
+    o["spell_mean_below"] = (ok & (lm * ctg < lt * cm)).sum(-2)
+    o["spell_mean_equal"] = (ok & (lm * ctg == lt * cm)).sum(-2)
+    o["spell_mean_valid"] = (cm > 0).sum(-2)
+    return o
+
+
+class EnsembleSpells(EnsembleFeed):
+    """On-device event durations of sampled roll-outs of B cases and of the target along a time window (tmg_ens_spell_step /
+    tmg_ens_spell_finalize): how long a pixel stays in an event and out of it.  An event k is (channel, value, ">" | "<"), strict, in
+    physical units ((0, 0.0, "<") is reverse flow), decided on the raw normalised values against raw_thresholds (u out_std > 0 keeps
+    the order); a value that compares false (NaN, an infinity on the wrong side) is in no event.  Rows 0 .. S - 1 are the members,
+    row S is the target.  Per row, case, event and pixel the indicator series e_0 .. e_{Tn-1} splits into runs, maximal stretches of
+    equal value: polarity 1 is a spell, 0 a gap.  A run is complete (it starts after step 0 and ends before step Tn - 1), left
+    (holds step 0), right (holds step Tn - 1) or both (the whole window); the three censored classes are kept apart, their true
+    length being unknown, and never enter a histogram.  Bin j - 1 of the L = max_len bins holds the complete runs of length j, the
+    last bin those of length >= L.
+
+    `steps` is Tn >= 2: only the steps of the window are fed.  Limits: 1 <= members <= 1024, B <= 65535, Tn <= 32767 (the 15-bit
+    run length of the state word), S Tn < 2^31 and Tn HW < 2^31.  Device memory: the state, one int32 word per (row, case, event,
+    pixel), (S + 1) B K HW 4 bytes, which max_state_bytes bounds (default 2^31); seven int32 maps, 28 B K HW bytes; the tables,
+    16 B K (S + 1) (L + 7) bytes.  No member buffer [S][..][C] is kept: a chunk is read straight from its NHWC rows.
+
+    Feeding protocol of EnsembleFeed without a time argument: every step's members in chunks of whole members, in member order
+    (m0 = 0 first), each step's chunks before the next step's; every chunk comes with the step's target, and the last chunk's is
+    the one that is used.  finalize() returns, per (case, event, row, polarity) and pooled over the pixels, int64 on the device:
+    spell_hist [B, K, S + 1, 2, L], spell_len [B, K, S + 1, 2], spell_cens, spell_cens_len [B, K, S + 1, 2, 3] (left, right, both);
+    spell_outputs' keys (fp32 / int64); the maps [B, K, H, W] int64 time_in_count (sum over members and steps of e_t),
+    time_spell_count (sum over members of the polarity-1 runs of any class), time_longest_sum, time_longest_max (sum and maximum over
+    the members of each member's longest spell of any class, 0 without one), target_in_count, target_spell_count, target_longest;
+    time_longest_mean = time_longest_sum / S, time_mean_duration = time_in_count / time_spell_count and target_mean_duration =
+    target_in_count / target_spell_count (fp32, NaN where the count is 0); and spell_bins [L] int64 = 1 .. L."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, events=((0, 0.0, "<"),), max_len=32,
+                 max_state_bytes=2 ** 31):
+        noun = "ensemble spells"
+        _ens_channels(noun, C)
+        if isinstance(steps, bool) or not isinstance(steps, numbers.Integral) or int(steps) < 2:
+            raise ValueError("%s need steps >= 2 (the time window), got %r" % (noun, steps))
+        ev, L = spell_args(events, max_len, C)
+        _ens_members(noun, members)
+        sd, mu = _ens_tables(C, _KEEPS_ORDER, out_std, out_mu)
+        u = _ens_u(u, B, C, _KEEPS_ORDER)
+        S, Tn, HW, K = int(members), int(steps), int(Hh) * int(Ww), len(ev)
+        if int(B) < 1 or int(Hh) < 1 or int(Ww) < 1:
+            raise ValueError("%s need B, H, W >= 1, got %d, %d, %d" % (noun, B, Hh, Ww))
+        if int(B) > SPELL_MAX_CASES:
+            raise ValueError("%s take at most %d cases, got %d" % (noun, SPELL_MAX_CASES, int(B)))
+        if Tn > SPELL_MAX_STEPS:
+            raise ValueError("steps = %d exceeds %d (the 15-bit run length of the state word)" % (Tn, SPELL_MAX_STEPS))
+        if S * Tn >= 2 ** 31:
+            raise ValueError("S Tn = %d * %d does not stay under 2^31 (the int32 per-pixel maps)" % (S, Tn))
+        if Tn * HW >= 2 ** 31:
+            raise ValueError("Tn HW = %d * %d does not stay under 2^31 (the int64 products of the duration ranks)" % (Tn, HW))
+        nbytes = (S + 1) * int(B) * K * HW * 4
+        if nbytes > int(max_state_bytes):
+            raise ValueError("the state buffer (S + 1) B K HW 4 = (%d + 1) * %d * %d * %d * 4 = %d bytes exceeds max_state_bytes = %d"
+                             % (S, int(B), K, HW, nbytes, int(max_state_bytes)))
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, C, Hh, Ww, steps)
+        self.Tn, self.L, self.K = self.Tk, L, K
+        self.events = ev
+        self.ev = _ens_directions(ev)
+        self.thr = raw_thresholds(ev, self.B, C, mu, sd, u).to(dev).contiguous()
+        self.plan = H.ens_spell_plan(S, self.B, HW, K, L, Tn)
+        self.state = torch.empty((S + 1, self.B, K, HW), device=dev, dtype=torch.int32)
+        self.table = torch.empty((self.B, K, S + 1, 2, L + 7), device=dev, dtype=torch.int64)
+        self.maps = torch.empty((H.SPELL_MAPS, self.B, K, HW), device=dev, dtype=torch.int32)
+        self.out = None
+
+    def add(self, y, m0, target):
+        """Advance the runs of the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last
+        view is an NHWC channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride
+        rule.  The step's last chunk advances the target's runs as row S."""
+        yn, tn, k, _, last = self.open_chunk(y, m0, None, target, required=True)
+        _on_device(yn, tn)
+        t = self._step
+        H.ens_spell_step(yn, self.thr, self.ev, self.state, self.table, self.maps, self.S, k, m0, self.Tn, t)
+        if last:
+            H.ens_spell_step(tn, self.thr, self.ev, self.state, self.table, self.maps, self.S, 1, self.S, self.Tn, t)
+        self.close_chunk(m0, k, None, last)
+
+    def finalize(self):
+        """-> dict of the outputs: the tables and maps on the device, spell_outputs' keys formed on the host."""
+        self.finalize_guard(timed=False)
+        if self.out is None:
+            H.ens_spell_finalize(self.state, self.table, self.maps, self.Tn)
+            dev, S, L = self.table.device, self.S, self.L
+            tab = self.table
+            raw = (tab[..., :L].contiguous(), tab[..., L].contiguous(), tab[..., L + 1:L + 4].contiguous(), tab[..., L + 4:L + 7].contiguous())
+            o = dict(zip(SPELL_TABLE_KEYS, raw))
+            for key, v in spell_outputs(*[v.cpu() for v in raw], S, self.Tn, self.H * self.W).items():
+                o[key] = v.to(dev)
+            maps = self.maps.to(torch.int64).view(H.SPELL_MAPS, self.B, self.K, self.H, self.W)
+            for i, key in enumerate(SPELL_MAP_KEYS):
+                o[key] = maps[i]
+            ratio = lambda a, b: (a.double() / b.double()).to(torch.float32)   # noqa: E731  (0 / 0: NaN)
+            o["time_longest_mean"] = (o["time_longest_sum"].double() / float(S)).to(torch.float32)
+            o["time_mean_duration"] = ratio(o["time_in_count"], o["time_spell_count"])
+            o["target_mean_duration"] = ratio(o["target_in_count"], o["target_spell_count"])
+            o["spell_bins"] = torch.arange(1, L + 1, dtype=torch.int64)
+            self.out = o
+        return self.out
+
+
 PDF_MAX_FIELDS = 8
 PDF_MAX_BINS = 128
 PDF_MAX_JOINT_BINS = 32

@@ -651,6 +651,57 @@ def modelPredEvents(args, model, testing_loader, log, samples=1, stride=1, tmax=
     return _ensembleStats("modelPredEvents", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
 
 
+def modelPredSpells(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, events=((0, 0.0, "<"),),
+                    max_len=32):
+    """modelPredStats plus the durations of the members' and the target's events over the kept steps t_start..Tk-1 (Tn = Tk - t_start
+    >= 2 of them), still without forming modelPred's [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleSpells).  modelPredEvents says,
+    step by step, whether a pixel is in an event; this says for how long: a member whose recirculation bubble flickers on and off
+    and one whose bubble persists get the same tables there and different ones here.  An event is (channel, value, ">" | "<"), strict,
+    in physical units, as modelPredEvents' (1 to 4 of them; (0, 0.0, "<") is reverse flow); a non-finite value is in no event.  Per
+    row (the S = samples members, then the target as row S), case, event and pixel the indicator series splits into runs of equal
+    value: polarity 1 is a spell (in the event), polarity 0 a gap.  A run that touches an end of the window is censored - its true
+    length is unknown - and is counted apart as left (holds the first step), right (holds the last) or both (the whole window):
+    censored runs are excluded from the histograms and the mean durations on purpose, so a short window biases neither towards short
+    runs it merely cut; read spell_cens beside spell_hist to see how much of the record is censored.  Durations are in kept steps:
+    `stride` scales them (a run of length l lasted between (l - 1) stride + 1 and (l + 1) stride - 1 model steps).  The target of
+    kept step j is series step j * stride; a series that is too short raises.  max_len: the L length bins, 1..64.  Tn <= 32767.
+    Same roll-outs as modelPredStats: under the same host RNG state the keys both return are identical.
+
+    Returns modelPredStats' dict plus (CPU tensors; K events, R = S + 1 rows with the target last, polarity 0 = gaps, 1 = spells):
+      spell_hist [N, K, R, 2, L]          int64: the complete runs by length, pooled over the pixels; bin j - 1 holds length j, the
+                                          last bin length >= L.  Compare a member's row with row S: mass at short lengths that the
+                                          target does not have is flicker
+      spell_len [N, K, R, 2]              int64: the sum of the complete runs' lengths
+      spell_cens, spell_cens_len [N, K, R, 2, 3]   int64: the numbers and length sums of the left, right and both runs.  All lengths
+                                          of a row over both polarities and all four classes sum to Tn H W
+      spell_mean [N, K, R, 2]             the mean complete duration, NaN without a complete run
+      spell_survival [N, K, R, 2, L]      entry j - 1: the share of complete runs that last at least j steps; a geometric decay
+                                          is what a memoryless (Markov) state gives
+      spell_p11, spell_p01 [N, K, R]      the probabilities to stay in the event and to enter it from one kept step to the next,
+                                          exact from the tables; NaN when the row is never in (out of) the event before the last step
+      spell_markov_mean [N, K, R]         1 / (1 - p11): the mean spell of a two-state chain with this persistence; spell_mean well
+                                          above it means the state is held longer than its one-step statistics explain
+      spell_w1 [N, K, S, 2], spell_w1_pooled [N, K, 2]   the Wasserstein-1 distance, in bins, between a member's (all members' pooled)
+                                          distribution of complete durations and the target's; NaN when either is empty
+      spell_mean_below, spell_mean_equal, spell_mean_valid [N, K, 2]   int64: of the members with a complete run (valid), those whose
+                                          mean duration is strictly below / equal to the target's: the exact rank of the target's
+                                          persistence within the ensemble (0 or valid: every member holds the state too long or too briefly)
+      time_in_count [N, K, H, W]          int64: member-steps in the event per pixel (modelPredEvents' time_event_count)
+      time_spell_count [N, K, H, W]       int64: the members' spells of any class per pixel
+      time_longest_sum, time_longest_max [N, K, H, W]   int64: the sum and the maximum over the members of each member's longest spell
+                                          of any class; time_longest_mean = time_longest_sum / S
+      time_mean_duration [N, K, H, W]     time_in_count / time_spell_count, censored spells included: where the ensemble holds the
+                                          event longest; NaN where no member is ever in it
+      target_in_count, target_spell_count, target_longest, target_mean_duration [N, K, H, W]   the same of the target
+      spell_bins [L] int64, events        the lengths 1..L of the bins and the events as given."""
+    import tmg_ops as ops
+    events, max_len = ops.spell_args(events, max_len, 3)
+    events = tuple(events)
+    acc = _Acc(lambda mb, S, T: ops.EnsembleSpells(S, mb.B, mb.C, mb.H, mb.W, T, mb.dev, mb.out_mu, mb.out_std, u=mb.u, events=events, max_len=max_len),
+               target=True, window=True, meta=("spell_bins",), extra={"events": events})
+    return _ensembleStats("modelPredSpells", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
+
+
 def modelPredPdfs(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, fields=("ux", "uy", "p", "vort"),
                   bins=64, ranges=None, joint=(("ux", "uy"),), joint_bins=32, regions=None, center=None):
     """modelPredStats plus the probability densities of the flow quantities themselves, pooled over regions of the flow, for the
