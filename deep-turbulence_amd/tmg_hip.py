@@ -20,7 +20,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmglow_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip", "tmg_phase.hip", "tmg_spod.hip", "tmg_budget.hip", "tmg_corr.hip", "tmg_flux.hip", "tmg_vortex.hip", "tmg_frank.hip", "tmg_xspec.hip", "tmg_spell.hip", "tmg_lagr.hip"]
+SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip", "tmg_phase.hip", "tmg_spod.hip", "tmg_budget.hip", "tmg_corr.hip", "tmg_flux.hip", "tmg_vortex.hip", "tmg_frank.hip", "tmg_xspec.hip", "tmg_spell.hip", "tmg_iscale.hip", "tmg_lagr.hip"]
 # Sources compiled WITHOUT the packed-fp32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32): beside MFMAs a packed
 # f32 instruction costs ~13 cycles more than the two scalar ones it replaces (MI355X_MICROARCH.md, cycle constants, 'price of one
 # filler beside MFMAs'), and the compiler SLP-packs adjacent scalar adds / multiplies by itself under -O3.  The matrix-core kernels'
@@ -107,6 +107,9 @@ XSPEC_EXPORTS = ["tmg_ens_xspec_plan", "tmg_ens_xspec_prep", "tmg_ens_xspec_cols
 # The event durations: spells, gaps and persistence along the time window (csrc/tmg_spell.hip), declared in
 # include/tmglow_hip_spell.h, a header of its own: ens_spell_plan / ens_spell_step / ens_spell_finalize below.
 SPELL_EXPORTS = ["tmg_ens_spell_plan", "tmg_ens_spell_step", "tmg_ens_spell_finalize"]
+# The intensity-scale verification: the Haar skill of the events by spatial scale (csrc/tmg_iscale.hip), declared in
+# include/tmglow_hip_iscale.h, a header of its own: ens_iscale_plan / ens_iscale_chunk / ens_iscale_step below.
+ISCALE_EXPORTS = ["tmg_ens_iscale_plan", "tmg_ens_iscale_chunk", "tmg_ens_iscale_step"]
 _P64 = ctypes.POINTER(ctypes.c_int64)
 FLUX_ARGTYPES = {
     "tmg_ens_flux_plan": [_P64, _P64, _P64],
@@ -123,6 +126,12 @@ SPELL_ARGTYPES = {
     "tmg_ens_spell_step": [ctypes.c_void_p, _P64, ctypes.c_void_p, _P64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _P64,
                            ctypes.c_void_p],
     "tmg_ens_spell_finalize": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _P64, ctypes.c_void_p],
+}
+ISCALE_ARGTYPES = {
+    "tmg_ens_iscale_plan": [_P64, _P64],
+    "tmg_ens_iscale_chunk": [ctypes.c_void_p, _P64, ctypes.c_void_p, _P64, ctypes.c_void_p, _P64, ctypes.c_void_p, ctypes.c_void_p,
+                             ctypes.c_void_p, ctypes.c_void_p, _P64, ctypes.c_void_p],
+    "tmg_ens_iscale_step": [ctypes.c_void_p, ctypes.c_void_p, _P64, ctypes.c_void_p, _P64, ctypes.c_void_p, _P64, ctypes.c_void_p],
 }
 XSPEC_ARGTYPES = {
     "tmg_ens_xspec_plan": [_P64, _P64],
@@ -151,7 +160,8 @@ def build(force=False, verbose=False):
                os.path.join(inc, "tmglow_hip_phase.h"), os.path.join(inc, "tmglow_hip_spod.h"), os.path.join(inc, "tmglow_hip_layout.h"),
                os.path.join(inc, "tmglow_hip_budget.h"), os.path.join(inc, "tmglow_hip_corr.h"), os.path.join(inc, "tmglow_hip_flux.h"),
                os.path.join(inc, "tmglow_hip_lagr.h"), os.path.join(inc, "tmglow_hip_vortex.h"),
-               os.path.join(inc, "tmglow_hip_frank.h"), os.path.join(inc, "tmglow_hip_xspec.h"), os.path.join(inc, "tmglow_hip_spell.h")]
+               os.path.join(inc, "tmglow_hip_frank.h"), os.path.join(inc, "tmglow_hip_xspec.h"), os.path.join(inc, "tmglow_hip_spell.h"),
+               os.path.join(inc, "tmglow_hip_iscale.h")]
     hmt = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -219,6 +229,9 @@ def lib():
         for name in SPELL_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
             getattr(_lib, name).argtypes = SPELL_ARGTYPES[name]
+        for name in ISCALE_EXPORTS:
+            getattr(_lib, name).restype = ctypes.c_int
+            getattr(_lib, name).argtypes = ISCALE_ARGTYPES[name]
     return _lib
 
 
@@ -1920,6 +1933,83 @@ def ens_spell_finalize(state, table, maps, Tn, code=False):
     if code:
         return rc
     _chk(rc, "tmg_ens_spell_finalize")
+
+
+ISCALE_PLAN_KEYS = ("tile", "tiles_x", "tiles_y", "grid_x", "grid_y", "grid_z", "blocks", "threads", "group", "lds_bytes", "step_lds_bytes",
+                    "member_words", "target_words", "ens_words")
+
+
+def ens_iscale_plan(S, B, H, W, K, L, code=False):
+    """The launch plan of ens_iscale_chunk / ens_iscale_step for S members of B cases of [H, W], K events and L Haar levels
+    (tmg_ens_iscale_plan; nothing is launched) -> dict of ISCALE_PLAN_KEYS (include/tmglow_hip_iscale.h) plus grid = (grid_x, grid_y,
+    grid_z).  code=True: the C return code instead of raising, as the second element of a pair."""
+    plan = (c_i64 * len(ISCALE_PLAN_KEYS))()
+    rc = lib().tmg_ens_iscale_plan(_i64(S, B, H, W, K, L), plan)
+    out = dict(zip(ISCALE_PLAN_KEYS, [int(v) for v in plan]))
+    out["grid"] = (out["grid_x"], out["grid_y"], out["grid_z"])
+    if code:
+        return out, rc
+    _chk(rc, "tmg_ens_iscale_plan")
+    return out
+
+
+def _iscale_buffers(name, bufs, dev):
+    """bufs: (key, tensor, dtype, shape) entries, each a contiguous array of that dtype and shape on dev."""
+    for key, t, dt, shape in bufs:
+        if not t.is_cuda or t.dtype != dt or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != dev:
+            raise RuntimeError("%s: %s is a contiguous %s %s array on %s, got %s %s" % (name, key, list(shape), dt, dev, t.dtype, tuple(t.shape)))
+        check_device(t)
+
+
+def _iscale_thr(name, thr, B, K, dev):
+    if thr.dtype != torch.float32 or tuple(thr.shape) != (B, K) or not thr.is_contiguous() or thr.device != dev:
+        raise RuntimeError("%s: thr is a contiguous fp32 [%d, %d] on %s, got %s %s" % (name, B, K, dev, thr.dtype, tuple(thr.shape)))
+
+
+def ens_iscale_chunk(y, target, thr, ev, cnt, member, target_tab, ens, S, k, m0, code=False):
+    """The block-count sums of one chunk of k members (y: NHWC [k*B, H, W, C] or a channel-slice view, rows member-major) against the
+    step's target (NHWC [B, H, W, C] or a channel-slice view) for the K events ev = ((channel, 1 for > / 0 for <), ..) with the raw
+    thresholds thr [B, K] (device): (A, X) of the members m0 .. m0 + k - 1 into member [B, K, S, L + 1, 2] int64, their indicators
+    into cnt [B, K, HW] int32 (m0 = 0 writes, later chunks add); the call with m0 = 0 zeroes member, target_tab [B, K, L + 1] and ens
+    [B, K, L + 1, 2] first and adds Cc into target_tab (tmg_ens_iscale_chunk, include/tmglow_hip_iscale.h).  code=True: the C return
+    code instead of raising."""
+    kB, Hh, Ww, Cc = y.shape
+    ptr, ps, co, _ = seg(y)
+    tptr, tps, tco, _ = seg(target)
+    check_device(y)
+    check_device(target)
+    B, K = kB // max(k, 1), len(ev)
+    L = ens.shape[2] - 1 if ens.dim() == 4 else 0
+    _iscale_buffers("ens_iscale_chunk", (("cnt", cnt, torch.int32, (B, K, Hh * Ww)), ("member", member, torch.int64, (B, K, S, L + 1, 2)),
+                                         ("target_tab", target_tab, torch.int64, (B, K, L + 1)), ("ens", ens, torch.int64, (B, K, L + 1, 2))),
+                    y.device)
+    _iscale_thr("ens_iscale_chunk", thr, B, K, y.device)
+    if tuple(target.shape) != (B, Hh, Ww, Cc) or target.device != y.device:
+        raise RuntimeError("ens_iscale_chunk: target is [%d, %d, %d, %d] on %s, got %s" % (B, Hh, Ww, Cc, y.device, tuple(target.shape)))
+    evf = [int(v) for e in ev for v in e]
+    rc = lib().tmg_ens_iscale_chunk(c_vp(ptr), _i64(ps, co), c_vp(tptr), _i64(tps, tco), _ptr(thr), _i64(*evf) if evf else None, _ptr(cnt),
+                                    _ptr(member), _ptr(target_tab), _ptr(ens), _i64(k, B, Hh, Ww, Cc, S, m0, K, L), _stream())
+    if code:
+        return rc
+    _chk(rc, "tmg_ens_iscale_chunk")
+
+
+def ens_iscale_step(cnt, target, thr, ev, ens, S, code=False):
+    """Once per kept step, after its last chunk: (AN, XN) of the member counts cnt [B, K, HW] int32 against target (NHWC [B, H, W, C]
+    or a channel-slice view) into ens [B, K, L + 1, 2] int64 (tmg_ens_iscale_step).  code=True: the C return code instead of raising."""
+    B, Hh, Ww, Cc = target.shape
+    tptr, tps, tco, _ = seg(target)
+    check_device(target)
+    K = len(ev)
+    L = ens.shape[2] - 1 if ens.dim() == 4 else 0
+    _iscale_buffers("ens_iscale_step", (("cnt", cnt, torch.int32, (B, K, Hh * Ww)), ("ens", ens, torch.int64, (B, K, L + 1, 2))), target.device)
+    _iscale_thr("ens_iscale_step", thr, B, K, target.device)
+    evf = [int(v) for e in ev for v in e]
+    rc = lib().tmg_ens_iscale_step(_ptr(cnt), c_vp(tptr), _i64(tps, tco), _ptr(thr), _i64(*evf) if evf else None, _ptr(ens),
+                                   _i64(S, B, Hh, Ww, Cc, K, L), _stream())
+    if code:
+        return rc
+    _chk(rc, "tmg_ens_iscale_step")
 
 
 XSPEC_PLAN_KEYS = ("prep_grid", "cols_grid_x", "cols_grid_y", "cols_lds_bytes", "accum_grid_x", "accum_grid_y", "threads", "f_floats",

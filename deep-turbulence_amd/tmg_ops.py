@@ -2372,6 +2372,175 @@ class EnsembleSpells(EnsembleFeed):
         return self.out
 
 
+ISCALE_MAX_LEVELS = 6
+ISCALE_RAW_KEYS = ("iscale_member_raw", "iscale_target_raw", "iscale_ens_raw")
+ISCALE_FLOAT_KEYS = ("iscale_mse", "iscale_skill", "iscale_energy", "iscale_energy_bias", "iscale_brier", "iscale_brier_skill",
+                     "iscale_spread", "iscale_spread_skill")
+
+
+def iscale_args(events, levels, C, H, W):
+    """The checks of EnsembleIntensityScale's events and levels arguments for C channels of [H, W].  events: event_args' rules and
+    messages (channel in 0..C-1, finite value, '>' or '<'; 1 to 4 of them).  levels: the number of Haar levels L, an integer in 1..6
+    (no bools, no floats), or None for max(1, min(6, floor(log2(min(H, W))))).  -> (events as tuples, L)."""
+    ev, _ = event_args(events, (1,), C)
+    if levels is None:
+        if int(H) < 1 or int(W) < 1:
+            raise ValueError("levels=None needs H, W >= 1, got %d, %d" % (H, W))
+        return ev, max(1, min(ISCALE_MAX_LEVELS, min(int(H), int(W)).bit_length() - 1))
+    if isinstance(levels, bool) or not isinstance(levels, numbers.Integral) or not 1 <= levels <= ISCALE_MAX_LEVELS:
+        raise ValueError("levels is an integer in 1..%d (the Haar levels) or None, got %r" % (ISCALE_MAX_LEVELS, levels))
+    return ev, int(levels)
+
+
+def _iscale_energy(Q):
+    """Q [..., L + 1] int64 level sums -> the integer numerators [..., L + 1] of the component energies and their divisors [L + 1]:
+    (4 Q[c-1] - Q[c]) over 4^c for the Haar components c = 1..L, Q[L] over 4^L for the remainder."""
+    L = Q.shape[-1] - 1
+    num = torch.cat([4 * Q[..., :L] - Q[..., 1:], Q[..., L:]], -1)
+    den = torch.tensor([4 ** c for c in range(1, L + 1)] + [4 ** L], dtype=torch.int64)
+    return num, den
+
+
+def iscale_outputs(member_raw, target_raw, ens_raw, S, HW, steps=1):
+    """The intensity-scale scores of the raw block sums of S members over `steps` steps of HW pixels (pooled: the sums of the steps'
+    tables): member_raw [..., S, L + 1, 2] = (A, X), target_raw [..., L + 1] = Cc, ens_raw [..., L + 1, 2] = (AN, XN), int64 CPU
+    tensors, level l = 0..L last but one.  Host only: every integer combination is exact in int64 (S HW steps < 2^31), every output
+    is one fp64 division (for the skills, subtracted from 1) rounded to fp32 once.  With N = HW steps, D = A - 2 X + Cc the level
+    sums of a member's error I_m - o, DN = AN - 2 S XN + S^2 Cc those of n - S o, SP = S sum_m A - AN, and E_c(Q) the component
+    energy (4 Q[c-1] - Q[c]) / 4^c for c = 1..L, Q[L] / 4^L for the remainder (components last, L + 1 of them; they sum to Q[0])
+    -> dict:
+      iscale_mse [..., S, L + 1]          E_c(D) / N: they sum to the member's share of mismatched pixels
+      iscale_skill [..., S, L + 1]        1 - (L + 1) mse_c / (f + o - 2 f o), f = A[0] / N and o = Cc[0] / N the event rates of the
+                                          member and the target; NaN when the random forecast's error is 0
+      iscale_energy [..., S + 1, L + 1]   E_c(A[m]) / N, and E_c(Cc) / N as row S
+      iscale_energy_bias [..., S, L + 1]  (Ef - Eo) / (Ef + Eo); NaN when both are 0
+      iscale_brier [..., L + 1]           E_c(DN) / (S^2 N): they sum to the Brier score
+      iscale_brier_skill [..., L + 1]     1 - (L + 1) brier_c / (mean p^2 + o - 2 mean p o) with p = n / S; NaN when that is 0
+      iscale_spread [..., L + 1]          E_c(SP) / (S^2 N) >= 0: the mean member mse minus iscale_brier
+      iscale_spread_skill [..., L + 1]    spread over brier; NaN at 0 / 0."""
+    S, HW, steps = int(S), int(HW), int(steps)
+    member_raw, target_raw, ens_raw = (torch.as_tensor(v) for v in (member_raw, target_raw, ens_raw))
+    lead = tuple(target_raw.shape[:-1])
+    L = target_raw.shape[-1] - 1 if target_raw.dim() >= 1 else 0
+    if S < 1 or HW < 1 or steps < 1 or L < 1 or any(v.dtype != torch.int64 for v in (member_raw, target_raw, ens_raw)) \
+            or tuple(member_raw.shape) != lead + (S, L + 1, 2) or tuple(ens_raw.shape) != lead + (L + 1, 2):
+        raise ValueError("iscale_outputs takes int64 tables [..., %d, L + 1, 2], [..., L + 1] and [..., L + 1, 2] with L >= 1, got %s, %s, %s"
+                         % (S, tuple(member_raw.shape), tuple(target_raw.shape), tuple(ens_raw.shape)))
+    N = HW * steps
+    if S * N >= 2 ** 31:
+        raise ValueError("S HW steps = %d * %d does not stay under 2^31 (the int64 products of the skill scores)" % (S, N))
+    member_raw, target_raw, ens_raw = member_raw.cpu(), target_raw.cpu(), ens_raw.cpu()
+    A, X, Cc = member_raw[..., 0], member_raw[..., 1], target_raw.unsqueeze(-2)
+    AN, XN = ens_raw[..., 0], ens_raw[..., 1]
+    ratio = lambda a, b: (a.double() / b.double()).to(torch.float32)          # noqa: E731  (one division; 0 / 0: NaN)
+    eD, den = _iscale_energy(A - 2 * X + Cc)
+    eA, _ = _iscale_energy(A)
+    eC, _ = _iscale_energy(Cc)
+    eDN, _ = _iscale_energy(AN - 2 * S * XN + S * S * target_raw)
+    eSP, _ = _iscale_energy(S * A.sum(-2) - AN)
+    A0, C0 = A[..., :1], Cc[..., :1]
+    rnd = A0 * N + C0 * N - 2 * A0 * C0                                        # N^2 (f + o - 2 f o)
+    P1 = A[..., 0].sum(-1, keepdim=True)                                       # sum n, as I^2 = I
+    rnb = AN[..., :1] * N + S * S * target_raw[..., :1] * N - 2 * S * P1 * target_raw[..., :1]     # S^2 N^2 (mean p^2 + o - 2 mean p o)
+    o = {"iscale_mse": ratio(eD, den * N)}
+    # 1 - (L + 1) N E_c / (4^c rnd): exact integers, multiplied in fp64 (N^2-sized products would leave int64), one division
+    skill = lambda e, r: (1.0 - (e.double() * float((L + 1) * N)) / (den.double() * r.double())).to(torch.float32)   # noqa: E731
+    o["iscale_skill"] = skill(eD, rnd)
+    o["iscale_energy"] = ratio(torch.cat([eA, eC], -2), den * N)
+    o["iscale_energy_bias"] = ratio(eA - eC, eA + eC)
+    o["iscale_brier"] = ratio(eDN, den * (S * S * N))
+    o["iscale_brier_skill"] = skill(eDN, rnb)
+    o["iscale_spread"] = ratio(eSP, den * (S * S * N))
+    o["iscale_spread_skill"] = ratio(eSP, eDN)
+    return o
+
+
+class EnsembleIntensityScale(EnsembleFeed):
+    """On-device intensity-scale verification of sampled roll-outs of B cases against the target (tmg_ens_iscale_chunk /
+    tmg_ens_iscale_step): at which spatial scale the error of an event forecast sits (Casati, Ross & Stephenson 2004; Casati 2010).
+    An event k is (channel, value, ">" | "<"), strict, in physical units ((0, 0.0, "<") is reverse flow), decided on the raw
+    normalised values against raw_thresholds (u out_std > 0 keeps the order); a value that compares false (NaN, an infinity on the
+    wrong side) is in no event.  Per case, kept step, event and pixel I_m is member m's indicator, o the target's, n = sum_m I_m.  The
+    blocks of level l = 0..L (L = levels, 1..6; None: max(1, min(6, floor(log2(min(H, W)))))) are the 2^l x 2^l squares aligned at
+    pixel (0, 0), the field counting as zero outside H x W.  The device forms the integer sums over the blocks of a level of squared
+    and multiplied block counts, (A, X) per member, Cc of the target, (AN, XN) of n; iscale_outputs turns them into the energies of
+    the orthogonal Haar components of block size 2, 4, .., 2^L and of the coarse remainder, of every member's binary error and of
+    the probability error n / S - o, whose components sum to EnsembleEvents' brier exactly.
+
+    The counts fold chunk by chunk and a chunk is read straight from its NHWC rows: no member buffer [S][..] is kept.  The device
+    memory of this class is O(B K HW) (the count n per pixel, int32, 4 B K HW bytes) plus the tables, 8 Tk B K (L + 1) (2 S + 3)
+    bytes.  Limits: members <= 1024, B <= 65535, S^2 4^L H_pad W_pad < 2^63 with H, W padded to multiples of 64, and
+    S HW Tk < 2^31 (the int64 products of the skill scores).
+
+    Feeding protocol of EnsembleFeed: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
+    chunks before the next step's; every chunk comes with the step's target (the target's indicator enters X of every member).
+    finalize() returns, with L + 1 levels or components last: iscale_member_raw [B, Tk, K, S, L + 1, 2], iscale_target_raw [B, Tk,
+    K, L + 1], iscale_ens_raw [B, Tk, K, L + 1, 2] int64 on the device; iscale_outputs' keys per step, [B, Tk, K, ...] fp32; time_
+    of every key, [B, K, ...], from the raw sums summed over the steps folded with time=True (Tn of them) with N = HW Tn: the
+    standard aggregation, not a mean of ratios; and iscale_blocks [L + 1] int64, the block sizes 2 .. 2^L, then 0 for the remainder."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, events=((0, 0.0, "<"),), levels=None):
+        noun = "ensemble intensity scales"
+        _ens_channels(noun, C)
+        if isinstance(steps, bool) or not isinstance(steps, numbers.Integral) or int(steps) < 1:
+            raise ValueError("%s need steps >= 1, got %r" % (noun, steps))
+        if int(B) < 1 or int(Hh) < 1 or int(Ww) < 1:
+            raise ValueError("%s need B, H, W >= 1, got %d, %d, %d" % (noun, B, Hh, Ww))
+        ev, L = iscale_args(events, levels, C, Hh, Ww)
+        _ens_members(noun, members)
+        sd, mu = _ens_tables(C, _KEEPS_ORDER, out_std, out_mu)
+        u = _ens_u(u, B, C, _KEEPS_ORDER)
+        S, Tk, HW, K = int(members), int(steps), int(Hh) * int(Ww), len(ev)
+        if int(B) > SPELL_MAX_CASES:
+            raise ValueError("%s take at most %d cases, got %d" % (noun, SPELL_MAX_CASES, int(B)))
+        pad = (-(-int(Hh) // 64) * 64) * (-(-int(Ww) // 64) * 64)
+        if S * S * 4 ** L * pad >= 2 ** 63:
+            raise ValueError("S^2 4^L H_pad W_pad = %d^2 * 4^%d * %d does not stay under 2^63 (the int64 raw sums)" % (S, L, pad))
+        if S * HW * Tk >= 2 ** 31:
+            raise ValueError("S HW Tk = %d * %d * %d does not stay under 2^31 (the int64 products of the skill scores)" % (S, HW, Tk))
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, C, Hh, Ww, steps)
+        self.L, self.K = L, K
+        self.events = ev
+        self.ev = _ens_directions(ev)
+        self.thr = raw_thresholds(ev, self.B, C, mu, sd, u).to(dev).contiguous()
+        self.plan = H.ens_iscale_plan(S, self.B, self.H, self.W, K, L)
+        i64 = dict(device=dev, dtype=torch.int64)
+        self.cnt = torch.empty((self.B, K, HW), device=dev, dtype=torch.int32)
+        self.member = torch.empty((Tk, self.B, K, S, L + 1, 2), **i64)
+        self.target = torch.empty((Tk, self.B, K, L + 1), **i64)
+        self.ens = torch.empty((Tk, self.B, K, L + 1, 2), **i64)
+
+    def add(self, y, m0, target, time=True):
+        """Fold the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
+        channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride rule.  The step's
+        first chunk zeroes the step's tables, its last chunk forms the sums of the ensemble count."""
+        yn, tn, k, _, last = self.open_chunk(y, m0, time, target, required=True)
+        _on_device(yn, tn)
+        t = self._step
+        H.ens_iscale_chunk(yn, tn, self.thr, self.ev, self.cnt, self.member[t], self.target[t], self.ens[t], self.S, k, m0)
+        if last:
+            H.ens_iscale_step(self.cnt, tn, self.thr, self.ev, self.ens[t], self.S)
+        self.close_chunk(m0, k, time, last)
+
+    def finalize(self):
+        """-> dict of the outputs; the time aggregates cover the steps folded with time=True."""
+        T = self.finalize_guard()
+        dev, S, HW = self.member.device, self.S, self.H * self.W
+        raw = [v.transpose(0, 1).contiguous() for v in (self.member, self.target, self.ens)]
+        o = dict(zip(ISCALE_RAW_KEYS, raw))
+        host = [v.cpu() for v in raw]
+        for key, v in iscale_outputs(*host, S, HW).items():
+            o[key] = v.to(dev)
+        timed = [v[:, self._timed].sum(1) for v in host]
+        for key, v in zip(ISCALE_RAW_KEYS, timed):
+            o["time_" + key] = v.to(dev)
+        for key, v in iscale_outputs(*timed, S, HW, T).items():
+            o["time_" + key] = v.to(dev)
+        o["iscale_blocks"] = torch.tensor([2 ** c for c in range(1, self.L + 1)] + [0], dtype=torch.int64)
+        return o
+
+
 PDF_MAX_FIELDS = 8
 PDF_MAX_BINS = 128
 PDF_MAX_JOINT_BINS = 32

@@ -702,6 +702,52 @@ def modelPredSpells(args, model, testing_loader, log, samples=1, stride=1, tmax=
     return _ensembleStats("modelPredSpells", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
 
 
+def modelPredIntensityScale(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, events=((0, 0.0, "<"),),
+                            levels=None):
+    """modelPredStats plus the intensity-scale verification of the members' events against the target's, still without forming
+    modelPred's [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleIntensityScale).  modelPredEvents says whether the event
+    probabilities are right pixel by pixel and, through the fractions skill score, from which neighbourhood width on they count as
+    skilful; this says at which spatial scale the error sits: a recirculation bubble drawn two pixels too long and one placed a
+    quarter of the domain away both lower the FSS at small widths, and differ here.  An event is (channel, value, ">" | "<"), strict,
+    in physical units, as modelPredEvents' (1 to 4 of them; (0, 0.0, "<") is reverse flow); a non-finite value is in no event.  The
+    binary error field I_member - I_target of every event is split into the orthogonal 2-D Haar components of dyadic block size 2,
+    4, .., 2^L (blocks aligned at pixel (0, 0), the field counting as zero outside H x W, so any H, W works) plus the coarse
+    remainder, and the mean squared error of each component is read against that of a spatially random forecast with the same event
+    rates (Casati, Ross & Stephenson 2004; the energy form of Casati 2010).  The same split of the probability error n / S - o
+    decomposes modelPredEvents' Brier score by scale, exactly, and the difference to the members' mean error is the ensemble's spread
+    at that scale.  levels: L in 1..6, None for max(1, min(6, floor(log2(min(H, W))))).  The target of kept step j is series step
+    j * stride; a series that is too short raises.  Same roll-outs as modelPredStats: under the same host RNG state the keys both
+    return are identical.
+
+    Returns modelPredStats' dict plus (CPU tensors; K events, S members, L + 1 components, the last the remainder):
+      iscale_member_raw [N, Tk, K, S, L+1, 2]   int64 (A, X): per level l = 0..L the sums over the blocks of s_l(I_m)^2 and s_l(I_m) s_l(o)
+      iscale_target_raw [N, Tk, K, L+1]         int64 Cc: of s_l(o)^2
+      iscale_ens_raw [N, Tk, K, L+1, 2]         int64 (AN, XN): of s_l(n)^2 and s_l(n) s_l(o), n the members in the event per pixel
+      iscale_mse [N, Tk, K, S, L+1]             the component energies of a member's error over H W; they sum to its share of
+                                                mismatched pixels
+      iscale_skill [N, Tk, K, S, L+1]           1 - (L+1) mse_c / (f + o - 2 f o), f and o the member's and the target's event
+                                                rates: 0 is no better than a random placement at that scale; NaN when that error is 0
+      iscale_energy [N, Tk, K, S+1, L+1]        the component energies of the members' indicators and, as row S, of the target's
+      iscale_energy_bias [N, Tk, K, S, L+1]     (Ef - Eo) / (Ef + Eo): too much (+) or too little (-) event structure at that
+                                                scale; NaN when both are 0
+      iscale_brier [N, Tk, K, L+1]              the component energies of n / S - o; they sum to modelPredEvents' brier
+      iscale_brier_skill [N, Tk, K, L+1]        against mean p^2 + o - 2 mean p o shared equally among the components; NaN at 0
+      iscale_spread [N, Tk, K, L+1]             the mean member mse minus iscale_brier, >= 0: the ensemble's spread at that scale
+      iscale_spread_skill [N, Tk, K, L+1]       spread over brier; NaN at 0 / 0
+      time_<key> [N, K, ...]                    every key above from the raw sums summed over the kept steps t_start..Tk-1, with the
+                                                event rates pooled: the standard aggregation, not a mean of ratios
+      iscale_blocks [L+1] int64, events         the block sizes 2 .. 2^L, then 0 for the remainder; the events as given."""
+    import tmg_ops as ops
+    events, _ = ops.event_args(events, (1,), 3)
+    events = tuple(events)
+    if levels is not None:
+        levels = ops.iscale_args(events, levels, 3, 1, 1)[1]
+    acc = _Acc(lambda mb, S, T: ops.EnsembleIntensityScale(S, mb.B, mb.C, mb.H, mb.W, T, mb.dev, mb.out_mu, mb.out_std, u=mb.u, events=events,
+                                                           levels=levels),
+               target=True, meta=("iscale_blocks",), extra={"events": events})
+    return _ensembleStats("modelPredIntensityScale", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
+
+
 def modelPredPdfs(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, fields=("ux", "uy", "p", "vort"),
                   bins=64, ranges=None, joint=(("ux", "uy"),), joint_bins=32, regions=None, center=None):
     """modelPredStats plus the probability densities of the flow quantities themselves, pooled over regions of the flow, for the
