@@ -2541,6 +2541,205 @@ class EnsembleIntensityScale(EnsembleFeed):
         return o
 
 
+MINK_MAX_FIELDS = 4
+MINK_MAX_LEVELS = 32
+MINK_CURVES = ("count", "edges", "euler4", "euler8")       # the four integer curves, in the order of the [.., 4, J] outputs
+MINK_L1_CURVES = ("area", "perimeter", "euler4", "euler8")  # the four curves of mink_l1
+MINK_INT_KEYS = ("mink_edges", "mink_euler4", "mink_euler8", "mink_below", "mink_equal")
+MINK_FLOAT_KEYS = ("mink_area", "mink_perimeter", "mink_euler4_density", "mink_euler8_density", "mink_mean", "mink_std", "mink_l1")
+
+
+def mink_args(fields, thresholds, C):
+    """The checks of EnsembleMorphology's fields and thresholds arguments for C channels.  fields: 1 to 4 distinct channel indices in
+    0..C-1 (no bools, no floats).  thresholds: per field a sequence of J strictly ascending finite values in physical units, 1 <= J <=
+    32, the same J for every field.  -> (fields as a tuple of ints, the ladder as a tuple of F tuples of J floats)."""
+    try:
+        fl = list(fields)
+    except TypeError:
+        raise ValueError("fields is a sequence of channel indices, got %r" % (fields,))
+    if not 1 <= len(fl) <= MINK_MAX_FIELDS:
+        raise ValueError("fields takes 1 to %d channels, got %d" % (MINK_MAX_FIELDS, len(fl)))
+    for i, c in enumerate(fl):
+        if isinstance(c, bool) or not isinstance(c, numbers.Integral) or not 0 <= c < C:
+            raise ValueError("fields are channel indices in 0..%d, got %r" % (C - 1, c))
+        if c in fl[:i]:
+            raise ValueError("fields must be distinct, got %r twice" % (c,))
+    try:
+        th = [list(t) for t in thresholds]
+    except TypeError:
+        raise ValueError("thresholds holds one sequence of values per field, got %r" % (thresholds,))
+    if len(th) != len(fl):
+        raise ValueError("thresholds holds one ladder per field: %d fields, %d ladders" % (len(fl), len(th)))
+    J = len(th[0])
+    if not 1 <= J <= MINK_MAX_LEVELS:
+        raise ValueError("a ladder holds 1 to %d levels, got %d" % (MINK_MAX_LEVELS, J))
+    for t in th:
+        if len(t) != J:
+            raise ValueError("every field takes the same number of levels, got %d and %d" % (J, len(t)))
+        for j, v in enumerate(t):
+            if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v):
+                raise ValueError("thresholds are finite numbers, got %r" % (v,))
+            if j and not t[j - 1] < v:
+                raise ValueError("a ladder is strictly ascending, got %r after %r" % (v, t[j - 1]))
+    return tuple(int(c) for c in fl), tuple(tuple(float(v) for v in t) for t in th)
+
+
+def mink_raw_ladder(levels, fields, mu, sd, u=None):
+    """The raw ladder of the physical one by raw_thresholds' rule, per case: levels [B, F, J] fp64 CPU tensor, fields the F channels,
+    mu, sd [C] fp32 CPU tensors, u [B, C] fp32 CPU tensor or None for 1 -> thr[b, f, j] = (levels / u[b, c] - out_mu[c]) / out_std[c]
+    in fp64, rounded once to fp32.  u out_std > 0 keeps the order; rounding may make neighbours equal."""
+    ch = list(fields)
+    B = levels.shape[0]
+    scd = torch.ones(B, mu.numel(), dtype=torch.float64) if u is None else u.double()
+    thr = (levels.double() / scd[:, ch].unsqueeze(-1) - mu.double()[ch].view(1, -1, 1)) / sd.double()[ch].view(1, -1, 1)
+    return thr.to(torch.float32)
+
+
+def mink_curves(raw):
+    """raw [..., J, 5] int64 (N, Nh, Nv, Nq, Nd) -> the four integer curves [..., 4, J] of MINK_CURVES: N, edges = 4 N - 2 Nh - 2 Nv,
+    chi4 = N - Nh - Nv + Nq, chi8 = chi4 - Nd."""
+    N, Nh, Nv, Nq, Nd = raw.unbind(-1)
+    chi4 = N - Nh - Nv + Nq
+    return torch.stack([N, 4 * N - 2 * Nh - 2 * Nv, chi4, chi4 - Nd], -2)
+
+
+def mink_outputs(raw, S, H, W, grid, steps=1, levels=None):
+    """The Minkowski functionals of the raw excursion-set counts of S members and the target over `steps` steps of H x W pixels
+    (pooled: the sums of the steps' tables): raw [..., S + 1, J, 5] int64 = (N, Nh, Nv, Nq, Nd), rows the members then the target,
+    grid = (dx along W, dy along H).  Host only: every integer combination is exact in int64, every float output is formed in fp64
+    and rounded to fp32 once.  With P = H W steps pixels and A = P dx dy the area -> dict:
+      mink_area [..., S + 1, J]             N / P: the share of the field above the level
+      mink_perimeter [..., S + 1, J]        (dy (2 N - 2 Nh) + dx (2 N - 2 Nv)) / A: boundary length per unit area, border included
+      mink_edges [..., S + 1, J] int64      4 N - 2 Nh - 2 Nv: exposed unit edges
+      mink_euler4, mink_euler8 [..., S + 1, J] int64   N - Nh - Nv + Nq (4-connected pieces minus 8-connected holes) and that minus
+                                            Nd (8-connected pieces minus 4-connected holes)
+      mink_euler4_density, mink_euler8_density [..., S + 1, J]   over A
+      mink_mean, mink_std [..., 4, J]       mean and population std over the members of the integer curves MINK_CURVES (N, edges,
+                                            chi4, chi8)
+      mink_below, mink_equal [..., 4, J] int64   the members whose curve lies strictly below / equals the target's: the exact rank
+                                            of the target within the ensemble, formed on the integers
+      mink_l1 [..., S, 4]                   with levels (the physical ladder, broadcastable to [..., J]): the trapezoid integral over
+                                            the ladder of |member - target| of MINK_L1_CURVES: area, perimeter and the two Euler
+                                            densities as above; 0 when J = 1."""
+    S, Hh, Ww, steps = int(S), int(H), int(W), int(steps)
+    raw = torch.as_tensor(raw)
+    if S < 1 or Hh < 1 or Ww < 1 or steps < 1 or raw.dtype != torch.int64 or raw.dim() < 3 or raw.shape[-3] != S + 1 or raw.shape[-1] != 5 \
+            or raw.shape[-2] < 1:
+        raise ValueError("mink_outputs takes an int64 table [..., %d, J, 5] with J >= 1 and S, H, W, steps >= 1, got %s %s"
+                         % (S + 1, raw.dtype, tuple(raw.shape)))
+    dx, dy = float(grid[0]), float(grid[1])
+    if not (math.isfinite(dx) and math.isfinite(dy) and dx > 0 and dy > 0):
+        raise ValueError("grid = (dx, dy) is finite and positive, got %r" % (grid,))
+    raw = raw.cpu()
+    P = Hh * Ww * steps
+    A = float(P) * dx * dy
+    f32 = lambda v: v.to(torch.float32)                                       # noqa: E731
+    length = lambda t: dy * (2 * t[..., 0] - 2 * t[..., 1]).double() + dx * (2 * t[..., 0] - 2 * t[..., 2]).double()   # noqa: E731
+    cur = mink_curves(raw)                                                    # [..., S + 1, 4, J]
+    o = {"mink_area": f32(raw[..., 0].double() / float(P)), "mink_perimeter": f32(length(raw) / A),
+         "mink_edges": cur[..., 1, :].contiguous(), "mink_euler4": cur[..., 2, :].contiguous(), "mink_euler8": cur[..., 3, :].contiguous()}
+    o["mink_euler4_density"] = f32(o["mink_euler4"].double() / A)
+    o["mink_euler8_density"] = f32(o["mink_euler8"].double() / A)
+    mem, tg = cur[..., :S, :, :], cur[..., S:, :, :]
+    md = mem.double()
+    mean = md.mean(-3, keepdim=True)
+    o["mink_mean"] = f32(mean.squeeze(-3))
+    o["mink_std"] = f32(((md - mean) ** 2).mean(-3).sqrt())
+    o["mink_below"] = (mem < tg).sum(-3)
+    o["mink_equal"] = (mem == tg).sum(-3)
+    if levels is not None:
+        lv = torch.as_tensor(levels, dtype=torch.float64).cpu()
+        J = raw.shape[-2]
+        if lv.shape[-1] != J:
+            raise ValueError("levels holds %d values per ladder, the table %d" % (lv.shape[-1], J))
+        dr = raw[..., :S, :, :] - raw[..., S:, :, :]                          # exact integer differences [..., S, J, 5]
+        dc = (mem - tg).abs().double()
+        d = torch.stack([dc[..., 0, :] / float(P), length(dr).abs() / A, dc[..., 2, :] / A, dc[..., 3, :] / A], -2)   # [..., S, 4, J]
+        wdt = (lv[..., 1:] - lv[..., :-1]).unsqueeze(-2).unsqueeze(-2)
+        o["mink_l1"] = f32((0.5 * (d[..., 1:] + d[..., :-1]) * wdt).sum(-1))
+    return o
+
+
+class EnsembleMorphology(EnsembleFeed):
+    """On-device excursion-set morphology of sampled roll-outs of B cases and of the target (tmg_ens_mink_chunk): the three Minkowski
+    functionals of the sets {x > level} of a field as the level moves up a ladder: how much area lies above the level, how long
+    its boundary is, and how many pieces and holes it has (the Euler characteristic, the "genus curve").  fields: 1 to 4 distinct
+    channels.  thresholds: per field J (1..32) strictly ascending physical values, [F][J] for all cases or [B, F, J] per case; they
+    are decided on the raw normalised values against the raw ladder of raw_thresholds' rule (u out_std > 0 keeps the order; rounding
+    may make neighbours equal).  The rank of a pixel is the number of levels strictly below its value: NaN and -Inf have rank 0,
+    +Inf rank J; the set of level j holds the pixels of rank > j.  Rows are the S members, then the target as row S.  Per row, case,
+    kept step, field and level the device counts the pixels in the set (N), the horizontal and vertical neighbour pairs with both in
+    (Nh, Nv), the 2 x 2 quads with all four in (Nq) and those with exactly a diagonal pair in (Nd), inside the field only;
+    mink_outputs forms the functionals on the host.  grid = (dx along W, dy along H).
+
+    A chunk is read straight from its NHWC rows, once for all fields and levels: no member buffer, no per-pixel state.  The device
+    memory of this class is the tables, 40 Tk B F (S + 1) J bytes.  Limits: members <= 1024, B <= 65535, H W < 2^31 - 256.
+
+    Feeding protocol of EnsembleFeed: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
+    chunks before the next step's; every chunk comes with the step's target (the step's first chunk counts it).
+    finalize() returns mink_raw [B, Tk, F, S + 1, J, 5] int64 on the device; mink_outputs' keys per step, [B, Tk, F, ...]; time_ of
+    every key, [B, F, ...], from the raw sums summed over the steps folded with time=True (Tn of them) with H W Tn pixels as the
+    area: the standard aggregation, not a mean of ratios; and mink_levels [B, F, J] float64, the physical ladder."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, fields=(0,), thresholds=((0.0,),), grid=(1.0, 1.0)):
+        noun = "ensemble morphology"
+        _ens_channels(noun, C)
+        if isinstance(steps, bool) or not isinstance(steps, numbers.Integral) or int(steps) < 1:
+            raise ValueError("%s needs steps >= 1, got %r" % (noun, steps))
+        if int(B) < 1 or int(Hh) < 1 or int(Ww) < 1:
+            raise ValueError("%s needs B, H, W >= 1, got %d, %d, %d" % (noun, B, Hh, Ww))
+        if int(B) > SPELL_MAX_CASES:
+            raise ValueError("%s takes at most %d cases, got %d" % (noun, SPELL_MAX_CASES, int(B)))
+        if int(Hh) * int(Ww) >= 2 ** 31 - 256:
+            raise ValueError("%s needs H W < 2^31 - 256, got %d x %d" % (noun, Hh, Ww))
+        if isinstance(thresholds, torch.Tensor) and thresholds.dim() == 3:     # a ladder per case
+            if thresholds.shape[0] != int(B):
+                raise ValueError("thresholds per case are [%d, F, J], got %s" % (int(B), tuple(thresholds.shape)))
+            rows = [mink_args(fields, t.tolist(), C) for t in thresholds.detach().double().cpu()]
+            fl, lv = rows[0][0], torch.tensor([r[1] for r in rows], dtype=torch.float64)
+        else:
+            fl, th = mink_args(fields, thresholds.tolist() if isinstance(thresholds, torch.Tensor) else thresholds, C)
+            lv = torch.tensor(th, dtype=torch.float64).unsqueeze(0).repeat(int(B), 1, 1)
+        dx, dy = float(grid[0]), float(grid[1])
+        if len(grid) != 2 or not (math.isfinite(dx) and math.isfinite(dy) and dx > 0 and dy > 0):
+            raise ValueError("grid = (dx, dy) is finite and positive, got %r" % (grid,))
+        _ens_members(noun, members)
+        sd, mu = _ens_tables(C, _KEEPS_ORDER, out_std, out_mu)
+        u = _ens_u(u, B, C, _KEEPS_ORDER)
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, C, Hh, Ww, steps)
+        self.fields, self.levels, self.grid = fl, lv, (dx, dy)
+        self.F, self.J = len(fl), lv.shape[2]
+        self.thr = mink_raw_ladder(lv, fl, mu, sd, u).to(dev).contiguous()
+        self.plan = H.ens_mink_plan(self.S, self.B, self.H, self.W, self.F, self.J)
+        self.table = torch.empty((self.Tk, self.B, self.F, self.S + 1, self.J, 5), device=dev, dtype=torch.int64)
+
+    def add(self, y, m0, target, time=True):
+        """Fold the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
+        channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride rule.  The step's
+        first chunk zeroes the step's table and counts the target's row."""
+        yn, tn, k, _, last = self.open_chunk(y, m0, time, target, required=True)
+        _on_device(yn, tn)
+        H.ens_mink_chunk(yn, tn, self.thr, self.fields, self.table[self._step], self.S, k, m0)
+        self.close_chunk(m0, k, time, last)
+
+    def finalize(self):
+        """-> dict of the outputs; the time aggregates cover the steps folded with time=True."""
+        T = self.finalize_guard()
+        dev, S = self.table.device, self.S
+        raw = self.table.transpose(0, 1).contiguous()
+        o = {"mink_raw": raw}
+        host = raw.cpu()
+        for key, v in mink_outputs(host, S, self.H, self.W, self.grid, 1, self.levels.unsqueeze(1)).items():
+            o[key] = v.to(dev)
+        timed = host[:, self._timed].sum(1)
+        o["time_mink_raw"] = timed.to(dev)
+        for key, v in mink_outputs(timed, S, self.H, self.W, self.grid, T, self.levels).items():
+            o["time_" + key] = v.to(dev)
+        o["mink_levels"] = self.levels.clone()
+        return o
+
+
 PDF_MAX_FIELDS = 8
 PDF_MAX_BINS = 128
 PDF_MAX_JOINT_BINS = 32

@@ -748,6 +748,77 @@ def modelPredIntensityScale(args, model, testing_loader, log, samples=1, stride=
     return _ensembleStats("modelPredIntensityScale", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
 
 
+def _morphology_factory(name, grid, stride, t_start, fields, thresholds, levels):
+    """The make of modelPredMorphology's record.  thresholds None: per case and field `levels` values evenly spaced on the mean +- 2
+    population std of the target's physical values over the kept steps from t_start on (plain torch in fp64; one level: the mean)."""
+    def make(mb, members, steps):
+        import tmg_ops as ops
+        th = thresholds
+        if th is None:
+            tk = mb.tgt[:, t_start * stride:(steps - 1) * stride + 1:stride, list(fields)].double()       # [B, Tn, F, H, W]
+            v = tk.permute(0, 2, 1, 3, 4).reshape(mb.B, len(fields), -1)
+            mean = v.mean(-1, keepdim=True)
+            sd = ((v - mean) ** 2).mean(-1, keepdim=True).sqrt()
+            bad = ~(torch.isfinite(sd) & (sd > 0) & torch.isfinite(mean)).reshape(mb.B, -1).all(1)
+            if bool(bad.any()):
+                raise ValueError("%s: a field of the target of case %d is constant or not finite: give thresholds"
+                                 % (name, mb.case0 + int(bad.nonzero()[0])))
+            pos = torch.linspace(-2.0, 2.0, levels, dtype=torch.float64, device=v.device) if levels > 1 \
+                else torch.zeros(1, dtype=torch.float64, device=v.device)
+            th = (mean + sd * pos).cpu()
+        return ops.EnsembleMorphology(members, mb.B, mb.C, mb.H, mb.W, steps, mb.dev, mb.out_mu, mb.out_std, u=mb.u, fields=fields,
+                                      thresholds=th, grid=grid)
+    return make
+
+
+def modelPredMorphology(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, fields=(0,), thresholds=None,
+                        levels=16):
+    """modelPredStats plus the excursion-set morphology of every member and of the target, still without forming modelPred's
+    [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleMorphology): the three Minkowski functionals of the sets {x > level} of a field
+    as the level moves up a ladder: how much area lies above the level, how long its boundary is, and how many pieces and holes it
+    has (the Euler characteristic or genus curve), the standard morphology diagnostic of random and turbulent fields.  The other
+    diagnostics judge a roll-out pixel by pixel, scale by scale, along time, or by vortex objects at one criterion; a member can have
+    the right pixel PDF and the right spectrum and still be speckled or over-smooth.  It then has the target's area curve, a wrong
+    boundary length and an Euler characteristic wrong by a factor.  Reading the keys: equal mink_area but larger mink_edges and
+    |mink_euler*| than the target's means speckle (many small pieces or holes); smaller means over-smooth; mink_euler4 and
+    mink_euler8 far apart means one-pixel diagonal structure (pieces that touch only at corners); mink_below / mink_equal say where the
+    target's curve ranks among the members', and mink_l1 is one number per member and curve for how far its curve is from the
+    target's.  fields: 1 to 4 distinct channels of (ux, uy, p).  thresholds: per field J (1..32) strictly ascending physical values,
+    the same for every case; None: per case and field `levels` (1..32) values evenly spaced on the mean +- 2 population std of the
+    target over the kept steps t_start..Tk-1 (one level: the mean); a constant target raises.  Compares are strict; NaN is in no set,
+    +Inf in every one.  The grid is (args.dx along W, args.dy along H); the target of kept step j is series step j * stride; a series
+    that is too short raises.  Same roll-outs as modelPredStats: under the same host RNG state the keys both return are identical.
+
+    Returns modelPredStats' dict plus (CPU tensors; F fields, R = S + 1 rows, the members then the target, J levels):
+      mink_raw [N, Tk, F, R, J, 5]             int64 (N, Nh, Nv, Nq, Nd): pixels in the set, horizontal / vertical pairs with both in,
+                                               2 x 2 quads with all four in, quads with exactly a diagonal pair in; in-field only
+      mink_area [N, Tk, F, R, J]               the share of the field above the level
+      mink_perimeter [N, Tk, F, R, J]          boundary length per unit area, the field's border included
+      mink_edges [N, Tk, F, R, J] int64        exposed unit edges 4 N - 2 Nh - 2 Nv
+      mink_euler4, mink_euler8 [.., R, J] int64   4-connected pieces minus 8-connected holes; 8-connected pieces minus 4-connected holes
+      mink_euler4_density, mink_euler8_density    per unit area
+      mink_mean, mink_std [N, Tk, F, 4, J]     mean and population std over the members of the curves (N, edges, euler4, euler8)
+      mink_below, mink_equal [N, Tk, F, 4, J]  int64: the members strictly below / equal to the target on those curves
+      mink_l1 [N, Tk, F, S, 4]                 the trapezoid integral over the physical ladder of |member - target| of (area,
+                                               perimeter, euler4 density, euler8 density); 0 when J = 1
+      time_<key> [N, F, ...]                   every key above from the raw counts summed over the kept steps t_start..Tk-1, with
+                                               H W Tn pixels as the area: the standard aggregation, not a mean of ratios
+      mink_levels [N, F, J] float64, fields    the physical ladder of every case; the fields as given.
+    Not supported: derived fields such as vorticity, periodic domains (pairs and quads across the border are not counted), a
+    Gaussian-random-field reference curve to read the genus curve against."""
+    import tmg_ops as ops
+    if thresholds is None:
+        if isinstance(levels, bool) or not isinstance(levels, numbers.Integral) or not 1 <= levels <= ops.MINK_MAX_LEVELS:
+            raise ValueError("levels is an integer in 1..%d, got %r" % (ops.MINK_MAX_LEVELS, levels))
+        fields = ops.mink_args(fields, [[0.0]] * (len(fields) if hasattr(fields, "__len__") else 1), 3)[0]
+    else:
+        fields, thresholds = ops.mink_args(fields, thresholds, 3)
+    acc = _Acc(_morphology_factory("modelPredMorphology", (float(args.dx), float(args.dy)), stride, t_start, fields, thresholds,
+                                   None if thresholds is not None else int(levels)),
+               target=True, extra={"fields": fields})
+    return _ensembleStats("modelPredMorphology", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
+
+
 def modelPredPdfs(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, fields=("ux", "uy", "p", "vort"),
                   bins=64, ranges=None, joint=(("ux", "uy"),), joint_bins=32, regions=None, center=None):
     """modelPredStats plus the probability densities of the flow quantities themselves, pooled over regions of the flow, for the
