@@ -2740,6 +2740,224 @@ class EnsembleMorphology(EnsembleFeed):
         return o
 
 
+DIST_MAX_CUTOFF = 255
+DIST_MAX_SIDE = 4096
+DIST_MAX_QUANTILES = 8
+DIST_INF = 1 << 30
+DIST_PAIR = ("nA", "nO", "nAO", "sOA1", "sOA2", "sAO1", "sAO2", "sD1", "sD2", "hOA", "hAO")    # the last axis of dist_pair_raw
+DIST_SUMMARY = ("dist_med_miss", "dist_med_false", "dist_med", "dist_hausdorff", "dist_baddeley", "dist_csi")   # dist_mean / dist_std
+DIST_FLOAT_KEYS = ("dist_med_miss", "dist_med_false", "dist_rms_miss", "dist_rms_false", "dist_med", "dist_hausdorff_miss",
+                   "dist_hausdorff_false", "dist_hausdorff", "dist_hausdorff_q", "dist_baddeley", "dist_baddeley1", "dist_csi",
+                   "dist_mean", "dist_std")
+
+
+def dist_args(events, cutoff, quantiles, C, H, W):
+    """The checks of EnsembleDistance's events, cutoff and quantiles arguments for C channels of [H, W].  events: event_args' rules
+    and messages (channel in 0..C-1, finite value, '>' or '<'; 1 to 4 of them).  cutoff: the distance c in whole pixels at which the
+    fixed-point distances saturate, an integer in 1..255 (no bools, no floats), or None for max(1, min(255, max(H, W) // 4)).
+    quantiles: 1 to 8 probabilities in (0, 1] (no bools) of the partial Hausdorff distance.  -> (events as tuples, c, quantiles as a
+    tuple of floats)."""
+    ev, _ = event_args(events, (1,), C)
+    if cutoff is None:
+        if int(H) < 1 or int(W) < 1:
+            raise ValueError("cutoff=None needs H, W >= 1, got %d, %d" % (H, W))
+        c = max(1, min(DIST_MAX_CUTOFF, max(int(H), int(W)) // 4))
+    elif isinstance(cutoff, bool) or not isinstance(cutoff, numbers.Integral) or not 1 <= cutoff <= DIST_MAX_CUTOFF:
+        raise ValueError("cutoff is an integer in 1..%d (whole pixels) or None, got %r" % (DIST_MAX_CUTOFF, cutoff))
+    else:
+        c = int(cutoff)
+    try:
+        ql = list(quantiles)
+    except TypeError:
+        raise ValueError("quantiles is a sequence of probabilities, got %r" % (quantiles,))
+    if not 1 <= len(ql) <= DIST_MAX_QUANTILES:
+        raise ValueError("quantiles takes 1 to %d probabilities, got %d" % (DIST_MAX_QUANTILES, len(ql)))
+    for q in ql:
+        if isinstance(q, bool) or not isinstance(q, numbers.Real) or not 0.0 < q <= 1.0:
+            raise ValueError("quantiles are probabilities in (0, 1], got %r" % (q,))
+    return ev, c, tuple(float(q) for q in ql)
+
+
+def dist_outputs(pair_raw, hist_raw, S, H, W, cutoff, quantiles, steps=1):
+    """The distance-map scores of the raw sums of S members over `steps` steps of H x W pixels (pooled: sums added, maxima maxed):
+    pair_raw [..., S, 11] = DIST_PAIR, hist_raw [..., S, 2, c + 1], int64, c = cutoff.  Host only: every float output is formed in
+    fp64 from the integers and rounded to fp32 once.  Distances are in pixels.  A is a member's event set, O the target's -> dict:
+      dist_med_miss [..., S]        sOA1 / (256 nO): the mean distance from the target's event pixels to the member's set (how far
+                                    the misses are), distances cut at c; NaN when O is empty
+      dist_med_false [..., S]       sAO1 / (256 nA): from the member's event pixels to the target's set (the false alarms); NaN when
+                                    A is empty
+      dist_rms_miss, dist_rms_false sqrt(sOA2 / nO) / 256 and sqrt(sAO2 / nA) / 256, NaN alike
+      dist_med [..., S]             max(dist_med_miss, dist_med_false): the modified Hausdorff distance of Dubuisson & Jain; NaN
+                                    when either is
+      dist_hausdorff_miss, dist_hausdorff_false, dist_hausdorff [..., S]   sqrt(hOA), sqrt(hAO) and the larger: the directed and
+                                    the symmetric Hausdorff distance, uncut; 0 when both sets are empty, inf when exactly one is (or
+                                    when a pooled step had one set empty against a non-empty other)
+      dist_hausdorff_q [..., S, 2, NQ]   the partial Hausdorff distance in whole pixels, miss then false: the smallest bin j whose
+                                    cumulative count reaches ceil(q n), formed on the integers (c stands for "c or more"); NaN for
+                                    an empty set
+      dist_baddeley [..., S]        sqrt(sD2 / (H W steps)) / 256: Baddeley's delta with p = 2 and the cutoff transform min(d, c)
+      dist_baddeley1 [..., S]       sD1 / (256 H W steps): the same with p = 1
+      dist_csi [..., S]             nAO / (nA + nO - nAO): the critical success index, NaN when both sets are empty
+      dist_mean, dist_std [..., 6]  mean and population std over the members of DIST_SUMMARY, non-finite values dropped; NaN
+                                    when none is left
+      dist_valid [..., 6] int64     the members kept."""
+    import fractions
+    S, Hh, Ww, steps = int(S), int(H), int(W), int(steps)
+    pair_raw, hist_raw = torch.as_tensor(pair_raw), torch.as_tensor(hist_raw)
+    _, c, ql = dist_args(((0, 0.0, "<"),), cutoff, quantiles, 2, Hh, Ww)
+    if S < 1 or Hh < 1 or Ww < 1 or steps < 1 or pair_raw.dtype != torch.int64 or hist_raw.dtype != torch.int64 or pair_raw.dim() < 2 \
+            or tuple(pair_raw.shape[-2:]) != (S, len(DIST_PAIR)) or tuple(hist_raw.shape) != tuple(pair_raw.shape[:-1]) + (2, c + 1):
+        raise ValueError("dist_outputs takes int64 tables [..., %d, %d] and [..., %d, 2, %d] and S, H, W, steps >= 1, got %s %s and %s %s"
+                         % (S, len(DIST_PAIR), S, c + 1, pair_raw.dtype, tuple(pair_raw.shape), hist_raw.dtype, tuple(hist_raw.shape)))
+    pair, hist = pair_raw.cpu(), hist_raw.cpu()
+    nA, nO, nAO, sOA1, sOA2, sAO1, sAO2, sD1, sD2, hOA, hAO = (v.double() for v in pair.unbind(-1))
+    P = float(Hh * Ww * steps)
+    o = {"dist_med_miss": sOA1 / (256.0 * nO), "dist_med_false": sAO1 / (256.0 * nA),
+         "dist_rms_miss": (sOA2 / nO).sqrt() / 256.0, "dist_rms_false": (sAO2 / nA).sqrt() / 256.0}
+    o["dist_med"] = torch.maximum(o["dist_med_miss"], o["dist_med_false"])
+    noA, noO = pair[..., 0] == 0, pair[..., 1] == 0
+    inf, zero = torch.full_like(nA, float("inf")), torch.zeros_like(nA)
+
+    def directed(h):
+        v = torch.where(h >= float(DIST_INF), inf, h.clamp(min=0.0).sqrt())
+        return torch.where(noA & noO, zero, torch.where(noA | noO, inf, v))
+    o["dist_hausdorff_miss"], o["dist_hausdorff_false"] = directed(hOA), directed(hAO)
+    o["dist_hausdorff"] = torch.maximum(o["dist_hausdorff_miss"], o["dist_hausdorff_false"])
+    # the quantiles: ceil(q n) in exact rational arithmetic on the integer n, then a count of the bins whose cumulative sum is short
+    cum = hist.cumsum(-1)
+    n = cum[..., -1]
+    hq = []
+    for q in ql:
+        fq = fractions.Fraction(q)
+        need = torch.tensor([-((-int(v) * fq.numerator) // fq.denominator) for v in n.reshape(-1).tolist()], dtype=torch.int64).reshape(n.shape)
+        j = (cum < need.unsqueeze(-1)).sum(-1).double()
+        hq.append(torch.where(n > 0, j, torch.full_like(j, float("nan"))))
+    o["dist_hausdorff_q"] = torch.stack(hq, -1)
+    o["dist_baddeley"] = (sD2 / P).sqrt() / 256.0
+    o["dist_baddeley1"] = sD1 / (256.0 * P)
+    o["dist_csi"] = nAO / (nA + nO - nAO)
+    stack = torch.stack([o[k] for k in DIST_SUMMARY], -1)                       # [..., S, 6]
+    ok = torch.isfinite(stack)
+    cnt = ok.sum(-2)
+    val = torch.where(ok, stack, torch.zeros_like(stack))
+    mean = val.sum(-2) / cnt.double()                                          # 0 / 0: NaN
+    dev = torch.where(ok, stack - mean.unsqueeze(-2), torch.zeros_like(stack))
+    o["dist_mean"] = mean
+    o["dist_std"] = ((dev * dev).sum(-2) / cnt.double()).sqrt()
+    o = {k: v.to(torch.float32) for k, v in o.items()}
+    o["dist_valid"] = cnt.to(torch.int64)
+    return o
+
+
+def dist_pool(pair_raw, hist_raw, dim):
+    """The tables of several steps pooled along `dim`: sums added, the two maxima (hOA, hAO) maxed, so that a -1 (an empty set)
+    stays only when every step's is -1 -> (pair, hist)."""
+    pair = torch.cat([pair_raw[..., :9].sum(dim), pair_raw[..., 9:].max(dim).values], -1)
+    return pair, hist_raw.sum(dim)
+
+
+class EnsembleDistance(EnsembleFeed):
+    """On-device distance-map verification of sampled roll-outs of B cases against the target (tmg_ens_edt_chunk / tmg_ens_edt_step):
+    how far a member's event set lies from the target's, which overlap, neighbourhood, scale and morphology scores do not say (a
+    bubble drawn six pixels downstream and one a quarter of the domain away both have zero overlap).  An event k is (channel, value,
+    ">" | "<"), strict, in physical units ((0, 0.0, "<") is reverse flow), decided on the raw normalised values against
+    raw_thresholds (u out_std > 0 keeps the order); a value that compares false (NaN, an infinity on the wrong side) is in no event.
+    Per case, kept step and event, A is a member's event set and O the target's.  The device forms the exact squared Euclidean
+    distance d2_A(p) of every pixel to A (an integer, in pixels, over the whole field, INF = 2^30 for an empty set), likewise d2_O,
+    and from them, with the fixed-point distance w = 256 c if d2 >= c^2 else isqrt(65536 d2) (floor(256 d), c = cutoff in 1..255
+    pixels, None: max(1, min(255, max(H, W) // 4))), the eleven integers DIST_PAIR per member, two histograms of the whole-pixel
+    distances and per-pixel sums; dist_outputs forms the mean error distance, the Hausdorff distances, their quantiles, Baddeley's
+    delta and the critical success index on the host.  Everything the device forms is an integer: bitwise the same for every
+    chunking and run.
+
+    A chunk is read straight from its NHWC rows.  The device memory of this class: the indicator words, 8 (S + 1) B K H ceil(W / 64)
+    bytes; the target's map and the step's member sum, 4 B K HW bytes each; the two time maps, 8 B K HW bytes each; the set sizes,
+    4 B K (S + 1) bytes; and the tables, 8 Tk B K S (11 + 2 (c + 1)) bytes.  Limits: members <= 1024, B <= 65535, H, W <= 4096,
+    H W < 2^31 - 256.  Not supported: anisotropic metrics (pixels are the unit, as for the FSS widths and the Haar blocks), periodic
+    domains, Pratt's figure of merit, distances finer than 1 / 256 pixel.
+
+    Feeding protocol of EnsembleFeed: every step's members in chunks of whole members, in member order (m0 = 0 first), each step's
+    chunks before the next step's; every chunk comes with the step's target (the step's first chunk forms its distance map).
+    finalize() returns dist_pair_raw [B, Tk, K, S, 11] and dist_hist_raw [B, Tk, K, S, 2, c + 1] int64 on the device; dist_outputs'
+    keys per step, [B, Tk, K, ...]; time_ of every key, [B, K, ...], from the raw sums pooled over the steps folded with time=True (Tn
+    of them: sums added, maxima maxed, H W Tn pixels as the area: the standard aggregation, not a mean of ratios);
+    time_dist_member_sum and time_dist_target_sum [B, K, H, W] int64, the sums over those steps (and the members) of w_A(p) and of
+    w_O(p); time_dist_mean_map = member_sum / (256 S Tn), the ensemble's mean distance from the pixel to the event, and
+    time_dist_bias_map = that minus target_sum / (256 Tn), positive where the ensemble keeps the event farther from the pixel than
+    the target does; dist_cutoff (int64 scalar) and dist_quantiles [NQ] float64."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, events=((0, 0.0, "<"),), cutoff=None,
+                 quantiles=(0.5, 0.75, 0.9)):
+        noun = "ensemble distance maps"
+        _ens_channels(noun, C)
+        if isinstance(steps, bool) or not isinstance(steps, numbers.Integral) or int(steps) < 1:
+            raise ValueError("%s need steps >= 1, got %r" % (noun, steps))
+        if int(B) < 1 or int(Hh) < 1 or int(Ww) < 1:
+            raise ValueError("%s need B, H, W >= 1, got %d, %d, %d" % (noun, B, Hh, Ww))
+        ev, c, ql = dist_args(events, cutoff, quantiles, C, Hh, Ww)
+        _ens_members(noun, members)
+        sd, mu = _ens_tables(C, _KEEPS_ORDER, out_std, out_mu)
+        u = _ens_u(u, B, C, _KEEPS_ORDER)
+        if int(B) > SPELL_MAX_CASES:
+            raise ValueError("%s take at most %d cases, got %d" % (noun, SPELL_MAX_CASES, int(B)))
+        if int(Hh) > DIST_MAX_SIDE or int(Ww) > DIST_MAX_SIDE:
+            raise ValueError("%s need H, W <= %d, got %d x %d" % (noun, DIST_MAX_SIDE, Hh, Ww))
+        if int(Hh) * int(Ww) >= 2 ** 31 - 256:
+            raise ValueError("%s need H W < 2^31 - 256, got %d x %d" % (noun, Hh, Ww))
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, C, Hh, Ww, steps)
+        S, Tk, HW, K = self.S, self.Tk, self.H * self.W, len(ev)
+        self.K, self.cutoff, self.quantiles = K, c, ql
+        self.events = ev
+        self.ev = _ens_directions(ev)
+        self.thr = raw_thresholds(ev, self.B, C, mu, sd, u).to(dev).contiguous()
+        self.plan = H.ens_edt_plan(S, self.B, self.H, self.W, K, c)
+        i32, i64 = dict(device=dev, dtype=torch.int32), dict(device=dev, dtype=torch.int64)
+        self.scratch = torch.empty((S + 1, self.B, K, self.H, self.plan["strips"]), **i64)
+        self.count = torch.empty((self.B, K, S + 1), **i32)
+        self.dmap = torch.empty((self.B, K, HW), **i32)
+        self.msum = torch.empty((self.B, K, HW), **i32)
+        self.pair = torch.empty((Tk, self.B, K, S, len(DIST_PAIR)), **i64)
+        self.hist = torch.empty((Tk, self.B, K, S, 2, c + 1), **i64)
+        self.tmem = torch.zeros((self.B, K, HW), **i64)
+        self.ttgt = torch.zeros((self.B, K, HW), **i64)
+
+    def add(self, y, m0, target, time=True):
+        """Fold the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
+        channel-slice; rows member-major); target: the step's normalised target [B, C, H, W] under the same stride rule.  The step's
+        first chunk presets the step's tables and forms the target's distance map; its last chunk, with time=True, folds the step
+        into the time maps."""
+        yn, tn, k, _, last = self.open_chunk(y, m0, time, target, required=True)
+        _on_device(yn, tn)
+        t = self._step
+        H.ens_edt_chunk(yn, tn, self.thr, self.ev, self.scratch, self.count, self.dmap, self.msum, self.pair[t], self.hist[t], self.S, k, m0)
+        if last and time:
+            H.ens_edt_step(self.msum, self.dmap, self.tmem, self.ttgt, self.H, self.W, self.cutoff)
+        self.close_chunk(m0, k, time, last)
+
+    def finalize(self):
+        """-> dict of the outputs; the time aggregates cover the steps folded with time=True."""
+        T = self.finalize_guard()
+        dev, S = self.pair.device, self.S
+        pair, hist = self.pair.transpose(0, 1).contiguous(), self.hist.transpose(0, 1).contiguous()
+        o = {"dist_pair_raw": pair, "dist_hist_raw": hist}
+        hp, hh = pair.cpu(), hist.cpu()
+        for key, v in dist_outputs(hp, hh, S, self.H, self.W, self.cutoff, self.quantiles).items():
+            o[key] = v.to(dev)
+        tp, th = dist_pool(hp[:, self._timed], hh[:, self._timed], 1)
+        o["time_dist_pair_raw"], o["time_dist_hist_raw"] = tp.to(dev), th.to(dev)
+        for key, v in dist_outputs(tp, th, S, self.H, self.W, self.cutoff, self.quantiles, T).items():
+            o["time_" + key] = v.to(dev)
+        shp = (self.B, self.K, self.H, self.W)
+        o["time_dist_member_sum"], o["time_dist_target_sum"] = self.tmem.view(shp), self.ttgt.view(shp)
+        mean = self.tmem.view(shp).double() / (256.0 * S * T)
+        o["time_dist_mean_map"] = mean.to(torch.float32)
+        o["time_dist_bias_map"] = (mean - self.ttgt.view(shp).double() / (256.0 * T)).to(torch.float32)
+        o["dist_cutoff"] = torch.tensor(self.cutoff, dtype=torch.int64)
+        o["dist_quantiles"] = torch.tensor(self.quantiles, dtype=torch.float64)
+        return o
+
+
 PDF_MAX_FIELDS = 8
 PDF_MAX_BINS = 128
 PDF_MAX_JOINT_BINS = 32

@@ -819,6 +819,65 @@ def modelPredMorphology(args, model, testing_loader, log, samples=1, stride=1, t
     return _ensembleStats("modelPredMorphology", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
 
 
+def modelPredDistance(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, events=((0, 0.0, "<"),),
+                      cutoff=None, quantiles=(0.5, 0.75, 0.9)):
+    """modelPredStats plus the distance-map verification of the members' events against the target's, still without forming
+    modelPred's [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleDistance).  modelPredEvents says whether the event probabilities
+    are right pixel by pixel and from which neighbourhood width on they count as skilful, modelPredIntensityScale at which dyadic
+    scale the error sits, modelPredMorphology how speckled the sets are; none says how FAR a member's event set lies from the
+    target's: a recirculation bubble drawn six pixels downstream of the target's and one drawn a quarter of the domain away both
+    give zero overlap, similar FSS at small widths and identical Minkowski curves, and differ here.  These are the distance-map
+    measures of spatial forecast verification (Gilleland 2011; Baddeley 1992; Dubuisson & Jain 1994), all formed from the exact
+    Euclidean distance transform of the event sets, in pixels.  An event is (channel, value, ">" | "<"), strict, in physical units,
+    as modelPredEvents' (1 to 4 of them; (0, 0.0, "<") is reverse flow); a non-finite value is in no event.  cutoff: the distance c
+    in whole pixels (1..255; None: max(1, min(255, max(H, W) // 4))) at which the distances behind the means and Baddeley's delta
+    saturate, so that one stray pixel far away cannot dominate them; the Hausdorff distances are uncut.  quantiles: the
+    probabilities of the partial Hausdorff distance.  Reading the keys: dist_med_miss large with dist_med_false small means the
+    member's event covers only part of the target's (the rest is far from anything forecast); the reverse means spurious event area
+    away from the target's; both of the size of a shift mean a displaced copy.  dist_hausdorff is the worst single pixel and reacts
+    to one speck; dist_hausdorff_q at 0.9 forgives a tenth of the pixels; dist_baddeley also sees where neither set is and is a
+    metric between the sets; dist_csi is the plain overlap, for contrast.  time_dist_bias_map > 0 marks where the ensemble keeps the
+    event farther from the pixel than the target does.  The target of kept step j is series step j * stride; a series that is too
+    short raises.  Same roll-outs as modelPredStats: under the same host RNG state the keys both return are identical.
+
+    Returns modelPredStats' dict plus (CPU tensors; K events, S members, A a member's event set, O the target's):
+      dist_pair_raw [N, Tk, K, S, 11]           int64 (nA, nO, nAO, sOA1, sOA2, sAO1, sAO2, sD1, sD2, hOA, hAO): set sizes and
+                                                overlap; the sums over O of w_A and w_A^2 and over A of w_O and w_O^2, w = floor(256
+                                                min(d, c)); the sums over all pixels of |w_A - w_O| and its square; the maxima over O
+                                                of d2_A and over A of d2_O (squared pixels, uncut; -1 for an empty set, 2^30 against
+                                                an empty set)
+      dist_hist_raw [N, Tk, K, S, 2, c+1]       int64: over O the counts by min(floor(d_A), c), over A by min(floor(d_O), c)
+      dist_med_miss, dist_med_false [N, Tk, K, S]   the mean error distances, target-to-member and member-to-target; NaN for an
+                                                empty O / A
+      dist_rms_miss, dist_rms_false             their root-mean-square forms
+      dist_med [N, Tk, K, S]                    the larger of the two means: the modified Hausdorff distance
+      dist_hausdorff_miss, dist_hausdorff_false, dist_hausdorff [N, Tk, K, S]   directed and symmetric Hausdorff distances; 0 when
+                                                both sets are empty, inf when exactly one is
+      dist_hausdorff_q [N, Tk, K, S, 2, NQ]     the partial Hausdorff distances in whole pixels (miss, false); c means "c or more";
+                                                NaN for an empty set
+      dist_baddeley, dist_baddeley1 [N, Tk, K, S]   Baddeley's delta with p = 2 and p = 1 on min(d, c)
+      dist_csi [N, Tk, K, S]                    nAO / (nA + nO - nAO); NaN when both sets are empty
+      dist_mean, dist_std [N, Tk, K, 6], dist_valid int64   mean and population std over the members of (dist_med_miss,
+                                                dist_med_false, dist_med, dist_hausdorff, dist_baddeley, dist_csi), non-finite
+                                                values dropped, and how many members were kept
+      time_<key> [N, K, ...]                    every key above from the raw sums pooled over the kept steps t_start..Tk-1 (sums
+                                                added, maxima maxed, H W Tn pixels as the area): not a mean of ratios
+      time_dist_member_sum, time_dist_target_sum [N, K, H, W] int64   the sums over those steps (and the members) of w_A(p), of w_O(p)
+      time_dist_mean_map [N, K, H, W]           member_sum / (256 S Tn): the ensemble's mean distance from the pixel to the event
+      time_dist_bias_map [N, K, H, W]           that minus target_sum / (256 Tn)
+      dist_cutoff, dist_quantiles, events       c (int64 scalar), the probabilities (float64), the events as given.
+    Not supported: anisotropic metrics (pixels are the unit, as for modelPredEvents' widths), periodic domains, Pratt's figure of
+    merit, distances finer than 1 / 256 pixel."""
+    import tmg_ops as ops
+    events, c0, quantiles = ops.dist_args(events, cutoff, quantiles, 3, 1, 1)
+    events = tuple(events)
+    cutoff = None if cutoff is None else c0
+    acc = _Acc(lambda mb, S, T: ops.EnsembleDistance(S, mb.B, mb.C, mb.H, mb.W, T, mb.dev, mb.out_mu, mb.out_std, u=mb.u, events=events,
+                                                     cutoff=cutoff, quantiles=quantiles),
+               target=True, meta=("dist_cutoff", "dist_quantiles"), extra={"events": events})
+    return _ensembleStats("modelPredDistance", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
+
+
 def modelPredPdfs(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, fields=("ux", "uy", "p", "vort"),
                   bins=64, ranges=None, joint=(("ux", "uy"),), joint_bins=32, regions=None, center=None):
     """modelPredStats plus the probability densities of the flow quantities themselves, pooled over regions of the flow, for the
