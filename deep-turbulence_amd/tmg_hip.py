@@ -20,7 +20,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmglow_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip", "tmg_phase.hip", "tmg_spod.hip", "tmg_budget.hip", "tmg_corr.hip", "tmg_flux.hip", "tmg_vortex.hip", "tmg_frank.hip", "tmg_xspec.hip", "tmg_spell.hip", "tmg_iscale.hip", "tmg_mink.hip", "tmg_edt.hip", "tmg_lagr.hip"]
+SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hip", "tmg_coupling.hip", "tmg_wino.hip", "tmg_thin.hip", "tmg_glue.hip", "tmg_ensemble.hip", "tmg_spectrum.hip", "tmg_scores.hip", "tmg_tspec.hip", "tmg_quant.hip", "tmg_gram.hip", "tmg_sfun.hip", "tmg_event.hip", "tmg_pdf.hip", "tmg_pod.hip", "tmg_phase.hip", "tmg_spod.hip", "tmg_budget.hip", "tmg_corr.hip", "tmg_flux.hip", "tmg_vortex.hip", "tmg_frank.hip", "tmg_xspec.hip", "tmg_spell.hip", "tmg_iscale.hip", "tmg_mink.hip", "tmg_edt.hip", "tmg_lspec.hip", "tmg_lagr.hip"]
 # Sources compiled WITHOUT the packed-fp32 vector instructions (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32): beside MFMAs a packed
 # f32 instruction costs ~13 cycles more than the two scalar ones it replaces (MI355X_MICROARCH.md, cycle constants, 'price of one
 # filler beside MFMAs'), and the compiler SLP-packs adjacent scalar adds / multiplies by itself under -O3.  The matrix-core kernels'
@@ -32,8 +32,9 @@ SOURCES = ["tmg_conv.hip", "tmg_pointwise.hip", "tmg_physics.hip", "tmg_mix16.hi
 # instruction rounds each half as the scalar one does).  tmg_spod.hip is listed for the same reason: the correction
 # x - xbar G of every fragment element is vector work between the MFMAs of the Gram product and of the synthesis.
 # tmg_xspec.hip is listed as tmg_spectrum.hip is: its column pass stores the accumulators between the MFMAs of the next row tile.
+# tmg_lspec.hip likewise: the Welford updates of a mode tile's epilogue are vector work between the MFMAs of the next tile.
 NO_PACKED_F32 = ["tmg_wino.hip", "tmg_conv.hip", "tmg_coupling.hip", "tmg_thin.hip", "tmg_mix16.hip", "tmg_spectrum.hip", "tmg_tspec.hip",
-                 "tmg_pod.hip", "tmg_spod.hip", "tmg_xspec.hip"]
+                 "tmg_pod.hip", "tmg_spod.hip", "tmg_xspec.hip", "tmg_lspec.hip"]
 _lib = None
 
 c_i64 = ctypes.c_int64
@@ -117,7 +118,16 @@ MINK_EXPORTS = ["tmg_ens_mink_plan", "tmg_ens_mink_chunk"]
 # the Hausdorff distances and Baddeley's delta (csrc/tmg_edt.hip), declared in include/tmglow_hip_edt.h, a header of its own:
 # ens_edt_plan / ens_edt_chunk / ens_edt_step / ens_edt_fixed below.
 EDT_EXPORTS = ["tmg_ens_edt_plan", "tmg_ens_edt_chunk", "tmg_ens_edt_step", "tmg_ens_edt_fixed"]
+# The line spectra: 1-D fluctuation, mean-flow and co-spectra along x or y (csrc/tmg_lspec.hip), declared in
+# include/tmglow_hip_lspec.h, a header of its own: ens_lspec_plan / ens_lspec_chunk / ens_lspec_step / ens_lspec_finalize below.
+LSPEC_EXPORTS = ["tmg_ens_lspec_plan", "tmg_ens_lspec_chunk", "tmg_ens_lspec_step", "tmg_ens_lspec_finalize"]
 _P64 = ctypes.POINTER(ctypes.c_int64)
+LSPEC_ARGTYPES = {
+    "tmg_ens_lspec_plan": [_P64, _P64],
+    "tmg_ens_lspec_chunk": [ctypes.c_void_p, _P64] + [ctypes.c_void_p] * 7 + [_P64, ctypes.c_void_p],
+    "tmg_ens_lspec_step": [ctypes.c_void_p] * 4 + [_P64, ctypes.c_void_p],
+    "tmg_ens_lspec_finalize": [ctypes.c_void_p] * 7 + [_P64, ctypes.c_void_p],
+}
 FLUX_ARGTYPES = {
     "tmg_ens_flux_plan": [_P64, _P64, _P64],
     "tmg_ens_flux_accum": [ctypes.c_void_p, _P64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _P64, _P64, ctypes.c_void_p],
@@ -179,7 +189,8 @@ def build(force=False, verbose=False):
                os.path.join(inc, "tmglow_hip_budget.h"), os.path.join(inc, "tmglow_hip_corr.h"), os.path.join(inc, "tmglow_hip_flux.h"),
                os.path.join(inc, "tmglow_hip_lagr.h"), os.path.join(inc, "tmglow_hip_vortex.h"),
                os.path.join(inc, "tmglow_hip_frank.h"), os.path.join(inc, "tmglow_hip_xspec.h"), os.path.join(inc, "tmglow_hip_spell.h"),
-               os.path.join(inc, "tmglow_hip_iscale.h"), os.path.join(inc, "tmglow_hip_mink.h"), os.path.join(inc, "tmglow_hip_edt.h")]
+               os.path.join(inc, "tmglow_hip_iscale.h"), os.path.join(inc, "tmglow_hip_mink.h"), os.path.join(inc, "tmglow_hip_edt.h"),
+               os.path.join(inc, "tmglow_hip_lspec.h")]
     hmt = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -256,6 +267,9 @@ def lib():
         for name in EDT_EXPORTS:
             getattr(_lib, name).restype = ctypes.c_int
             getattr(_lib, name).argtypes = EDT_ARGTYPES[name]
+        for name in LSPEC_EXPORTS:
+            getattr(_lib, name).restype = ctypes.c_int
+            getattr(_lib, name).argtypes = LSPEC_ARGTYPES[name]
     return _lib
 
 
@@ -2146,6 +2160,79 @@ def ens_edt_fixed(d2, c):
     out = (c_i64 * max(len(v), 1))()
     _chk(lib().tmg_ens_edt_fixed(_i64(*v) if v else (c_i64 * 1)(), len(v), int(c), out), "tmg_ens_edt_fixed")
     return [int(out[i]) for i in range(len(v))]
+
+
+LSPEC_PLAN_KEYS = ("tiles", "mode_tiles", "grid_x", "grid_y", "threads", "lds_bytes", "nq", "nqp", "part_floats", "mean_floats",
+                   "comom_floats", "operand_floats")
+
+
+def ens_lspec_plan(k, S, B, C, L, N, code=False):
+    """The launch plan and buffer sizes of ens_lspec_chunk for a chunk of k of S members of B cases, C channels, L lines of N points
+    (tmg_ens_lspec_plan; nothing is launched) -> dict of LSPEC_PLAN_KEYS (include/tmglow_hip_lspec.h).  code=True: the C return code
+    instead of raising, as the second element of a pair."""
+    plan = (c_i64 * len(LSPEC_PLAN_KEYS))()
+    rc = lib().tmg_ens_lspec_plan(_i64(k, S, B, C, L, N), plan)
+    out = dict(zip(LSPEC_PLAN_KEYS, [int(v) for v in plan]))
+    if code:
+        return out, rc
+    _chk(rc, "tmg_ens_lspec_plan")
+    return out
+
+
+def _lspec_f32(name, bufs, dev):
+    for what, t in bufs:
+        if t is not None and (t.dtype != torch.float32 or t.device != dev or not t.is_contiguous()):
+            raise RuntimeError("%s: %s must be a contiguous fp32 tensor on %s" % (name, what, dev))
+
+
+def ens_lspec_chunk(y, u, out_mu, out_std, op, mean, comom, part, S, k, m0, t_before, timed, columns=False, code=False):
+    """The line transforms of one chunk of k members (y: NHWC [k*B, H, W, C] or a channel-slice view, rows member-major): lines are
+    the rows of an image (L = H, N = W), or its columns with columns=True (L = W, N = H).  op [2, N, NQP]: the operand; part
+    [>= k*B*tiles*F*NQ]: the tiles' line sums of the planes of X; timed: the running means mean [S, B, C, L, NQ, 2] and the co-moments
+    comom [S, B, F, L, NQ] of the members m0 .. m0 + k - 1 take one more step (t_before: the steps they hold)
+    (tmg_ens_lspec_chunk, include/tmglow_hip_lspec.h).  code=True: the C return code instead of raising."""
+    kB, Hh, Ww, Cc = y.shape
+    ptr, ps, co, _ = seg(y)
+    check_device(y)
+    _lspec_f32("ens_lspec_chunk", (("u", u), ("out_mu", out_mu), ("out_std", out_std), ("op", op), ("mean", mean), ("comom", comom),
+                                   ("part", part)), y.device)
+    B = kB // max(k, 1)
+    L, N, ls, pstr = (Ww, Hh, 1, Ww) if columns else (Hh, Ww, Ww, 1)
+    rc = lib().tmg_ens_lspec_chunk(c_vp(ptr), _i64(ps, co), _ptr(u), _ptr(out_mu), _ptr(out_std), _ptr(op), _ptr(mean), _ptr(comom),
+                                   _ptr(part), _i64(k, S, B, Cc, L, N, ls, pstr, m0, t_before, 1 if timed else 0, part.numel(),
+                                                    0 if mean is None else mean.numel(), 0 if comom is None else comom.numel(),
+                                                    op.numel()), _stream())
+    if code:
+        return rc
+    _chk(rc, "tmg_ens_lspec_chunk")
+
+
+def ens_lspec_step(part, state, mean_out, std_out, k, L, N, n_before, S, t, last, code=False):
+    """Fold one chunk's partials (ens_lspec_chunk) into the step's statistics over the members: state [2, B, F, NQ] is the
+    sequential Welford's (mean, M2); last: the mean and the population std go to mean_out / std_out [B, Tk, F, NQ] at step t
+    (tmg_ens_lspec_step).  code=True: the C return code instead of raising."""
+    _, B, F, _ = state.shape
+    Tk = mean_out.shape[1]
+    _lspec_f32("ens_lspec_step", (("part", part), ("state", state), ("mean_out", mean_out), ("std_out", std_out)), part.device)
+    rc = lib().tmg_ens_lspec_step(_ptr(part), _ptr(state), _ptr(mean_out), _ptr(std_out),
+                                  _i64(k, B, F, L, N, n_before, S, Tk, t, 1 if last else 0), _stream())
+    if code:
+        return rc
+    _chk(rc, "tmg_ens_lspec_step")
+
+
+def ens_lspec_finalize(mean, comom, outs, member_out, T, code=False):
+    """Mean and population std over the members of the fluctuation and of the mean-flow spectra from the members' state (mean
+    [S, B, C, L, NQ, 2], comom [S, B, F, L, NQ]) after T timed steps -> outs = (fluct_mean, fluct_std, flow_mean, flow_std), each
+    [B, F, L, NQ]; member_out [B, S, F, L, NQ] or None (tmg_ens_lspec_finalize).  code=True: the C return code instead of raising."""
+    S, B, C, L, NQ, _ = mean.shape
+    _lspec_f32("ens_lspec_finalize", (("mean", mean), ("comom", comom), ("member_out", member_out)) + tuple(("out", o) for o in outs),
+               mean.device)
+    rc = lib().tmg_ens_lspec_finalize(_ptr(mean), _ptr(comom), *[_ptr(o) for o in outs], _ptr(member_out),
+                                      _i64(S, B, C, L, 2 * (NQ - 1), T), _stream())
+    if code:
+        return rc
+    _chk(rc, "tmg_ens_lspec_finalize")
 
 
 XSPEC_PLAN_KEYS = ("prep_grid", "cols_grid_x", "cols_grid_y", "cols_lds_bytes", "accum_grid_x", "accum_grid_y", "threads", "f_floats",

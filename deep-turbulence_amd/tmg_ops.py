@@ -5316,6 +5316,164 @@ class EnsembleSpectralSkill(EnsembleFeed):
         return o
 
 
+LSPEC_AXES = ("x", "y")
+
+
+def lspec_fields(C):
+    """The names of the F = C + 2 planes of a line spectrum, in plane order: the C autospectra, then uv_co, uv_quad."""
+    return tuple(("uu", "vv", "pp", "ss")[c] for c in range(C)) + ("uv_co", "uv_quad")
+
+
+def lspec_args(C, Hh, Ww, grid, axis, window, members):
+    """The argument checks of the line spectra (EnsembleLineSpectra, utils.modelPredLineSpectra), every failure a ValueError before
+    any device work, in this order: channels, N, L, grid, axis, window, members.  N (the points of a line) and L (the lines) are read
+    as for axis "x" (N = W, L = H) unless axis is "y" (N = H, L = W); an axis that is neither is reported at its turn.
+    -> (grid as floats, N, L, d): d the cell size along the line (dx for "x", dy for "y")."""
+    noun = "line spectra"
+    if isinstance(C, bool) or not isinstance(C, numbers.Integral):
+        raise ValueError("%s need an integer number of channels, got %r" % (noun, C))
+    _ens_channels(noun, C, " (the co-spectrum is that of channels 0 and 1)")
+    N, L = (Hh, Ww) if isinstance(axis, str) and axis == "y" else (Ww, Hh)
+    if isinstance(N, bool) or not isinstance(N, numbers.Integral) or not (16 <= N <= 512 and N % 16 == 0):
+        raise ValueError("%s need a line of N points, N a multiple of 16 in [16, 512], got %r" % (noun, N))
+    if isinstance(L, bool) or not isinstance(L, numbers.Integral) or L < 1:
+        raise ValueError("%s need L >= 1 lines, got %r" % (noun, L))
+    try:
+        grid = tuple(float(g) for g in grid)
+    except (TypeError, ValueError):
+        raise ValueError("grid needs two positive finite cell sizes (dx, dy), got %r" % (grid,)) from None
+    if len(grid) != 2 or not all(math.isfinite(g) and g > 0 for g in grid):
+        raise ValueError("grid needs two positive finite cell sizes (dx, dy), got %s" % (grid,))
+    if not isinstance(axis, str) or axis not in LSPEC_AXES:
+        raise ValueError("axis must be 'x' (along W) or 'y' (along H), got %r" % (axis,))
+    if window not in ("hann", None):
+        raise ValueError("window must be 'hann' or None, got %r" % (window,))
+    if isinstance(members, bool) or not isinstance(members, numbers.Integral):
+        raise ValueError("%s need an integer number of members, got %r" % (noun, members))
+    _ens_members(noun, members)
+    return grid, int(N), int(L), grid[0] if axis == "x" else grid[1]
+
+
+def _lspec_operand(N, window):
+    """[2, N, NQP] fp32 (re, im) of the one-sided transform of a line of N points: op[n][q] = (w[n] / N) exp(-2 pi i ((q n) mod N) / N)
+    for q = 0 .. N/2, the argument reduced with integers, built in fp64 and rounded once (_spectrum_operand's rule); the columns from
+    NQ = N/2 + 1 up to NQP = 16 ceil(NQ / 16) are exactly zero.  w: the periodic Hann window over sqrt(mean(w^2)), or 1."""
+    NQ = N // 2 + 1
+    NQP = (NQ + 15) // 16 * 16
+    n = torch.arange(N, dtype=torch.int64)
+    q = torch.arange(NQ, dtype=torch.int64)
+    ang = ((n[:, None] * q[None, :]) % N).to(torch.float64) * (-2.0 * math.pi / N)
+    w = torch.ones(N, dtype=torch.float64)
+    if window == "hann":
+        w = 0.5 - 0.5 * torch.cos(2.0 * math.pi * n.to(torch.float64) / N)
+        w = w / torch.sqrt(torch.mean(w * w))
+    w = (w / N)[:, None]
+    op = torch.zeros((2, N, NQP), dtype=torch.float32)
+    op[0, :, :NQ] = (w * torch.cos(ang)).to(torch.float32)
+    op[1, :, :NQ] = (w * torch.sin(ang)).to(torch.float32)
+    return op.contiguous()
+
+
+def lspec_outputs(fluct, k, C):
+    """The host-formed outputs of the line spectra from the ensemble-mean fluctuation planes fluct [B, F, L, NQ] (F = C + 2) and the
+    wavenumbers k [NQ]: fp64 work on CPU copies, no device -> dict of float64 CPU tensors
+      time_lspec_energy [B, F, L]        the sum over q (for an autospectrum: the line's windowed variance, by Parseval)
+      time_lspec_centroid [B, C, L]      sum_{q >= 1} k Phi_cc / sum_{q >= 1} Phi_cc, NaN at 0 / 0
+      time_lspec_coherence [B, L, NQ]    (co^2 + quad^2) / (Phi_00 Phi_11), NaN at 0 / 0."""
+    P = torch.as_tensor(fluct).detach().cpu().to(torch.float64)
+    k = torch.as_tensor(k).detach().cpu().to(torch.float64).reshape(-1)
+    C = int(C)
+    if P.dim() != 4 or P.shape[1] != C + 2 or P.shape[3] != k.numel():
+        raise ValueError("fluct is [B, %d, L, %d], got %s" % (C + 2, k.numel(), tuple(P.shape)))
+    A = P[:, :C, :, 1:]
+    return {"time_lspec_energy": P.sum(-1), "time_lspec_centroid": _xs_ratio((A * k[1:]).sum(-1), A.sum(-1)),
+            "time_lspec_coherence": _xs_ratio(P[:, C] ** 2 + P[:, C + 1] ** 2, P[:, 0] * P[:, 1])}
+
+
+class EnsembleLineSpectra(EnsembleFeed):
+    """On-device one-dimensional line spectra of sampled roll-outs of B cases (tmg_ens_lspec_chunk / tmg_ens_lspec_step /
+    tmg_ens_lspec_finalize): the streamwise (or wall-normal) spectrum of u'u', v'v', p'p' and the u'v' co-spectrum at every line, the
+    map k Phi(k, y) that says at which scales a member carries its Reynolds stress.  axis="x" transforms along W: the lines are the
+    L = H rows, N = W, d = dx; axis="y" along H: the L = W columns, N = H, d = dy.  N is a multiple of 16 in 16..512, L >= 1 is free.
+    Per case, member, kept step, channel c and line l, with yh = u[b, c] (out_std[c] y + out_mu[c]):
+      X_c[l, q] = (1 / N) sum_n w[n] yh_c[l, n] exp(-2 pi i q n / N), q = 0 .. N/2 (NQ = N/2 + 1), w the periodic Hann window over its
+      RMS (window=None: 1); a dense DFT on the fp32 matrix pipe with w / N folded into its operand
+      planes (F = C + 2: lspec_fields): a_q |X_c|^2, then uv_co = a_q Re(X_0 conj X_1), uv_quad = a_q Im(X_0 conj X_1); a_q = 1 at
+      q = 0 and q = N/2, else 2
+      total spectrum of a step: the planes of X; mean-flow spectrum of a member: the planes of Xbar = mean_t X over the steps folded
+      with time=True; fluctuation spectrum: Phi = a_q (1 / T) sum_t (X_t - Xbar) conj(Y_t - Ybar), a population moment as time_rms
+      is, accumulated as a running mean and co-moment (Welford) in ONE pass, never as mean|X|^2 - |Xbar|^2.
+    Parseval: sum_q Phi_cc[l, q] = mean_n w[n]^2 var_t(yh_c[l, n]).
+
+    Feeding protocol of EnsembleFeed; add(y, m0, time=True) takes no target.  Device memory: the members' state takes
+    4 (3 C + 2) S B L NQ bytes (44 S B L NQ at C = 3: 2 C floats of running mean and C + 2 of co-moments per member, line and mode),
+    the partials of the largest chunk 4 k B ceil(L / 16) F NQ.  Every sum has a fixed order and the step's Welford over the members is
+    sequential across chunks: all outputs are bitwise equal for every chunking.
+    Outputs (device tensors, fp32): lspec_mean, lspec_std [B, Tk, F, NQ] (the line-averaged total spectra: mean and population std over
+    the members); finalize() adds time_lspec_fluct_mean / _std and time_lspec_flow_mean / _std [B, F, L, NQ] (over the members), with
+    per_member time_lspec_fluct_member [B, S, F, L, NQ], and from lspec_outputs on the host in fp64 time_lspec_energy [B, F, L],
+    time_lspec_centroid [B, C, L], time_lspec_coherence [B, L, NQ]; lspec_k [NQ] (float64: 2 pi q / (N d)) and lspec_fields.
+
+    Not supported: two-dimensional fluctuation spectra, wavenumber-frequency spectra, Welch segments, sizes off the 16 grid, a CPU
+    path, non-finite members (the outputs they touch are unspecified; no address depends on the data)."""
+
+    def __init__(self, members, B, C, Hh, Ww, steps, device, out_mu, out_std, u=None, grid=(1.0, 1.0), axis="x", window="hann",
+                 per_member=False):
+        noun = "line spectra"
+        grid, N, L, d = lspec_args(C, Hh, Ww, grid, axis, window, members)
+        if int(B) < 1 or int(steps) < 1:
+            raise ValueError("%s need B >= 1 cases and steps >= 1, got %d and %d" % (noun, int(B), int(steps)))
+        sd, mu = _ens_tables(C, "the fields are un-normalised with it", out_std, out_mu)
+        u = _ens_u(u, int(B), C, "the fields are scaled with it")
+        dev = _ens_device(noun, device)
+        EnsembleFeed.__init__(self, members, B, C, Hh, Ww, steps)
+        self.grid, self.axis, self.window, self.per_member = grid, axis, window, bool(per_member)
+        self.N, self.L, self.NQ, self.F = N, L, N // 2 + 1, C + 2
+        self.k = torch.arange(self.NQ, dtype=torch.float64) * (2.0 * math.pi / (N * d))
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.mu, self.sd = mu.to(dev).contiguous(), sd.to(dev).contiguous()
+        self.u = None if u is None else u.to(dev).contiguous()
+        self.op = _lspec_operand(N, window).to(dev)
+        self.plan = H.ens_lspec_plan(1, self.S, self.B, C, L, N)
+        self.mean_state = torch.empty((self.S, self.B, C, L, self.NQ, 2), **f32)
+        self.comom_state = torch.empty((self.S, self.B, self.F, L, self.NQ), **f32)
+        self.step_state = torch.empty((2, self.B, self.F, self.NQ), **f32)
+        self.out = {"lspec_mean": torch.empty((self.B, self.Tk, self.F, self.NQ), **f32),
+                    "lspec_std": torch.empty((self.B, self.Tk, self.F, self.NQ), **f32)}
+        self._part = None                 # workspace of the largest chunk: the tiles' line sums
+
+    def add(self, y, m0, time=True):
+        """Fold the step's members m0 .. m0 + k - 1 of y (API-shaped [k*B, C, H, W], any strides whose channels-last view is an NHWC
+        channel-slice; rows member-major)."""
+        yn, _, k, t_before, last = self.open_chunk(y, m0, time)
+        _on_device(yn)
+        need = k * self.plan["part_floats"]
+        if self._part is None or self._part.numel() < need:
+            self._part = torch.empty(need, device=self.step_state.device, dtype=torch.float32)
+        H.ens_lspec_chunk(yn, self.u, self.mu, self.sd, self.op, self.mean_state, self.comom_state, self._part, self.S, k, m0, t_before,
+                          bool(time), columns=self.axis == "y")
+        H.ens_lspec_step(self._part, self.step_state, self.out["lspec_mean"], self.out["lspec_std"], k, self.L, self.N, self._n, self.S,
+                         self._step, last)
+        self.close_chunk(m0, k, time, last)
+
+    def finalize(self):
+        """-> dict of the outputs; the time statistics cover the steps folded with time=True."""
+        T = self.finalize_guard()
+        dev = self.step_state.device
+        o = dict(self.out)
+        names = ("time_lspec_fluct_mean", "time_lspec_fluct_std", "time_lspec_flow_mean", "time_lspec_flow_std")
+        for n in names:
+            o[n] = empty((self.B, self.F, self.L, self.NQ), dev)
+        mem = empty((self.B, self.S, self.F, self.L, self.NQ), dev) if self.per_member else None
+        H.ens_lspec_finalize(self.mean_state, self.comom_state, [o[n] for n in names], mem, T)
+        if mem is not None:
+            o["time_lspec_fluct_member"] = mem
+        o.update(lspec_outputs(o["time_lspec_fluct_mean"], self.k, self.C))
+        o["lspec_k"] = self.k
+        o["lspec_fields"] = lspec_fields(self.C)
+        return o
+
+
 def _tspec_window(Tn, window):
     """fp64 [Tn]: the periodic Hann window w_n = 0.5 - 0.5 cos(2 pi n / Tn) over sqrt(mean(w^2)), or ones."""
     n = torch.arange(Tn, dtype=torch.float64)

@@ -406,6 +406,61 @@ def modelPredSpectralSkill(args, model, testing_loader, log, samples=1, stride=1
     return _ensembleStats("modelPredSpectralSkill", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, False, [acc])
 
 
+def _lspec_log_distance(ens, tgt, C):
+    """ens, tgt [N, F, L, NQ] -> [N, C, L] float64: the RMS over q = 1 .. NQ-1 of 10 log10(ens / tgt) of the C autospectra, NaN where
+    either is not positive at any of those modes."""
+    a, b = ens[:, :C, :, 1:].double(), tgt[:, :C, :, 1:].double()
+    ok = (a > 0) & (b > 0)
+    r = 10.0 * torch.log10(torch.where(ok, a, torch.ones_like(a)) / torch.where(ok, b, torch.ones_like(b)))
+    d = torch.sqrt((r * r).mean(-1))
+    return torch.where(ok.all(-1), d, torch.full_like(d, float("nan")))
+
+
+def modelPredLineSpectra(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64, axis="x", window="hann",
+                         per_member=False):
+    """modelPredTurbulence plus the one-dimensional line spectra of every channel at every line of the field, still without forming
+    modelPred's [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleLineSpectra): the spectrum of u'u', v'v', p'p' and the co-spectrum of
+    u'v' along x at each height y (axis="x": lines are the rows, d = args.dx) or along y at each station x (axis="y": the columns,
+    d = args.dy), of the fluctuations about each member's own time mean.  time_tke_* and time_uv_* give the integral over scales of
+    what these resolve by scale; modelPredSpectra's E(k) includes the mean flow.  Same roll-outs as modelPredTurbulence: under the
+    same host RNG state the keys both return are identical.
+
+    Per case, member, kept step, channel c and line l: X_c[l, q] = (1 / N) sum_n w[n] yh_c[l, n] exp(-2 pi i q n / N), q = 0 .. N/2,
+    w the periodic Hann window over its RMS (window=None: 1); planes (lspec_fields): a_q |X_c|^2 of the C channels, then
+    uv_co = a_q Re(X_0 conj X_1) and uv_quad = a_q Im(X_0 conj X_1), a_q = 1 at q = 0 and N/2, else 2.  The line length must be a
+    multiple of 16 in 16..512.  Kept steps t_start..Tk-1 are the timed ones (T of them).
+
+    Returns modelPredTurbulence's dict plus (CPU tensors; F = C + 2, L lines, NQ = N/2 + 1):
+      lspec_mean, lspec_std [N, Tk, F, NQ]           mean / population std over the members of the line-averaged planes of X, per
+                                                     kept step (the total spectrum: mean flow included)
+      time_lspec_fluct_mean, time_lspec_fluct_std [N, F, L, NQ]
+                                                     ... of each member's fluctuation spectrum a_q (1 / T) sum_t (X_t - Xbar) conj(Y_t - Ybar)
+                                                     (a population moment, as time_rms; one pass, Welford)
+      time_lspec_flow_mean, time_lspec_flow_std      ... of the planes of each member's time-mean coefficient Xbar
+      time_lspec_fluct_member [N, S, F, L, NQ]       every member's fluctuation spectrum (per_member=True only)
+      time_lspec_energy [N, F, L], time_lspec_centroid [N, C, L], time_lspec_coherence [N, L, NQ]
+                                                     float64, of time_lspec_fluct_mean: the sum over q; sum_{q>=1} k Phi / sum_{q>=1} Phi;
+                                                     (co^2 + quad^2) / (Phi_00 Phi_11); NaN at 0 / 0
+      target_lspec [N, T, F, NQ], target_time_lspec_fluct, target_time_lspec_flow [N, F, L, NQ]
+                                                     the same of the target series at the timed steps (target step j * stride for
+                                                     kept step j), through the same kernels as a one-member ensemble
+      lspec_log_distance [N, C, L]                   float64: the RMS over q = 1..NQ-1 of 10 log10(time_lspec_fluct_mean /
+                                                     target_time_lspec_fluct) of the autospectra, NaN where either is not positive
+      lspec_k [NQ] float64 (2 pi q / (N d)), lspec_fields (the plane names).
+    Not supported: two-dimensional fluctuation spectra, wavenumber-frequency spectra, Welch segments, sizes off the 16 grid."""
+    import tmg_ops as ops
+    grid = (getattr(args, "dx", 1.0), getattr(args, "dy", 1.0)) if args is not None else (1.0, 1.0)
+    ops.lspec_args(3, 16, 16, grid, axis, window, int(samples) if int(samples) >= 1 else 1)
+    acc = _Acc(lambda mb, S, T: ops.EnsembleLineSpectra(S, mb.B, mb.C, mb.H, mb.W, T, mb.dev, mb.out_mu, mb.out_std, u=mb.u, grid=grid,
+                                                        axis=axis, window=window, per_member=bool(per_member)),
+               meta=("lspec_k", "lspec_fields"),
+               tail=(("target_lspec", "lspec_mean"), ("target_time_lspec_fluct", "time_lspec_fluct_mean"),
+                     ("target_time_lspec_flow", "time_lspec_flow_mean")))
+    res = _ensembleStats("modelPredLineSpectra", args, model, testing_loader, log, samples, stride, tmax, t_start, max_rows, True, [acc])
+    res["lspec_log_distance"] = _lspec_log_distance(res["time_lspec_fluct_mean"], res["target_time_lspec_fluct"], 3)
+    return res
+
+
 def modelPredScores(args, model, testing_loader, log, samples=1, stride=1, tmax=1, t_start=0, max_rows=64):
     """modelPredStats plus the ensemble's calibration scores against the target the loader carries, still without forming modelPred's
     [samples, N, T, C, H, W] tensor (tmg_ops.EnsembleScores).  The target of kept step j is series step j * stride.  Same roll-outs
